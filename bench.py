@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- 30 s audio chunks/s through the MI355X hot path (mel frontend + CNNRNNModel forward).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 32] [--cosched 4] [--streams 4] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 32] [--cosched 4] [--streams 4] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-sections]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one pass of the hot path over one batch of `--batch` synthetic 30 s / 16 kHz chunks
@@ -14,14 +15,18 @@ Chunks are independent (main.py:258-266 keeps no cross-chunk state), so N GPUs r
 schedules with no data-path collective (weak scaling); the only collectives are the timing barrier
 and a MAX over ranks of the elapsed time.
 
+A plain run sets up, warms up, times the K steps, writes the last step's logits with --dump-outputs and prints the line.
+Everything else it can measure runs only with --full (the un-overlapped passes, the CPU baseline and the sections below).
+
 Rank 0 prints ONE JSON line of at most 4 KB as the LAST line of stdout (compact_line): the contract fields,
   roofline     -- the kernel that dominates the step, timed with HIP events on the launch stream (recorded
-                  natively by mt_cnnrnn_forward_ex) in an un-overlapped pass of this run: ONE forward of the
+                  natively by mt_cnnrnn_forward_ex) in an un-overlapped pass of this run (--full; a plain run
+                  reads the events of the timed region, where forwards overlap): ONE forward of the
                   timed region's shape in flight; roofline.all = {stage: fraction of its roofline};
-  cpu_baseline -- the CPU oracle (a port of the reference path, oracle/*.py) timed on this node's
+  cpu_baseline -- (--full) the CPU oracle (a port of the reference path, oracle/*.py) timed on this node's
                   host cores on a bounded sample of the same workload, rank 0, N = 1 only;
-  configs1_literal_b32 -- BASELINE configs[1] as written: ONE batch of 32 chunks per forward;
-  sections     -- one short object per neighbouring BASELINE config (Large inference, both training steps, corpus).
+  configs1_literal_b32 -- (--full) BASELINE configs[1] as written: ONE batch of 32 chunks per forward;
+  sections     -- (--full) one short object per neighbouring BASELINE config (Large inference, both training steps, corpus).
 Everything else (stage tables of every pass, schedules, autotune lists, samples) goes to bench_detail.json
 (repo root and gpurun_out/; MT_BENCH_DETAIL overrides the path).
 """
@@ -126,6 +131,24 @@ def log(*a):
     print("[bench]", *a, file=sys.stderr, flush=True)
 
 
+DUMP_LIMIT = 64 << 20      # bytes: --dump-outputs writes at most this much in all
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT):
+    """--dump-outputs: the tensors the timed path returned in its last step, one float32 DIR/<name>.npy each, so that two builds can
+    be compared output for output on the same seeded inputs.  Over `limit` bytes in all, every array keeps the same leading fraction
+    of its chunks (dim 0): a fixed sample."""
+    import numpy as np
+    arrs = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrs.values())
+    if total > limit:
+        arrs = {k: (a[:max(1, int(len(a) * limit / total))] if a.ndim else a) for k, a in arrs.items()}
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    log(f"dumped {', '.join(f'{k}{tuple(a.shape)}' for k, a in arrs.items())} to {path}")
+
+
 def bench_large(args):
     """BASELINE.json configs[2]: CNNRNNModelLarge (89M), batch 16, 1 GPU -- informational (not the bench line)."""
     import numpy as np
@@ -156,6 +179,8 @@ def bench_large(args):
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
     model.model.raise_on_handoff_timeout(B, T)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out)
     flops = 326.47e9 * B * T / 938.0
     print(json.dumps({"metric": "30 s audio chunks/sec (mel+CNNRNNModelLarge forward)", "value": round(B * K / el, 2), "unit": "chunks/s",
                       "n_gpus": 1, "steps": K, "warmup": W, "ms_per_step": round(1e3 * el / K, 3), "higher_is_better": True,
@@ -241,6 +266,8 @@ def bench_train(args):
     if world > 1:
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
     el = float(el.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"loss": loss})
     if rank == 0:
         flops = 3.0 * (72.76e9 if mtype == "cnn_rnn" else 326.47e9) * B * world * T / 938.0
         print(json.dumps({"metric": f"30 s audio chunks/sec ({'CNNRNNModel' if mtype == 'cnn_rnn' else 'CNNRNNModelLarge'} training step)", "value": round(B * world * K / el, 2),
@@ -846,14 +873,21 @@ def main():
     ap.add_argument("--cosched", type=int, default=4,
                     help="batches (steps) co-scheduled into ONE forward: the recurrence interleaves their batch groups inside one "
                          "persistent launch (csrc/lstm.hip, NG).  1 = one batch per forward, as in round 1")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-sections", action="store_true", help="only the headline line: skip the 1-stream pass and the configs[2] / configs[3] sections")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the un-overlapped per-kernel passes, the CPU baseline and the sections "
+                         "(other schedules, configs[2] - configs[4], training); a plain run only times the K steps")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-sections", action="store_true", help="with --full: skip the 1-stream pass and the configs[2] / configs[3] sections")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last step returned as DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--model", choices=["cnn_rnn", "cnn_rnn_large"], default="cnn_rnn",
                     help="cnn_rnn = the bench line (BASELINE configs[1]); cnn_rnn_large = informational run of configs[2] "
                          "(use --batch 16): whole-step timing only")
     ap.add_argument("--mode", choices=["infer", "train"], default="infer",
                     help="infer = the bench line; train = informational run of configs[3] (use --batch 16 --steps 5)")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline = args.no_sections = True
     if args.mode == "train":
         # a training-only process: 32 hardware queues, so that the step's side streams never share one with the calling stream (a shared
         # queue serialises them: 46 instead of 42 ms per CNNRNNModelLarge step; tools/train_large_queue_probe.py, profiles/r04_train_large_stream_mapping.txt).
@@ -1003,6 +1037,8 @@ def main():
     for nb_ in sorted({nb_ for _, nb_ in sched}):
         net.raise_on_handoff_timeout(nb_ * B, T)
     log(f"timed region: {elapsed:.3f} s for {K} steps")
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"logits": logits[-B:]})        # the last step = the last batch of the last forward
     if world > 1:
         tt = torch.tensor([elapsed], device=dev if backend == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)

@@ -881,12 +881,12 @@ def test_oversubscribed_persistent_launches_fail_fast(mta):
 
 # ------------------------------------------------------------------ the driver's command
 def test_bench_line_contract(tmp_path):
-    """`python bench.py --steps K --warmup W` prints ONE JSON line with the contract's fields; K steps of 32 chunks are timed
+    """`python bench.py --steps K --warmup W --full` prints ONE JSON line with the contract's fields; K steps of 32 chunks are timed
     whether or not K is a multiple of the batches per forward (the left-over steps run as one smaller forward)."""
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     detail_path = str(tmp_path / "detail.json")
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "10", "--warmup", "4", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "10", "--warmup", "4", "--full", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=600, env=dict(os.environ, MT_BENCH_DETAIL=detail_path))
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -919,6 +919,27 @@ def test_bench_line_contract(tmp_path):
     assert cz["chunks"] > 2000 and cz["finite"] and cz["notes"] > 1000 and cz["value"] > 500
     cp = full["configs4_corpus_from_pcm"]
     assert cp["finite"] and cp["notes"] > 1000 and cp["value"] > 100 and cp["chunks"] == cz["chunks"]
+
+
+def test_bench_plain_run_dumps_the_last_step(tmp_path):
+    """A plain `python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` times K steps and nothing else (no CPU baseline, no
+    sections), and writes the last step's logits; two runs with the same arguments see the same inputs and write the same logits."""
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    outs = []
+    for i in range(2):
+        dump = tmp_path / f"out{i}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--dump-outputs", str(dump)],
+                           capture_output=True, text=True, timeout=300, env=dict(os.environ, MT_BENCH_DETAIL=str(tmp_path / "detail.json")))
+        assert r.returncode == 0, r.stderr[-3000:]
+        d = json.loads(r.stdout.rstrip().splitlines()[-1])
+        assert d["steps"] == 6 and d["warmup"] == 2 and d["unit"] == "chunks/s" and d["higher_is_better"] is True and d["dtype"] == "f16"
+        assert abs(d["value"] - 32 * 6 / (d["ms_per_step"] * 6 / 1e3)) / d["value"] < 1e-3
+        assert d["cpu_baseline"] is None and d["sections"] == {} and "configs1_literal_b32" not in d
+        assert sorted(os.listdir(dump)) == ["logits.npy"]
+        outs.append(np.load(str(dump / "logits.npy")))
+    assert outs[0].dtype == np.float32 and outs[0].shape == (32, 88, 938) and np.isfinite(outs[0]).all()
+    assert np.array_equal(outs[0], outs[1])
 
 
 def test_bench_two_ranks_rehearsal(tmp_path):

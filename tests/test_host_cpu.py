@@ -408,6 +408,22 @@ def test_bench_compact_line_survives_a_bounded_tail():
     assert len(line2) <= 4096 and d2["value"] == full["value"] and d2["roofline"]["frac"] == rf["frac"] and "cpu_baseline" in d2
 
 
+def test_bench_dump_outputs_stays_under_its_limit(tmp_path):
+    """bench.py --dump-outputs writes float32 .npy files; over the size limit every array keeps the same leading chunks."""
+    import bench
+    logits = torch.arange(10 * 4 * 5, dtype=torch.float64).reshape(10, 4, 5)
+    bench.dump_outputs(str(tmp_path / "all"), {"logits": logits, "loss": torch.tensor(0.25)})
+    a = np.load(str(tmp_path / "all" / "logits.npy"))
+    assert a.dtype == np.float32 and np.array_equal(a, logits.float().numpy())
+    assert np.load(str(tmp_path / "all" / "loss.npy")) == np.float32(0.25)
+    bench.dump_outputs(str(tmp_path / "cut"), {"frame": logits, "onset": logits + 1}, limit=2 * 3 * 4 * 5 * 4)
+    for k, off in (("frame", 0), ("onset", 1)):
+        b = np.load(str(tmp_path / "cut" / (k + ".npy")))
+        assert b.shape == (3, 4, 5) and np.array_equal(b, logits[:3].float().numpy() + off)
+    assert sum(os.path.getsize(str(p)) - 128 for p in (tmp_path / "cut").iterdir()) <= 2 * 3 * 4 * 5 * 4
+    assert bench.DUMP_LIMIT == 64 << 20
+
+
 def test_side_stream_tables_use_one_key_per_device(mta):
     """a tuner built with the caller's device='cuda' must forget / restore the streams the step created under
     x.device = cuda:0 (the tables were keyed by str(device): 'cuda' != 'cuda:0' and the tuner measured one pair four times)."""
