@@ -111,6 +111,28 @@ int    mt_mel_plan_init(void* plan, size_t plan_bytes, int sr, int hop, int n_me
 int    mt_mel_db_f32(const void* plan, const mt_mel_desc* desc, const float* wave, int B, int n_samples,
                      float* mel_db, float* chunk_max_power, int apply_clamp, mt_stream_t stream);
 
+/* Ragged batch of windows of a long device-resident store (csrc/rawbatch.hip), collated as collate_fn pads.
+ * Window b = store[win_off[b] : win_off[b] + win_len[b]] (64-bit offsets, in floats); its samples at window
+ * positions >= rec_end[b] read as 0 (a recording shorter than the window); frames are centre-padded at the
+ * WINDOW's edges.  chunk_max_power[b] is the max over all 1 + win_len[b]/hop frames; mel_db[B][1][n_mels][T_out]
+ * holds frames < t_keep[b] clamped at max-80 dB and 0.0 from t_keep[b] on.  Per window this equals
+ * mt_mel_db_f32(apply_clamp=1) on a contiguous copy of it, trimmed and zero-padded, bit for bit.
+ * max_win_len >= every win_len[b]; the store must hold one readable float past each window's readable end.
+ * All tables are device pointers.                                                                           */
+int    mt_mel_db_windows_f32(const void* plan, const mt_mel_desc* desc, const float* store, const long long* win_off,
+                             const int* win_len, const int* rec_end, int B, int max_win_len, int T_out,
+                             const int* t_keep, float* mel_db, float* chunk_max_power, mt_stream_t stream);
+
+/* Piano-roll labels of the same windows: roll[B][88][T_out] f32 in {0,1}.  spans = int32 pairs (u, v): the sorted,
+ * disjoint frame ranges [u, v) in which pitch 21 + p sounds in recording r (notes, sustain-pedal extension and
+ * instrument widths already applied), pairs pitch_off[r*89 + p] .. pitch_off[r*89 + p + 1] - 1.
+ * win_cols[b] >= 0 (chunk mode): column n < win_ncols[b] - 1 is any over frames [cols[c+n], cols[c+n+1]) (one frame
+ * when equal), c = win_cols[b], and the last column is 0 (pretty_midi get_piano_roll(times=...)); win_cols[b] < 0
+ * (full file): column n is frame n.  Columns >= t_keep[b] are 0.  cols may be NULL when no window is in chunk mode. */
+int    mt_roll_windows(const int* spans, const long long* pitch_off, const int* cols, const int* win_rec,
+                       const long long* win_cols, const int* win_ncols, const int* t_keep, int B, int T_out,
+                       float* roll, mt_stream_t stream);
+
 /* ------------------------------------------------------------------ CNN blocks
  * CNNRNNModel.cnn (cnn_rnn_model.py:29-39; Large: conv1, :178-183), eval mode; BatchNorm
  * running statistics are folded into (w, bias) by the host at load_state_dict time.

@@ -82,6 +82,8 @@ _SIGS = {
     "mt_mel_plan_bytes": (sz, [i32]),
     "mt_mel_plan_init": (i32, [vp, sz, i32, i32, i32, C.POINTER(MelDesc), vp]),
     "mt_mel_db_f32": (i32, [vp, C.POINTER(MelDesc), vp, i32, i32, vp, vp, i32, vp]),
+    "mt_mel_db_windows_f32": (i32, [vp, C.POINTER(MelDesc), vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
+    "mt_roll_windows": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp]),
     "mt_conv1_bn_relu_pool": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "mt_conv2_bn_relu_pool": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "mt_conv1_bn_relu_pool_dt": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),

@@ -1,0 +1,381 @@
+"""MAESTRO recordings -> training batches on the device, without a preprocessed cache (the reference's MaestroDataset /
+HybridMaestroDataset, data/dataset.py:9-200 and data/cached_dataset.py:91-141).
+
+One split lives on the GPU:
+  * audio: every recording decoded and resampled once (transcribe.load_audio_device) into ONE f32 device buffer with a
+    per-recording (offset, n_samples) table (RecordingStore).  A split larger than `max_resident_bytes` keeps an LRU of
+    whole recordings and re-decodes an evicted one when a batch needs it: same bytes, slower;
+  * labels: per recording and pitch the sorted, disjoint frame spans in which the pitch sounds (label_spans: note spans
+    int(start*fs):int(end*fs), the sustain-pedal running maximum, instrument widths int(fs*end_time), drums dropped),
+    built on the host in float64 exactly as midi.Instrument.get_piano_roll renders them, and kilobytes per recording;
+  * per chunk: the column grid round(linspace(start, end, int((end-start)*fs)) * fs) of pretty_midi's `times`, built on
+    the host with numpy itself at construction (4 bytes per frame), so the device needs no float64 index arithmetic.
+A batch is then two launches (csrc/rawbatch.hip): mt_mel_db_windows_f32 (mel of the ragged windows, trimmed and padded)
+and mt_roll_windows (labels), with the same bytes a cache record written by preprocess_and_cache holds, collated as
+data.collate_fn does.  A chunk is sliced from the recording resampled once, as the cache writer does; the reference
+resamples each slice on its own (librosa.load(offset, duration), soxr).
+"""
+from __future__ import annotations
+
+import os
+import pickle
+import warnings
+from collections import OrderedDict
+from typing import Dict, Optional, Sequence
+
+import numpy as np
+import torch
+from torch.utils.data import BatchSampler, Dataset, RandomSampler, SequentialSampler
+
+from . import _lib
+from ._lib import check, lib, ptr
+from .frontend import get_frontend
+from .midi import MidiFile
+from .preprocess import build_chunk_index, read_maestro_csv, wav_duration
+from .transcribe import load_audio_device
+
+PITCH_LO, N_PITCH = 21, 88
+_ALIGN = 64                  # floats: recordings start on 256-byte boundaries of the store
+_PAD = 64                    # readable floats past the last recording (the mel kernel reads whole sample pairs)
+
+
+# ------------------------------------------------------------------ labels
+def label_spans(midi: MidiFile, fs: float):
+    """Active frame spans of `midi` on the grid of get_piano_roll(fs): (spans int32 (K, 2) of [u, v), pitch_off int64 (89,)
+    -- pitch row p (MIDI 21 + p) owns spans[pitch_off[p]:pitch_off[p + 1]], sorted and disjoint --, the full-file roll
+    width int(fs * end_time) over the instruments with notes (drums included, as get_piano_roll's width), and whether any
+    instrument has notes (a roll of width 0 otherwise).
+
+    Per non-drum instrument of width W: a note covers [int(start*fs), int(end*fs)); a sustain pedal interval [t_on, t_off)
+    (CC 64 crossing 64 upwards, then downwards; one still down at the end sustains nothing) extends a note that sounds in it
+    to min(t_off, W) from its first frame there (np.maximum.accumulate over non-negative velocities).  Only the last pedal
+    interval starting before a note's end can reach past it: the intervals are disjoint and ordered."""
+    us, vs, ps = [], [], []
+    full_width, has_notes = 0, False
+    for inst in midi.instruments:
+        if not inst.notes:
+            continue
+        has_notes = True
+        width = int(fs * inst.get_end_time())
+        full_width = max(full_width, width)
+        if inst.is_drum:
+            continue
+        pitch = np.array([n.pitch for n in inst.notes], dtype=np.int64)
+        a = np.minimum((np.array([n.start for n in inst.notes]) * fs).astype(np.int64), width)
+        b = np.minimum((np.array([n.end for n in inst.notes]) * fs).astype(np.int64), width)
+        ons, offs, t_on, on = [], [], 0, False
+        for number, value, t in inst.control_changes:
+            if number != 64:
+                continue
+            now, cur = int(t * fs), value >= 64
+            if not on and cur:
+                t_on, on = now, True
+            elif on and not cur:
+                ons.append(t_on)
+                offs.append(now)
+                on = False
+        end = b.copy()
+        if ons:
+            ons_a, offs_a = np.array(ons, dtype=np.int64), np.minimum(np.array(offs, dtype=np.int64), width)
+            k = np.searchsorted(ons_a, b, side="left") - 1          # last pedal interval starting before the note's end
+            has = k >= 0
+            kk = np.where(has, k, 0)
+            g0 = np.maximum(a, ons_a[kk])                            # the note's first frame inside the interval
+            ext = has & (g0 < np.minimum(b, offs_a[kk]))
+            end = np.where(ext, np.maximum(b, offs_a[kk]), b)
+        keep = (a < b) & (pitch >= PITCH_LO) & (pitch < PITCH_LO + N_PITCH)
+        us.append(a[keep])
+        vs.append(end[keep])
+        ps.append(pitch[keep] - PITCH_LO)
+    u = np.concatenate(us) if us else np.zeros(0, np.int64)
+    v = np.concatenate(vs) if vs else np.zeros(0, np.int64)
+    p = np.concatenate(ps) if ps else np.zeros(0, np.int64)
+    # merge per pitch: keyed by pitch * BIG + frame, overlapping or touching spans join
+    big = int(max(int(v.max()) if v.size else 0, 1)) + 2
+    order = np.lexsort((u, p))
+    u, v, p = u[order] + p[order] * big, v[order] + p[order] * big, p[order]
+    if u.size:
+        reach = np.maximum.accumulate(v)
+        start = np.ones(u.size, dtype=bool)
+        start[1:] = u[1:] > reach[:-1]
+        mu, mv, mp = u[start], np.maximum.reduceat(v, np.flatnonzero(start)), p[start]
+        spans = np.stack([mu - mp * big, mv - mp * big], 1).astype(np.int32)
+    else:
+        mp = p
+        spans = np.zeros((0, 2), np.int32)
+    pitch_off = np.searchsorted(mp, np.arange(N_PITCH + 1), side="left").astype(np.int64)
+    return spans, pitch_off, full_width, has_notes
+
+
+def column_grid(start_time: float, end_time: float, fs: float) -> np.ndarray:
+    """pretty_midi's column boundaries for midi.chunk_roll: round(linspace(start, end, int((end - start) * fs)) * fs)."""
+    times = np.linspace(start_time, end_time, int((end_time - start_time) * fs))
+    return np.array(np.round(np.asarray(times, dtype=np.float64) * fs), dtype=np.int64)
+
+
+def roll_from_spans(spans: np.ndarray, pitch_off: np.ndarray, t_keep: int, cols: Optional[np.ndarray]) -> np.ndarray:
+    """Host rendering of mt_roll_windows' rule for one window (tests / documentation): (88, t_keep) float32 {0, 1}."""
+    out = np.zeros((N_PITCH, t_keep), np.float32)
+    if cols is None:
+        s = np.arange(t_keep)
+        e = s + 1
+        valid = np.ones(t_keep, bool)
+    else:
+        n = np.arange(t_keep)
+        valid = n + 1 < len(cols)
+        s = np.where(valid, cols[np.minimum(n, len(cols) - 1)], 0)
+        e = np.where(valid, cols[np.minimum(n + 1, len(cols) - 1)], 0)
+        e = np.where(e == s, s + 1, e)
+    for p in range(N_PITCH):
+        sp = spans[pitch_off[p]:pitch_off[p + 1]]
+        if not len(sp):
+            continue
+        k = np.searchsorted(sp[:, 1], s, side="right")               # first span with v > s
+        hit = (k < len(sp)) & (sp[np.minimum(k, len(sp) - 1), 0] < e)
+        out[p] = (valid & hit).astype(np.float32)
+    return out
+
+
+# ------------------------------------------------------------------ audio
+class RecordingStore:
+    """Decoded recordings in one f32 device buffer (64-bit offsets), LRU of whole recordings when over budget."""
+
+    def __init__(self, paths: Sequence[str], sr: int, device, est_samples: Sequence[int], max_resident_bytes: Optional[int] = None):
+        self.paths, self.sr, self.device = list(paths), int(sr), torch.device(device)
+        if max_resident_bytes is None:
+            max_resident_bytes = torch.cuda.mem_get_info(self.device)[0] // 2
+        want = sum(int(n) + 2 * _ALIGN for n in est_samples)
+        self.capacity = int(min(int(max_resident_bytes) // 4, want))
+        self.capacity -= self.capacity % _ALIGN
+        self.buf = torch.zeros(self.capacity + _PAD, dtype=torch.float32, device=self.device)
+        self.n = [0] * len(self.paths)                      # decoded samples per recording
+        self.loc: "OrderedDict[int, int]" = OrderedDict()  # resident recording -> offset (LRU order, most recent last)
+        self.decodes = 0
+        self._warned = False
+        for r in range(len(self.paths)):
+            self._load(r, ())
+
+    @property
+    def resident_bytes(self) -> int:
+        return sum(self.n[r] for r in self.loc) * 4
+
+    def _load(self, r: int, pinned) -> None:
+        y = load_audio_device(self.paths[r], self.sr, self.device)
+        self.decodes += 1
+        n = int(y.numel())
+        self.n[r] = n
+        off = self._alloc(n, pinned)
+        self.buf[off:off + n].copy_(y)
+        self.loc[r] = off
+
+    def _alloc(self, n: int, pinned) -> int:
+        need = -(-max(n, 1) // _ALIGN) * _ALIGN
+        if need > self.capacity:
+            raise RuntimeError(f"RecordingStore: a recording of {n} samples exceeds max_resident_bytes ({self.capacity * 4} B)")
+        while True:
+            pos = 0                                         # first fit between the resident recordings
+            for off, r in sorted((o, k) for k, o in self.loc.items()):
+                if off - pos >= need:
+                    return pos
+                pos = off + -(-max(self.n[r], 1) // _ALIGN) * _ALIGN
+            if self.capacity - pos >= need:
+                return pos
+            victim = next((k for k in self.loc if k not in pinned), None)
+            if victim is None:
+                raise _NoRoom()
+            if not self._warned:
+                warnings.warn(f"RecordingStore: the split does not fit in max_resident_bytes ({self.capacity * 4} B); evicted recordings "
+                              f"are decoded again when a batch needs them (same data, slower)", RuntimeWarning, stacklevel=4)
+                self._warned = True
+            del self.loc[victim]
+
+    def offsets(self, recs: Sequence[int]) -> Dict[int, int]:
+        """Make `recs` resident (together) and return their offsets in `buf` (floats).  When the free space around the
+        batch's resident recordings is too fragmented, the store is emptied and the batch's recordings are loaded side by side."""
+        pinned = sorted(set(int(r) for r in recs))
+        try:
+            for r in pinned:
+                if r in self.loc:
+                    self.loc.move_to_end(r)
+                else:
+                    self._load(r, pinned)
+        except _NoRoom:
+            self.loc.clear()
+            try:
+                for r in pinned:
+                    self._load(r, pinned)
+            except _NoRoom:
+                raise RuntimeError(f"RecordingStore: max_resident_bytes ({self.capacity * 4} B) cannot hold the recordings of one batch") from None
+        return {r: self.loc[r] for r in pinned}
+
+
+class _NoRoom(Exception):
+    pass
+
+
+def _in_worker() -> bool:
+    return torch.utils.data.get_worker_info() is not None
+
+
+# ------------------------------------------------------------------ datasets
+class MaestroDataset(Dataset):
+    """The reference's MaestroDataset (same arguments; items (mel (1, n_mels, T), roll (88, T)) CPU tensors, the bytes
+    preprocess_and_cache writes for the same chunk), built on the device.  get_batch(indices) gives collate_fn's batch with
+    mel and roll on the device in one launch of each kernel; DeviceBatchLoader is the DataLoader for it.  chunk_length=None:
+    one item per recording (whole file)."""
+
+    def __init__(self, root_dir, csv_path=None, year=None, split="train", sr=16000, n_mels=229, hop_length=512, subset_size=None,
+                 chunk_length=None, overlap=0.0, return_waveform=False, device=None, max_resident_bytes=None):
+        if return_waveform:
+            raise NotImplementedError("return_waveform=True is the AST experiment's data path (out of scope)")
+        self.root_dir, self.sr, self.n_mels, self.hop_length = root_dir, int(sr), int(n_mels), int(hop_length)
+        self.chunk_length, self.overlap, self.return_waveform = chunk_length, overlap, return_waveform
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.rows = read_maestro_csv(root_dir, split, year, subset_size, csv_path)
+        paths = [os.path.join(root_dir, r["audio_filename"]) for r in self.rows]
+        durations = [wav_duration(p) for p in paths]
+        self.chunks = build_chunk_index(durations, chunk_length, overlap, self.sr) if chunk_length is not None else []
+        fs = self.sr / self.hop_length
+        self.store = RecordingStore(paths, self.sr, self.device, [int(np.ceil(d * self.sr)) + 1 for d in durations], max_resident_bytes)
+        # labels: span tables of every recording, one device array
+        spans, poffs, fullw, notes, base = [], [], [], [], 0
+        for r in self.rows:
+            sp, po, fw, hn = label_spans(MidiFile(os.path.join(root_dir, r["midi_filename"])), fs)
+            spans.append(sp)
+            poffs.append(po + base)
+            fullw.append(fw)
+            notes.append(hn)
+            base += len(sp)
+        n_rec = np.array(self.store.n, dtype=np.int64)
+        if chunk_length is not None:
+            c = self.chunks
+            self.rec = np.array([x["file_idx"] for x in c], dtype=np.int64)
+            self.start = np.array([x["start_sample"] for x in c], dtype=np.int64)
+            self.win_len = np.array([x["end_sample"] - x["start_sample"] for x in c], dtype=np.int64)
+            grids = [column_grid(x["start_time"], x["end_time"], fs) for x in c]
+            self.ncols = np.array([len(g) for g in grids], dtype=np.int64)
+            self.col_off = np.concatenate([[0], np.cumsum(self.ncols)[:-1]]).astype(np.int64) if c else np.zeros(0, np.int64)
+            roll_w = np.where(np.array([notes[f] for f in self.rec], dtype=bool), self.ncols, 0) if c else np.zeros(0, np.int64)
+            cols = np.concatenate(grids).astype(np.int32) if grids and self.ncols.sum() else np.zeros(1, np.int32)
+        else:
+            self.rec = np.arange(len(self.rows), dtype=np.int64)
+            self.start = np.zeros(len(self.rows), dtype=np.int64)
+            self.win_len = n_rec.copy()
+            self.ncols = np.zeros(len(self.rows), dtype=np.int64)
+            self.col_off = np.full(len(self.rows), -1, dtype=np.int64)
+            roll_w = np.array([fw if hn else 0 for fw, hn in zip(fullw, notes)], dtype=np.int64)
+            cols = np.zeros(1, np.int32)
+        self.t_keep = np.minimum(1 + self.win_len // self.hop_length, roll_w).astype(np.int64)
+        if self.win_len.size and int(self.win_len.max()) * 4 + 8 >= 0x7FFFFFFF:
+            raise ValueError("MaestroDataset: a window longer than 2^29 samples")
+        dev = self.device
+        sp_all = np.concatenate(spans) if base else np.zeros((1, 2), np.int32)
+        self.spans = torch.from_numpy(np.ascontiguousarray(sp_all, dtype=np.int32)).to(dev)
+        self.pitch_off = torch.from_numpy(np.concatenate(poffs) if poffs else np.zeros(N_PITCH + 1, np.int64)).to(dev)
+        self.cols = torch.from_numpy(cols).to(dev)
+        self.fe = get_frontend(self.sr, self.n_mels, self.hop_length, dev)
+
+    def __len__(self):
+        return len(self.rec)
+
+    @property
+    def num_frames(self) -> np.ndarray:
+        """Frames of every item (the T of its mel and roll)."""
+        return self.t_keep
+
+    def get_batch(self, indices):
+        """collate_fn([self[i] for i in indices]) with mel (B, 1, n_mels, T) and roll (B, 88, T) on the device and lengths
+        (int64) on the host, as the loss reads them.  Window tables go up in one pinned copy each; nothing comes back."""
+        if _in_worker():
+            raise RuntimeError("MaestroDataset builds batches on the GPU and cannot run in a DataLoader worker process: "
+                               "use DeviceBatchLoader, or a DataLoader with num_workers=0")
+        idx = np.asarray(list(indices), dtype=np.int64)
+        B = len(idx)
+        if B == 0:
+            raise ValueError("get_batch: empty batch")
+        recs = self.rec[idx]
+        offs = self.store.offsets(recs.tolist())
+        n_rec = np.array(self.store.n, dtype=np.int64)
+        t_keep = self.t_keep[idx]
+        T_out = int(t_keep.max())
+        h64 = torch.empty((2, B), dtype=torch.int64, pin_memory=True)
+        h64[0] = torch.from_numpy(np.array([offs[int(r)] for r in recs], dtype=np.int64) + self.start[idx])
+        h64[1] = torch.from_numpy(self.col_off[idx])
+        h32 = torch.empty((5, B), dtype=torch.int32, pin_memory=True)
+        h32.copy_(torch.from_numpy(np.stack([self.win_len[idx], n_rec[recs] - self.start[idx], t_keep, recs, self.ncols[idx]])))
+        dev = self.device
+        with torch.cuda.device(dev):
+            d64, d32 = h64.to(dev, non_blocking=True), h32.to(dev, non_blocking=True)
+            mel = torch.empty(B, 1, self.n_mels, T_out, dtype=torch.float32, device=dev)
+            cmax = torch.empty(B, dtype=torch.float32, device=dev)
+            roll = torch.empty(B, N_PITCH, T_out, dtype=torch.float32, device=dev)
+            st = _lib.stream_ptr()
+            check(lib.mt_mel_db_windows_f32(ptr(self.fe.plan), self.fe.desc, ptr(self.store.buf), ptr(d64[0]), ptr(d32[0]), ptr(d32[1]), B,
+                                            int(self.win_len[idx].max()), T_out, ptr(d32[2]), ptr(mel), ptr(cmax), st), "mt_mel_db_windows_f32")
+            check(lib.mt_roll_windows(ptr(self.spans), ptr(self.pitch_off), ptr(self.cols), ptr(d32[3]), ptr(d64[1]), ptr(d32[4]), ptr(d32[2]),
+                                      B, T_out, ptr(roll), st), "mt_roll_windows")
+        return mel, roll, torch.from_numpy(t_keep.copy())
+
+    def __getitem__(self, idx):
+        if _in_worker():
+            raise RuntimeError("MaestroDataset items are built on the GPU and cannot be read in a DataLoader worker process "
+                               "(the reference's loaders use 8): use DeviceBatchLoader, or a DataLoader with num_workers=0")
+        mel, roll, _ = self.get_batch([idx])
+        return mel[0].cpu(), roll[0].cpu()
+
+
+class HybridMaestroDataset(Dataset):
+    """data/cached_dataset.py:91-141: the cache when its metadata's chunk_length and overlap equal the request, else MaestroDataset."""
+
+    def __init__(self, root_dir, cache_dir="cached_dataset", split="train", chunk_length=None, overlap=0.0, **kwargs):
+        from .data import CachedMaestroDataset
+        self.use_cache = False
+        try:
+            metadata_path = os.path.join(cache_dir, f"{split}_metadata.pkl")
+            if os.path.exists(metadata_path):
+                with open(metadata_path, "rb") as f:
+                    metadata = pickle.load(f)
+                if metadata.get("chunk_length") == chunk_length and metadata.get("overlap") == overlap:
+                    self.cached_dataset = CachedMaestroDataset(cache_dir, split)
+                    self.use_cache = True
+                    print("✓ Using cached dataset (fast mode!)")
+                    return
+        except Exception:
+            pass
+        self.dataset = MaestroDataset(root_dir=root_dir, split=split, chunk_length=chunk_length, overlap=overlap, **kwargs)
+        print("⚠ Using raw dataset (slow mode). Run preprocess_dataset.py for 10-50x speedup!")
+
+    def __len__(self):
+        return len(self.cached_dataset) if self.use_cache else len(self.dataset)
+
+    def __getitem__(self, idx):
+        return self.cached_dataset[idx] if self.use_cache else self.dataset[idx]
+
+    def get_batch(self, indices):
+        if self.use_cache:
+            from .data import collate_fn
+            return collate_fn([self.cached_dataset[i] for i in indices])
+        return self.dataset.get_batch(indices)
+
+
+class DeviceBatchLoader:
+    """DataLoader(dataset, batch_size, shuffle, sampler, drop_last, generator, collate_fn=collate_fn) for a dataset with
+    get_batch: the same index batches in the same order (the iterator draws the DataLoader's base seed first, so the global
+    RNG advances as it would), each built by one get_batch call in this process.  Works with DistributedSampler."""
+
+    def __init__(self, dataset, batch_size=1, shuffle=False, sampler=None, drop_last=False, generator=None):
+        if sampler is not None and shuffle:
+            raise ValueError("sampler option is mutually exclusive with shuffle")
+        self.dataset, self.batch_size, self.drop_last, self.generator = dataset, batch_size, drop_last, generator
+        if sampler is None:
+            sampler = RandomSampler(dataset, generator=generator) if shuffle else SequentialSampler(dataset)
+        self.sampler = sampler
+        self.batch_sampler = BatchSampler(sampler, batch_size, drop_last)
+
+    def __len__(self):
+        return len(self.batch_sampler)
+
+    def __iter__(self):
+        torch.empty((), dtype=torch.int64).random_(generator=self.generator)      # DataLoader's _base_seed draw
+        for indices in self.batch_sampler:
+            yield self.dataset.get_batch(indices)

@@ -11,8 +11,10 @@ over the samples.  On the device: the model runs once per sample (samples of equ
 sample's logits are what batch 1 gives), thresholding and the TP / FP / FN counts are one integer pass (mt_f1_sweep_counts);
 with `--tune_threshold` every candidate threshold of the reference's coarse-to-fine schedule is another counts pass over the SAME
 logits instead of another run of the model.  With more than one rank the samples are sharded contiguously (no data-path
-collective) and the per-sample values gathered by one small all-reduce.  Full-file evaluation (`--data_source full`), MIDI /
-plot outputs, background mode and the results browser are out of scope.
+collective) and the per-sample values gathered by one small all-reduce.  `--data_source full` (and `auto` without a cache)
+evaluates whole recordings under --root_dir, one sample per recording (MaestroDataset with chunk_length=None, featurised on
+the GPU); a recording longer than the inference recurrence takes (T * hidden_size < 2^24 frames) ends the run with an error
+naming it.  MIDI / plot outputs, background mode and the results browser are out of scope.
 """
 import argparse
 import json
@@ -34,6 +36,8 @@ def main():
     ap.add_argument("--batch_size", type=int, default=1, help="accepted for compatibility: samples of equal length are batched on the device")
     ap.add_argument("--data_source", type=str, default="auto", choices=["auto", "cache", "full"])
     ap.add_argument("--cache_dir", type=str, default="cached_dataset_mels320")
+    ap.add_argument("--root_dir", type=str, default="maestro-v3.0.0", help="Path to MAESTRO dataset (for full files, default: maestro-v3.0.0)")
+    ap.add_argument("--year", type=str, default=None, help="Year filter (full files only, e.g., 2017)")
     ap.add_argument("--n_mels", type=int, default=None, help="Number of mel bins (auto-detected from cache if not specified)")
     ap.add_argument("--model_type", type=str, default="cnn_rnn_large")
     ap.add_argument("--hidden_size", type=int, default=512)
@@ -53,11 +57,17 @@ def main():
         print(f"Error: Model checkpoint not found: {args.model}")
         return 1
     meta_path = os.path.join(args.cache_dir, f"{args.split}_metadata.pkl")
-    if args.data_source == "full" or not os.path.exists(meta_path):
-        print(f"Error: no cached split at {meta_path} (full-file evaluation is not part of this build: run scripts/preprocess_dataset.py first)")
+    full = args.data_source == "full" or (args.data_source == "auto" and not os.path.exists(meta_path))
+    if full and not os.path.exists(args.root_dir):
+        print(f"Error: neither cache ({meta_path}) nor dataset ({args.root_dir}) found")
+        return 1
+    if not full and not os.path.exists(meta_path):
+        print(f"Error: no cached split at {meta_path} (run scripts/preprocess_dataset.py, or use --data_source full --root_dir ...)")
         return 1
     n_mels = args.n_mels
-    if n_mels is None:                                  # evaluate.py:151-156: n_mels from the cache metadata
+    if full:
+        n_mels = n_mels or 320
+    elif n_mels is None:                                # evaluate.py:151-156: n_mels from the cache metadata
         with open(meta_path, "rb") as f:
             n_mels = pickle.load(f).get("n_mels", 320)
         say(f"Auto-detected n_mels={n_mels} from cache metadata")
@@ -82,12 +92,23 @@ def main():
     from music_transcription_amd import evaluate as E
 
     say(f"Using device: {dev}")
+    if full:                                           # recordings first: one past the recurrence's limit ends the run before the model loads
+        say(f"Loading full-file dataset from: {args.root_dir}")
+        ds = mta.MaestroDataset(args.root_dir, split=args.split, year=args.year, n_mels=n_mels, subset_size=args.subset, chunk_length=None,
+                                device=dev)
+        t_max = ((1 << 24) - 1) // args.hidden_size        # lstm.hip: the inference recurrence takes T * H < 2^24
+        for row, t in zip(ds.rows, ds.num_frames):
+            if int(t) > t_max:
+                print(f"Error: recording {row['audio_filename']} has T={int(t)} frames; the inference recurrence takes at most "
+                      f"{t_max} at hidden_size={args.hidden_size} (T * hidden_size < 2^24)")
+                return 1
     model = mta.TranscriptionModel(model_type=args.model_type, device=dev, n_mels=n_mels, hidden_size=args.hidden_size,
                                    num_layers=args.num_layers, dropout=args.dropout)
     model.load_state_dict(torch.load(args.model, map_location=dev))
     model.eval()
-    say(f"Loading cached dataset from: {args.cache_dir}")
-    ds = mta.CachedMaestroDataset(args.cache_dir, args.split)
+    if not full:
+        say(f"Loading cached dataset from: {args.cache_dir}")
+        ds = mta.CachedMaestroDataset(args.cache_dir, args.split)
     threshold = args.threshold
     if args.tune_threshold:
         threshold, tuned_f1 = E.tune_threshold(model, ds, dev, subset=args.subset, tune_range=tuple(args.tune_range), tune_step=args.tune_step,

@@ -4,6 +4,13 @@ over the GPUs of one node (the training half of the reference's scripts/train_cn
 
     python scripts/train_cnn.py --cached_dir cached_dataset --batch_size 16 --epochs 25
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 scripts/train_cnn.py ...
+    python scripts/train_cnn.py --root_dir maestro-v3.0.0 --chunk_length 30 --chunk_overlap 0.25    # no cache needed
+
+Data source: the cache under --cached_dir when it exists and its metadata's chunk_length / overlap equal the request (a
+chunk flag left out takes the cache's value, so invocations without them train from the cache as before); otherwise the
+recordings under --root_dir, decoded onto the GPU once and featurised per step (MaestroDataset + DeviceBatchLoader,
+music_transcription_amd/rawdata.py), where --subset_size counts recordings as in the reference.  Full-file training
+(no --chunk_length and no usable cache) is refused before the first step.
 
 One process per GPU.  Every step is the HIP training step (train-mode forward, backward, fused clip + Adam); with more
 than one rank each rank draws its own shard of the shuffled chunk indices (DistributedSampler) and the flat gradient
@@ -30,6 +37,10 @@ os.environ.setdefault("GPU_MAX_HW_QUEUES", "32")
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cached_dir", default="cached_dataset")
+    ap.add_argument("--root_dir", default="maestro-v3.0.0", help="MAESTRO root, used when the cache is missing or does not match")
+    ap.add_argument("--year", default=None, help="year filter of the raw recordings (e.g. 2017)")
+    ap.add_argument("--chunk_length", type=float, default=None, help="chunk length in seconds (default: the cache's)")
+    ap.add_argument("--chunk_overlap", type=float, default=None, help="overlap ratio between training chunks (default: the cache's, else 0.0)")
     ap.add_argument("--subset_size", type=int, default=None)
     ap.add_argument("--batch_size", type=int, default=8, help="per GPU")
     ap.add_argument("--epochs", type=int, default=25)
@@ -50,6 +61,23 @@ def main():
     ap.add_argument("--num_workers", type=int, default=4)
     ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args()
+
+    import pickle
+    meta_path = os.path.join(args.cached_dir, "train_metadata.pkl")
+    meta = None
+    if os.path.exists(meta_path):
+        with open(meta_path, "rb") as f:
+            meta = pickle.load(f)
+    if meta is not None:
+        chunk_length = args.chunk_length if args.chunk_length is not None else meta.get("chunk_length")
+        overlap = args.chunk_overlap if args.chunk_overlap is not None else meta.get("overlap")
+        use_cache = meta.get("chunk_length") == chunk_length and meta.get("overlap") == overlap
+    else:
+        chunk_length, overlap, use_cache = args.chunk_length, args.chunk_overlap or 0.0, False
+    if not use_cache and chunk_length is None:
+        print("Error: full-file training is not supported (the training recurrence takes chunk-length sequences): "
+              "pass --chunk_length (e.g. 30.0) or a matching --cached_dir", file=sys.stderr)
+        return 2
 
     import torch
     import torch.distributed as dist
@@ -72,15 +100,29 @@ def main():
     if args.model not in ("cnn_rnn", "cnn+rnn", "cnn_rnn_large", "large"):
         raise SystemExit(f"model={args.model}: the HIP training step exists for cnn_rnn and cnn_rnn_large")
     torch.manual_seed(args.seed)                       # same initial weights on every rank
-    train_ds = mta.CachedMaestroDataset(args.cached_dir, "train")
-    val_ds = mta.CachedMaestroDataset(args.cached_dir, "validation")
-    if args.subset_size:
-        train_ds = Subset(train_ds, range(min(args.subset_size, len(train_ds))))
-        val_ds = Subset(val_ds, range(min(max(1, args.subset_size // 4), len(val_ds))))
+    if use_cache:
+        if rank == 0:
+            print(f"Data source: cache {args.cached_dir} (chunk_length={chunk_length}, overlap={overlap})", flush=True)
+        train_ds = mta.CachedMaestroDataset(args.cached_dir, "train")
+        val_ds = mta.CachedMaestroDataset(args.cached_dir, "validation")
+        if args.subset_size:
+            train_ds = Subset(train_ds, range(min(args.subset_size, len(train_ds))))
+            val_ds = Subset(val_ds, range(min(max(1, args.subset_size // 4), len(val_ds))))
+    else:
+        if rank == 0:
+            why = "no cache" if meta is None else f"cache has chunk_length={meta.get('chunk_length')}, overlap={meta.get('overlap')}"
+            print(f"Data source: raw recordings {args.root_dir} on the GPU (chunk_length={chunk_length}, overlap={overlap}; {why})", flush=True)
+        kw_raw = dict(year=args.year, n_mels=args.n_mels, subset_size=args.subset_size, chunk_length=chunk_length, device=dev)
+        train_ds = mta.MaestroDataset(args.root_dir, split="train", overlap=overlap, **kw_raw)
+        val_ds = mta.MaestroDataset(args.root_dir, split="validation", overlap=0.0, **kw_raw)
     sampler = DistributedSampler(train_ds, num_replicas=world, rank=rank, shuffle=True, seed=args.seed, drop_last=True) if world > 1 else None
-    kw = dict(collate_fn=mta.collate_fn, num_workers=args.num_workers, pin_memory=True)
-    train_loader = DataLoader(train_ds, batch_size=args.batch_size, shuffle=sampler is None, sampler=sampler, drop_last=world > 1, **kw)
-    val_loader = DataLoader(val_ds, batch_size=args.batch_size, shuffle=False, **kw)
+    if use_cache:
+        kw = dict(collate_fn=mta.collate_fn, num_workers=args.num_workers, pin_memory=True)
+        train_loader = DataLoader(train_ds, batch_size=args.batch_size, shuffle=sampler is None, sampler=sampler, drop_last=world > 1, **kw)
+        val_loader = DataLoader(val_ds, batch_size=args.batch_size, shuffle=False, **kw)
+    else:                                              # batches are built on the GPU in this process: no workers
+        train_loader = mta.DeviceBatchLoader(train_ds, batch_size=args.batch_size, shuffle=sampler is None, sampler=sampler, drop_last=world > 1)
+        val_loader = mta.DeviceBatchLoader(val_ds, batch_size=args.batch_size, shuffle=False)
 
     model = mta.TranscriptionModel(model_type=args.model, n_mels=args.n_mels, hidden_size=args.hidden_size, num_layers=args.num_layers,
                                    dropout=args.dropout, device=str(dev), use_attention=args.use_attention,
@@ -129,7 +171,8 @@ def main():
             json.dump(history, f)
     if world > 1:
         dist.destroy_process_group()
+    return 0
 
 
 if __name__ == "__main__":
-    main()
+    sys.exit(main())
