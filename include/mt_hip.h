@@ -412,6 +412,21 @@ int    mt_f1_sweep_counts(const float* logits, const float* target, const long l
 int    mt_roll_to_notes(const float* src, int src_mode, float threshold, int NB, int P, int T, int* counts, int* starts, int* ends,
                         int capacity, mt_stream_t stream);
 
+/* Note-level evaluation (csrc/notes.hip, DESIGN.md "Note-level F1"): counts[b] = {n_ref, n_est, tp_onset, tp_onset_offset} (uint64)
+ * of mir_eval's precision_recall_f1_overlap on the 32 ms frame grid.  Estimated notes: with onset_logits == NULL the runs of
+ * (sigmoid(frame) > thr_frame) (the mt_roll_to_notes decoder); otherwise the onset-gated decoder -- a note opens at each rising edge
+ * of (sigmoid(onset) > thr_onset) and lasts while frame OR onset is active.  Reference notes: the runs of (ref_roll > 0).  Frames
+ * at or past lengths[b] (int64, device, NULL = all T) are inactive on both sides.  A match needs |d onset| <= 1 frame, and for
+ * tp_onset_offset also |d offset| <= 1 or 5 |d offset| <= reference length; each tp is a maximum matching.  frame_logits,
+ * onset_logits and ref_roll are [B][P][T] rows (onset_logits may be out[1] of the Large forward).  0 < thresholds < 1.  */
+int    mt_note_match_counts(const float* frame_logits, const float* onset_logits, float thr_frame, float thr_onset,
+                            const float* ref_roll, const long long* lengths, unsigned long long* counts, int B, int P, int T,
+                            mt_stream_t stream);
+/* The onset-gated decoder with mt_roll_to_notes' contract: the NB chunks of frame_logits / onset_logits [NB][P][T] are one
+ * recording of NB*T frames per pitch; counts[p], starts / ends in the reference's note order, capacity protocol unchanged. */
+int    mt_heads_to_notes(const float* frame_logits, const float* onset_logits, float thr_frame, float thr_onset, int NB, int P, int T,
+                         int* counts, int* starts, int* ends, int capacity, mt_stream_t stream);
+
 /* ------------------------------------------------------------------ optimizer step (training)
  * clip_grad_norm_(max_norm) + torch.optim.Adam with coupled L2 weight decay over flat f32 buffers
  * (train_transcriber.py:134-144, train_cnn.py:290); a NaN/Inf gradient norm skips the step (:137-142).

@@ -16,6 +16,7 @@ import torch
 
 from . import transcribe as tr
 from .frontend import get_frontend
+from .notes import heads_to_notes_device, note_match_counts, note_prf
 from .ops import framewise_f1, predict_from_logits
 
 SR, CH, HOP = 16000, 480000, 512
@@ -25,11 +26,16 @@ SR, CH, HOP = 16000, 480000, 512
 def transcribe_shard(model, rec_ids: Sequence[int], chunks_of: Callable[[int], torch.Tensor], *, n_mels: int, device,
                      batch: int = 128, streams: int = 3, threshold: float = 0.5, want_notes: bool = True,
                      reference_roll_of: Optional[Callable[[int, int], Optional[torch.Tensor]]] = None,
-                     midi_path_of: Optional[Callable[[int], Optional[str]]] = None, warm: bool = True) -> Dict[str, object]:
+                     midi_path_of: Optional[Callable[[int], Optional[str]]] = None, warm: bool = True, decoder: str = "frame",
+                     onset_threshold: float = 0.5, note_metrics: bool = False) -> Dict[str, object]:
     """rec_ids: the recordings of this rank; chunks_of(i) -> (n_i, 480000) float32 CUDA tensor (decode + resample + split for
     real audio: part of the measured time; a view of resident synthetic audio otherwise).  Returns {"wall_s", "chunks",
     "notes": {i: [(pitch, start, end)]}, "f1": {i: float}, "n_notes", "finite"}; wall_s covers slab assembly, every forward,
-    the note extraction and the F1 counts (one device synchronisation at the end)."""
+    the note extraction and the F1 counts (one device synchronisation at the end).  decoder="onset": notes from the onset-gated
+    decoder (notes.heads_to_notes_device; cnn_rnn_large with heads only).  note_metrics=True with reference rolls: "note_f1" =
+    {i: (onset F1, onset+offset F1)} against the runs of the reference roll, estimated notes from the same decoder."""
+    tr.check_decoder(decoder, model=model)
+    heads = decoder == "onset"
     dev = torch.device(device)
     net = model.model
     fe = get_frontend(SR, n_mels, HOP, str(dev))
@@ -50,12 +56,14 @@ def transcribe_shard(model, rec_ids: Sequence[int], chunks_of: Callable[[int], t
     pending: List[torch.Tensor] = []             # decoded chunks not yet in a slab
     n_pending, n_slabs = 0, 0
     # Logits are held PER SLAB and only until every recording with chunks in the slab has been turned into notes: a slab's entry
-    # is [logits (batch, 88, T), event behind its forward, recordings still to read it].
+    # is [logits (batch, 88, T), event behind its forward, recordings still to read it, onset logits or None].
     slabs: List[list] = []
     segs: Dict[int, List[tuple]] = {}            # recording -> [(slab, first row, rows)] in chunk order
     open_recs: List[tuple] = []                  # (recording, first chunk of the shard, n chunks): chunks not yet all in launched slabs
     order: List[int] = []                        # recordings whose chunks are all in launched slabs, oldest first
     res: Dict[str, object] = {"chunks": 0, "notes": {}, "f1": {}, "n_notes": 0, "finite": True}
+    if note_metrics:
+        res["note_f1"] = {}
     finite_flags: List[torch.Tensor] = []
     fs = SR / HOP
     pos, cut = 0, 0                              # chunks decoded / chunks in launched slabs
@@ -66,12 +74,16 @@ def transcribe_shard(model, rec_ids: Sequence[int], chunks_of: Callable[[int], t
         st.wait_stream(main)                     # the slab was assembled on the main stream
         with torch.cuda.stream(st):
             mel, cmax = fe(slab, clamp=False)
-            lg = net(mel, chunk_max_power=cmax)
+            if heads:
+                out = net(mel, chunk_max_power=cmax, return_all_heads=True)
+                lg, on = out["frame"], out["onset"]
+            else:
+                lg, on = net(mel, chunk_max_power=cmax), None
             slab.record_stream(st)
             ev = torch.cuda.Event()
             ev.record(st)
         k, n = n_slabs, int(slab.shape[0])
-        slabs.append([lg, ev, 0])
+        slabs.append([lg, ev, 0, on])
         # which recordings' chunks are rows [0, n) of this slab
         a = cut
         for rec in list(open_recs):
@@ -87,20 +99,24 @@ def transcribe_shard(model, rec_ids: Sequence[int], chunks_of: Callable[[int], t
         n_slabs += 1
 
     f1_dev: Dict[int, torch.Tensor] = {}
+    note_dev: Dict[int, torch.Tensor] = {}
 
     def finish(i):
         """Recording i's logits (its rows of the slabs it spans) -> notes / F1 on the device; the slabs are released behind it."""
         mine = segs.pop(i, [])
         if not mine:
             return
-        parts = []
+        parts, parts_on = [], []
         for k, a, n in mine:
             main.wait_event(slabs[k][1])
             parts.append(slabs[k][0][a:a + n])
+            if heads:
+                parts_on.append(slabs[k][3][a:a + n])
         lg = parts[0] if len(parts) == 1 else torch.cat(parts)
+        on = (parts_on[0] if len(parts_on) == 1 else torch.cat(parts_on)) if heads else None
         finite_flags.append(torch.isfinite(lg).all())
         if want_notes:
-            notes = tr.notes_from_logits_device(lg, threshold, fs)
+            notes = heads_to_notes_device(lg, on, threshold, onset_threshold, fs) if heads else tr.notes_from_logits_device(lg, threshold, fs)
             res["notes"][i] = notes
             res["n_notes"] += len(notes)
             path = midi_path_of(i) if midi_path_of else None
@@ -112,11 +128,15 @@ def transcribe_shard(model, rec_ids: Sequence[int], chunks_of: Callable[[int], t
                 roll = predict_from_logits(lg, threshold).permute(1, 0, 2).reshape(88, -1)
                 L = min(int(ref.shape[1]), int(roll.shape[1]))
                 f1_dev[i] = framewise_f1(roll[None, :, :L].contiguous(), ref[None, :, :L].contiguous().float())
-        del parts, lg
+                if note_metrics:
+                    rows = lambda x: x.permute(1, 0, 2).reshape(88, -1)[:, :L].contiguous()
+                    note_dev[i] = note_match_counts(rows(lg), ref[:, :L].contiguous().float(), threshold,
+                                                    rows(on) if heads else None, onset_threshold)
+        del parts, parts_on, lg, on
         for k, _, _ in mine:
             slabs[k][2] -= 1
             if slabs[k][2] == 0:
-                slabs[k][0] = None               # (the caching allocator reuses the block for a later slab's logits)
+                slabs[k][0] = slabs[k][3] = None               # (the caching allocator reuses the block for a later slab's logits)
 
     def drain(keep_in_flight: int):
         """Finish the recordings whose last slab has at least `keep_in_flight` younger slabs queued behind it (the host blocks on
@@ -151,6 +171,8 @@ def transcribe_shard(model, rec_ids: Sequence[int], chunks_of: Callable[[int], t
         main.wait_stream(st)
     res["chunks"] = pos
     res["f1"] = {i: float(v[0]) for i, v in f1_dev.items()}
+    if note_metrics:
+        res["note_f1"] = {i: (m["onset"][2], m["onset_offset"][2]) for i, v in note_dev.items() for m in note_prf(v)}
     if finite_flags:
         res["finite"] = bool(torch.stack(finite_flags).all())
     torch.cuda.synchronize(dev)

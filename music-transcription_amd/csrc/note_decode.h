@@ -1,0 +1,39 @@
+// Note decoding rules shared by the kernels of notes.hip (one wave64 walks one pitch row in 64-frame windows).
+//
+// Activity is the expression of mt_predict_threshold / note_active in post.hip, so ties break the same way everywhere.
+// Onset-gated decoder (the Onsets-and-Frames rule): a = frame-active OR onset-active; a note opens at every rising edge of
+// the onset mask, stays open while a holds, and closes at the first frame where a drops or the next onset edge starts a new
+// note (a re-struck key).  With onset := frame this is the plain run-length decoder of mt_roll_to_notes.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace mt {
+
+__device__ __forceinline__ bool logit_active(float x, float thr) { return 1.0f / (1.0f + expf(-x)) > thr; }
+
+// One 64-frame window of the decoder.  Lane l holds frame g0 + l; o / a are that frame's onset-active and (frame OR onset)
+// activity.  Carries in: o_prev = onset activity of frame g0 - 1, open_prev = a note is open after frame g0 - 1; both are
+// updated for the next window.  Out: starts (bit l = a note opens at g0 + l) and closes (bit l = the open note ends there).
+struct WindowEvents {
+    unsigned long long starts, closes;
+};
+
+__device__ __forceinline__ WindowEvents decode_window(bool o, bool a, int lane, unsigned long long& o_prev, unsigned long long& open_prev) {
+    const unsigned long long om = __ballot(o), am = __ballot(a);
+    const unsigned long long st = om & ~((om << 1) | o_prev);
+    // open at lane l  <=>  a holds on every frame from the last start of this a-run up to l (or from before the window)
+    const unsigned long long upto = (2ull << lane) - 1ull;                 // bits 0..lane (all ones at lane 63)
+    const unsigned long long gaps = ~am & upto;
+    const int z = gaps ? 63 - __clzll((long long)gaps) : -1;              // last inactive frame at or below l
+    const unsigned long long since = z >= 0 ? ~((2ull << z) - 1ull) : ~0ull;
+    const bool open = a && ((st & upto & since) != 0ull || (z < 0 && open_prev));
+    const unsigned long long opm = __ballot(open);
+    WindowEvents ev;
+    ev.starts = st;
+    ev.closes = ((opm << 1) | open_prev) & (~am | st);
+    o_prev = om >> 63;
+    open_prev = opm >> 63;
+    return ev;
+}
+
+}  // namespace mt

@@ -6,6 +6,9 @@
   * `tune_threshold` = run_threshold_tuning (evaluate.py:556-618) with the same coarse-to-fine schedule, but the
     model runs ONCE: logits stay on the device and every candidate threshold is an integer-count pass
     (mt_f1_sweep_counts, up to 16 thresholds per pass).
+  * `note_metrics_dataset` = note-level precision / recall / F1 (mir_eval's onset and onset+offset criteria on the frame grid)
+    against the runs of the label roll, for the frame decoder or the onset-gated one; decoding and matching are one counting
+    pass over the logits (notes.note_match_counts), samples of any length batched through `lengths`.
   * recordings / chunks shard over ranks with no data-path collective (parallel.py); per-sample F1 values are
     gathered with one small all-reduce.
 """
@@ -27,9 +30,21 @@ def _f1(tp, fp, fn) -> float:
     return 0.0 if d == 0 else 2.0 * tp / d
 
 
+def require_heads(model, what: str) -> None:
+    """Raise unless `model` is a CNNRNNModelLarge with its onset / offset heads (what the onset-gated decoder reads)."""
+    from .model import CNNRNNModelLarge
+    net = getattr(model, "model", model)
+    if not isinstance(net, CNNRNNModelLarge) or not net.use_onset_offset_heads:
+        raise ValueError(f"{what} needs the onset head: a cnn_rnn_large model with use_onset_offset_heads=True "
+                         f"(got {type(net).__name__}{'' if not isinstance(net, CNNRNNModelLarge) else ' without heads'})")
+
+
 @torch.no_grad()
-def collect_logits(model, dataset, indices: Sequence[int], device="cuda", max_batch: int = 128):
-    """Forward every sample once; returns [(index, logits (88, T) on device, roll (88, T) on device)]."""
+def collect_logits(model, dataset, indices: Sequence[int], device="cuda", max_batch: int = 128, all_heads: bool = False):
+    """Forward every sample once; returns [(index, logits (88, T) on device, roll (88, T) on device)], with all_heads=True
+    [(index, frame logits, roll, onset logits)]."""
+    if all_heads:
+        require_heads(model, "collect_logits(all_heads=True)")
     by_len = defaultdict(list)
     for i in indices:
         mel, roll = dataset[i]
@@ -39,9 +54,14 @@ def collect_logits(model, dataset, indices: Sequence[int], device="cuda", max_ba
         for s in range(0, len(items), max_batch):
             grp = items[s:s + max_batch]
             mel = torch.stack([m for _, m, _ in grp]).to(device)                    # (b, 1, n_mels, T): equal T, no padding
-            logits = model(mel)
-            for (i, _, roll), lg in zip(grp, logits):
-                out.append((i, lg.contiguous(), roll.to(device).float().contiguous()))
+            if all_heads:
+                heads = model(mel, return_all_heads=True)
+                for (i, _, roll), lg, on in zip(grp, heads["frame"], heads["onset"]):
+                    out.append((i, lg.contiguous(), roll.to(device).float().contiguous(), on.contiguous()))
+            else:
+                logits = model(mel)
+                for (i, _, roll), lg in zip(grp, logits):
+                    out.append((i, lg.contiguous(), roll.to(device).float().contiguous()))
     net = getattr(model, "model", model)
     if hasattr(net, "raise_on_handoff_timeout"):
         net.raise_on_handoff_timeout(sync=True)        # a timed-out recurrence would have left NaN logits: fail loudly, once per pass
@@ -82,6 +102,38 @@ def evaluate_dataset(model, dataset, threshold: float = 0.5, device="cuda", subs
     vals = f1_at_thresholds(lr, [threshold])[:, 0] if lr else np.zeros(0)
     allv = gather_values(mine, vals.tolist(), n)
     return (float(np.mean(allv)) if allv else 0.0), allv
+
+
+NOTE_METRIC_KEYS = tuple(f"{c}_{m}" for c in ("onset", "onset_offset") for m in ("precision", "recall", "f1"))
+
+
+def note_metrics_dataset(model, dataset, threshold: float = 0.5, onset_threshold: Optional[float] = None, device="cuda",
+                         subset: Optional[int] = None, max_batch: int = 128, rank: int = 0, world: int = 1) -> dict:
+    """Note-level metrics of every sample, identical on every rank: {"mean": {key: value}, "per_sample": {key: [values]}} over
+    NOTE_METRIC_KEYS (onset / onset_offset x precision / recall / f1).  onset_threshold=None: notes are the runs of
+    sigmoid(frame) > threshold (the frame decoder); otherwise the onset-gated decoder with the onset head at onset_threshold.
+    Reference notes are the runs of the dataset's label roll.  Unweighted means over samples, as evaluate_dataset."""
+    from .notes import note_match_counts, note_prf
+    n = len(dataset) if subset is None else min(subset, len(dataset))
+    mine = list(shard_range(n, rank, world))
+    onset = onset_threshold is not None
+    lr = collect_logits(model, dataset, mine, device, all_heads=onset)
+    vals = {k: [] for k in NOTE_METRIC_KEYS}
+    for s in range(0, len(lr), max_batch):            # one counts pass per group; unequal lengths padded and masked by `lengths`
+        grp = lr[s:s + max_batch]
+        lengths = [int(x[1].shape[-1]) for x in grp]
+        T = max(lengths)
+        pad = lambda t: torch.nn.functional.pad(t, (0, T - t.shape[-1]))
+        frame = torch.stack([pad(x[1]) for x in grp])
+        roll = torch.stack([pad(x[2]) for x in grp])
+        on = torch.stack([pad(x[3]) for x in grp]) if onset else None
+        counts = note_match_counts(frame, roll, threshold, on, onset_threshold if onset else 0.5, lengths)
+        for m in note_prf(counts):
+            for c in ("onset", "onset_offset"):
+                for k, v in zip(("precision", "recall", "f1"), m[c]):
+                    vals[f"{c}_{k}"].append(v)
+    per = {k: gather_values(mine, v, n) for k, v in vals.items()}
+    return {"mean": {k: (float(np.mean(v)) if v else 0.0) for k, v in per.items()}, "per_sample": per}
 
 
 def tune_threshold(model, dataset, device="cuda", subset: Optional[int] = None, tune_range=(0.05, 0.95), tune_step=0.1,

@@ -43,10 +43,19 @@ def make_optimizer(model, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-
     return opt
 
 
+def _forward(model, mel, all_heads: bool):
+    """all_heads: the frame / onset / offset dict of CNNRNNModelLarge, whose loss is 0.5 frame + 0.25 onset + 0.25 offset;
+    otherwise the frame logits alone (the reference's training loss)."""
+    return model(mel, return_all_heads=True) if all_heads else model(mel)
+
+
 def train_one_epoch(model, dataloader: Iterable, optimizer: FusedAdamClip, device, max_grad_norm: float = 1.0,
-                    log=None) -> Tuple[float, List[float]]:
+                    log=None, all_heads: bool = False) -> Tuple[float, List[float]]:
     if not isinstance(optimizer, FusedAdamClip):
         raise TypeError("train_one_epoch drives the fused HIP optimizer: build it with make_optimizer(model, ...)")
+    if all_heads:
+        from .evaluate import require_heads
+        require_heads(model, "train_one_epoch(all_heads=True)")
     model.train()
     optimizer.max_norm = float(max_grad_norm)
     total, step_losses, nan_count, n_batches = 0.0, [], 0, 0
@@ -64,7 +73,7 @@ def train_one_epoch(model, dataloader: Iterable, optimizer: FusedAdamClip, devic
         optimizer.zero_grad()
         mel, roll, lengths = batch
         mel, roll = mel.to(device, non_blocking=True), roll.to(device, non_blocking=True)
-        logits = model(mel)
+        logits = _forward(model, mel, all_heads)
         loss = model.compute_loss(logits, roll, lengths)
         step_loss = float(loss.item())
         bad = math.isnan(step_loss) or math.isinf(step_loss)
@@ -99,12 +108,15 @@ def train_one_epoch(model, dataloader: Iterable, optimizer: FusedAdamClip, devic
 
 
 @torch.no_grad()
-def evaluate(model, dataloader: Iterable, device) -> float:
-    """Mean validation loss (train_transcriber.py:161-191)."""
+def evaluate(model, dataloader: Iterable, device, all_heads: bool = False) -> float:
+    """Mean validation loss (train_transcriber.py:161-191); all_heads as in train_one_epoch."""
+    if all_heads:
+        from .evaluate import require_heads
+        require_heads(model, "evaluate(all_heads=True)")
     model.eval()
     total, n = 0.0, 0
     for mel, roll, lengths in dataloader:
-        logits = model(mel.to(device, non_blocking=True))
+        logits = _forward(model, mel.to(device, non_blocking=True), all_heads)
         total += float(model.compute_loss(logits, roll.to(device, non_blocking=True), lengths).item())
         n += 1
     return total / max(n, 1)

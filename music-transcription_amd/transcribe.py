@@ -263,20 +263,47 @@ def notes_from_logits_device(logits: torch.Tensor, threshold: float = THRESHOLD,
     return [(int(pp), float(a) / fs, float(b) / fs) for pp, a, b in zip(pitches, s, e) if b > a]
 
 
+DECODERS = ("frame", "onset")
+
+
+def check_decoder(decoder: str, model_type: str = None, model=None) -> None:
+    """The onset decoder reads the onset head: refuse it for a model without one, before any GPU work."""
+    if decoder not in DECODERS:
+        raise ValueError(f"decoder must be one of {DECODERS}, got {decoder!r}")
+    if decoder != "onset":
+        return
+    if model is not None:
+        from .evaluate import require_heads
+        require_heads(model, "decoder='onset'")
+    elif model_type is not None and model_type.lower() not in ("cnn_rnn_large", "large"):
+        raise ValueError(f"decoder='onset' needs the onset head of cnn_rnn_large (model type {model_type!r} has none)")
+
+
 @torch.no_grad()
 def transcribe_chunks_to_notes(model: "TranscriptionModel", chunks, threshold: float = THRESHOLD, batch: int = 128, n_mels: int = N_MELS,
-                               device: str = "cuda") -> List[Tuple[int, float, float]]:
-    """(n, 480000) waveform chunks -> notes; mel, forward, threshold, concatenation and run-length all on the GPU."""
+                               device: str = "cuda", decoder: str = "frame", onset_threshold: float = THRESHOLD) -> List[Tuple[int, float, float]]:
+    """(n, 480000) waveform chunks -> notes; mel, forward, threshold, concatenation and run-length all on the GPU.  decoder="onset":
+    notes start at rising edges of the onset head and last while frame or onset is active (notes.heads_to_notes_device)."""
+    check_decoder(decoder, model=model)
     fe = get_frontend(SR, n_mels, HOP_LENGTH, device)
     if not torch.is_tensor(chunks):
         chunks = torch.from_numpy(np.ascontiguousarray(chunks, dtype=np.float32))
     chunks = chunks.to(device)
     net = model.model
-    outs = []
+    outs, onsets = [], []
     for i in range(0, len(chunks), batch):
         mel, cmax = fe(chunks[i:i + batch].contiguous(), clamp=False)
-        outs.append(net(mel, chunk_max_power=cmax))
-    notes = notes_from_logits_device(torch.cat(outs), threshold, SR / HOP_LENGTH)
+        if decoder == "onset":
+            heads = net(mel, chunk_max_power=cmax, return_all_heads=True)
+            outs.append(heads["frame"])
+            onsets.append(heads["onset"])
+        else:
+            outs.append(net(mel, chunk_max_power=cmax))
+    if decoder == "onset":
+        from .notes import heads_to_notes_device
+        notes = heads_to_notes_device(torch.cat(outs), torch.cat(onsets), threshold, onset_threshold, SR / HOP_LENGTH)
+    else:
+        notes = notes_from_logits_device(torch.cat(outs), threshold, SR / HOP_LENGTH)
     net.raise_on_handoff_timeout(sync=False)               # (the copies above synchronised with every forward)
     return notes
 
@@ -343,7 +370,9 @@ def transcribe_chunks(model: TranscriptionModel, chunks, threshold: float = THRE
     return np.concatenate(rolls, axis=1)
 
 
-def transcribe_audio(audio_path: str, model_path: str, output_path=None, device=None, threshold: float = THRESHOLD, **model_kw):
+def transcribe_audio(audio_path: str, model_path: str, output_path=None, device=None, threshold: float = THRESHOLD, decoder: str = "frame",
+                     onset_threshold: float = THRESHOLD, **model_kw):
+    check_decoder(decoder, model_type=model_kw.get("model_type", MODEL_TYPE))
     device = device or ("cuda" if torch.cuda.is_available() else "cpu")
     if device != "cuda":
         raise RuntimeError("music_transcription_amd runs on the GPU only (-d cuda)")
@@ -352,7 +381,8 @@ def transcribe_audio(audio_path: str, model_path: str, output_path=None, device=
     y = load_audio_device(audio_path, SR, device)       # decode + resample on the GPU; the waveform never visits the host
     chunks, duration = split_into_chunks_device(y)
     print(f"Audio duration: {duration:.2f} seconds; {len(chunks)} chunks of {CHUNK_LENGTH}s")
-    notes = transcribe_chunks_to_notes(model, chunks, threshold, n_mels=model_kw.get("n_mels", N_MELS), device=device)
+    notes = transcribe_chunks_to_notes(model, chunks, threshold, n_mels=model_kw.get("n_mels", N_MELS), device=device, decoder=decoder,
+                                       onset_threshold=onset_threshold)
     if output_path is None:
         p = Path(audio_path)
         output_path = p.parent / f"{p.stem}_transcription.mid"

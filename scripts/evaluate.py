@@ -45,6 +45,14 @@ def main():
     ap.add_argument("--dropout", type=float, default=0.2)
     ap.add_argument("--out_dir", type=str, default="eval_outputs", help="results.json is written here unless --headless")
     ap.add_argument("--headless", action="store_true", help="Headless mode: only print EVAL_MEAN_F1=<value>")
+    ap.add_argument("--note_metrics", action="store_true",
+                    help="also report note-level precision / recall / F1 (onset within 50 ms; onset + offset within max(50 ms, 20%% of the "
+                         "note), mir_eval's criteria on the 32 ms frame grid) against the runs of the label roll; headless prints "
+                         "EVAL_NOTE_ONSET_F1= and EVAL_NOTE_ONSET_OFFSET_F1= after EVAL_MEAN_F1=")
+    ap.add_argument("--decoder", choices=["frame", "onset"], default="frame",
+                    help="note decoder for --note_metrics: frame = runs of active frames (default); onset = notes start at rising edges "
+                         "of the onset head (cnn_rnn_large trained with --train_all_heads; untrained heads make it meaningless)")
+    ap.add_argument("--onset_threshold", type=float, default=0.5, help="threshold of the onset head for --decoder onset (default: 0.5)")
     ap.add_argument("--tune_threshold", action="store_true")
     ap.add_argument("--tune_rounds", type=int, default=6)
     ap.add_argument("--tune_range", type=float, nargs=2, default=[0.05, 0.95])
@@ -55,6 +63,9 @@ def main():
 
     if not os.path.exists(args.model):
         print(f"Error: Model checkpoint not found: {args.model}")
+        return 1
+    if args.note_metrics and args.decoder == "onset" and args.model_type not in ("cnn_rnn_large", "large"):
+        print(f"Error: --decoder onset needs the onset head of cnn_rnn_large (model_type {args.model_type} has none)")
         return 1
     meta_path = os.path.join(args.cache_dir, f"{args.split}_metadata.pkl")
     full = args.data_source == "full" or (args.data_source == "auto" and not os.path.exists(meta_path))
@@ -116,15 +127,28 @@ def main():
                                                log=say if rank == 0 else None)
         say(f"Best threshold: {threshold:.4f} (mean F1 {tuned_f1:.6f})")
     mean_f1, per_sample = E.evaluate_dataset(model, ds, threshold, dev, subset=args.subset, rank=rank, world=world)
+    notes = None
+    if args.note_metrics:
+        notes = E.note_metrics_dataset(model, ds, threshold, args.onset_threshold if args.decoder == "onset" else None, dev,
+                                       subset=args.subset, rank=rank, world=world)
     if rank == 0:
         if args.headless:
             print(f"EVAL_MEAN_F1={mean_f1:.6f}")
+            if notes is not None:
+                print(f"EVAL_NOTE_ONSET_F1={notes['mean']['onset_f1']:.6f}")
+                print(f"EVAL_NOTE_ONSET_OFFSET_F1={notes['mean']['onset_offset_f1']:.6f}")
         else:
             print(f"\nMean framewise F1 over {len(per_sample)} samples at threshold {threshold:.4f}: {mean_f1:.6f}")
+            results = {"mean_f1": mean_f1, "threshold": threshold, "per_sample_f1": per_sample, "split": args.split,
+                       "num_samples": len(per_sample), "model": args.model, "model_type": args.model_type}
+            if notes is not None:
+                m = notes["mean"]
+                print(f"Mean note F1 ({args.decoder} decoder): onset {m['onset_f1']:.6f}, onset+offset {m['onset_offset_f1']:.6f}")
+                results["note_metrics"] = {"decoder": args.decoder, "onset_threshold": args.onset_threshold if args.decoder == "onset" else None,
+                                           **notes}
             os.makedirs(args.out_dir, exist_ok=True)
             with open(os.path.join(args.out_dir, "results.json"), "w") as f:
-                json.dump({"mean_f1": mean_f1, "threshold": threshold, "per_sample_f1": per_sample, "split": args.split,
-                           "num_samples": len(per_sample), "model": args.model, "model_type": args.model_type}, f)
+                json.dump(results, f)
             print(f"Results written to {os.path.join(args.out_dir, 'results.json')}")
     if world > 1:
         dist.destroy_process_group()

@@ -57,10 +57,18 @@ def main():
     ap.add_argument("--no_attention", action="store_false", dest="use_attention")
     ap.add_argument("--use_onset_offset_heads", action="store_true", default=True, help="onset / offset heads (cnn_rnn_large only)")
     ap.add_argument("--no_onset_offset_heads", action="store_false", dest="use_onset_offset_heads")
+    ap.add_argument("--train_all_heads", action="store_true",
+                    help="train the onset and offset heads too: loss 0.5 frame + 0.25 onset + 0.25 offset (cnn_rnn_large with heads "
+                         "only).  Default off = the reference's frame-only loss, which leaves the onset head untrained, so "
+                         "--decoder onset is meaningless on such a checkpoint")
     ap.add_argument("--run_dir", default="outputs/train_cnn")
     ap.add_argument("--num_workers", type=int, default=4)
     ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args()
+    if args.train_all_heads and (args.model not in ("cnn_rnn_large", "large") or not args.use_onset_offset_heads):
+        print("Error: --train_all_heads needs --model cnn_rnn_large with its onset / offset heads (not --no_onset_offset_heads)",
+              file=sys.stderr)
+        return 2
 
     import pickle
     meta_path = os.path.join(args.cached_dir, "train_metadata.pkl")
@@ -148,10 +156,10 @@ def main():
         if sampler is not None:
             sampler.set_epoch(epoch)
         t0 = time.perf_counter()
-        train_loss, step_losses = T.train_one_epoch(model, train_loader, opt, dev, max_grad_norm=1.0)
+        train_loss, step_losses = T.train_one_epoch(model, train_loader, opt, dev, max_grad_norm=1.0, all_heads=args.train_all_heads)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
-        val_loss = T.evaluate(model, val_loader, dev) if rank == 0 else float("nan")
+        val_loss = T.evaluate(model, val_loader, dev, all_heads=args.train_all_heads) if rank == 0 else float("nan")
         if rank == 0:
             rec = {"epoch": epoch, "train_loss": train_loss, "val_loss": val_loss, "steps": len(step_losses),
                    "chunks_per_s": round(len(step_losses) * args.batch_size * world / max(dt, 1e-9), 2)}

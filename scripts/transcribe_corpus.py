@@ -34,6 +34,13 @@ def main():
     ap.add_argument("--hidden-size", type=int, default=512)
     ap.add_argument("--num-layers", type=int, default=3)
     ap.add_argument("--threshold", type=float, default=0.5)
+    ap.add_argument("--decoder", choices=["frame", "onset"], default="frame",
+                    help="frame: notes are runs of active frames (default); onset: onset-gated decoder on the onset head (cnn_rnn_large "
+                         "trained with --train_all_heads)")
+    ap.add_argument("--onset-threshold", type=float, default=0.5, help="threshold of the onset head for --decoder onset")
+    ap.add_argument("--note-metrics", action="store_true",
+                    help="also score notes against the runs of the reference roll (onset / onset+offset F1, mir_eval's criteria on the "
+                         "32 ms grid): adds mean_note_onset_f1 / mean_note_onset_offset_f1 to the JSON line")
     ap.add_argument("--batch", type=int, default=128,
                     help="chunks per forward (the recurrence interleaves up to four batch groups of 32 in one persistent launch)")
     ap.add_argument("--streams", type=int, default=4, help="forwards in flight (at most 3 for cnn_rnn_large: two recurrence launches each)")
@@ -58,6 +65,7 @@ def main():
 
     import music_transcription_amd as mta
     from music_transcription_amd import transcribe as tr
+    tr.check_decoder(args.decoder, model_type=args.model_type)
     from music_transcription_amd.parallel import lpt_assign, gather_values
     SR, CH = 16000, 480000
 
@@ -107,7 +115,8 @@ def main():
         dist.barrier()
     t0 = time.perf_counter()
     res = corpus.transcribe_shard(model, mine, chunks_of, n_mels=args.n_mels, device=dev, batch=args.batch, streams=NS,
-                                  threshold=args.threshold, want_notes=True, reference_roll_of=reference_roll_of, midi_path_of=midi_path_of)
+                                  threshold=args.threshold, want_notes=True, reference_roll_of=reference_roll_of, midi_path_of=midi_path_of,
+                                  decoder=args.decoder, onset_threshold=args.onset_threshold, note_metrics=args.note_metrics)
     if args.dump_rolls:                     # (debug / tests: the rolls are rebuilt from the notes -- they never left the GPU as rolls)
         os.makedirs(args.dump_rolls, exist_ok=True)
         fs = SR / 512
@@ -126,11 +135,16 @@ def main():
     n_notes = gather_values([rank], [float(res["n_notes"])], world)
     allf1 = gather_values(mine, f1s, len(names))
     tot_chunks = gather_values([rank], [float(n_chunks)], world)
+    extra = {}
+    if args.note_metrics:
+        nf = res["note_f1"]
+        for k, key in enumerate(("mean_note_onset_f1", "mean_note_onset_offset_f1")):
+            extra[key] = float(np.mean(gather_values(mine, [nf[i][k] if i in nf else 0.0 for i in mine], len(names))))
     if rank == 0:
-        print(json.dumps({"workload": "offline corpus transcription (BASELINE.json configs[4])", "recordings": len(names),
+        print(json.dumps({**{"workload": "offline corpus transcription (BASELINE.json configs[4])", "recordings": len(names),
                           "audio_hours": round(sum(durations) / 3600.0, 2) if not args.wav_dir else None, "n_gpus": world,
                           "chunks": int(sum(tot_chunks)), "wall_s": round(wall, 3), "chunks_per_s": round(sum(tot_chunks) / wall, 1),
-                          "notes": int(sum(n_notes)), "mean_f1": float(np.mean(allf1)), "per_recording_f1": [float(v) for v in allf1], "model": args.model_type, "data": "wav" if args.wav_dir else "synthetic"}))
+                          "notes": int(sum(n_notes)), "mean_f1": float(np.mean(allf1)), "per_recording_f1": [float(v) for v in allf1], "model": args.model_type, "data": "wav" if args.wav_dir else "synthetic"}, **extra}))
     if world > 1:
         dist.destroy_process_group()
 

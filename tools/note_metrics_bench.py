@@ -1,0 +1,103 @@
+"""Device time of mt_note_match_counts (DESIGN.md "Note-level F1"), frame and onset-gated decoders, on two shapes:
+
+  * chunks:     a batch of 128 chunks x 88 pitches x 938 frames (one forward's worth of 30 s chunks);
+  * recordings: a padded batch of 8 whole recordings of 10-25 minutes (T up to ~47 000 frames), masked by `lengths`.
+
+Inputs are seeded synthetic logits and rolls with note-like runs (~6 % of the cells active).  Each case is warmed up, then
+timed with device events over --iters launches; GB/s counts the bytes the pass must read: the valid frames of the frame
+logits, the reference roll and (onset decoder) the onset logits.
+
+    python tools/note_metrics_bench.py [--iters 50] [--out note_metrics.json]
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+FS = 16000 / 512
+
+
+def runs(gen, shape, p_on, p_off, device):
+    """Boolean rows of runs (a two-state chain along the last axis), built on the device."""
+    import torch
+    state = torch.rand(shape[:-1], device=device, generator=gen) < p_on / (p_on + p_off)
+    u = torch.rand(shape, device=device, generator=gen)
+    out = torch.empty(shape, dtype=torch.bool, device=device)
+    for t in range(shape[-1]):
+        state = torch.where(state, u[..., t] >= p_off, u[..., t] < p_on)
+        out[..., t] = state
+    return out
+
+
+def make_case(B, P, T, lengths, seed, device):
+    import torch
+    gen = torch.Generator(device=device).manual_seed(seed)
+    ref = runs(gen, (B, P, T), 0.02, 0.3, device)
+    flip = torch.rand((B, P, T), device=device, generator=gen) < 0.01
+    est = ref ^ flip
+    mag = torch.rand((B, P, T), device=device, generator=gen) * 4.0 + 0.01
+    frame = torch.where(est, mag, -mag)
+    onset = torch.where(est & ~torch.nn.functional.pad(est, (1, 0))[..., :-1], mag, -mag)
+    if lengths is not None:
+        for b, n in enumerate(lengths):
+            ref[b, :, n:] = False
+    return frame.contiguous(), onset.contiguous(), ref.float().contiguous()
+
+
+def time_case(name, frame, onset, ref, lengths, iters):
+    import torch
+    from music_transcription_amd.notes import note_match_counts
+    B, P, T = frame.shape
+    valid = B * T if lengths is None else int(sum(lengths))
+    out = {"case": name, "B": B, "P": P, "T": T, "valid_frames": valid}
+    for dec, on in (("frame", None), ("onset", onset)):
+        for _ in range(3):
+            c = note_match_counts(frame, ref, 0.5, on, 0.5, lengths)
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(iters):
+            note_match_counts(frame, ref, 0.5, on, 0.5, lengths)
+        e1.record()
+        torch.cuda.synchronize()
+        ms = e0.elapsed_time(e1) / iters
+        nbytes = valid * P * 4 * (3 if on is not None else 2)
+        cs = c.sum(0).tolist()
+        out[dec] = {"ms": round(ms, 4), "read_MB": round(nbytes / 1e6, 2), "GB_per_s": round(nbytes / (ms * 1e-3) / 1e9, 1),
+                    "n_ref": cs[0], "n_est": cs[1], "tp_onset": cs[2], "tp_onset_offset": cs[3]}
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    import torch
+    import music_transcription_amd  # noqa: F401  (loads libmt_hip.so)
+    if not torch.cuda.is_available():
+        raise SystemExit("note_metrics_bench measures on the GPU only")
+    dev = "cuda"
+    res = []
+    frame, onset, ref = make_case(128, 88, 938, None, 1, dev)
+    res.append(time_case("chunks 128 x 88 x 938", frame, onset, ref, None, args.iters))
+    minutes = np.random.default_rng(2).uniform(10.0, 25.0, size=8)
+    minutes[0] = 25.0
+    lengths = [int(m * 60 * FS) for m in minutes]
+    frame, onset, ref = make_case(8, 88, max(lengths), lengths, 3, dev)
+    res.append(time_case("recordings 8 x 10-25 min, padded", frame, onset, ref, lengths, args.iters))
+    res[-1]["lengths"] = lengths
+    for r in res:
+        print(json.dumps(r))
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
