@@ -133,6 +133,14 @@ int    mt_roll_windows(const int* spans, const long long* pitch_off, const int* 
                        const long long* win_cols, const int* win_ncols, const int* t_keep, int B, int T_out,
                        float* roll, mt_stream_t stream);
 
+/* Overlapping windows on one frame grid (csrc/stitch.hip, windows.py): src[Bw][P][Tw] holds the rows of Bw windows, which may
+ * come from several recordings.  For each window b, local frames t in [keep_lo[b], keep_hi[b]) of every row p are copied to
+ * dst[dst_row[b]][p][dst_frame0[b] + t] of dst[R][P][T_dst]; nothing else in dst is written (the caller pre-fills padding).
+ * All tables are device pointers; their contents are the caller's contract (0 <= keep_lo <= keep_hi <= Tw, destination
+ * frames < T_dst, rows < R).  64-bit indexing.                                                                          */
+int    mt_stitch_windows(const float* src, int Bw, int P, int Tw, const int* dst_row, const long long* dst_frame0,
+                         const int* keep_lo, const int* keep_hi, float* dst, int R, long long T_dst, mt_stream_t stream);
+
 /* ------------------------------------------------------------------ CNN blocks
  * CNNRNNModel.cnn (cnn_rnn_model.py:29-39; Large: conv1, :178-183), eval mode; BatchNorm
  * running statistics are folded into (w, bias) by the host at load_state_dict time.

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Inference CLI with the reference's interface (main.py:290-362):
 
-    python main.py audio_file model_file [-o OUT.mid] [-d {cpu,cuda}] [-t THRESHOLD] [--decoder {frame,onset}]
+    python main.py audio_file model_file [-o OUT.mid] [-d {cpu,cuda}] [-t THRESHOLD] [--decoder {frame,onset}] [--overlap SECONDS]
 
 Exit code 1 with a message when a file is missing or transcription fails.  The checkpoint must be a
 CNNRNNModelLarge(320, 512, 3) state_dict as in the reference (main.py:16-20); --model-type/--n-mels/
@@ -25,6 +25,11 @@ def main():
                     help="frame: notes are runs of active frames (default); onset: notes start at rising edges of the onset head and "
                          "last while frame or onset is active (needs a cnn_rnn_large checkpoint trained with --train_all_heads)")
     ap.add_argument("--onset-threshold", type=float, default=0.5, help="threshold of the onset head for --decoder onset (default: 0.5)")
+    ap.add_argument("--overlap", type=float, default=0.0,
+                    help="seconds of overlap between 30 s windows (0.256 to 15; default 0 = the reference's chunk concatenation, which "
+                         "places chunk k's notes 16 ms x k late because a 480000-sample chunk spans 937.5 hops but yields 938 frames). "
+                         "With an overlap the windows start on the 512-sample hop and their centres are stitched on the recording's "
+                         "own frame grid: no drift, and no cold network start at the chunk boundaries")
     ap.add_argument("--model-type", default="cnn_rnn_large")
     ap.add_argument("--n-mels", type=int, default=320)
     ap.add_argument("--hidden-size", type=int, default=512)
@@ -40,7 +45,7 @@ def main():
     try:
         from music_transcription_amd.transcribe import transcribe_audio
         out = transcribe_audio(args.audio_file, args.model_file, args.output, args.device, args.threshold,
-                               decoder=args.decoder, onset_threshold=args.onset_threshold, model_type=args.model_type, n_mels=args.n_mels, hidden_size=args.hidden_size,
+                               decoder=args.decoder, onset_threshold=args.onset_threshold, overlap=args.overlap, model_type=args.model_type, n_mels=args.n_mels, hidden_size=args.hidden_size,
                                num_layers=args.num_layers)
         print("=" * 60 + f"\nTranscription completed successfully!\nOutput: {out}\n" + "=" * 60)
     except Exception as e:

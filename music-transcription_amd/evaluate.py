@@ -9,6 +9,8 @@
   * `note_metrics_dataset` = note-level precision / recall / F1 (mir_eval's onset and onset+offset criteria on the frame grid)
     against the runs of the label roll, for the frame decoder or the onset-gated one; decoding and matching are one counting
     pass over the logits (notes.note_match_counts), samples of any length batched through `lengths`.
+  * `window_overlap` (seconds, whole-file datasets): every recording runs in overlapping 30 s windows stitched on its own
+    frame grid (windows.collect_logits_windows) instead of one recurrence over the whole file;
   * recordings / chunks shard over ranks with no data-path collective (parallel.py); per-sample F1 values are
     gathered with one small all-reduce.
 """
@@ -93,12 +95,21 @@ def f1_at_thresholds(logits_rolls, thresholds: Sequence[float]) -> np.ndarray:
     return per_sample
 
 
+def _collect(model, dataset, indices, device, window_overlap: Optional[float], all_heads: bool = False):
+    """collect_logits, or with window_overlap (seconds) collect_logits_windows over a whole-file dataset."""
+    if window_overlap is None:
+        return collect_logits(model, dataset, indices, device, all_heads=all_heads)
+    from .windows import collect_logits_windows
+    return collect_logits_windows(model, dataset, indices, window_overlap, device, all_heads=all_heads)
+
+
 def evaluate_dataset(model, dataset, threshold: float = 0.5, device="cuda", subset: Optional[int] = None,
-                     rank: int = 0, world: int = 1) -> Tuple[float, List[float]]:
-    """-> (mean F1 over ALL samples, per-sample F1 list), identical on every rank."""
+                     rank: int = 0, world: int = 1, window_overlap: Optional[float] = None) -> Tuple[float, List[float]]:
+    """-> (mean F1 over ALL samples, per-sample F1 list), identical on every rank.  window_overlap (seconds): a whole-file
+    dataset runs in overlapping 30 s windows stitched on each recording's frame grid (windows.collect_logits_windows)."""
     n = len(dataset) if subset is None else min(subset, len(dataset))
     mine = list(shard_range(n, rank, world))
-    lr = collect_logits(model, dataset, mine, device)
+    lr = _collect(model, dataset, mine, device, window_overlap)
     vals = f1_at_thresholds(lr, [threshold])[:, 0] if lr else np.zeros(0)
     allv = gather_values(mine, vals.tolist(), n)
     return (float(np.mean(allv)) if allv else 0.0), allv
@@ -108,16 +119,17 @@ NOTE_METRIC_KEYS = tuple(f"{c}_{m}" for c in ("onset", "onset_offset") for m in 
 
 
 def note_metrics_dataset(model, dataset, threshold: float = 0.5, onset_threshold: Optional[float] = None, device="cuda",
-                         subset: Optional[int] = None, max_batch: int = 128, rank: int = 0, world: int = 1) -> dict:
+                         subset: Optional[int] = None, max_batch: int = 128, rank: int = 0, world: int = 1,
+                         window_overlap: Optional[float] = None) -> dict:
     """Note-level metrics of every sample, identical on every rank: {"mean": {key: value}, "per_sample": {key: [values]}} over
     NOTE_METRIC_KEYS (onset / onset_offset x precision / recall / f1).  onset_threshold=None: notes are the runs of
     sigmoid(frame) > threshold (the frame decoder); otherwise the onset-gated decoder with the onset head at onset_threshold.
-    Reference notes are the runs of the dataset's label roll.  Unweighted means over samples, as evaluate_dataset."""
+    Reference notes are the runs of the dataset's label roll.  Unweighted means over samples, as evaluate_dataset (window_overlap too)."""
     from .notes import note_match_counts, note_prf
     n = len(dataset) if subset is None else min(subset, len(dataset))
     mine = list(shard_range(n, rank, world))
     onset = onset_threshold is not None
-    lr = collect_logits(model, dataset, mine, device, all_heads=onset)
+    lr = _collect(model, dataset, mine, device, window_overlap, all_heads=onset)
     vals = {k: [] for k in NOTE_METRIC_KEYS}
     for s in range(0, len(lr), max_batch):            # one counts pass per group; unequal lengths padded and masked by `lengths`
         grp = lr[s:s + max_batch]
@@ -137,12 +149,12 @@ def note_metrics_dataset(model, dataset, threshold: float = 0.5, onset_threshold
 
 
 def tune_threshold(model, dataset, device="cuda", subset: Optional[int] = None, tune_range=(0.05, 0.95), tune_step=0.1,
-                   tune_min_step=0.01, tune_rounds=6, rank: int = 0, world: int = 1, log=print):
+                   tune_min_step=0.01, tune_rounds=6, rank: int = 0, world: int = 1, log=print, window_overlap: Optional[float] = None):
     """Coarse-to-fine search of evaluate.py:556-618 (same candidate grids, same strict-improvement rule, same window
-    and stopping rule); returns (best_threshold, best_mean_f1)."""
+    and stopping rule); returns (best_threshold, best_mean_f1).  window_overlap: as evaluate_dataset."""
     n = len(dataset) if subset is None else min(subset, len(dataset))
     mine = list(shard_range(n, rank, world))
-    lr = collect_logits(model, dataset, mine, device)          # the only forward passes
+    lr = _collect(model, dataset, mine, device, window_overlap)          # the only forward passes
     tune_min, tune_max = tune_range
     step = tune_step
     best_t, best_f1 = 0.5, -1.0

@@ -370,19 +370,45 @@ def transcribe_chunks(model: TranscriptionModel, chunks, threshold: float = THRE
     return np.concatenate(rolls, axis=1)
 
 
+@torch.no_grad()
+def transcribe_windows_to_notes(model: "TranscriptionModel", y: torch.Tensor, overlap: float, threshold: float = THRESHOLD, batch: int = 128,
+                                n_mels: int = N_MELS, decoder: str = "frame", onset_threshold: float = THRESHOLD) -> List[Tuple[int, float, float]]:
+    """1-D device recording -> notes decoded from ONE (1, 88, 1 + n // 512) logit roll on the recording's frame grid, stitched from
+    overlapping 30 s windows (windows.transcribe_windows): no per-chunk drift, no cold chunk edges inside the recording."""
+    from .windows import transcribe_windows
+    check_decoder(decoder, model=model)
+    heads = transcribe_windows(model, [y], overlap, batch=batch, all_heads=decoder == "onset", n_mels=n_mels)[0]
+    if decoder == "onset":
+        from .notes import heads_to_notes_device
+        return heads_to_notes_device(heads[0][None], heads[1][None], threshold, onset_threshold, SR / HOP_LENGTH)
+    return notes_from_logits_device(heads[None], threshold, SR / HOP_LENGTH)
+
+
 def transcribe_audio(audio_path: str, model_path: str, output_path=None, device=None, threshold: float = THRESHOLD, decoder: str = "frame",
-                     onset_threshold: float = THRESHOLD, **model_kw):
+                     onset_threshold: float = THRESHOLD, overlap: float = 0.0, **model_kw):
+    """overlap = 0: the reference's chunk concatenation (main.py:60-100, :164-186); overlap > 0 (seconds): overlapping windows
+    stitched on the recording's own frame grid (transcribe_windows_to_notes)."""
     check_decoder(decoder, model_type=model_kw.get("model_type", MODEL_TYPE))
+    if overlap:
+        from .windows import overlap_frames
+        overlap_frames(overlap)                          # refuse an out-of-range overlap before any GPU work
     device = device or ("cuda" if torch.cuda.is_available() else "cpu")
     if device != "cuda":
         raise RuntimeError("music_transcription_amd runs on the GPU only (-d cuda)")
     print(f"Using device: {device}")
     model = load_model(model_path, device, **model_kw)
     y = load_audio_device(audio_path, SR, device)       # decode + resample on the GPU; the waveform never visits the host
-    chunks, duration = split_into_chunks_device(y)
-    print(f"Audio duration: {duration:.2f} seconds; {len(chunks)} chunks of {CHUNK_LENGTH}s")
-    notes = transcribe_chunks_to_notes(model, chunks, threshold, n_mels=model_kw.get("n_mels", N_MELS), device=device, decoder=decoder,
-                                       onset_threshold=onset_threshold)
+    if overlap:
+        from .windows import plan_windows
+        print(f"Audio duration: {y.numel() / SR:.2f} seconds; {len(plan_windows(y.numel(), overlap).start)} windows of {CHUNK_LENGTH}s "
+              f"overlapping by {overlap}s")
+        notes = transcribe_windows_to_notes(model, y, overlap, threshold, n_mels=model_kw.get("n_mels", N_MELS), decoder=decoder,
+                                            onset_threshold=onset_threshold)
+    else:
+        chunks, duration = split_into_chunks_device(y)
+        print(f"Audio duration: {duration:.2f} seconds; {len(chunks)} chunks of {CHUNK_LENGTH}s")
+        notes = transcribe_chunks_to_notes(model, chunks, threshold, n_mels=model_kw.get("n_mels", N_MELS), device=device, decoder=decoder,
+                                           onset_threshold=onset_threshold)
     if output_path is None:
         p = Path(audio_path)
         output_path = p.parent / f"{p.stem}_transcription.mid"

@@ -14,7 +14,8 @@ logits instead of another run of the model.  With more than one rank the samples
 collective) and the per-sample values gathered by one small all-reduce.  `--data_source full` (and `auto` without a cache)
 evaluates whole recordings under --root_dir, one sample per recording (MaestroDataset with chunk_length=None, featurised on
 the GPU); a recording longer than the inference recurrence takes (T * hidden_size < 2^24 frames) ends the run with an error
-naming it.  MIDI / plot outputs, background mode and the results browser are out of scope.
+naming it.  `--window_overlap SECONDS` instead runs every recording in overlapping 30 s windows stitched on its own frame grid
+(windows.py), which has no such limit.  MIDI / plot outputs, background mode and the results browser are out of scope.
 """
 import argparse
 import json
@@ -53,6 +54,10 @@ def main():
                     help="note decoder for --note_metrics: frame = runs of active frames (default); onset = notes start at rising edges "
                          "of the onset head (cnn_rnn_large trained with --train_all_heads; untrained heads make it meaningless)")
     ap.add_argument("--onset_threshold", type=float, default=0.5, help="threshold of the onset head for --decoder onset (default: 0.5)")
+    ap.add_argument("--window_overlap", type=float, default=None,
+                    help="full files only: run every recording in overlapping 30 s windows (this many seconds of overlap, 0.256 to 15) "
+                         "stitched on its own frame grid, instead of one recurrence over the whole file; lifts the T * hidden_size < 2^24 "
+                         "length limit")
     ap.add_argument("--tune_threshold", action="store_true")
     ap.add_argument("--tune_rounds", type=int, default=6)
     ap.add_argument("--tune_range", type=float, nargs=2, default=[0.05, 0.95])
@@ -75,6 +80,16 @@ def main():
     if not full and not os.path.exists(meta_path):
         print(f"Error: no cached split at {meta_path} (run scripts/preprocess_dataset.py, or use --data_source full --root_dir ...)")
         return 1
+    if args.window_overlap is not None:
+        if not full:
+            print(f"Error: --window_overlap evaluates whole recordings and needs --data_source full (the cache at {meta_path} holds chunks)")
+            return 1
+        try:
+            from music_transcription_amd.windows import overlap_frames
+            overlap_frames(args.window_overlap)
+        except ValueError as e:
+            print(f"Error: --window_overlap: {e}")
+            return 1
     n_mels = args.n_mels
     if full:
         n_mels = n_mels or 320
@@ -109,7 +124,7 @@ def main():
                                 device=dev)
         t_max = ((1 << 24) - 1) // args.hidden_size        # lstm.hip: the inference recurrence takes T * H < 2^24
         for row, t in zip(ds.rows, ds.num_frames):
-            if int(t) > t_max:
+            if int(t) > t_max and args.window_overlap is None:          # (in windows every forward is 938 frames)
                 print(f"Error: recording {row['audio_filename']} has T={int(t)} frames; the inference recurrence takes at most "
                       f"{t_max} at hidden_size={args.hidden_size} (T * hidden_size < 2^24)")
                 return 1
@@ -124,13 +139,14 @@ def main():
     if args.tune_threshold:
         threshold, tuned_f1 = E.tune_threshold(model, ds, dev, subset=args.subset, tune_range=tuple(args.tune_range), tune_step=args.tune_step,
                                                tune_min_step=args.tune_min_step, tune_rounds=args.tune_rounds, rank=rank, world=world,
-                                               log=say if rank == 0 else None)
+                                               log=say if rank == 0 else None, window_overlap=args.window_overlap)
         say(f"Best threshold: {threshold:.4f} (mean F1 {tuned_f1:.6f})")
-    mean_f1, per_sample = E.evaluate_dataset(model, ds, threshold, dev, subset=args.subset, rank=rank, world=world)
+    mean_f1, per_sample = E.evaluate_dataset(model, ds, threshold, dev, subset=args.subset, rank=rank, world=world,
+                                             window_overlap=args.window_overlap)
     notes = None
     if args.note_metrics:
         notes = E.note_metrics_dataset(model, ds, threshold, args.onset_threshold if args.decoder == "onset" else None, dev,
-                                       subset=args.subset, rank=rank, world=world)
+                                       subset=args.subset, rank=rank, world=world, window_overlap=args.window_overlap)
     if rank == 0:
         if args.headless:
             print(f"EVAL_MEAN_F1={mean_f1:.6f}")
