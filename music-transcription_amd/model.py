@@ -164,17 +164,31 @@ class _HipForward:
                 raise _lib.MtError(f"LSTM {n}: inter-workgroup hand-off ({kind} spin) timed out at step {(st & 0x3fffffff) - (0 if st & 0x40000000 else 1)}: "
                                    "the launch was not fully resident (too many persistent launches in flight on this GPU?)")
 
+    _TRAIN_SYNC_KEEP = 256
+
+    def _note_train_sync(self, buf, stride):
+        """Called by every training forward with its status slots (one per persistent launch of the step, `stride` bytes apart)."""
+        pending = self.__dict__.setdefault("_train_syncs", [])
+        pending.append((buf, stride))
+        del pending[:-self._TRAIN_SYNC_KEEP]         # a caller that never checks keeps the latest steps only
+
     def raise_on_train_handoff_timeout(self):
-        """The same for the persistent launches of the last training step (forward and backward recurrences); the
-        caller has synchronised with the step (train.train_one_epoch reads the loss and the optimizer's statistics)."""
-        ts = getattr(self, "_train_sync", None)
-        if ts is None:
+        """The same for the persistent launches (forward and backward recurrences) of every training step since the last call
+        -- several may have been in flight (gradient accumulation); the caller has synchronised with them (train.train_one_epoch
+        reads the loss and the optimizer's statistics).  The pending steps are forgotten afterwards."""
+        pending = getattr(self, "_train_syncs", None)
+        if not pending:
             return
-        buf, stride = ts
-        vals = buf.view(torch.int32)[:: stride // 4].cpu().tolist()
-        for i, st in enumerate(vals):
-            if st != 0:
-                raise _lib.MtError(f"training step: persistent recurrence launch {i} timed out in its inter-workgroup hand-off (status {st:#x})")
+        self._train_syncs = []
+        words = [buf.view(torch.int32)[:: stride // 4] for buf, stride in pending]
+        vals = torch.cat(words).cpu().tolist()
+        o = 0
+        for k, w in enumerate(words):
+            for i, st in enumerate(vals[o:o + w.numel()]):
+                if st != 0:
+                    raise _lib.MtError(f"training step {k + 1} of {len(words)} since the last check: persistent recurrence launch {i} "
+                                       f"timed out in its inter-workgroup hand-off (status {st:#x})")
+            o += w.numel()
 
     def _check_inflight_bound(self, key, bound, what):
         """Co-residency rule of the persistent recurrence kernels: at most `bound` forwards of this

@@ -87,7 +87,8 @@ def train_one_epoch(model, dataloader: Iterable, optimizer: FusedAdamClip, devic
             nan_count += 1
             if nan_count > 10:
                 raise RuntimeError("Too many NaN losses - training unstable!")
-            continue
+            del logits, loss                           # drop the step's graph now: its workspace lease goes back to the pool
+            continue                                   # before the next forward (train_step / step_pool)
         loss.backward()
         stats = optimizer.step().tolist()              # {grad norm before clipping, 1.0 if the step was taken}
         if tuner is not None:

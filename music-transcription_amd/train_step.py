@@ -10,7 +10,9 @@ Numerics: GEMM/conv operands bf16, accumulation f32, LSTM state/gates f32 (the r
 convs/fc, fp32 LSTM), BatchNorm statistics f64-accumulated.  Dropout masks come from a counter-based hash seeded
 from torch's CPU generator (reproducible under torch.manual_seed; not bit-identical to cuDNN's Philox stream).
 
-One training step may be in flight per model: scratch buffers are cached per (B, T) and reused by the next call.
+Several steps may be in flight (gradient accumulation, interleaved forwards): the BPTT workspaces are pooled per (B, T) and leased
+to one step from its forward to its backward (step_pool); the packed operands are re-packed by every forward from the same
+parameters, so a pending backward reads the values its forward used as long as no optimizer step runs in between.
 """
 from __future__ import annotations
 
@@ -20,7 +22,7 @@ import os
 
 import torch
 
-from . import _lib
+from . import _lib, step_pool
 from ._lib import lib, check, ptr
 
 BN_EPS, BN_MOMENTUM = 1e-5, 0.1
@@ -232,21 +234,21 @@ def forward_train(model, x: torch.Tensor, dropout: float, seed: int):
         d = pk["dims"]
         Hp_, L_ = d["Hp"], d["L"]
         # (persistent per (B, T): as per-step allocations used on two streams they came back to the allocator late, and a step that has to
-        #  hipMalloc a fresh 0.5 GB block waits ~80 ms for it -- see train_step_large._StepWorkspace)
-        pool = model.__dict__.setdefault("_bptt_parts", {})
-        pkey = (int(B), int(T), Hp_, str(dev))
-        if pkey not in pool:
-            if len(pool) >= 2:
-                pool.pop(next(iter(pool)))
-            pool[pkey] = [torch.empty(lib.mt_lstm_bwd_part_bytes(B, T, Hp_), device=dev, dtype=torch.uint8) for _ in range(min(2, L_))]
-        parts = pool[pkey]
+        #  hipMalloc a fresh 0.5 GB block waits ~80 ms for it -- see train_step_large._StepWorkspace).  Leased to this step until its
+        #  backward pass has run or its graph is dropped: a second step in flight gets its own (step_pool).
+        nbytes = lib.mt_lstm_bwd_part_bytes(B, T, Hp_)
+
+        def make_parts():
+            return _BpttParts([torch.empty(nbytes, device=dev, dtype=torch.uint8) for _ in range(min(2, L_))])
+        ent, lease = step_pool.acquire(model.__dict__.setdefault("_bptt_parts", {}), (int(B), int(T), Hp_, str(dev)), make_parts, make_parts)
+        parts = ent.parts
     H, Hp, L, F1, K0, K1 = d["H"], d["Hp"], d["L"], d["F1"], d["K0"], d["K1"]
     M, Mpad = T * B, _ru(T * B, 128)
     x = x.contiguous().float()
     bf = dict(device=dev, dtype=torch.bfloat16)
     f32 = dict(device=dev, dtype=torch.float32)
     sums = torch.zeros(512, device=dev, dtype=torch.float64)
-    sv: Dict[str, object] = {"pk": pk, "x": x, "B": B, "T": T, "dropout": dropout, "seed": seed}
+    sv: Dict[str, object] = {"pk": pk, "x": x, "B": B, "T": T, "dropout": dropout, "seed": seed, "lease": lease}
     bn1, bn2 = model.cnn[1], model.cnn[5]
     with torch.cuda.device(dev):
         # ---- conv1: batch statistics of the recomputed pre-BN activation, folded into the inference kernel's weights
@@ -291,7 +293,7 @@ def forward_train(model, x: torch.Tensor, dropout: float, seed: int):
         # slot only, so the host can read every launch's hand-off status after the step (model.raise_on_train_handoff_timeout)
         sstride = _ru(lib.mt_lstm_sync_bytes(B, Hp), 256)
         sync_all = torch.zeros(2 * L * sstride, device=dev, dtype=torch.uint8)
-        model._train_sync = (sync_all, sstride)
+        model._note_train_sync(sync_all, sstride)
         sv["sync_all"], sv["sync_stride"] = sync_all, sstride
         for l in range(L):
             sync = sync_all[l * sstride:(l + 1) * sstride]
@@ -521,7 +523,24 @@ def backward_train(model, sv, dlogits: torch.Tensor, debug: dict = None) -> Dict
                                ptr(g["cnn.1.bias"]), B, F, T, _st()), "mt_conv1_bwd")
         main.wait_stream(side)                       # every gradient is complete in the caller's stream order
     del keep
+    step_pool.release(sv)                            # the BPTT workspaces may serve the next forward (its uses are ordered on this stream)
     return g
+
+
+class _BpttParts:
+    """The BPTT hand-off workspaces of one step (a step_pool entry)."""
+
+    def __init__(self, parts):
+        self.parts, self.busy = parts, False
+
+
+def _require_saved(ctx):
+    """A step's saved state (and its workspace lease) is handed back by its one backward pass: a second one -- retain_graph=True
+    included -- fails the way torch fails for a graph whose saved tensors were freed."""
+    if ctx.sv is None:
+        raise RuntimeError("Trying to backward through the graph a second time (or directly access saved tensors after they have "
+                           "already been freed). The HIP training step frees its saved state and hands its workspaces to the next "
+                           "step in its backward pass, so it supports one backward per forward, even with retain_graph=True.")
 
 
 class CnnRnnTrainFn(torch.autograd.Function):
@@ -535,6 +554,7 @@ class CnnRnnTrainFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dlogits):
+        _require_saved(ctx)
         g = backward_train(ctx.model, ctx.sv, dlogits)
         for n in ctx.sv.get("direct_grads", ()):        # already in the flat gradient buffer
             g[n] = None
@@ -547,4 +567,8 @@ def train_forward(model, x: torch.Tensor) -> torch.Tensor:
     params = [p for _, p in model.named_parameters()]
     p = float(model.rnn.dropout) if model.num_layers > 1 else 0.0
     seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if p > 0.0 else 0
-    return CnnRnnTrainFn.apply(model, x, p, seed, names, *params)
+    if torch.is_grad_enabled():
+        return CnnRnnTrainFn.apply(model, x, p, seed, names, *params)
+    logits, sv = forward_train(model, x, p, seed)
+    step_pool.release(sv)                            # no backward pass will follow
+    return logits

@@ -26,9 +26,9 @@ from typing import Dict, List
 
 import torch
 
-from . import _lib
+from . import _lib, step_pool
 from ._lib import lib, check, ptr
-from .train_step import _ru, _st, _gemm, _gather4, BN_EPS, BN_MOMENTUM, device_key
+from .train_step import _ru, _st, _gemm, _gather4, _require_saved, BN_EPS, BN_MOMENTUM, device_key
 
 LN_EPS, ATTN_CLIP = 1e-6, 10.0
 DROPOUT2D_P = (0.1, 0.1, 0.15)          # cnn_rnn_model.py:188,:192,:202 (hard-coded in the reference)
@@ -232,8 +232,8 @@ class _StepWorkspace:
     128-row / 64-column tiles, so their rows and columns beyond the live region must hold zeros -- and no kernel ever writes there, so
     they still do in the next step.  Round 3 called torch.zeros for ~40 such tensors per step (2.3 GB of fills at B = 16, T = 937, most
     of them alone on the GPU in front of the kernel that needed the buffer).  What IS accumulated into (f64 statistic sums, status
-    words) stays a per-step torch.zeros.  One step per workspace at a time: a second forward before the first one's backward gets
-    fresh tensors (_FreshZeros)."""
+    words) stays a per-step torch.zeros.  One step per workspace at a time (a step_pool lease, from the forward to the backward or
+    to the drop of the graph): a second forward before the first one's backward gets fresh tensors (_FreshZeros)."""
 
     def __init__(self):
         self.t, self.busy = {}, False
@@ -268,19 +268,10 @@ class _FreshZeros:
 
 
 def _workspace(model, B, T, dev):
+    """-> (workspace, lease or None): the pooled _StepWorkspace of (B, T) (at most two shapes: ragged batches), leased to this step."""
     if os.environ.get("MT_TRAIN_WS_CACHE", "1") == "0":
-        return _FreshZeros()
-    pool = model.__dict__.setdefault("_train_ws", {})
-    key = (int(B), int(T), str(dev))
-    ws = pool.get(key)
-    if ws is None:
-        for k_ in [k_ for k_, v_ in pool.items() if not v_.busy][:max(0, len(pool) - 1)]:     # keep at most two shapes (ragged batches: T varies)
-            del pool[k_]
-        ws = pool[key] = _StepWorkspace()
-    if ws.busy:
-        return _FreshZeros()
-    ws.busy = True
-    return ws
+        return _FreshZeros(), None
+    return step_pool.acquire(model.__dict__.setdefault("_train_ws", {}), (int(B), int(T), str(dev)), _StepWorkspace, _FreshZeros)
 
 
 # ---------------------------------------------------------------------------------------------------------------- small wrappers
@@ -530,13 +521,14 @@ def forward_train_large(model, x: torch.Tensor, p_drop: float, seed: int, p2d=DR
     x = x.contiguous().float()
     bf = dict(device=dev, dtype=torch.bfloat16)
     f32 = dict(device=dev, dtype=torch.float32)
-    ws = _workspace(model, B, T, dev)
-    sv: Dict[str, object] = dict(pk=pk, x=x, B=B, T=T, p=p_drop, seed=seed, p2d=p2d, ws=ws)
+    ws, lease = _workspace(model, B, T, dev)
+    sv: Dict[str, object] = dict(pk=pk, x=x, B=B, T=T, p=p_drop, seed=seed, p2d=p2d, ws=ws, lease=lease)
     nsync = 2 * (L + 1)
     stride = _ru(max(lib.mt_lstm_sync_bytes(B, Hp), lib.mt_lstm_sync_bytes(B, Hlp)), 256)
     sync_all = torch.zeros(nsync * stride, device=dev, dtype=torch.uint8)       # one status slot per persistent launch of the step
     slots = [sync_all[i * stride:(i + 1) * stride] for i in range(nsync)]
     sv["sync_all"], sv["sync_stride"], sv["sync_free"] = sync_all, stride, slots
+    model._note_train_sync(sync_all, stride)
     with torch.cuda.device(dev):
         # ---- conv1: statistics of the recomputed pre-BN activation, folded into the inference kernel's weights
         bn1 = model.conv1[1]
@@ -984,7 +976,8 @@ def backward_train_large(model, sv, dlogits: torch.Tensor) -> Dict[str, torch.Te
             evj = torch.cuda.Event()
             evj.record(side_a)
             main_st.wait_event(evj)
-    return g
+    step_pool.release(sv)                               # the step's workspace may serve the next forward (stream order: the backward
+    return g                                            # pass joined its side streams into the calling stream above)
 
 
 class CnnRnnLargeTrainFn(torch.autograd.Function):
@@ -994,15 +987,14 @@ class CnnRnnLargeTrainFn(torch.autograd.Function):
     def forward(ctx, model, x, p_drop, seed, p2d, names, frame_only, *params):
         logits, sv = forward_train_large(model, x, p_drop, seed, p2d)
         ctx.model, ctx.sv, ctx.names, ctx.frame_only = model, sv, names, frame_only
-        model._train_sync = (sv["sync_all"], sv["sync_stride"])
         return logits
 
     @staticmethod
     def backward(ctx, dlogits):
+        _require_saved(ctx)
         g = backward_train_large(ctx.model, ctx.sv, dlogits)
         direct = ctx.sv.get("direct_grads", set())
-        ctx.sv["ws"].busy = False                       # the step's workspace may serve the next forward (stream order: the backward
-        ctx.sv = None                                   # pass joined its side streams into the calling stream before it returned)
+        ctx.sv = None
         if ctx.frame_only:
             # model(mel) of the reference's loop returns the frame logits only (cnn_rnn_model.py:343-349,
             # train_transcriber.py:119): the onset / offset heads are not part of the graph, their .grad stays None and
@@ -1037,8 +1029,7 @@ def train_forward_large(model, x: torch.Tensor, return_all_heads: bool = False):
         out = CnnRnnLargeTrainFn.apply(model, x, p, seed, p2d, names, frame_only, *params)
     else:
         out, sv = forward_train_large(model, x, p, seed, p2d)
-        sv["ws"].busy = False                           # no backward pass will follow
-        model._train_sync = (sv["sync_all"], sv["sync_stride"])
+        step_pool.release(sv)                           # no backward pass will follow
     if model.use_onset_offset_heads and return_all_heads:
         return {"frame": out[0], "onset": out[1], "offset": out[2]}
     return out[0]

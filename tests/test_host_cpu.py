@@ -523,3 +523,44 @@ def test_pack_job_record_matches_the_c_struct(tmp_path):
     assert out[0] == JOB_DTYPE.itemsize
     assert out[1:] == [JOB_DTYPE.fields[n][1] for n in fields]
     assert one(5, 3) == (1, 1 << 30, 5, 0, 3) and two(4, 32, 24, 7, 1) == (4, 32, 24, 7, 1)
+
+
+def test_step_pool_leases_without_gpu():
+    """The workspace pool of the training steps (step_pool): a lease per step in flight, a private workspace when the pooled one
+    is leased, eviction of idle entries only, release by the backward pass or by dropping the lease (the graph)."""
+    import gc
+    import music_transcription_amd.step_pool as sp
+
+    class Ws:
+        def __init__(self):
+            self.busy = False
+
+    class Fresh:
+        pass
+    pool = {}
+    w1, l1 = sp.acquire(pool, "T1", Ws, Fresh)
+    assert isinstance(w1, Ws) and l1 is not None and w1.busy and list(pool) == ["T1"]
+    w2, l2 = sp.acquire(pool, "T1", Ws, Fresh)                   # second step in flight, same shape: private, no lease
+    assert isinstance(w2, Fresh) and l2 is None
+    l1.release()
+    assert not w1.busy
+    l1.release()                                                 # idempotent
+    w3, l3 = sp.acquire(pool, "T1", Ws, Fresh)                   # single-step path: the SAME pooled entry every step
+    assert w3 is w1 and w3.busy
+    w4, l4 = sp.acquire(pool, "T2", Ws, Fresh)
+    assert list(pool) == ["T1", "T2"] and w4.busy
+    w5, l5 = sp.acquire(pool, "T3", Ws, Fresh)                   # full pool of leased entries: nothing evicted, private workspace
+    assert isinstance(w5, Fresh) and l5 is None and list(pool) == ["T1", "T2"] and pool["T1"] is w1
+    sv = {"lease": l3}
+    sp.release(sv)                                               # end of a backward pass
+    assert not w1.busy
+    del l4                                                       # the graph holding T2's step is dropped without a backward
+    gc.collect()
+    assert not w4.busy
+    w6, l6 = sp.acquire(pool, "T3", Ws, Fresh)                   # evicts the oldest idle entry only
+    assert list(pool) == ["T2", "T3"] and w6.busy and pool["T2"] is w4
+    w7, l7 = sp.acquire(pool, "T2", Ws, Fresh)
+    assert w7 is w4
+    sp.release({})                                               # no lease (private workspace): nothing to do
+    del l6, l7
+    assert not any(e.busy for e in pool.values())
