@@ -186,7 +186,8 @@ def test_f16_gate_preactivations_equal_the_rounded_f32_ones(mta, B, T, H, K):
     """MT_GX_F16 (include/mt_hip.h): the projection GEMM stores W_ih x + b as f16 -- bit for bit the round-to-nearest-even of what
     it stores as f32, in the same layout, through every epilogue (per-element, 16-B rows, the LDS-staged whole-tile path at
     B % 32 == 0 and H % 256 == 0) -- and the recurrence fed with them (one to four interleaved batch groups, its loader wave
-    streaming 2-KB blocks) publishes exactly the h of the f32 recurrence fed with those rounded values."""
+    streaming 2-KB blocks) publishes exactly the h of the f32 recurrence fed with those rounded values.
+    (A bit-identity check between two kernel paths; both images against an exact CPU reference: tests/test_gpu_gemm.py, test_gx_exact.)"""
     from music_transcription_amd._lib import lib, check, ptr, stream_ptr, DT_F16, GX_F16
     g = torch.Generator().manual_seed(B * 7 + T * 3 + H)
     bound = 1.0 / np.sqrt(H)

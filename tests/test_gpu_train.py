@@ -571,7 +571,8 @@ def test_gather4_helper(mta, n, s):
 def test_gemm_lstm_dh_matches_gemm_plus_relayout(mta, B, T, H, Hv, K, p):
     """mt_gemm_lstm_dh (the dh layout + dropout mask as a GEMM epilogue) against the two-pass path it replaces,
     mt_gemm_bf16_f32acc + mt_lstm_dh_relayout: bit-identical, on the 128-tile kernel, the 256-tile kernel's hoisted path
-    (4 | B) and its generic one, with padded units (Hv < H) and a ragged last batch group."""
+    (4 | B) and its generic one, with padded units (Hv < H) and a ragged last batch group.
+    (A bit-identity check between two kernel paths; the epilogue against an exact CPU reference: tests/test_gpu_gemm.py, test_dh_exact.)"""
     from music_transcription_amd._lib import lib, check, ptr, stream_ptr
     torch.manual_seed(B * T + H)
     M, N = T * B, 2 * Hv
