@@ -30,6 +30,9 @@ def _bf(x):
 @pytest.mark.parametrize("C1,C2,Cout,KH,pool,F,T", [(32, 0, 64, 3, 0, 20, 37), (64, 32, 64, 3, 1, 20, 37), (64, 0, 128, 3, 0, 10, 50),
                                                     (128, 64, 128, 3, 0, 9, 33), (128, 0, 256, 7, 1, 12, 40), (128, 0, 256, 7, 1, 7, 16)])
 def test_conv_cl_matches_torch(mta, C1, C2, Cout, KH, pool, F, T):
+    """mt_conv_cl_bf16 on random bf16 data against torch at the bf16 output rounding, and the two output modes against each other.
+    (Every instantiation, epilogue and operand type against an exact CPU reference, with guard bands: tests/test_gpu_conv.py,
+    test_conv_cl_every_setting.)"""
     from music_transcription_amd._lib import lib, check, ptr, stream_ptr
     g = torch.Generator().manual_seed(C1 + Cout + KH)
     B = 2

@@ -204,7 +204,8 @@ def test_conv_weight_gradient_direct(mta, B, F_, T, Cin, Cout, KH, xp, dp):
 
 
 def test_conv_cl_channel_slices_and_accumulate(mta):
-    """mt_conv_cl_ex: the 256-channel input gradient of freq_aware_conv as two accumulating calls over channel halves."""
+    """mt_conv_cl_ex: the 256-channel input gradient of freq_aware_conv as two accumulating calls over channel halves.
+    (The two half-calls on exact data, the other half of the channels NaN: tests/test_gpu_conv.py, test_conv_cl_channel_slices_exact.)"""
     lib, check, ptr, st = _lib()
     from music_transcription_amd import _lib as L
     g = torch.Generator().manual_seed(5)
