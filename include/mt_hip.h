@@ -430,6 +430,15 @@ int    mt_roll_to_notes(const float* src, int src_mode, float threshold, int NB,
 int    mt_note_match_counts(const float* frame_logits, const float* onset_logits, float thr_frame, float thr_onset,
                             const float* ref_roll, const long long* lengths, unsigned long long* counts, int B, int P, int T,
                             mt_stream_t stream);
+/* mt_note_match_counts against a note list instead of a roll: same decoders, activity expression, lengths and counts, but the
+ * reference notes of row (b, p) are ref_on / ref_off[ref_ptr[b*P + p] .. ref_ptr[b*P + p + 1]) (int32, device; ref_ptr has B*P + 1
+ * entries), in ticks of 100 us, sorted by onset, 0 <= on < off; they may be arbitrarily close (re-struck keys).  One frame is 320
+ * ticks: estimated note [s, e) in frames has times 320 s, 320 e.  A match needs |d onset| <= 500 ticks, and for tp_onset_offset also
+ * 5 |d offset| <= max(2500, reference length); each tp is a maximum matching.  With L = min(T, lengths[b]) frames
+ * valid, reference notes with on >= 320 L are not counted and offsets are clipped to 320 L.  Needs 320 T < 2^31.  Exact integers. */
+int    mt_note_match_list(const float* frame_logits, const float* onset_logits, float thr_frame, float thr_onset,
+                          const int* ref_on, const int* ref_off, const long long* ref_ptr, const long long* lengths,
+                          unsigned long long* counts, int B, int P, int T, mt_stream_t stream);
 /* The onset-gated decoder with mt_roll_to_notes' contract: the NB chunks of frame_logits / onset_logits [NB][P][T] are one
  * recording of NB*T frames per pitch; counts[p], starts / ends in the reference's note order, capacity protocol unchanged. */
 int    mt_heads_to_notes(const float* frame_logits, const float* onset_logits, float thr_frame, float thr_onset, int NB, int P, int T,

@@ -7,8 +7,9 @@
     model runs ONCE: logits stay on the device and every candidate threshold is an integer-count pass
     (mt_f1_sweep_counts, up to 16 thresholds per pass).
   * `note_metrics_dataset` = note-level precision / recall / F1 (mir_eval's onset and onset+offset criteria on the frame grid)
-    against the runs of the label roll, for the frame decoder or the onset-gated one; decoding and matching are one counting
-    pass over the logits (notes.note_match_counts), samples of any length batched through `lengths`.
+    against the runs of the label roll (note_reference="roll") or the MIDI note list of whole recordings ("midi": re-struck keys
+    are reference notes of their own, times in 100 us ticks), for the frame decoder or the onset-gated one; decoding and matching
+    are one counting pass over the logits (notes.note_match_counts / note_match_list), samples of any length batched through `lengths`.
   * `window_overlap` (seconds, whole-file datasets): every recording runs in overlapping 30 s windows stitched on its own
     frame grid (windows.collect_logits_windows) instead of one recurrence over the whole file;
   * recordings / chunks shard over ranks with no data-path collective (parallel.py); per-sample F1 values are
@@ -120,12 +121,19 @@ NOTE_METRIC_KEYS = tuple(f"{c}_{m}" for c in ("onset", "onset_offset") for m in 
 
 def note_metrics_dataset(model, dataset, threshold: float = 0.5, onset_threshold: Optional[float] = None, device="cuda",
                          subset: Optional[int] = None, max_batch: int = 128, rank: int = 0, world: int = 1,
-                         window_overlap: Optional[float] = None) -> dict:
+                         window_overlap: Optional[float] = None, note_reference: str = "roll") -> dict:
     """Note-level metrics of every sample, identical on every rank: {"mean": {key: value}, "per_sample": {key: [values]}} over
     NOTE_METRIC_KEYS (onset / onset_offset x precision / recall / f1).  onset_threshold=None: notes are the runs of
     sigmoid(frame) > threshold (the frame decoder); otherwise the onset-gated decoder with the onset head at onset_threshold.
-    Reference notes are the runs of the dataset's label roll.  Unweighted means over samples, as evaluate_dataset (window_overlap too)."""
-    from .notes import note_match_counts, note_prf
+    Reference notes: note_reference="roll", the runs of the dataset's label roll; "midi", the MIDI note list of each recording
+    (dataset.ref_notes: a whole-file MaestroDataset built with onset_labels="midi").  Unweighted means over samples, as
+    evaluate_dataset (window_overlap too)."""
+    from .notes import note_match_counts, note_match_list, note_prf
+    if note_reference not in ("roll", "midi"):
+        raise ValueError(f"note_reference must be 'roll' or 'midi', got {note_reference!r}")
+    if note_reference == "midi" and (getattr(dataset, "onset_labels", None) != "midi" or getattr(dataset, "chunk_length", 0) is not None):
+        raise ValueError("note_reference='midi' scores against the MIDI note list of whole recordings: it needs "
+                         "MaestroDataset(chunk_length=None, onset_labels='midi') (scripts/evaluate.py --data_source full)")
     n = len(dataset) if subset is None else min(subset, len(dataset))
     mine = list(shard_range(n, rank, world))
     onset = onset_threshold is not None
@@ -137,9 +145,12 @@ def note_metrics_dataset(model, dataset, threshold: float = 0.5, onset_threshold
         T = max(lengths)
         pad = lambda t: torch.nn.functional.pad(t, (0, T - t.shape[-1]))
         frame = torch.stack([pad(x[1]) for x in grp])
-        roll = torch.stack([pad(x[2]) for x in grp])
         on = torch.stack([pad(x[3]) for x in grp]) if onset else None
-        counts = note_match_counts(frame, roll, threshold, on, onset_threshold if onset else 0.5, lengths)
+        if note_reference == "midi":
+            counts = note_match_list(frame, dataset.ref_notes([x[0] for x in grp]), threshold, on, onset_threshold if onset else 0.5, lengths)
+        else:
+            roll = torch.stack([pad(x[2]) for x in grp])
+            counts = note_match_counts(frame, roll, threshold, on, onset_threshold if onset else 0.5, lengths)
         for m in note_prf(counts):
             for c in ("onset", "onset_offset"):
                 for k, v in zip(("precision", "recall", "f1"), m[c]):

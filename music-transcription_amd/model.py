@@ -556,7 +556,7 @@ class TranscriptionModel(nn.Module):
         return self.model(x)
 
     def compute_loss(self, logits, targets, lengths=None):
-        """Masked BCE-with-logits (single tensor or frame/onset/offset dict); see ops.compute_loss."""
+        """Masked BCE-with-logits (single tensor or frame/onset/offset dict; targets a roll or a frame/onset dict); see ops.compute_loss."""
         from . import ops
         return ops.compute_loss(logits, targets, lengths)
 

@@ -63,7 +63,16 @@ def onset_offset_targets(targets):
 
 
 def compute_loss(logits, targets, lengths=None):
-    """Single-head or dict (frame/onset/offset, weights .5/.25/.25) masked BCE."""
+    """Single-head or dict (frame/onset/offset, weights .5/.25/.25) masked BCE.  With dict logits, `targets` may be the dict
+    {"frame": roll, "onset": onset_roll} of MaestroDataset(onset_labels="midi"): the onset head is then trained against the given
+    onset roll (the MIDI note-ons) instead of the roll's rising edges; frame and offset terms as with a tensor."""
+    if isinstance(targets, dict):
+        if not isinstance(logits, dict):
+            raise ValueError("compute_loss: dict targets (frame / onset) go with the three-head dict of logits")
+        roll = targets["frame"]
+        _, off = onset_offset_targets(roll)
+        return (masked_bce(logits["frame"], roll, lengths, 0.5) + masked_bce(logits["onset"], targets["onset"], lengths, 0.25)
+                + masked_bce(logits["offset"], off, lengths, 0.25))
     if isinstance(logits, dict):
         on, off = onset_offset_targets(targets)
         return (masked_bce(logits["frame"], targets, lengths, 0.5) + masked_bce(logits["onset"], on, lengths, 0.25)

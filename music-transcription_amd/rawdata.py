@@ -21,7 +21,7 @@ import os
 import pickle
 import warnings
 from collections import OrderedDict
-from typing import Dict, Optional, Sequence
+from typing import Dict, NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -40,6 +40,58 @@ _PAD = 64                    # readable floats past the last recording (the mel 
 
 
 # ------------------------------------------------------------------ labels
+def _pedal_extend(start, end, ped_on, ped_off):
+    """label_spans' pedal rule on one axis (frames or seconds): a note [start, end) that sounds inside a pedal interval
+    [on, off) lasts to max(end, off).  Only the last interval starting before the note's end can reach past it."""
+    if not len(ped_on):
+        return end.copy()
+    k = np.searchsorted(ped_on, end, side="left") - 1               # last pedal interval starting before the note's end
+    has = k >= 0
+    kk = np.where(has, k, 0)
+    g0 = np.maximum(start, ped_on[kk])                               # the note's first frame inside the interval
+    ext = has & (g0 < np.minimum(end, ped_off[kk]))
+    return np.where(ext, np.maximum(end, ped_off[kk]), end)
+
+
+def _instrument_notes(midi: MidiFile, fs: float):
+    """The per-instrument work label_spans and label_notes share: (per non-drum instrument with notes, a dict of its kept notes:
+    pitch row p, frames [a, end) and seconds [t0, t1), both pedal-extended), the full-file roll width, whether any instrument has
+    notes.  Kept = pitch in range and a < b on the frame grid."""
+    out, full_width, has_notes = [], 0, False
+    for inst in midi.instruments:
+        if not inst.notes:
+            continue
+        has_notes = True
+        t_end = inst.get_end_time()
+        width = int(fs * t_end)
+        full_width = max(full_width, width)
+        if inst.is_drum:
+            continue
+        pitch = np.array([n.pitch for n in inst.notes], dtype=np.int64)
+        t0 = np.array([n.start for n in inst.notes], dtype=np.float64)
+        t1 = np.array([n.end for n in inst.notes], dtype=np.float64)
+        a = np.minimum((t0 * fs).astype(np.int64), width)
+        b = np.minimum((t1 * fs).astype(np.int64), width)
+        ons, offs, ons_t, offs_t, t_on, s_on, on = [], [], [], [], 0, 0.0, False
+        for number, value, t in inst.control_changes:
+            if number != 64:
+                continue
+            now, cur = int(t * fs), value >= 64
+            if not on and cur:
+                t_on, s_on, on = now, t, True
+            elif on and not cur:
+                ons.append(t_on)
+                offs.append(now)
+                ons_t.append(s_on)
+                offs_t.append(t)
+                on = False
+        end = _pedal_extend(a, b, np.array(ons, dtype=np.int64), np.minimum(np.array(offs, dtype=np.int64), width))
+        t_off = _pedal_extend(t0, t1, np.array(ons_t, dtype=np.float64), np.minimum(np.array(offs_t, dtype=np.float64), t_end))
+        keep = (a < b) & (pitch >= PITCH_LO) & (pitch < PITCH_LO + N_PITCH)
+        out.append({"p": pitch[keep] - PITCH_LO, "a": a[keep], "end": end[keep], "t0": t0[keep], "t1": t_off[keep]})
+    return out, full_width, has_notes
+
+
 def label_spans(midi: MidiFile, fs: float):
     """Active frame spans of `midi` on the grid of get_piano_roll(fs): (spans int32 (K, 2) of [u, v), pitch_off int64 (89,)
     -- pitch row p (MIDI 21 + p) owns spans[pitch_off[p]:pitch_off[p + 1]], sorted and disjoint --, the full-file roll
@@ -50,46 +102,16 @@ def label_spans(midi: MidiFile, fs: float):
     (CC 64 crossing 64 upwards, then downwards; one still down at the end sustains nothing) extends a note that sounds in it
     to min(t_off, W) from its first frame there (np.maximum.accumulate over non-negative velocities).  Only the last pedal
     interval starting before a note's end can reach past it: the intervals are disjoint and ordered."""
-    us, vs, ps = [], [], []
-    full_width, has_notes = 0, False
-    for inst in midi.instruments:
-        if not inst.notes:
-            continue
-        has_notes = True
-        width = int(fs * inst.get_end_time())
-        full_width = max(full_width, width)
-        if inst.is_drum:
-            continue
-        pitch = np.array([n.pitch for n in inst.notes], dtype=np.int64)
-        a = np.minimum((np.array([n.start for n in inst.notes]) * fs).astype(np.int64), width)
-        b = np.minimum((np.array([n.end for n in inst.notes]) * fs).astype(np.int64), width)
-        ons, offs, t_on, on = [], [], 0, False
-        for number, value, t in inst.control_changes:
-            if number != 64:
-                continue
-            now, cur = int(t * fs), value >= 64
-            if not on and cur:
-                t_on, on = now, True
-            elif on and not cur:
-                ons.append(t_on)
-                offs.append(now)
-                on = False
-        end = b.copy()
-        if ons:
-            ons_a, offs_a = np.array(ons, dtype=np.int64), np.minimum(np.array(offs, dtype=np.int64), width)
-            k = np.searchsorted(ons_a, b, side="left") - 1          # last pedal interval starting before the note's end
-            has = k >= 0
-            kk = np.where(has, k, 0)
-            g0 = np.maximum(a, ons_a[kk])                            # the note's first frame inside the interval
-            ext = has & (g0 < np.minimum(b, offs_a[kk]))
-            end = np.where(ext, np.maximum(b, offs_a[kk]), b)
-        keep = (a < b) & (pitch >= PITCH_LO) & (pitch < PITCH_LO + N_PITCH)
-        us.append(a[keep])
-        vs.append(end[keep])
-        ps.append(pitch[keep] - PITCH_LO)
-    u = np.concatenate(us) if us else np.zeros(0, np.int64)
-    v = np.concatenate(vs) if vs else np.zeros(0, np.int64)
-    p = np.concatenate(ps) if ps else np.zeros(0, np.int64)
+    insts, full_width, has_notes = _instrument_notes(midi, fs)
+    u = np.concatenate([i["a"] for i in insts]) if insts else np.zeros(0, np.int64)
+    v = np.concatenate([i["end"] for i in insts]) if insts else np.zeros(0, np.int64)
+    p = np.concatenate([i["p"] for i in insts]) if insts else np.zeros(0, np.int64)
+    spans, pitch_off = _merge_spans(u, v, p)
+    return spans, pitch_off, full_width, has_notes
+
+
+def _merge_spans(u, v, p):
+    """Per pitch row, the union of the frame spans [u, v) as sorted, disjoint spans: (spans int32 (K, 2), pitch_off int64 (89,))."""
     # merge per pitch: keyed by pitch * BIG + frame, overlapping or touching spans join
     big = int(max(int(v.max()) if v.size else 0, 1)) + 2
     order = np.lexsort((u, p))
@@ -104,7 +126,58 @@ def label_spans(midi: MidiFile, fs: float):
         mp = p
         spans = np.zeros((0, 2), np.int32)
     pitch_off = np.searchsorted(mp, np.arange(N_PITCH + 1), side="left").astype(np.int64)
-    return spans, pitch_off, full_width, has_notes
+    return spans, pitch_off
+
+
+TICKS_PER_SECOND = 10000     # note times in ticks of 100 us: one model frame (512 / 16000 s) is exactly 320 ticks
+TICKS_PER_FRAME = 320
+
+
+class NoteTable(NamedTuple):
+    """label_notes' result.  Pitch row p owns entries pitch_off[p]:pitch_off[p + 1], sorted by onset (on_tick strictly rising)."""
+    on_frame: np.ndarray      # int32: int(start * fs), the frame label_spans starts the note's span at
+    end_frame: np.ndarray     # int32: the pedal-extended end of that span, un-cut (merging [on_frame, end_frame) gives label_spans)
+    on_tick: np.ndarray       # int32: round(start * 1e4)
+    off_tick: np.ndarray      # int32: round(pedal-extended end * 1e4), cut at the pitch's next onset; > on_tick
+    pitch_off: np.ndarray     # int64 (89,)
+
+
+def label_notes(midi: MidiFile, fs: float) -> NoteTable:
+    """The notes behind label_spans, kept apart: what the merge into runs of the roll throws away.  Same instruments, pitch
+    range, a < b and pedal rule as label_spans (shared code).  Per pitch row, sorted by onset: a note sounds from its note-on
+    to its pedal-extended end (label_spans' rule on seconds: a note that sounds inside a pedal interval lasts to that
+    interval's end); notes with the same (pitch, on_tick) collapse into the longest one; then a note is cut at the next
+    onset of its pitch (a key cannot sound twice); off_tick >= on_tick + 1."""
+    insts, _, _ = _instrument_notes(midi, fs)
+    cat = lambda k, dt: np.concatenate([i[k] for i in insts]).astype(dt) if insts else np.zeros(0, dt)
+    p, a, end = cat("p", np.int64), cat("a", np.int64), cat("end", np.int64)
+    on = np.round(cat("t0", np.float64) * TICKS_PER_SECOND).astype(np.int64)
+    off = np.round(cat("t1", np.float64) * TICKS_PER_SECOND).astype(np.int64)
+    order = np.lexsort((-off, on, p))                                # per pitch by onset, the longest of equal onsets first
+    p, a, end, on, off = p[order], a[order], end[order], on[order], off[order]
+    first = np.ones(p.size, dtype=bool)
+    first[1:] = (p[1:] != p[:-1]) | (on[1:] != on[:-1])
+    if p.size:
+        at = np.flatnonzero(first)
+        a, end = np.minimum.reduceat(a, at), np.maximum.reduceat(end, at)   # the collapsed note covers its duplicates' frames
+        p, on, off = p[first], on[first], off[first]
+        nxt = np.full(p.size, np.iinfo(np.int64).max)
+        same = p[1:] == p[:-1]
+        nxt[:-1][same] = on[1:][same]
+        off = np.maximum(np.minimum(off, nxt), on + 1)
+    pitch_off = np.searchsorted(p, np.arange(N_PITCH + 1), side="left").astype(np.int64)
+    i32 = lambda x: np.ascontiguousarray(x, dtype=np.int32)
+    return NoteTable(i32(a), i32(end), i32(on), i32(off), pitch_off)
+
+
+def onset_spans(notes: NoteTable):
+    """The note-ons as a span table for mt_roll_windows: point spans [on_frame, on_frame + 1), de-duplicated per pitch, hence
+    sorted and disjoint.  (spans int32 (K, 2), pitch_off int64 (89,))."""
+    rows = np.repeat(np.arange(N_PITCH), np.diff(notes.pitch_off))
+    key = np.unique(rows.astype(np.int64) * (1 << 32) + notes.on_frame.astype(np.int64))
+    p, f = key >> 32, key & 0xFFFFFFFF
+    spans = np.stack([f, f + 1], 1).astype(np.int32) if key.size else np.zeros((0, 2), np.int32)
+    return spans, np.searchsorted(p, np.arange(N_PITCH + 1), side="left").astype(np.int64)
 
 
 def column_grid(start_time: float, end_time: float, fs: float) -> np.ndarray:
@@ -222,12 +295,20 @@ class MaestroDataset(Dataset):
     """The reference's MaestroDataset (same arguments; items (mel (1, n_mels, T), roll (88, T)) CPU tensors, the bytes
     preprocess_and_cache writes for the same chunk), built on the device.  get_batch(indices) gives collate_fn's batch with
     mel and roll on the device in one launch of each kernel; DeviceBatchLoader is the DataLoader for it.  chunk_length=None:
-    one item per recording (whole file)."""
+    one item per recording (whole file).
+
+    onset_labels="midi" keeps every recording's note list (label_notes) on the device as well: get_batch then returns the
+    labels as {"frame": roll, "onset": onset_roll}, the onset roll marking the MIDI note-ons (re-struck keys included) on
+    the roll's column grid, and ref_notes(indices) gives the note lists notes.note_match_list scores against.  The default
+    "roll" builds neither table and returns what it always did."""
 
     def __init__(self, root_dir, csv_path=None, year=None, split="train", sr=16000, n_mels=229, hop_length=512, subset_size=None,
-                 chunk_length=None, overlap=0.0, return_waveform=False, device=None, max_resident_bytes=None):
+                 chunk_length=None, overlap=0.0, return_waveform=False, device=None, max_resident_bytes=None, onset_labels="roll"):
         if return_waveform:
             raise NotImplementedError("return_waveform=True is the AST experiment's data path (out of scope)")
+        if onset_labels not in ("roll", "midi"):
+            raise ValueError(f"onset_labels must be 'roll' or 'midi', got {onset_labels!r}")
+        self.onset_labels = onset_labels
         self.root_dir, self.sr, self.n_mels, self.hop_length = root_dir, int(sr), int(n_mels), int(hop_length)
         self.chunk_length, self.overlap, self.return_waveform = chunk_length, overlap, return_waveform
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -239,8 +320,12 @@ class MaestroDataset(Dataset):
         self.store = RecordingStore(paths, self.sr, self.device, [int(np.ceil(d * self.sr)) + 1 for d in durations], max_resident_bytes)
         # labels: span tables of every recording, one device array
         spans, poffs, fullw, notes, base = [], [], [], [], 0
+        tables = []                                         # onset_labels="midi": every recording's NoteTable
         for r in self.rows:
-            sp, po, fw, hn = label_spans(MidiFile(os.path.join(root_dir, r["midi_filename"])), fs)
+            midi = MidiFile(os.path.join(root_dir, r["midi_filename"]))
+            sp, po, fw, hn = label_spans(midi, fs)
+            if onset_labels == "midi":
+                tables.append(label_notes(midi, fs))
             spans.append(sp)
             poffs.append(po + base)
             fullw.append(fw)
@@ -274,6 +359,57 @@ class MaestroDataset(Dataset):
         self.pitch_off = torch.from_numpy(np.concatenate(poffs) if poffs else np.zeros(N_PITCH + 1, np.int64)).to(dev)
         self.cols = torch.from_numpy(cols).to(dev)
         self.fe = get_frontend(self.sr, self.n_mels, self.hop_length, dev)
+        if onset_labels == "midi":
+            self._upload_note_tables(tables)
+
+    def _upload_note_tables(self, tables) -> None:
+        """Note-on point spans of every recording for mt_roll_windows (the layout of spans / pitch_off), and for whole-file items
+        the note lists in ticks, cut to each item's frames: notes with on_tick < 320 * t_keep, offsets clipped to it."""
+        dev, on_sp, on_po, base = self.device, [], [], 0
+        for nt in tables:
+            sp, po = onset_spans(nt)
+            on_sp.append(sp)
+            on_po.append(po + base)
+            base += len(sp)
+        sp_all = np.concatenate(on_sp) if base else np.zeros((1, 2), np.int32)
+        self.onset_spans = torch.from_numpy(np.ascontiguousarray(sp_all, dtype=np.int32)).to(dev)
+        self.onset_pitch_off = torch.from_numpy(np.concatenate(on_po) if on_po else np.zeros(N_PITCH + 1, np.int64)).to(dev)
+        if self.chunk_length is not None:
+            return
+        if self.hop_length * TICKS_PER_SECOND != TICKS_PER_FRAME * self.sr:
+            raise ValueError(f"onset_labels='midi': note lists are kept on the grid of {TICKS_PER_FRAME} ticks per frame "
+                             f"(sr 16000, hop 512); got sr {self.sr}, hop {self.hop_length}")
+        ons, offs, ptrs, self.note_base = [], [], [], [0]
+        for nt, t in zip(tables, self.t_keep):
+            end = TICKS_PER_FRAME * int(t)
+            keep = nt.on_tick < end
+            rows = np.repeat(np.arange(N_PITCH), np.diff(nt.pitch_off))[keep]
+            ons.append(nt.on_tick[keep])
+            offs.append(np.minimum(nt.off_tick[keep], end))
+            ptrs.append(np.searchsorted(rows, np.arange(N_PITCH), side="left").astype(np.int64))      # 88 row starts, item-local
+            self.note_base.append(self.note_base[-1] + int(keep.sum()))
+        cat = lambda xs, dt: torch.from_numpy(np.ascontiguousarray(np.concatenate(xs) if xs else np.zeros(0), dtype=dt)).to(dev)
+        self.note_on, self.note_off, self.note_ptr = cat(ons, np.int32), cat(offs, np.int32), cat(ptrs, np.int64)
+
+    def ref_notes(self, indices) -> Dict[str, torch.Tensor]:
+        """The reference notes of whole-file items for notes.note_match_list: {"on", "off"} int32 ticks of 100 us and "ptr" int64
+        (len(indices) * 88 + 1,), on the device -- row (b, p) owns on/off[ptr[b*88 + p]:ptr[b*88 + p + 1]], sorted by onset;
+        notes with on_tick < 320 * t_keep, offsets clipped to 320 * t_keep.  Device slices of the tables uploaded at construction."""
+        if self.onset_labels != "midi":
+            raise RuntimeError("ref_notes needs a dataset built with onset_labels='midi'")
+        if self.chunk_length is not None:
+            raise NotImplementedError("ref_notes: note lists are kept for whole recordings only (chunk_length=None; the scripts' "
+                                      "--data_source full)")
+        idx = [int(i) for i in indices]
+        on, off, ptr, acc = [], [], [], 0
+        for i in idx:
+            lo, hi = self.note_base[i], self.note_base[i + 1]
+            on.append(self.note_on[lo:hi])
+            off.append(self.note_off[lo:hi])
+            ptr.append(self.note_ptr[i * N_PITCH:(i + 1) * N_PITCH] + acc)
+            acc += hi - lo
+        ptr.append(torch.full((1,), acc, dtype=torch.int64, device=self.device))
+        return {"on": torch.cat(on) if on else self.note_on[:0], "off": torch.cat(off) if off else self.note_off[:0], "ptr": torch.cat(ptr)}
 
     def __len__(self):
         return len(self.rec)
@@ -314,6 +450,11 @@ class MaestroDataset(Dataset):
                                             int(self.win_len[idx].max()), T_out, ptr(d32[2]), ptr(mel), ptr(cmax), st), "mt_mel_db_windows_f32")
             check(lib.mt_roll_windows(ptr(self.spans), ptr(self.pitch_off), ptr(self.cols), ptr(d32[3]), ptr(d64[1]), ptr(d32[4]), ptr(d32[2]),
                                       B, T_out, ptr(roll), st), "mt_roll_windows")
+            if self.onset_labels == "midi":                 # the note-ons on the same columns: point spans through the same kernel
+                onset_roll = torch.empty_like(roll)
+                check(lib.mt_roll_windows(ptr(self.onset_spans), ptr(self.onset_pitch_off), ptr(self.cols), ptr(d32[3]), ptr(d64[1]),
+                                          ptr(d32[4]), ptr(d32[2]), B, T_out, ptr(onset_roll), st), "mt_roll_windows")
+                return mel, {"frame": roll, "onset": onset_roll}, torch.from_numpy(t_keep.copy())
         return mel, roll, torch.from_numpy(t_keep.copy())
 
     def __getitem__(self, idx):
@@ -321,6 +462,8 @@ class MaestroDataset(Dataset):
             raise RuntimeError("MaestroDataset items are built on the GPU and cannot be read in a DataLoader worker process "
                                "(the reference's loaders use 8): use DeviceBatchLoader, or a DataLoader with num_workers=0")
         mel, roll, _ = self.get_batch([idx])
+        if isinstance(roll, dict):                          # items keep the reference's (mel, roll) shape; the onset roll is a batch label
+            roll = roll["frame"]
         return mel[0].cpu(), roll[0].cpu()
 
 

@@ -43,6 +43,13 @@ def make_optimizer(model, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-
     return opt
 
 
+def _to_device(targets, device):
+    """A roll, or the {"frame", "onset"} dict of rolls of MaestroDataset(onset_labels="midi"), on `device`."""
+    if isinstance(targets, dict):
+        return {k: v.to(device, non_blocking=True) for k, v in targets.items()}
+    return targets.to(device, non_blocking=True)
+
+
 def _forward(model, mel, all_heads: bool):
     """all_heads: the frame / onset / offset dict of CNNRNNModelLarge, whose loss is 0.5 frame + 0.25 onset + 0.25 offset;
     otherwise the frame logits alone (the reference's training loss)."""
@@ -72,7 +79,7 @@ def train_one_epoch(model, dataloader: Iterable, optimizer: FusedAdamClip, devic
             tuner.step_begin()
         optimizer.zero_grad()
         mel, roll, lengths = batch
-        mel, roll = mel.to(device, non_blocking=True), roll.to(device, non_blocking=True)
+        mel, roll = mel.to(device, non_blocking=True), _to_device(roll, device)
         logits = _forward(model, mel, all_heads)
         loss = model.compute_loss(logits, roll, lengths)
         step_loss = float(loss.item())
@@ -118,6 +125,6 @@ def evaluate(model, dataloader: Iterable, device, all_heads: bool = False) -> fl
     total, n = 0.0, 0
     for mel, roll, lengths in dataloader:
         logits = _forward(model, mel.to(device, non_blocking=True), all_heads)
-        total += float(model.compute_loss(logits, roll.to(device, non_blocking=True), lengths).item())
+        total += float(model.compute_loss(logits, _to_device(roll, device), lengths).item())
         n += 1
     return total / max(n, 1)

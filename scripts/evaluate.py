@@ -15,7 +15,9 @@ collective) and the per-sample values gathered by one small all-reduce.  `--data
 evaluates whole recordings under --root_dir, one sample per recording (MaestroDataset with chunk_length=None, featurised on
 the GPU); a recording longer than the inference recurrence takes (T * hidden_size < 2^24 frames) ends the run with an error
 naming it.  `--window_overlap SECONDS` instead runs every recording in overlapping 30 s windows stitched on its own frame grid
-(windows.py), which has no such limit.  MIDI / plot outputs, background mode and the results browser are out of scope.
+(windows.py), which has no such limit.  `--note_metrics --note_reference midi` (whole recordings only) scores the decoded notes
+against the MIDI note list of each recording, in which a re-struck key is a note of its own, instead of the runs of the label roll.
+MIDI / plot outputs, background mode and the results browser are out of scope.
 """
 import argparse
 import json
@@ -50,6 +52,10 @@ def main():
                     help="also report note-level precision / recall / F1 (onset within 50 ms; onset + offset within max(50 ms, 20%% of the "
                          "note), mir_eval's criteria on the 32 ms frame grid) against the runs of the label roll; headless prints "
                          "EVAL_NOTE_ONSET_F1= and EVAL_NOTE_ONSET_OFFSET_F1= after EVAL_MEAN_F1=")
+    ap.add_argument("--note_reference", choices=["roll", "midi"], default="roll",
+                    help="reference notes of --note_metrics: roll = the runs of the label roll (default; pedalled and gapless re-strikes are "
+                         "one note); midi = the recording's MIDI note list in 100 us ticks, pedal-extended and cut at the pitch's next onset "
+                         "(needs --data_source full)")
     ap.add_argument("--decoder", choices=["frame", "onset"], default="frame",
                     help="note decoder for --note_metrics: frame = runs of active frames (default); onset = notes start at rising edges "
                          "of the onset head (cnn_rnn_large trained with --train_all_heads; untrained heads make it meaningless)")
@@ -66,6 +72,10 @@ def main():
     args = ap.parse_args()
     say = (lambda *a, **k: None) if args.headless else print
 
+    if args.note_reference == "midi" and args.data_source != "full":
+        print("Error: --note_reference midi scores against the MIDI note list of whole recordings and needs --data_source full "
+              "(cache records hold rolls of chunks, not notes)")
+        return 1
     if not os.path.exists(args.model):
         print(f"Error: Model checkpoint not found: {args.model}")
         return 1
@@ -121,7 +131,7 @@ def main():
     if full:                                           # recordings first: one past the recurrence's limit ends the run before the model loads
         say(f"Loading full-file dataset from: {args.root_dir}")
         ds = mta.MaestroDataset(args.root_dir, split=args.split, year=args.year, n_mels=n_mels, subset_size=args.subset, chunk_length=None,
-                                device=dev)
+                                device=dev, onset_labels="midi" if args.note_reference == "midi" else "roll")
         t_max = ((1 << 24) - 1) // args.hidden_size        # lstm.hip: the inference recurrence takes T * H < 2^24
         for row, t in zip(ds.rows, ds.num_frames):
             if int(t) > t_max and args.window_overlap is None:          # (in windows every forward is 938 frames)
@@ -146,7 +156,8 @@ def main():
     notes = None
     if args.note_metrics:
         notes = E.note_metrics_dataset(model, ds, threshold, args.onset_threshold if args.decoder == "onset" else None, dev,
-                                       subset=args.subset, rank=rank, world=world, window_overlap=args.window_overlap)
+                                       subset=args.subset, rank=rank, world=world, window_overlap=args.window_overlap,
+                                       note_reference=args.note_reference)
     if rank == 0:
         if args.headless:
             print(f"EVAL_MEAN_F1={mean_f1:.6f}")
@@ -159,8 +170,9 @@ def main():
                        "num_samples": len(per_sample), "model": args.model, "model_type": args.model_type}
             if notes is not None:
                 m = notes["mean"]
-                print(f"Mean note F1 ({args.decoder} decoder): onset {m['onset_f1']:.6f}, onset+offset {m['onset_offset_f1']:.6f}")
-                results["note_metrics"] = {"decoder": args.decoder, "onset_threshold": args.onset_threshold if args.decoder == "onset" else None,
+                print(f"Mean note F1 ({args.decoder} decoder, {args.note_reference} reference): onset {m['onset_f1']:.6f}, onset+offset {m['onset_offset_f1']:.6f}")
+                results["note_metrics"] = {"decoder": args.decoder, "note_reference": args.note_reference,
+                                           "onset_threshold": args.onset_threshold if args.decoder == "onset" else None,
                                            **notes}
             os.makedirs(args.out_dir, exist_ok=True)
             with open(os.path.join(args.out_dir, "results.json"), "w") as f:

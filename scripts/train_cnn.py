@@ -10,7 +10,9 @@ Data source: the cache under --cached_dir when it exists and its metadata's chun
 chunk flag left out takes the cache's value, so invocations without them train from the cache as before); otherwise the
 recordings under --root_dir, decoded onto the GPU once and featurised per step (MaestroDataset + DeviceBatchLoader,
 music_transcription_amd/rawdata.py), where --subset_size counts recordings as in the reference.  Full-file training
-(no --chunk_length and no usable cache) is refused before the first step.
+(no --chunk_length and no usable cache) is refused before the first step.  `--train_all_heads --onset_labels midi` trains the
+onset head against the MIDI note-ons (a key struck again under the pedal or without a gap gets its onset) instead of the rising
+edges of the label roll; cache records hold no note list, so it always reads the recordings under --root_dir.
 
 One process per GPU.  Every step is the HIP training step (train-mode forward, backward, fused clip + Adam); with more
 than one rank each rank draws its own shard of the shuffled chunk indices (DistributedSampler) and the flat gradient
@@ -61,6 +63,10 @@ def main():
                     help="train the onset and offset heads too: loss 0.5 frame + 0.25 onset + 0.25 offset (cnn_rnn_large with heads "
                          "only).  Default off = the reference's frame-only loss, which leaves the onset head untrained, so "
                          "--decoder onset is meaningless on such a checkpoint")
+    ap.add_argument("--onset_labels", choices=["roll", "midi"], default="roll",
+                    help="onset targets of --train_all_heads: roll = rising edges of the label roll (default); midi = the MIDI note-ons, "
+                         "re-struck keys included.  midi reads the recordings under --root_dir even where a cache matches (cache records "
+                         "hold no note list)")
     ap.add_argument("--run_dir", default="outputs/train_cnn")
     ap.add_argument("--num_workers", type=int, default=4)
     ap.add_argument("--seed", type=int, default=0)
@@ -68,6 +74,10 @@ def main():
     if args.train_all_heads and (args.model not in ("cnn_rnn_large", "large") or not args.use_onset_offset_heads):
         print("Error: --train_all_heads needs --model cnn_rnn_large with its onset / offset heads (not --no_onset_offset_heads)",
               file=sys.stderr)
+        return 2
+    midi_onsets = args.onset_labels == "midi"
+    if midi_onsets and not args.train_all_heads:
+        print("Error: --onset_labels midi sets the onset head's targets and needs --train_all_heads", file=sys.stderr)
         return 2
 
     import pickle
@@ -82,10 +92,25 @@ def main():
         use_cache = meta.get("chunk_length") == chunk_length and meta.get("overlap") == overlap
     else:
         chunk_length, overlap, use_cache = args.chunk_length, args.chunk_overlap or 0.0, False
+    cache_matches = use_cache
+    if midi_onsets:
+        use_cache = False
     if not use_cache and chunk_length is None:
         print("Error: full-file training is not supported (the training recurrence takes chunk-length sequences): "
               "pass --chunk_length (e.g. 30.0) or a matching --cached_dir", file=sys.stderr)
         return 2
+    if midi_onsets:
+        from music_transcription_amd.preprocess import read_maestro_csv
+        try:
+            n_rec = len(read_maestro_csv(args.root_dir, "train", args.year, args.subset_size, None))
+        except (OSError, ValueError) as e:
+            n_rec, why_none = 0, str(e)
+        else:
+            why_none = "its csv lists no train recordings"
+        if n_rec == 0:
+            print(f"Error: --onset_labels midi reads the MIDI note lists of the recordings under --root_dir, and {args.root_dir} "
+                  f"has none ({why_none})", file=sys.stderr)
+            return 2
 
     import torch
     import torch.distributed as dist
@@ -119,8 +144,11 @@ def main():
     else:
         if rank == 0:
             why = "no cache" if meta is None else f"cache has chunk_length={meta.get('chunk_length')}, overlap={meta.get('overlap')}"
+            if midi_onsets and cache_matches:
+                why = "the cache matches, but --onset_labels midi needs the MIDI note lists and cache records hold none"
             print(f"Data source: raw recordings {args.root_dir} on the GPU (chunk_length={chunk_length}, overlap={overlap}; {why})", flush=True)
-        kw_raw = dict(year=args.year, n_mels=args.n_mels, subset_size=args.subset_size, chunk_length=chunk_length, device=dev)
+        kw_raw = dict(year=args.year, n_mels=args.n_mels, subset_size=args.subset_size, chunk_length=chunk_length, device=dev,
+                      onset_labels=args.onset_labels)
         train_ds = mta.MaestroDataset(args.root_dir, split="train", overlap=overlap, **kw_raw)
         val_ds = mta.MaestroDataset(args.root_dir, split="validation", overlap=0.0, **kw_raw)
     sampler = DistributedSampler(train_ds, num_replicas=world, rank=rank, shuffle=True, seed=args.seed, drop_last=True) if world > 1 else None

@@ -1,11 +1,13 @@
-"""Device time of mt_note_match_counts (DESIGN.md "Note-level F1"), frame and onset-gated decoders, on two shapes:
+"""Device time of mt_note_match_counts and mt_note_match_list (DESIGN.md "Note-level F1"), frame and onset-gated decoders, on two shapes:
 
   * chunks:     a batch of 128 chunks x 88 pitches x 938 frames (one forward's worth of 30 s chunks);
   * recordings: a padded batch of 8 whole recordings of 10-25 minutes (T up to ~47 000 frames), masked by `lengths`.
 
 Inputs are seeded synthetic logits and rolls with note-like runs (~6 % of the cells active).  Each case is warmed up, then
 timed with device events over --iters launches; GB/s counts the bytes the pass must read: the valid frames of the frame
-logits, the reference roll and (onset decoder) the onset logits.
+logits, the reference roll and (onset decoder) the onset logits.  The list matcher runs in the same process on the same logits,
+its note list being the runs of the same roll (so its counts must equal the roll matcher's); it reads the note list instead of
+the roll, and `list_over_roll` is its time over mt_note_match_counts'.
 
     python tools/note_metrics_bench.py [--iters 50] [--out note_metrics.json]
 """
@@ -49,9 +51,21 @@ def make_case(B, P, T, lengths, seed, device):
     return frame.contiguous(), onset.contiguous(), ref.float().contiguous()
 
 
+def roll_notes(ref):
+    """The runs of the (B, P, T) roll as a note list in ticks (320 per frame) on the device: {"on", "off", "ptr"}."""
+    import torch
+    B, P, T = ref.shape
+    r = torch.nn.functional.pad(ref.reshape(B * P, T) > 0, (1, 1))
+    rows, s = torch.nonzero(r[:, 1:] & ~r[:, :-1], as_tuple=True)          # row-major: every row's runs in time order
+    _, e = torch.nonzero(~r[:, 1:] & r[:, :-1], as_tuple=True)
+    ptr = torch.zeros(B * P + 1, dtype=torch.int64, device=ref.device)
+    ptr[1:] = torch.cumsum(torch.bincount(rows, minlength=B * P), 0)
+    return {"on": (320 * s).int().contiguous(), "off": (320 * e).int().contiguous(), "ptr": ptr}
+
+
 def time_case(name, frame, onset, ref, lengths, iters):
     import torch
-    from music_transcription_amd.notes import note_match_counts
+    from music_transcription_amd.notes import note_match_counts, note_match_list
     B, P, T = frame.shape
     valid = B * T if lengths is None else int(sum(lengths))
     out = {"case": name, "B": B, "P": P, "T": T, "valid_frames": valid}
@@ -70,6 +84,28 @@ def time_case(name, frame, onset, ref, lengths, iters):
         cs = c.sum(0).tolist()
         out[dec] = {"ms": round(ms, 4), "read_MB": round(nbytes / 1e6, 2), "GB_per_s": round(nbytes / (ms * 1e-3) / 1e9, 1),
                     "n_ref": cs[0], "n_est": cs[1], "tp_onset": cs[2], "tp_onset_offset": cs[3]}
+    notes = roll_notes(ref)
+    out["list_notes"] = int(notes["on"].numel())
+    for dec, on in (("frame", None), ("onset", onset)):
+        for _ in range(3):
+            c = note_match_list(frame, notes, 0.5, on, 0.5, lengths)
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(iters):
+            note_match_list(frame, notes, 0.5, on, 0.5, lengths)
+        e1.record()
+        torch.cuda.synchronize()
+        ms = e0.elapsed_time(e1) / iters
+        nbytes = valid * P * 4 * (2 if on is not None else 1) + 8 * out["list_notes"]
+        cs = c.sum(0).tolist()
+        out[dec + "_list"] = {"ms": round(ms, 4), "read_MB": round(nbytes / 1e6, 2), "GB_per_s": round(nbytes / (ms * 1e-3) / 1e9, 1),
+                              "list_over_roll": round(ms / out[dec]["ms"], 3), "n_ref": cs[0], "n_est": cs[1], "tp_onset": cs[2],
+                              "tp_onset_offset": cs[3]}
+        same = [out[dec][k] == out[dec + "_list"][k] for k in ("n_ref", "n_est", "tp_onset", "tp_onset_offset")]
+        if not all(same):
+            raise SystemExit(f"{name} ({dec}): the list matcher's counts differ from the roll matcher's on the roll's own runs: "
+                             f"{out[dec]} vs {out[dec + '_list']}")
     return out
 
 
