@@ -439,6 +439,17 @@ int    mt_note_match_counts(const float* frame_logits, const float* onset_logits
 int    mt_note_match_list(const float* frame_logits, const float* onset_logits, float thr_frame, float thr_onset,
                           const int* ref_on, const int* ref_off, const long long* ref_ptr, const long long* lengths,
                           unsigned long long* counts, int B, int P, int T, mt_stream_t stream);
+/* mt_note_match_counts / mt_note_match_list for a grid of thresholds in one pass: counts[b][i][j] (uint64 [B][Kf][Ko][4], zeroed on the
+ * stream) is bit for bit what the single-pair entry point returns for (thr_frame[i], thr_onset[j]) on the same inputs.  thr_frame[Kf]
+ * and thr_onset[Ko] are HOST arrays, taken by value at the call (no device copy, no synchronisation); any order, repeats allowed,
+ * every value in (0, 1).  1 <= Kf, Ko <= 16 and Kf * Ko <= 64.  With onset_logits == NULL (the frame decoder) Ko must be 1 and
+ * thr_onset may be NULL.  Every logit is read, and its sigmoid evaluated, once per launch.  Dimension limits as the single-pair calls. */
+int    mt_note_sweep_counts(const float* frame_logits, const float* onset_logits, const float* thr_frame, int Kf, const float* thr_onset,
+                            int Ko, const float* ref_roll, const long long* lengths, unsigned long long* counts, int B, int P, int T,
+                            mt_stream_t stream);
+int    mt_note_sweep_list(const float* frame_logits, const float* onset_logits, const float* thr_frame, int Kf, const float* thr_onset,
+                          int Ko, const int* ref_on, const int* ref_off, const long long* ref_ptr, const long long* lengths,
+                          unsigned long long* counts, int B, int P, int T, mt_stream_t stream);
 /* The onset-gated decoder with mt_roll_to_notes' contract: the NB chunks of frame_logits / onset_logits [NB][P][T] are one
  * recording of NB*T frames per pitch; counts[p], starts / ends in the reference's note order, capacity protocol unchanged. */
 int    mt_heads_to_notes(const float* frame_logits, const float* onset_logits, float thr_frame, float thr_onset, int NB, int P, int T,

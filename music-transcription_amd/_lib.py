@@ -145,6 +145,8 @@ _SIGS = {
     "mt_roll_to_notes": (i32, [vp, i32, C.c_float, i32, i32, i32, vp, vp, vp, i32, vp]),
     "mt_note_match_counts": (i32, [vp, vp, C.c_float, C.c_float, vp, vp, vp, i32, i32, i32, vp]),
     "mt_note_match_list": (i32, [vp, vp, C.c_float, C.c_float, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "mt_note_sweep_counts": (i32, [vp, vp, vp, i32, vp, i32, vp, vp, vp, i32, i32, i32, vp]),
+    "mt_note_sweep_list": (i32, [vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "mt_heads_to_notes": (i32, [vp, vp, C.c_float, C.c_float, i32, i32, i32, vp, vp, vp, i32, vp]),
     "mt_conv1_stats": (i32, [vp, vp, vp, vp, i32, i32, i32, vp]),
     "mt_bn_finalize": (i32, [vp, C.c_double, vp, vp, vp, vp, C.c_float, C.c_float, vp, vp, i32, vp, vp, vp, vp, i32, vp]),

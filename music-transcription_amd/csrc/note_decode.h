@@ -9,7 +9,9 @@
 
 namespace mt {
 
-__device__ __forceinline__ bool logit_active(float x, float thr) { return 1.0f / (1.0f + expf(-x)) > thr; }
+// (the sweep kernels evaluate logit_sigmoid once per cell and compare it with every threshold: the same bits as logit_active)
+__device__ __forceinline__ float logit_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
+__device__ __forceinline__ bool logit_active(float x, float thr) { return logit_sigmoid(x) > thr; }
 
 // One 64-frame window of the decoder.  Lane l holds frame g0 + l; o / a are that frame's onset-active and (frame OR onset)
 // activity.  Carries in: o_prev = onset activity of frame g0 - 1, open_prev = a note is open after frame g0 - 1; both are

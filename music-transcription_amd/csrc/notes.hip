@@ -5,6 +5,8 @@
 //   mt_note_match_list:   the same counts against a per-row note list in ticks of 100 us (the MIDI notes), which may hold re-struck keys;
 //   mt_heads_to_notes:    the onset-gated decoder with mt_roll_to_notes' output contract (main.py's note list).
 // One wave64 per pitch row; it walks the row in 64-frame windows (note_decode.h), SLAB windows of loads in flight at a time.
+#include <type_traits>
+
 #include "mt_common.h"
 #include "note_decode.h"
 
@@ -31,9 +33,18 @@ struct MatchState {
     int ref_on, ref_off, est_on, est_off;           // latest reference / estimate note (on = -8 before the first)
     int taken_r_on, taken_e_on;                     // onset-only: ends of the last taken edge
     int taken_r_onoff, taken_e_onoff;               // onset+offset: ends of the last taken edge
-    Edge q[4];
+    Edge q0, q1, q2, q3;                            // the queue, oldest first (named members: an array of them ends up in scratch)
     int nq;
 };
+
+// d = e if `take` (a select per member: four stores under four branches are merged into one store through a pointer that names
+// its queue slot at run time, and that keeps the whole queue in scratch)
+__device__ __forceinline__ void edge_copy(Edge& d, const Edge& e, bool take = true) {
+    d.r_on = take ? e.r_on : d.r_on;
+    d.r_off = take ? e.r_off : d.r_off;
+    d.e_on = take ? e.e_on : d.e_on;
+    d.e_off = take ? e.e_off : d.e_off;
+}
 
 __device__ __forceinline__ bool offset_ok(const Edge& e) {
     const int d = abs(e.r_off - e.e_off);
@@ -47,37 +58,98 @@ __device__ __forceinline__ void edge_found(MatchState& s) {
         s.taken_e_on = s.est_on;
     }
     const Edge e{s.ref_on, s.ref_off, s.est_on, s.est_off};
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-        if (k == (s.nq & 3)) s.q[k] = e;
-    s.nq = (s.nq & 3) + 1;
+    const int at = s.nq & 3;
+    edge_copy(s.q0, e, at == 0);
+    edge_copy(s.q1, e, at == 1);
+    edge_copy(s.q2, e, at == 2);
+    edge_copy(s.q3, e, at == 3);
+    s.nq = at + 1;
 }
 
 __device__ __forceinline__ void resolve(MatchState& s) {
-    while (s.nq > 0 && s.q[0].r_off >= 0 && s.q[0].e_off >= 0) {
-        const Edge e = s.q[0];
+    while (s.nq > 0 && s.q0.r_off >= 0 && s.q0.e_off >= 0) {
+        const Edge e{s.q0.r_on, s.q0.r_off, s.q0.e_on, s.q0.e_off};
         if (offset_ok(e) && e.r_on != s.taken_r_onoff && e.e_on != s.taken_e_onoff) {
             ++s.tp_onoff;
             s.taken_r_onoff = e.r_on;
             s.taken_e_onoff = e.e_on;
         }
-        s.q[0] = s.q[1]; s.q[1] = s.q[2]; s.q[2] = s.q[3];
+        edge_copy(s.q0, s.q1);
+        edge_copy(s.q1, s.q2);
+        edge_copy(s.q2, s.q3);
         --s.nq;
     }
 }
 
 __device__ __forceinline__ void est_close(MatchState& s, int g) {
     s.est_off = g;
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-        if (k < s.nq && s.q[k].e_on == s.est_on) s.q[k].e_off = g;
+    if (0 < s.nq && s.q0.e_on == s.est_on) s.q0.e_off = g;
+    if (1 < s.nq && s.q1.e_on == s.est_on) s.q1.e_off = g;
+    if (2 < s.nq && s.q2.e_on == s.est_on) s.q2.e_off = g;
+    if (3 < s.nq && s.q3.e_on == s.est_on) s.q3.e_off = g;
 }
 
 __device__ __forceinline__ void ref_close(MatchState& s, int g) {
     s.ref_off = g;
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-        if (k < s.nq && s.q[k].r_on == s.ref_on) s.q[k].r_off = g;
+    if (0 < s.nq && s.q0.r_on == s.ref_on) s.q0.r_off = g;
+    if (1 < s.nq && s.q1.r_on == s.ref_on) s.q1.r_off = g;
+    if (2 < s.nq && s.q2.r_on == s.ref_on) s.q2.r_off = g;
+    if (3 < s.nq && s.q3.r_on == s.ref_on) s.q3.r_off = g;
+}
+
+__device__ __forceinline__ void match_init(MatchState& s) {
+    s.n_ref = s.n_est = s.tp_on = s.tp_onoff = 0;
+    s.ref_on = s.est_on = -8;
+    s.ref_off = s.est_off = -8;
+    s.taken_r_on = s.taken_e_on = s.taken_r_onoff = s.taken_e_onoff = -8;
+    const Edge none{0, 0, 0, 0};
+    edge_copy(s.q0, none);
+    edge_copy(s.q1, none);
+    edge_copy(s.q2, none);
+    edge_copy(s.q3, none);
+    s.nq = 0;
+}
+
+// The events of the 64-frame window at g0 in frame order: the estimate's starts / closes and the reference's run edges rs / re.
+// Wave-uniform state.
+__device__ __forceinline__ void match_window(MatchState& s, const WindowEvents& est, unsigned long long rs, unsigned long long re, int g0) {
+    unsigned long long ev = est.starts | est.closes | rs | re;
+    while (ev) {
+        const int l = __ffsll((long long)ev) - 1;
+        const unsigned long long bit = 1ull << l;
+        const int g = g0 + l;
+        if (est.closes & bit) est_close(s, g);
+        if (re & bit) ref_close(s, g);
+        if (est.starts & bit) {
+            ++s.n_est;
+            s.est_on = g;
+            s.est_off = -1;
+            if (s.ref_on == g - 1) edge_found(s);
+        }
+        if (rs & bit) {
+            ++s.n_ref;
+            s.ref_on = g;
+            s.ref_off = -1;
+            if (s.est_on >= g - 1) edge_found(s);
+        }
+        resolve(s);
+        ev &= ev - 1;
+    }
+}
+
+// Notes that run to the end (or into the padding) end at L.
+__device__ __forceinline__ void match_finish(MatchState& s, bool est_open, bool ref_open, int L) {
+    if (est_open) est_close(s, L);
+    if (ref_open) ref_close(s, L);
+    resolve(s);
+}
+
+// c[0..4) += {n_ref, n_est, tp_onset, tp_onset_offset} of one pitch row (one lane calls this).
+__device__ __forceinline__ void counts_add(unsigned long long* c, int n_ref, int n_est, int tp_on, int tp_onoff) {
+    if (n_ref) atomicAdd(c + 0, (unsigned long long)n_ref);
+    if (n_est) atomicAdd(c + 1, (unsigned long long)n_est);
+    if (tp_on) atomicAdd(c + 2, (unsigned long long)tp_on);
+    if (tp_onoff) atomicAdd(c + 3, (unsigned long long)tp_onoff);
 }
 
 // counts[b] += {n_ref, n_est, tp_onset, tp_onset_offset} of pitch row (b, p).  Frames at or past lengths[b] are inactive on both sides.
@@ -92,11 +164,7 @@ __global__ __launch_bounds__(64 * NOTE_WAVES) void note_match_kernel(const float
     const int L = lengths ? (int)min((long long)T, max(0ll, lengths[b])) : T;
     const size_t base = (size_t)row * T;
     MatchState s;
-    s.n_ref = s.n_est = s.tp_on = s.tp_onoff = 0;
-    s.ref_on = s.est_on = -8;
-    s.ref_off = s.est_off = -8;
-    s.taken_r_on = s.taken_e_on = s.taken_r_onoff = s.taken_e_onoff = -8;
-    s.nq = 0;
+    match_init(s);
     unsigned long long o_prev = 0, open_prev = 0, r_prev = 0;
     for (int s0 = 0; s0 < L; s0 += 64 * NOTE_SLAB) {
         float xf[NOTE_SLAB], xo[NOTE_SLAB], xr[NOTE_SLAB];
@@ -119,40 +187,11 @@ __global__ __launch_bounds__(64 * NOTE_WAVES) void note_match_kernel(const float
             const unsigned long long rm = __ballot(in && xr[w] > 0.0f);
             const unsigned long long rs = rm & ~((rm << 1) | r_prev), re = ~rm & ((rm << 1) | r_prev);
             r_prev = rm >> 63;
-            unsigned long long ev = est.starts | est.closes | rs | re;
-            while (ev) {                                       // events of this window in frame order; wave-uniform state
-                const int l = __ffsll((long long)ev) - 1;
-                const unsigned long long bit = 1ull << l;
-                const int g = g0 + l;
-                if (est.closes & bit) est_close(s, g);
-                if (re & bit) ref_close(s, g);
-                if (est.starts & bit) {
-                    ++s.n_est;
-                    s.est_on = g;
-                    s.est_off = -1;
-                    if (s.ref_on == g - 1) edge_found(s);
-                }
-                if (rs & bit) {
-                    ++s.n_ref;
-                    s.ref_on = g;
-                    s.ref_off = -1;
-                    if (s.est_on >= g - 1) edge_found(s);
-                }
-                resolve(s);
-                ev &= ev - 1;
-            }
+            match_window(s, est, rs, re, g0);
         }
     }
-    if (open_prev) est_close(s, L);                             // notes that run to the end (or into the padding) end at L
-    if (r_prev) ref_close(s, L);
-    resolve(s);
-    if (lane == 0) {
-        unsigned long long* c = counts + 4 * (size_t)b;
-        if (s.n_ref) atomicAdd(c + 0, (unsigned long long)s.n_ref);
-        if (s.n_est) atomicAdd(c + 1, (unsigned long long)s.n_est);
-        if (s.tp_on) atomicAdd(c + 2, (unsigned long long)s.tp_on);
-        if (s.tp_onoff) atomicAdd(c + 3, (unsigned long long)s.tp_onoff);
-    }
+    match_finish(s, open_prev != 0, r_prev != 0, L);
+    if (lane == 0) counts_add(counts + 4 * (size_t)b, s.n_ref, s.n_est, s.tp_on, s.tp_onoff);
 }
 
 // ------------------------------------------------------------------------------------------------ matching against a note list
@@ -230,6 +269,61 @@ __device__ __forceinline__ void drain(RefCursor& r, int lane, int limit, int end
     }
 }
 
+// The row's slice of the note list, positioned at note `at` (0 at the start of a row; the sweep kernel comes back to a parked position).
+__device__ __forceinline__ void cursor_open(RefCursor& r, const int* ref_on, const int* ref_off, const long long* ref_ptr, int row, int at,
+                                            int lane) {
+    const long long p0 = ref_ptr[row];
+    r.on = ref_on + p0;
+    r.off = ref_off + p0;
+    r.n = (int)min(2147483647ll, max(0ll, ref_ptr[row + 1] - p0));
+    r.at = at;
+    cursor_load(r, at >> 6, lane, r.c_on, r.c_off);
+    cursor_load(r, (at >> 6) + 1, lane, r.n_on, r.n_off);
+}
+
+struct ListState {
+    ListCrit c_on, c_onoff;
+    int n_ref, n_est;
+    int prev_on, prev_off, cur_on, cur_off;           // the previous and the latest estimate, in ticks
+};
+
+__device__ __forceinline__ void list_init(ListState& s) {
+    s.c_on = s.c_onoff = ListCrit{0, 0, 0, 0, 0};
+    s.n_ref = s.n_est = 0;
+    s.prev_on = s.prev_off = s.cur_on = s.cur_off = NO_NOTE;
+}
+
+// The estimate's events of the 64-frame window at g0 in frame order.  Wave-uniform state.
+__device__ __forceinline__ void list_window(ListState& s, RefCursor& r, const WindowEvents& est, int g0, int lane, int end_tick) {
+    unsigned long long ev = est.starts | est.closes;
+    while (ev) {
+        const int l = __ffsll((long long)ev) - 1;
+        const unsigned long long bit = 1ull << l;
+        const int tick = TICKS_PER_FRAME * (g0 + l);
+        if (est.closes & bit) s.cur_off = tick;
+        if (est.starts & bit) {                            // the latest estimate has ended: settle what cannot reach the new one
+            drain(r, lane, min(tick - ONSET_TOL, end_tick), end_tick, s.prev_on, s.prev_off, s.cur_on, s.cur_off, s.n_ref, s.c_on, s.c_onoff);
+            crit_shift(s.c_on);
+            crit_shift(s.c_onoff);
+            s.prev_on = s.cur_on;
+            s.prev_off = s.cur_off;
+            s.cur_on = tick;
+            ++s.n_est;
+        }
+        ev &= ev - 1;
+    }
+}
+
+// A note that runs to the end (or into the padding) ends at L; the rest of the list is read; the last components close.
+__device__ __forceinline__ void list_finish(ListState& s, RefCursor& r, bool est_open, int lane, int end_tick, int& tp_on, int& tp_onoff) {
+    if (est_open) s.cur_off = end_tick;
+    drain(r, lane, end_tick, end_tick, s.prev_on, s.prev_off, s.cur_on, s.cur_off, s.n_ref, s.c_on, s.c_onoff);
+    crit_shift(s.c_on);
+    crit_shift(s.c_onoff);
+    tp_on = s.c_on.tp + min(s.c_on.e_a, s.c_on.v_a);
+    tp_onoff = s.c_onoff.tp + min(s.c_onoff.e_a, s.c_onoff.v_a);
+}
+
 // counts[b] += {n_ref, n_est, tp_onset, tp_onset_offset} of pitch row (b, p) against the notes ref_on/ref_off[ref_ptr[row] .. ref_ptr[row+1]).
 // Frames at or past L = lengths[b] are inactive; reference notes with on >= 320 L are not read and offsets are clipped to 320 L.
 __global__ __launch_bounds__(64 * NOTE_WAVES) void note_match_list_kernel(const float* __restrict__ frame, const float* __restrict__ onset,
@@ -244,17 +338,10 @@ __global__ __launch_bounds__(64 * NOTE_WAVES) void note_match_list_kernel(const 
     const int L = lengths ? (int)min((long long)T, max(0ll, lengths[b])) : T;
     const int end_tick = TICKS_PER_FRAME * L;
     const size_t base = (size_t)row * T;
-    const long long p0 = ref_ptr[row];
     RefCursor r;
-    r.on = ref_on + p0;
-    r.off = ref_off + p0;
-    r.n = (int)min(2147483647ll, max(0ll, ref_ptr[row + 1] - p0));
-    r.at = 0;
-    cursor_load(r, 0, lane, r.c_on, r.c_off);
-    cursor_load(r, 1, lane, r.n_on, r.n_off);
-    ListCrit c_on{0, 0, 0, 0, 0}, c_onoff{0, 0, 0, 0, 0};
-    int n_ref = 0, n_est = 0;
-    int prev_on = NO_NOTE, prev_off = NO_NOTE, cur_on = NO_NOTE, cur_off = NO_NOTE;
+    cursor_open(r, ref_on, ref_off, ref_ptr, row, 0, lane);
+    ListState s;
+    list_init(s);
     unsigned long long o_prev = 0, open_prev = 0;
     for (int s0 = 0; s0 < L; s0 += 64 * NOTE_SLAB) {
         float xf[NOTE_SLAB], xo[NOTE_SLAB];
@@ -273,37 +360,12 @@ __global__ __launch_bounds__(64 * NOTE_WAVES) void note_match_list_kernel(const 
             const bool f = in && logit_active(xf[w], thr_f);
             const bool o = onset ? (in && logit_active(xo[w], thr_o)) : f;
             const WindowEvents est = decode_window(o, f || o, lane, o_prev, open_prev);
-            unsigned long long ev = est.starts | est.closes;
-            while (ev) {                                       // events of this window in frame order; wave-uniform state
-                const int l = __ffsll((long long)ev) - 1;
-                const unsigned long long bit = 1ull << l;
-                const int tick = TICKS_PER_FRAME * (g0 + l);
-                if (est.closes & bit) cur_off = tick;
-                if (est.starts & bit) {                        // the latest estimate has ended: settle what cannot reach the new one
-                    drain(r, lane, min(tick - ONSET_TOL, end_tick), end_tick, prev_on, prev_off, cur_on, cur_off, n_ref, c_on, c_onoff);
-                    crit_shift(c_on);
-                    crit_shift(c_onoff);
-                    prev_on = cur_on;
-                    prev_off = cur_off;
-                    cur_on = tick;
-                    ++n_est;
-                }
-                ev &= ev - 1;
-            }
+            list_window(s, r, est, g0, lane, end_tick);
         }
     }
-    if (open_prev) cur_off = end_tick;                          // a note that runs to the end (or into the padding) ends at L
-    drain(r, lane, end_tick, end_tick, prev_on, prev_off, cur_on, cur_off, n_ref, c_on, c_onoff);
-    crit_shift(c_on);
-    crit_shift(c_onoff);
-    const int tp_on = c_on.tp + min(c_on.e_a, c_on.v_a), tp_onoff = c_onoff.tp + min(c_onoff.e_a, c_onoff.v_a);
-    if (lane == 0) {
-        unsigned long long* c = counts + 4 * (size_t)b;
-        if (n_ref) atomicAdd(c + 0, (unsigned long long)n_ref);
-        if (n_est) atomicAdd(c + 1, (unsigned long long)n_est);
-        if (tp_on) atomicAdd(c + 2, (unsigned long long)tp_on);
-        if (tp_onoff) atomicAdd(c + 3, (unsigned long long)tp_onoff);
-    }
+    int tp_on, tp_onoff;
+    list_finish(s, r, open_prev != 0, lane, end_tick, tp_on, tp_onoff);
+    if (lane == 0) counts_add(counts + 4 * (size_t)b, s.n_ref, s.n_est, tp_on, tp_onoff);
 }
 
 // ------------------------------------------------------------------------------------------------ onset-gated notes
@@ -357,6 +419,184 @@ __global__ __launch_bounds__(64 * NOTE_WAVES) void heads_notes_kernel(const floa
     }
 }
 
+// ------------------------------------------------------------------------------------------------ threshold sweep
+// The counts of note_match_kernel / note_match_list_kernel for every pair (thr_f[i], thr_o[j]) of a grid, in one pass over the logits.
+// One workgroup of SWEEP_WAVES = NOTE_SLAB waves per pitch row.  Per slab of 64 * NOTE_SLAB frames, wave w loads window w of the slab
+// (the next slab's loads are issued before the walk), evaluates logit_sigmoid once per cell and leaves one ballot per threshold in
+// LDS -- Kf + Ko compares per cell where Kf * Ko pairs would take 2 Kf Ko -- with the roll's run edges of the window beside them.
+// Then wave w walks pairs w, w + SWEEP_WAVES, ... over the slab with decode_window and the matchers above, reading its masks from LDS
+// (one address per wave: a broadcast).  A pair's matcher state is wave-uniform; between slabs it is parked in LDS (one lane writes
+// it, readfirstlane brings it back into scalar registers), the list cursor as its position alone (its 64-note chunks come back from L2).
+constexpr int SWEEP_WAVES = NOTE_SLAB;
+constexpr int SWEEP_MAX_K = 16;           // thresholds per axis
+constexpr int SWEEP_MAX_PAIRS = 64;
+
+struct SweepThr {
+    float f[SWEEP_MAX_K], o[SWEEP_MAX_K];
+};
+
+struct RollPair {
+    MatchState s;
+    int o_prev, open_prev;                // decode_window's carries
+};
+
+struct ListPair {
+    ListState s;
+    int at;                               // RefCursor::at
+    int o_prev, open_prev;
+};
+
+__device__ __forceinline__ void pair_init(RollPair& p) {
+    match_init(p.s);
+    p.o_prev = p.open_prev = 0;
+}
+
+__device__ __forceinline__ void pair_init(ListPair& p) {
+    list_init(p.s);
+    p.at = p.o_prev = p.open_prev = 0;
+}
+
+template <typename S>
+__device__ __forceinline__ void park(const S& st, int* slot, int lane) {
+    constexpr int N = sizeof(S) / 4;
+    static_assert(sizeof(S) == 4 * N, "parked state is whole dwords");
+    int v[N];
+    __builtin_memcpy(v, &st, sizeof(S));
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) slot[k] = v[k];
+    }
+}
+
+template <typename S>
+__device__ __forceinline__ void unpark(S& st, const int* slot) {
+    constexpr int N = sizeof(S) / 4;
+    int v[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] = __builtin_amdgcn_readfirstlane(slot[k]);
+    __builtin_memcpy(&st, v, sizeof(S));
+}
+
+__device__ __forceinline__ unsigned long long uniform64(unsigned long long v) {
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
+    return ((unsigned long long)hi << 32) | lo;
+}
+
+// counts[b][i][j] += the four counts of pitch row (b, p) = blockIdx.x at thresholds (thr.f[i], thr.o[j]); i < Kf, j < Ko, Kf Ko <= 64.
+// LIST: against ref_on / ref_off / ref_ptr as note_match_list_kernel, otherwise against the roll `ref` as note_match_kernel.
+template <bool LIST>
+__global__ __launch_bounds__(64 * SWEEP_WAVES) void note_sweep_kernel(const float* __restrict__ frame, const float* __restrict__ onset, SweepThr thr,
+                                                                      int Kf, int Ko, const float* __restrict__ ref, const int* __restrict__ ref_on,
+                                                                      const int* __restrict__ ref_off, const long long* __restrict__ ref_ptr,
+                                                                      const long long* __restrict__ lengths,
+                                                                      unsigned long long* __restrict__ counts, int P, int T) {
+    using Pair = typename std::conditional<LIST, ListPair, RollPair>::type;
+    constexpr int PARK = sizeof(Pair) / 4;
+    __shared__ unsigned long long fmask[NOTE_SLAB][SWEEP_MAX_K], omask[NOTE_SLAB][SWEEP_MAX_K];     // [window][threshold]: active lanes
+    __shared__ unsigned long long rmask[NOTE_SLAB], rstart[NOTE_SLAB], rend[NOTE_SLAB];             // roll: active, run starts, run ends
+    __shared__ int parked[SWEEP_MAX_PAIRS][PARK];
+    __shared__ float thr_f[SWEEP_MAX_K], thr_o[SWEEP_MAX_K];   // the kernel arguments, moved here once: 32 scalar registers less in the walk
+    const int row = blockIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int lane = threadIdx.x & 63;
+    const int b = row / P;
+    const int L = lengths ? (int)min((long long)T, max(0ll, lengths[b])) : T;
+    if (L <= 0) return;                                        // no frame, no note: the counts stay zero (the whole workgroup leaves)
+    const int end_tick = TICKS_PER_FRAME * L;
+    const size_t base = (size_t)row * T;
+    const int n_pairs = Kf * Ko;
+    float xf, xo, xr = 0.0f, xb = 0.0f;                        // this wave's window of the slab: frame, onset, roll, roll one frame before it
+    const auto load = [&](int s0) {
+        const int g0 = s0 + 64 * wave, g = g0 + lane;
+        const bool in = g < L;
+        xf = in ? frame[base + g] : 0.0f;
+        xo = (in && onset) ? onset[base + g] : 0.0f;
+        if (!LIST) {
+            xr = in ? ref[base + g] : 0.0f;
+            xb = (g0 > 0 && g0 <= L) ? ref[base + g0 - 1] : 0.0f;
+        }
+    };
+    load(0);
+#pragma unroll
+    for (int k = 0; k < SWEEP_MAX_K; ++k)
+        if ((int)threadIdx.x == k) {
+            thr_f[k] = thr.f[k];
+            thr_o[k] = thr.o[k];
+        }
+    __syncthreads();
+    for (int s0 = 0; s0 < L; s0 += 64 * NOTE_SLAB) {
+        const bool last = s0 + 64 * NOTE_SLAB >= L;
+        {                                                      // stage window `wave` of the slab
+            const bool in = s0 + 64 * wave + lane < L;
+            const float sf = logit_sigmoid(xf), so = logit_sigmoid(xo);
+#pragma unroll
+            for (int i = 0; i < SWEEP_MAX_K; ++i)
+                if (i < Kf) {
+                    const unsigned long long m = __ballot(in && sf > thr_f[i]);
+                    if (lane == 0) fmask[wave][i] = m;
+                }
+            if (onset) {
+#pragma unroll
+                for (int j = 0; j < SWEEP_MAX_K; ++j)
+                    if (j < Ko) {
+                        const unsigned long long m = __ballot(in && so > thr_o[j]);
+                        if (lane == 0) omask[wave][j] = m;
+                    }
+            }
+            if (!LIST) {
+                const unsigned long long rm = __ballot(in && xr > 0.0f);
+                const unsigned long long r_prev = __ballot(xb > 0.0f) ? 1ull : 0ull;
+                if (lane == 0) {
+                    rmask[wave] = rm;
+                    rstart[wave] = rm & ~((rm << 1) | r_prev);
+                    rend[wave] = ~rm & ((rm << 1) | r_prev);
+                }
+            }
+        }
+        if (!last) load(s0 + 64 * NOTE_SLAB);
+        __syncthreads();
+        for (int pair = wave; pair < n_pairs; pair += SWEEP_WAVES) {
+            const int i = pair / Ko, j = pair - i * Ko;
+            Pair st;
+            if (s0 == 0) pair_init(st);
+            else unpark(st, parked[pair]);
+            RefCursor r;
+            if constexpr (LIST) cursor_open(r, ref_on, ref_off, ref_ptr, row, st.at, lane);
+            unsigned long long o_prev = (unsigned long long)st.o_prev, open_prev = (unsigned long long)st.open_prev;
+#pragma unroll 1
+            for (int w = 0; w < NOTE_SLAB; ++w) {
+                const int g0 = s0 + 64 * w;
+                if (g0 >= L) break;
+                const unsigned long long fm = uniform64(fmask[w][i]);
+                const unsigned long long om = onset ? uniform64(omask[w][j]) : fm;
+                const bool f = (fm >> lane) & 1ull, o = (om >> lane) & 1ull;
+                const WindowEvents est = decode_window(o, f || o, lane, o_prev, open_prev);
+                if constexpr (LIST) list_window(st.s, r, est, g0, lane, end_tick);
+                else match_window(st.s, est, uniform64(rstart[w]), uniform64(rend[w]), g0);
+            }
+            if (!last) {
+                st.o_prev = (int)o_prev;
+                st.open_prev = (int)open_prev;
+                if constexpr (LIST) st.at = r.at;
+                park(st, parked[pair], lane);
+            } else {
+                unsigned long long* c = counts + 4 * ((size_t)b * n_pairs + pair);
+                if constexpr (LIST) {
+                    int tp_on, tp_onoff;
+                    list_finish(st.s, r, open_prev != 0, lane, end_tick, tp_on, tp_onoff);
+                    if (lane == 0) counts_add(c, st.s.n_ref, st.s.n_est, tp_on, tp_onoff);
+                } else {
+                    const unsigned long long rm = uniform64(rmask[((L - 1 - s0) >> 6)]);
+                    match_finish(st.s, open_prev != 0, (rm >> 63) != 0, L);
+                    if (lane == 0) counts_add(c, st.s.n_ref, st.s.n_est, st.s.tp_on, st.s.tp_onoff);
+                }
+            }
+        }
+        if (!last) __syncthreads();                            // the next slab's masks replace these
+    }
+}
+
 }  // namespace mt
 
 using namespace mt;
@@ -389,6 +629,51 @@ extern "C" int mt_note_match_list(const float* frame_logits, const float* onset_
     const int rows = B * P;
     hipLaunchKernelGGL(note_match_list_kernel, dim3((rows + NOTE_WAVES - 1) / NOTE_WAVES), dim3(64 * NOTE_WAVES), 0, st, frame_logits, onset_logits,
                        thr_frame, thr_onset, ref_on, ref_off, ref_ptr, lengths, counts, B, P, T);
+    MT_CHECK_LAUNCH();
+    return MT_OK;
+}
+
+// The checks the two sweep entry points share; the thresholds end up in `thr`, which the kernel takes by value.
+static int sweep_arguments(const char* who, const float* onset_logits, const float* thr_frame, int Kf, const float* thr_onset, int Ko, SweepThr& thr) {
+    MT_REQUIRE(thr_frame && (thr_onset || !onset_logits), MT_EINVAL, "%s: null threshold array", who);
+    MT_REQUIRE(Kf >= 1 && Kf <= SWEEP_MAX_K && Ko >= 1 && Ko <= SWEEP_MAX_K && Kf * Ko <= SWEEP_MAX_PAIRS, MT_EINVAL,
+               "%s: needs 1 <= Kf, Ko <= %d and Kf * Ko <= %d, got Kf = %d, Ko = %d", who, SWEEP_MAX_K, SWEEP_MAX_PAIRS, Kf, Ko);
+    MT_REQUIRE(onset_logits || Ko == 1, MT_EINVAL, "%s: without onset logits (the frame decoder) Ko must be 1, got %d", who, Ko);
+    for (int k = 0; k < SWEEP_MAX_K; ++k) {
+        thr.f[k] = k < Kf ? thr_frame[k] : 0.5f;
+        thr.o[k] = (onset_logits && k < Ko) ? thr_onset[k] : 0.5f;
+        MT_REQUIRE(thr.f[k] > 0.0f && thr.f[k] < 1.0f && thr.o[k] > 0.0f && thr.o[k] < 1.0f, MT_EINVAL, "%s: thresholds must lie in (0, 1)", who);
+    }
+    return MT_OK;
+}
+
+extern "C" int mt_note_sweep_counts(const float* frame_logits, const float* onset_logits, const float* thr_frame, int Kf, const float* thr_onset,
+                                    int Ko, const float* ref_roll, const long long* lengths, unsigned long long* counts, int B, int P, int T,
+                                    mt_stream_t stream) {
+    MT_REQUIRE(frame_logits && ref_roll && counts, MT_EINVAL, "mt_note_sweep_counts: null pointer");
+    MT_REQUIRE(B > 0 && P > 0 && T > 0 && (long long)B * P < 2147483647ll && T < (1 << 30), MT_EINVAL, "mt_note_sweep_counts: bad dims");
+    SweepThr thr;
+    if (const int rc = sweep_arguments("mt_note_sweep_counts", onset_logits, thr_frame, Kf, thr_onset, Ko, thr)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    MT_CHECK_HIP(hipMemsetAsync(counts, 0, (size_t)B * Kf * Ko * 4 * sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(note_sweep_kernel<false>, dim3(B * P), dim3(64 * SWEEP_WAVES), 0, st, frame_logits, onset_logits, thr, Kf, Ko, ref_roll,
+                       (const int*)nullptr, (const int*)nullptr, (const long long*)nullptr, lengths, counts, P, T);
+    MT_CHECK_LAUNCH();
+    return MT_OK;
+}
+
+extern "C" int mt_note_sweep_list(const float* frame_logits, const float* onset_logits, const float* thr_frame, int Kf, const float* thr_onset,
+                                  int Ko, const int* ref_on, const int* ref_off, const long long* ref_ptr, const long long* lengths,
+                                  unsigned long long* counts, int B, int P, int T, mt_stream_t stream) {
+    MT_REQUIRE(frame_logits && ref_on && ref_off && ref_ptr && counts, MT_EINVAL, "mt_note_sweep_list: null pointer");
+    MT_REQUIRE(B > 0 && P > 0 && T > 0 && (long long)B * P < 2147483647ll && (long long)T * TICKS_PER_FRAME < 2147483647ll - 64 * NOTE_SLAB,
+               MT_EINVAL, "mt_note_sweep_list: bad dims (frame times must fit 31 bits of 100 us ticks)");
+    SweepThr thr;
+    if (const int rc = sweep_arguments("mt_note_sweep_list", onset_logits, thr_frame, Kf, thr_onset, Ko, thr)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    MT_CHECK_HIP(hipMemsetAsync(counts, 0, (size_t)B * Kf * Ko * 4 * sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(note_sweep_kernel<true>, dim3(B * P), dim3(64 * SWEEP_WAVES), 0, st, frame_logits, onset_logits, thr, Kf, Ko,
+                       (const float*)nullptr, ref_on, ref_off, ref_ptr, lengths, counts, P, T);
     MT_CHECK_LAUNCH();
     return MT_OK;
 }

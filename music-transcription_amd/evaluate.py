@@ -10,6 +10,9 @@
     against the runs of the label roll (note_reference="roll") or the MIDI note list of whole recordings ("midi": re-struck keys
     are reference notes of their own, times in 100 us ticks), for the frame decoder or the onset-gated one; decoding and matching
     are one counting pass over the logits (notes.note_match_counts / note_match_list), samples of any length batched through `lengths`.
+  * `tune_note_thresholds` = tune_threshold's schedule on note F1, over the frame threshold and (onset-gated decoder) the onset
+    threshold at once: the model runs once, every round is one sweep pass per group (notes.note_sweep_counts: each cell's sigmoid is
+    evaluated once for the whole grid).  `search_note_thresholds` is the search alone, on any callable.
   * `window_overlap` (seconds, whole-file datasets): every recording runs in overlapping 30 s windows stitched on its own
     frame grid (windows.collect_logits_windows) instead of one recurrence over the whole file;
   * recordings / chunks shard over ranks with no data-path collective (parallel.py); per-sample F1 values are
@@ -129,34 +132,45 @@ def note_metrics_dataset(model, dataset, threshold: float = 0.5, onset_threshold
     (dataset.ref_notes: a whole-file MaestroDataset built with onset_labels="midi").  Unweighted means over samples, as
     evaluate_dataset (window_overlap too)."""
     from .notes import note_match_counts, note_match_list, note_prf
-    if note_reference not in ("roll", "midi"):
-        raise ValueError(f"note_reference must be 'roll' or 'midi', got {note_reference!r}")
-    if note_reference == "midi" and (getattr(dataset, "onset_labels", None) != "midi" or getattr(dataset, "chunk_length", 0) is not None):
-        raise ValueError("note_reference='midi' scores against the MIDI note list of whole recordings: it needs "
-                         "MaestroDataset(chunk_length=None, onset_labels='midi') (scripts/evaluate.py --data_source full)")
+    _check_note_reference(dataset, note_reference)
     n = len(dataset) if subset is None else min(subset, len(dataset))
     mine = list(shard_range(n, rank, world))
     onset = onset_threshold is not None
     lr = _collect(model, dataset, mine, device, window_overlap, all_heads=onset)
     vals = {k: [] for k in NOTE_METRIC_KEYS}
-    for s in range(0, len(lr), max_batch):            # one counts pass per group; unequal lengths padded and masked by `lengths`
-        grp = lr[s:s + max_batch]
-        lengths = [int(x[1].shape[-1]) for x in grp]
-        T = max(lengths)
-        pad = lambda t: torch.nn.functional.pad(t, (0, T - t.shape[-1]))
-        frame = torch.stack([pad(x[1]) for x in grp])
-        on = torch.stack([pad(x[3]) for x in grp]) if onset else None
+    for frame, on, ref, lengths in _note_groups(lr, dataset, onset, note_reference, max_batch):
         if note_reference == "midi":
-            counts = note_match_list(frame, dataset.ref_notes([x[0] for x in grp]), threshold, on, onset_threshold if onset else 0.5, lengths)
+            counts = note_match_list(frame, ref, threshold, on, onset_threshold if onset else 0.5, lengths)
         else:
-            roll = torch.stack([pad(x[2]) for x in grp])
-            counts = note_match_counts(frame, roll, threshold, on, onset_threshold if onset else 0.5, lengths)
+            counts = note_match_counts(frame, ref, threshold, on, onset_threshold if onset else 0.5, lengths)
         for m in note_prf(counts):
             for c in ("onset", "onset_offset"):
                 for k, v in zip(("precision", "recall", "f1"), m[c]):
                     vals[f"{c}_{k}"].append(v)
     per = {k: gather_values(mine, v, n) for k, v in vals.items()}
     return {"mean": {k: (float(np.mean(v)) if v else 0.0) for k, v in per.items()}, "per_sample": per}
+
+
+def _check_note_reference(dataset, note_reference: str) -> None:
+    if note_reference not in ("roll", "midi"):
+        raise ValueError(f"note_reference must be 'roll' or 'midi', got {note_reference!r}")
+    if note_reference == "midi" and (getattr(dataset, "onset_labels", None) != "midi" or getattr(dataset, "chunk_length", 0) is not None):
+        raise ValueError("note_reference='midi' scores against the MIDI note list of whole recordings: it needs "
+                         "MaestroDataset(chunk_length=None, onset_labels='midi') (scripts/evaluate.py --data_source full)")
+
+
+def _note_groups(lr, dataset, onset: bool, note_reference: str, max_batch: int):
+    """The collected samples in groups of max_batch, one counts pass each: (frame (b, 88, T), onset or None, reference roll or note
+    list, lengths); unequal lengths padded to the group's longest and masked by `lengths`."""
+    for s in range(0, len(lr), max_batch):
+        grp = lr[s:s + max_batch]
+        lengths = [int(x[1].shape[-1]) for x in grp]
+        T = max(lengths)
+        pad = lambda t: torch.nn.functional.pad(t, (0, T - t.shape[-1]))
+        frame = torch.stack([pad(x[1]) for x in grp])
+        on = torch.stack([pad(x[3]) for x in grp]) if onset else None
+        ref = dataset.ref_notes([x[0] for x in grp]) if note_reference == "midi" else torch.stack([pad(x[2]) for x in grp])
+        yield frame, on, ref, lengths
 
 
 def tune_threshold(model, dataset, device="cuda", subset: Optional[int] = None, tune_range=(0.05, 0.95), tune_step=0.1,
@@ -189,3 +203,76 @@ def tune_threshold(model, dataset, device="cuda", subset: Optional[int] = None, 
         if step < tune_min_step:
             break
     return best_t, best_f1
+
+
+def search_note_thresholds(mean_f1, two_axes: bool = True, tune_range=(0.05, 0.95), tune_step=0.1, tune_min_step=0.01, tune_rounds=6, log=None):
+    """tune_threshold's coarse-to-fine schedule on the frame threshold and, with two_axes, the onset threshold at once (no GPU in
+    here).  mean_f1(frame_ths, onset_ths) -> (Kf, Ko) array of the objective; onset_ths is None and Ko = 1 without two_axes.  A
+    round's candidates on each axis are np.arange(min, max + step / 2, step); pairs are visited frame-major and replace the best
+    only on strict improvement, starting from (0.5, 0.5) at -1; the next window on each axis is best +- 2 step clipped to
+    [0.01, 0.99]; the step halves, and the search ends when it falls below tune_min_step or after tune_rounds.
+    -> (frame threshold, onset threshold or None, best value)."""
+    f_min, f_max = tune_range
+    o_min, o_max = tune_range
+    step = tune_step
+    best_f, best_o, best = 0.5, 0.5, -1.0
+    for rnd in range(1, tune_rounds + 1):
+        fts = np.arange(f_min, f_max + step / 2, step)
+        ots = np.arange(o_min, o_max + step / 2, step) if two_axes else None
+        means = np.asarray(mean_f1(fts, ots), dtype=np.float64).reshape(len(fts), len(ots) if two_axes else 1)
+        for i, t in enumerate(fts):
+            for j in range(means.shape[1]):
+                if means[i, j] > best:
+                    best, best_f = float(means[i, j]), float(t)
+                    if two_axes:
+                        best_o = float(ots[j])
+        if log:
+            log(f"=== Round {rnd}/{tune_rounds} | frame=[{f_min:.4f}, {f_max:.4f}]" + (f" onset=[{o_min:.4f}, {o_max:.4f}]" if two_axes else "")
+                + f" step={step:.4f} -> t={best_f:.4f}" + (f" onset_t={best_o:.4f}" if two_axes else "") + f" f1={best:.6f}")
+        f_min, f_max = max(0.01, best_f - 2 * step), min(0.99, best_f + 2 * step)
+        o_min, o_max = max(0.01, best_o - 2 * step), min(0.99, best_o + 2 * step)
+        step = step / 2
+        if step < tune_min_step:
+            break
+    return best_f, (best_o if two_axes else None), best
+
+
+def tune_note_thresholds(model, dataset, device="cuda", subset: Optional[int] = None, decoder: str = "onset", note_reference: str = "roll",
+                         objective: str = "onset", tune_range=(0.05, 0.95), tune_step=0.1, tune_min_step=0.01, tune_rounds=6,
+                         rank: int = 0, world: int = 1, log=print, window_overlap: Optional[float] = None, max_batch: int = 128):
+    """The thresholds of the note decoder that maximise the mean note F1 (`objective`: "onset" or "onset_offset"; unweighted mean
+    over samples, as note_metrics_dataset) by search_note_thresholds: decoder="onset" searches (frame, onset) pairs, "frame" the
+    frame threshold alone.  The model runs once; every round is one sweep pass over each group of note_metrics_dataset.
+    -> (frame threshold, onset threshold or None, best mean F1), identical on every rank.  A candidate at or past 1 (the schedule's
+    last grid point can be) decodes no note and scores 0, as it does for tune_threshold."""
+    from .notes import note_prf, note_sweep_counts
+    if decoder not in ("onset", "frame"):
+        raise ValueError(f"decoder must be 'onset' or 'frame', got {decoder!r}")
+    if objective not in ("onset", "onset_offset"):
+        raise ValueError(f"objective must be 'onset' or 'onset_offset', got {objective!r}")
+    _check_note_reference(dataset, note_reference)
+    onset = decoder == "onset"
+    n = len(dataset) if subset is None else min(subset, len(dataset))
+    mine = list(shard_range(n, rank, world))
+    lr = _collect(model, dataset, mine, device, window_overlap, all_heads=onset)          # the only forward passes
+
+    def mean_f1(fts, ots):
+        fts = np.asarray(fts, dtype=np.float64)
+        ots = np.asarray(ots, dtype=np.float64) if onset else np.full(1, 0.5)
+        if (fts <= 0.0).any() or (ots <= 0.0).any():
+            raise ValueError("tune_note_thresholds: candidate thresholds must be positive (tune_range)")
+        fi, oj = np.flatnonzero(np.float32(fts) < 1.0), np.flatnonzero(np.float32(ots) < 1.0)
+        K = len(fts) * len(ots)
+        local = np.zeros((len(lr), len(fts), len(ots)))                                   # thresholds >= 1: no notes, F1 0
+        at = 0
+        if len(fi) and len(oj):
+            for frame, on, ref, lengths in _note_groups(lr, dataset, onset, note_reference, max_batch):
+                counts = note_sweep_counts(frame, ref, fts[fi], on, ots[oj] if onset else None, lengths)
+                f1 = np.array([m[objective][2] for m in note_prf(counts)]).reshape(len(lengths), len(fi), len(oj))
+                local[at:at + len(lengths), fi[:, None], oj[None, :]] = f1
+                at += len(lengths)
+        flat_idx = [i * K + k for i in mine for k in range(K)]
+        allv = gather_values(flat_idx, local.reshape(-1).tolist(), n * K)
+        return np.asarray(allv).reshape(n, len(fts), len(ots)).mean(axis=0) if n else np.zeros((len(fts), len(ots)))
+
+    return search_note_thresholds(mean_f1, onset, tune_range, tune_step, tune_min_step, tune_rounds, log)

@@ -6,6 +6,8 @@
     mt_roll_to_notes) or, given onset logits, from the onset-gated decoder.
   * `note_match_list` = the same counts against a note list in ticks of 100 us (the MIDI notes of MaestroDataset.ref_notes), in
     which re-struck keys are notes of their own: mir_eval's criteria in integers, a maximum matching per criterion.
+  * `note_sweep_counts` = either of them for a whole grid of (frame, onset) thresholds in one pass over the logits
+    (mt_note_sweep_counts / mt_note_sweep_list): every cell's sigmoid is evaluated once, whatever the size of the grid.
   * `note_prf` turns those counts into precision / recall / F1 on the host (0 for an empty denominator, as mir_eval).
   * `heads_to_notes_device` = transcribe.notes_from_logits_device with the onset-gated decoder (mt_heads_to_notes).
 """
@@ -40,6 +42,32 @@ def _check_threshold(t: float, name: str) -> float:
     return t
 
 
+def _lengths(lengths, B: int, dev) -> Optional[torch.Tensor]:
+    if lengths is None:
+        return None
+    ln = torch.as_tensor(lengths, dtype=torch.int64).reshape(-1).to(dev).contiguous()
+    if ln.numel() != B:
+        raise ValueError(f"lengths has {ln.numel()} entries for a batch of {B}")
+    return ln
+
+
+def _note_tables(ref_notes: Dict[str, torch.Tensor], B: int, P: int, dev):
+    """The checked, contiguous (on, off, ptr) of a note list for B x P rows."""
+    r_on, r_off, r_ptr = (ref_notes[k] for k in ("on", "off", "ptr"))
+    for t, dt, name in ((r_on, torch.int32, "on"), (r_off, torch.int32, "off"), (r_ptr, torch.int64, "ptr")):
+        if not torch.is_tensor(t) or t.device != dev or t.dtype != dt or t.dim() != 1:
+            raise ValueError(f"ref_notes[{name!r}]: expected a 1-d {dt} tensor on {dev}")
+    if r_ptr.numel() != B * P + 1 or r_on.numel() != r_off.numel():
+        raise ValueError(f"ref_notes: ptr has {r_ptr.numel()} entries for {B} x {P} rows, on / off have {r_on.numel()} / {r_off.numel()}")
+    # the kernel indexes on / off through ptr: refuse a table that points outside them (one small read-back, evaluation only)
+    bad = (r_ptr[0] != 0) | (r_ptr[-1] != r_on.numel()) | (r_ptr[1:] < r_ptr[:-1]).any()
+    if bool(bad):
+        raise ValueError("ref_notes: ptr must rise from 0 to the number of notes")
+    if r_on.numel() == 0:                                   # no notes at all: the kernel still wants readable tables
+        r_on = r_off = torch.zeros(1, dtype=torch.int32, device=dev)
+    return r_on.contiguous(), r_off.contiguous(), r_ptr.contiguous()
+
+
 def note_match_counts(frame_logits: torch.Tensor, ref_roll: torch.Tensor, threshold: float = 0.5, onset_logits: Optional[torch.Tensor] = None,
                       onset_threshold: float = 0.5, lengths=None) -> torch.Tensor:
     """(B, P, T) frame logits (and onset logits for the onset-gated decoder) and (B, P, T) reference roll on the device -> (B, 4)
@@ -53,11 +81,7 @@ def note_match_counts(frame_logits: torch.Tensor, ref_roll: torch.Tensor, thresh
     othr = _check_threshold(onset_threshold, "onset_threshold") if on is not None else 0.5
     B, P, T = x.shape
     dev = x.device
-    ln = None
-    if lengths is not None:
-        ln = torch.as_tensor(lengths, dtype=torch.int64).reshape(-1).to(dev).contiguous()
-        if ln.numel() != B:
-            raise ValueError(f"lengths has {ln.numel()} entries for a batch of {B}")
+    ln = _lengths(lengths, B, dev)
     counts = torch.empty(B, 4, dtype=torch.int64, device=dev)
     with torch.cuda.device(dev):
         check(lib.mt_note_match_counts(ptr(x), ptr(on), thr, othr, ptr(ref), ptr(ln), ptr(counts), B, P, T, _lib.stream_ptr()),
@@ -82,28 +106,76 @@ def note_match_list(frame_logits: torch.Tensor, ref_notes: Dict[str, torch.Tenso
     othr = _check_threshold(onset_threshold, "onset_threshold") if on is not None else 0.5
     B, P, T = x.shape
     dev = x.device
-    r_on, r_off, r_ptr = (ref_notes[k] for k in ("on", "off", "ptr"))
-    for t, dt, name in ((r_on, torch.int32, "on"), (r_off, torch.int32, "off"), (r_ptr, torch.int64, "ptr")):
-        if not torch.is_tensor(t) or t.device != dev or t.dtype != dt or t.dim() != 1:
-            raise ValueError(f"ref_notes[{name!r}]: expected a 1-d {dt} tensor on {dev}")
-    if r_ptr.numel() != B * P + 1 or r_on.numel() != r_off.numel():
-        raise ValueError(f"ref_notes: ptr has {r_ptr.numel()} entries for {B} x {P} rows, on / off have {r_on.numel()} / {r_off.numel()}")
-    # the kernel indexes on / off through ptr: refuse a table that points outside them (one small read-back, evaluation only)
-    bad = (r_ptr[0] != 0) | (r_ptr[-1] != r_on.numel()) | (r_ptr[1:] < r_ptr[:-1]).any()
-    if bool(bad):
-        raise ValueError("ref_notes: ptr must rise from 0 to the number of notes")
-    if r_on.numel() == 0:                                   # no notes at all: the kernel still wants readable tables
-        r_on = r_off = torch.zeros(1, dtype=torch.int32, device=dev)
-    ln = None
-    if lengths is not None:
-        ln = torch.as_tensor(lengths, dtype=torch.int64).reshape(-1).to(dev).contiguous()
-        if ln.numel() != B:
-            raise ValueError(f"lengths has {ln.numel()} entries for a batch of {B}")
+    r_on, r_off, r_ptr = _note_tables(ref_notes, B, P, dev)
+    ln = _lengths(lengths, B, dev)
     counts = torch.empty(B, 4, dtype=torch.int64, device=dev)
     with torch.cuda.device(dev):
-        check(lib.mt_note_match_list(ptr(x), ptr(on), thr, othr, ptr(r_on.contiguous()), ptr(r_off.contiguous()), ptr(r_ptr.contiguous()),
-                                     ptr(ln), ptr(counts), B, P, T, _lib.stream_ptr()), "mt_note_match_list")
+        check(lib.mt_note_match_list(ptr(x), ptr(on), thr, othr, ptr(r_on), ptr(r_off), ptr(r_ptr), ptr(ln), ptr(counts), B, P, T,
+                                     _lib.stream_ptr()), "mt_note_match_list")
     return counts
+
+
+SWEEP_MAX_K, SWEEP_MAX_PAIRS = 16, 64              # mt_note_sweep_*: thresholds per axis, pairs per call
+
+
+def _threshold_array(values, name: str) -> np.ndarray:
+    a = np.atleast_1d(np.asarray(values, dtype=np.float64)).astype(np.float32)
+    if a.ndim != 1 or a.size == 0:
+        raise ValueError(f"{name}: expected a non-empty 1-d list of thresholds")
+    for t in a:
+        _check_threshold(t, name)
+    return a
+
+
+def note_sweep_counts(frame_logits: torch.Tensor, ref, thresholds, onset_logits: Optional[torch.Tensor] = None, onset_thresholds=None,
+                      lengths=None) -> torch.Tensor:
+    """note_match_counts (ref = a (B, P, T) roll) or note_match_list (ref = the {"on", "off", "ptr"} note list) at every pair of
+    `thresholds` x `onset_thresholds` -> (B, Kf, Ko, 4) int64 device tensor; [b, i, j] is exactly what the single call returns at
+    (thresholds[i], onset_thresholds[j]).  Without onset logits (the frame decoder) Ko = 1 and onset_thresholds is not read.  The
+    logits are read, and their sigmoids evaluated, once per call of the kernel; a grid past its limits (16 per axis, 64 pairs) is
+    cut into several calls here.  Nothing is allocated on the device but the result, and with a roll nothing synchronises (a note
+    list's ptr table is checked with one small read-back, as in note_match_list)."""
+    x = _rows(frame_logits, "frame_logits")
+    on = None if onset_logits is None else _rows(onset_logits, "onset_logits")
+    if on is not None and on.shape != x.shape:
+        raise ValueError(f"shape mismatch: frame {tuple(x.shape)}, onset {tuple(on.shape)}")
+    B, P, T = x.shape
+    dev = x.device
+    tf = _threshold_array(thresholds, "thresholds")
+    if on is not None:
+        if onset_thresholds is None:
+            raise ValueError("onset_thresholds: needed with onset_logits")
+        to = _threshold_array(onset_thresholds, "onset_thresholds")
+    else:
+        to = np.full(1, 0.5, np.float32)
+    as_list = isinstance(ref, dict)
+    if as_list:
+        r_on, r_off, r_ptr = _note_tables(ref, B, P, dev)
+    else:
+        roll = _rows(ref, "ref_roll")
+        if roll.shape != x.shape:
+            raise ValueError(f"shape mismatch: frame {tuple(x.shape)}, ref {tuple(roll.shape)}")
+    ln = _lengths(lengths, B, dev)
+    Kf, Ko = len(tf), len(to)
+    out = torch.empty(B, Kf, Ko, 4, dtype=torch.int64, device=dev)
+    ko = min(Ko, SWEEP_MAX_K)                                # tiles of kf x ko <= 64 pairs, the onset axis as wide as it goes
+    kf = min(Kf, SWEEP_MAX_K, SWEEP_MAX_PAIRS // ko)
+    with torch.cuda.device(dev):
+        for i0 in range(0, Kf, kf):
+            for j0 in range(0, Ko, ko):
+                a, b = np.ascontiguousarray(tf[i0:i0 + kf]), np.ascontiguousarray(to[j0:j0 + ko])
+                whole = len(a) == Kf and len(b) == Ko
+                c = out if whole else torch.empty(B, len(a), len(b), 4, dtype=torch.int64, device=dev)
+                tb = b.ctypes.data if on is not None else None
+                if as_list:
+                    check(lib.mt_note_sweep_list(ptr(x), ptr(on), a.ctypes.data, len(a), tb, len(b), ptr(r_on), ptr(r_off), ptr(r_ptr), ptr(ln),
+                                                 ptr(c), B, P, T, _lib.stream_ptr()), "mt_note_sweep_list")
+                else:
+                    check(lib.mt_note_sweep_counts(ptr(x), ptr(on), a.ctypes.data, len(a), tb, len(b), ptr(roll), ptr(ln), ptr(c), B, P, T,
+                                                   _lib.stream_ptr()), "mt_note_sweep_counts")
+                if not whole:
+                    out[:, i0:i0 + len(a), j0:j0 + len(b)] = c
+    return out
 
 
 def _prf(tp: int, n_ref: int, n_est: int) -> Tuple[float, float, float]:

@@ -17,6 +17,8 @@ the GPU); a recording longer than the inference recurrence takes (T * hidden_siz
 naming it.  `--window_overlap SECONDS` instead runs every recording in overlapping 30 s windows stitched on its own frame grid
 (windows.py), which has no such limit.  `--note_metrics --note_reference midi` (whole recordings only) scores the decoded notes
 against the MIDI note list of each recording, in which a re-struck key is a note of its own, instead of the runs of the label roll.
+`--note_metrics --tune_note_thresholds` first chooses the note decoder's thresholds for the best mean note F1 (one model run, one
+sweep pass over the logits per group and round: evaluate.tune_note_thresholds) and reports the note metrics at those.
 MIDI / plot outputs, background mode and the results browser are out of scope.
 """
 import argparse
@@ -69,12 +71,23 @@ def main():
     ap.add_argument("--tune_range", type=float, nargs=2, default=[0.05, 0.95])
     ap.add_argument("--tune_step", type=float, default=0.1)
     ap.add_argument("--tune_min_step", type=float, default=0.01)
+    ap.add_argument("--tune_note_thresholds", action="store_true",
+                    help="with --note_metrics: choose the note decoder's thresholds (--decoder frame: the frame threshold; onset: the "
+                         "frame and the onset threshold together) for the best mean note F1 by the coarse-to-fine schedule of "
+                         "--tune_threshold (--tune_rounds / --tune_range / --tune_step / --tune_min_step), one model run, and report the "
+                         "note metrics there; headless adds EVAL_NOTE_THRESHOLD= (and EVAL_NOTE_ONSET_THRESHOLD=).  Framewise F1 keeps "
+                         "--threshold / --tune_threshold")
+    ap.add_argument("--tune_note_objective", choices=["onset", "onset_offset"], default="onset",
+                    help="the note F1 that --tune_note_thresholds maximises (default: onset)")
     args = ap.parse_args()
     say = (lambda *a, **k: None) if args.headless else print
 
     if args.note_reference == "midi" and args.data_source != "full":
         print("Error: --note_reference midi scores against the MIDI note list of whole recordings and needs --data_source full "
               "(cache records hold rolls of chunks, not notes)")
+        return 1
+    if args.tune_note_thresholds and not args.note_metrics:
+        print("Error: --tune_note_thresholds tunes the thresholds of --note_metrics and needs that flag")
         return 1
     if not os.path.exists(args.model):
         print(f"Error: Model checkpoint not found: {args.model}")
@@ -154,8 +167,16 @@ def main():
     mean_f1, per_sample = E.evaluate_dataset(model, ds, threshold, dev, subset=args.subset, rank=rank, world=world,
                                              window_overlap=args.window_overlap)
     notes = None
+    note_threshold, note_onset_threshold = threshold, (args.onset_threshold if args.decoder == "onset" else None)
+    if args.tune_note_thresholds:
+        note_threshold, note_onset_threshold, tuned_note_f1 = E.tune_note_thresholds(
+            model, ds, dev, subset=args.subset, decoder=args.decoder, note_reference=args.note_reference, objective=args.tune_note_objective,
+            tune_range=tuple(args.tune_range), tune_step=args.tune_step, tune_min_step=args.tune_min_step, tune_rounds=args.tune_rounds,
+            rank=rank, world=world, log=say if rank == 0 else None, window_overlap=args.window_overlap)
+        say(f"Best note thresholds: frame {note_threshold:.4f}" + ("" if note_onset_threshold is None else f", onset {note_onset_threshold:.4f}")
+            + f" (mean {args.tune_note_objective} note F1 {tuned_note_f1:.6f})")
     if args.note_metrics:
-        notes = E.note_metrics_dataset(model, ds, threshold, args.onset_threshold if args.decoder == "onset" else None, dev,
+        notes = E.note_metrics_dataset(model, ds, note_threshold, note_onset_threshold, dev,
                                        subset=args.subset, rank=rank, world=world, window_overlap=args.window_overlap,
                                        note_reference=args.note_reference)
     if rank == 0:
@@ -164,6 +185,10 @@ def main():
             if notes is not None:
                 print(f"EVAL_NOTE_ONSET_F1={notes['mean']['onset_f1']:.6f}")
                 print(f"EVAL_NOTE_ONSET_OFFSET_F1={notes['mean']['onset_offset_f1']:.6f}")
+                if args.tune_note_thresholds:
+                    print(f"EVAL_NOTE_THRESHOLD={note_threshold:.4f}")
+                    if note_onset_threshold is not None:
+                        print(f"EVAL_NOTE_ONSET_THRESHOLD={note_onset_threshold:.4f}")
         else:
             print(f"\nMean framewise F1 over {len(per_sample)} samples at threshold {threshold:.4f}: {mean_f1:.6f}")
             results = {"mean_f1": mean_f1, "threshold": threshold, "per_sample_f1": per_sample, "split": args.split,
@@ -172,8 +197,10 @@ def main():
                 m = notes["mean"]
                 print(f"Mean note F1 ({args.decoder} decoder, {args.note_reference} reference): onset {m['onset_f1']:.6f}, onset+offset {m['onset_offset_f1']:.6f}")
                 results["note_metrics"] = {"decoder": args.decoder, "note_reference": args.note_reference,
-                                           "onset_threshold": args.onset_threshold if args.decoder == "onset" else None,
+                                           "onset_threshold": note_onset_threshold,
                                            **notes}
+                if args.tune_note_thresholds:
+                    results["note_metrics"].update(threshold=note_threshold, tuned_objective=args.tune_note_objective)
             os.makedirs(args.out_dir, exist_ok=True)
             with open(os.path.join(args.out_dir, "results.json"), "w") as f:
                 json.dump(results, f)
