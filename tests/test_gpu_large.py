@@ -68,6 +68,7 @@ def test_conv_cl_matches_torch(mta, C1, C2, Cout, KH, pool, F, T):
 
 
 def test_attention_pieces(mta):
+    """(Both operand types, more shapes, wide rows and per-element bounds: tests/test_gpu_attn.py.)"""
     from music_transcription_amd._lib import lib, check, ptr, stream_ptr
     g = torch.Generator().manual_seed(0)
     rows, T, Tp = 37, 50, 64
@@ -93,7 +94,8 @@ def test_attention_pieces(mta):
 def test_attention_fused_matches_torch(mta, B, T, heads, dp, dt):
     """csrc/attn_fused.hip against the module's own arithmetic (cnn_rnn_model.py:118-139) in fp32 on the same 16-bit q, k, v:
     scale, clamp +-10 BEFORE the softmax (a third of the scores here are at the clamp), softmax over all T keys (no mask), P V.
-    Rows whose query index is past T are not written; every other output column of the row is."""
+    Rows whose query index is past T are not written; every other output column of the row is.
+    (Per-element bounds, every sub-block mask and query-block edge, wide rows, NaN pads: tests/test_gpu_attn.py.)"""
     from music_transcription_amd._lib import lib, check, ptr, stream_ptr, DT_F16, DT_BF16
     tdt = torch.float16 if dt == "f16" else torch.bfloat16
     g = torch.Generator().manual_seed(B * 1000 + T)

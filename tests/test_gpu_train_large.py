@@ -229,6 +229,7 @@ def test_conv_cl_channel_slices_and_accumulate(mta):
 
 @pytest.mark.parametrize("p", [0.0, 0.25])
 def test_attention_softmax_forward_backward_vs_autograd(mta, p):
+    """(Per-element bounds, the dropout mask against the host replica, the clamp edge and more shapes: tests/test_gpu_attn.py.)"""
     lib, check, ptr, st = _lib()
     g = torch.Generator().manual_seed(3)
     rows, T, Tp = 10, 100, 128
@@ -260,6 +261,7 @@ def test_attention_softmax_forward_backward_vs_autograd(mta, p):
 
 
 def test_layernorm_residual_forward_backward_vs_autograd(mta):
+    """(Per-element bounds, n up to 2048, more rows than slices, rows with a large mean: tests/test_gpu_attn.py.)"""
     lib, check, ptr, st = _lib()
     g = torch.Generator().manual_seed(9)
     rows, n, ld = 300, 48, 64
