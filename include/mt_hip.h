@@ -406,7 +406,7 @@ int    mt_predict_threshold(const float* logits, float* roll, long long n, float
 /* counts[b] = {TP, FP, FN} (uint64) over the first lengths[b] frames (evaluate.py:361-373). */
 int    mt_f1_counts(const float* pred, const float* target, const long long* lengths,
                     unsigned long long* counts, int B, int P, int T, mt_stream_t stream);
-/* counts[b][k] = {TP, FP, FN} of (sigmoid(logits) > thresholds[k]) for K <= 16 thresholds in one pass:
+/* counts[b][k] = {TP, FP, FN} of (sigmoid(logits) > thresholds[k]) for 1 <= K <= 16 thresholds (else MT_EINVAL) in one pass:
  * the data side of evaluate.py's threshold tuning (:524-618) without re-running the model.          */
 int    mt_f1_sweep_counts(const float* logits, const float* target, const long long* lengths,
                           const float* thresholds, int K, unsigned long long* counts, int B, int P, int T,
@@ -461,7 +461,8 @@ int    mt_heads_to_notes(const float* frame_logits, const float* onset_logits, f
  * step = 1-based step count.  stats (2 floats, may be NULL) = {norm before clipping, 1 if stepped else 0}.
  * With data parallelism, all-reduce `grads` over RCCL before calling this: the mean, or (_ex) the SUM with
  * grad_scale = 1 / world -- the scale is applied on the fly in the norm and in the update, `grads` is not written.
- * _ex, keep_ranges: HOST array of n_keep <= 16 ascending disjoint [lo, hi) element ranges (NULL / 0 = everything).
+ * _ex, grad_scale > 0; keep_ranges: HOST array of n_keep <= 16 ascending disjoint [lo, hi) element ranges inside [0, n), empty
+ * (lo == hi) and adjacent ones allowed (NULL / 0 = everything); anything else is MT_EINVAL and nothing is written.
  * Only those elements are counted in the norm, clipped and updated; the rest keep params and moments -- torch's
  * behaviour for parameters whose .grad is None (the onset / offset heads under the reference's frame-only loss,
  * train_transcriber.py:119 + cnn_rnn_model.py:343-349: no weight decay, no moment update).                  */

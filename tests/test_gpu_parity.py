@@ -323,7 +323,7 @@ def test_predict_and_f1(mta, golden_dir):
         want = np.unpackbits(z[f"small_a_pred{int(th * 10)}"])[: B * P * T].reshape(B, P, T)
         got = mta.predict_from_logits(logits.cuda(), th).cpu().numpy()
         assert set(np.unique(got)) <= {0.0, 1.0}
-        # the reference compares sigmoid(x) > t in fp32, the kernel x > log(t / (1 - t)): a cell may differ only where fp32's
+        # the reference and the kernel both compare sigmoid(x) > t in fp32, each with its own expf: a cell may differ only where fp32's
         # sigmoid cannot tell x from the threshold (|x - logit(t)| of a few ulp of sigmoid = 6e-8 / (t (1 - t)))
         bad = got != want
         assert bad.mean() < 1e-4 and np.abs(logits.numpy()[bad] - np.log(th / (1 - th))).max(initial=0.0) < 2e-6, (th, int(bad.sum()))
