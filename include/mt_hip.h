@@ -454,6 +454,18 @@ int    mt_note_sweep_list(const float* frame_logits, const float* onset_logits, 
  * recording of NB*T frames per pitch; counts[p], starts / ends in the reference's note order, capacity protocol unchanged. */
 int    mt_heads_to_notes(const float* frame_logits, const float* onset_logits, float thr_frame, float thr_onset, int NB, int P, int T,
                          int* counts, int* starts, int* ends, int capacity, mt_stream_t stream);
+/* The notes of a padded batch of whole recordings (csrc/notes_batch.hip): row (b, p) is frame_logits[(b*P + p)*T + t]
+ * (onset_logits alike, NULL = the frame decoder) and its valid frames are [0, L_b), L_b = clamp(lengths[b], 0, T) (int64, device,
+ * NULL = all T).  Frames at or past L_b are inactive and never read -- the padding may hold anything, NaN included -- and a note still
+ * open at L_b ends at L_b.  The notes of a row are exactly those of mt_roll_to_notes (src_mode 0) / mt_heads_to_notes on a contiguous
+ * [1][1][L_b] copy of it.  counts[b*P + p] (int32) and row_off[0 .. B*P] (int64, the exclusive prefix of counts in row order,
+ * row_off[B*P] = all notes) are always written; note k of row (b, p) is frames [starts[i], ends[i]) at i = row_off[b*P + p] + k: per
+ * recording the reference's note order.  A row is written only when row_off + count <= capacity and nothing at or past `capacity` is
+ * touched: the host compares row_off[B*P] with it (capacity 0: counts only, starts / ends may be NULL).  Up to three launches on
+ * `stream`; no synchronisation, allocation or copy.  0 < thresholds < 1; B*P and T below 2^31; all indexing is 64-bit. */
+int    mt_notes_batch(const float* frame_logits, const float* onset_logits, float thr_frame, float thr_onset, const long long* lengths,
+                      int B, int P, long long T, int* counts, long long* row_off, int* starts, int* ends, long long capacity,
+                      mt_stream_t stream);
 
 /* ------------------------------------------------------------------ optimizer step (training)
  * clip_grad_norm_(max_norm) + torch.optim.Adam with coupled L2 weight decay over flat f32 buffers

@@ -6,6 +6,10 @@ cross-chunk state (main.py:258-266), so here they are batched ACROSS recordings:
 runs mel + forward on stream f % streams.  Per recording the device then turns its logits into notes (threshold + chunk
 concatenation + per-pitch run-length: mt_roll_to_notes, main.py:153-226), so what crosses PCIe per recording is its note list
 (two ints per note), not its piano roll; framewise F1 against a reference roll, when one is given, is computed on the device too.
+
+`transcribe_shard_windows` is the same job on the window grid of windows.py: whole recordings in overlapping 30 s
+windows on one frame grid, grouped so that a group's stitched logits are one padded batch with lengths; notes and scores of a
+group leave the device together (notes.notes_batch_device), not recording by recording.
 """
 from __future__ import annotations
 
@@ -15,9 +19,10 @@ from typing import Callable, Dict, List, Optional, Sequence
 import torch
 
 from . import transcribe as tr
+from . import windows as W
 from .frontend import get_frontend
-from .notes import heads_to_notes_device, note_match_counts, note_prf
-from .ops import framewise_f1, predict_from_logits
+from .notes import heads_to_notes_device, note_match_counts, note_prf, notes_batch_device
+from .ops import f1_counts, f1_from_counts, framewise_f1, predict_from_logits
 
 SR, CH, HOP = 16000, 480000, 512
 
@@ -183,6 +188,192 @@ def transcribe_shard(model, rec_ids: Sequence[int], chunks_of: Callable[[int], t
     return res
 
 
+class _Grouper:
+    """plan_groups' rule, one recording at a time: add() returns the groups that the recording closes."""
+
+    def __init__(self, group_windows: int, group_bytes: int, heads: int = 1):
+        if group_windows < 1 or group_bytes < 1 or heads < 1:
+            raise ValueError(f"group_windows, group_bytes and heads must be positive, got {group_windows}, {group_bytes}, {heads}")
+        self.gw, self.gb, self.heads = int(group_windows), int(group_bytes), int(heads)
+        self.cur: List[int] = []
+        self.windows, self.t_max, self.n = 0, 0, 0
+
+    def _bytes(self, R: int, t_max: int) -> int:
+        return self.heads * R * 88 * t_max * 4
+
+    def add(self, n_windows: int, n_frames: int) -> List[List[int]]:
+        closed = []
+        if self.cur and self._bytes(len(self.cur) + 1, max(self.t_max, int(n_frames))) > self.gb:
+            closed += self.flush()
+        self.cur.append(self.n)
+        self.n += 1
+        self.windows += int(n_windows)
+        self.t_max = max(self.t_max, int(n_frames))
+        if self.windows >= self.gw:
+            closed += self.flush()
+        return closed
+
+    def flush(self) -> List[List[int]]:
+        g, self.cur, self.windows, self.t_max = self.cur, [], 0, 0
+        return [g] if g else []
+
+
+def plan_groups(n_windows: Sequence[int], n_frames: Sequence[int], group_windows: int, group_bytes: int = 1 << 30,
+                heads: int = 1) -> List[List[int]]:
+    """Consecutive groups of recordings, as positions 0 .. len - 1 in the given order (host integers only).  n_windows[k] / n_frames[k]:
+    windows and frames (Tg) of recording k.  A group closes when its windows reach group_windows; it closes before a recording that
+    would push its stitched logits, heads * R * 88 * T_max * 4 bytes for R recordings padded to the longest, past group_bytes; a
+    recording over that limit on its own is a group of one."""
+    if len(n_windows) != len(n_frames):
+        raise ValueError(f"{len(n_windows)} window counts for {len(n_frames)} frame counts")
+    g = _Grouper(group_windows, group_bytes, heads)
+    out: List[List[int]] = []
+    for w, t in zip(n_windows, n_frames):
+        out += g.add(w, t)
+    return out + g.flush()
+
+
+@torch.no_grad()
+def transcribe_shard_windows(model, rec_ids: Sequence[int], audio_of: Callable[[int], torch.Tensor], *, overlap_s: float, n_mels: int, device,
+                             batch: int = 128, streams: int = 3, group_windows: Optional[int] = None, group_bytes: int = 1 << 30,
+                             threshold: float = 0.5, decoder: str = "frame", onset_threshold: float = 0.5, want_notes: bool = True,
+                             reference_roll_of: Optional[Callable[[int, int], Optional[torch.Tensor]]] = None,
+                             midi_path_of: Optional[Callable[[int], Optional[str]]] = None, note_metrics: bool = False,
+                             warm: bool = True) -> Dict[str, object]:
+    """transcribe_shard on the window grid.  audio_of(i) -> recording i as 1-D float32 at 16 kHz on the device, any length (0 samples
+    included).  Recordings are taken in rec_ids order into groups (plan_groups; group_windows defaults to batch * streams).  A group
+    runs exactly the slabs of windows.transcribe_windows(model, [its recordings], overlap_s, batch, all_heads) into zero-filled
+    (R, 88, T_max) logits per head; slab f, counted over the whole shard, runs on side stream f % streams (at most 3 streams for
+    cnn_rnn_large, two recurrence launches per forward: more are clamped to 3).  A group is finished on the main stream with lengths
+    = its recordings' frame counts: notes of all its recordings from one notes_batch_device call, F1 counts, note counts and a finite
+    flag; the host waits for group g's notes only after group g + 1's slabs are queued.  reference_roll_of(i, frames) -> (88, >= 1)
+    roll on the recording's frame grid or None; scored over min(frames, reference frames).  Returns transcribe_shard's keys with
+    "windows" for "chunks", and "groups" (lists of recording ids) and "frames" {i: 1 + n_i // 512}."""
+    tr.check_decoder(decoder, model=model)
+    W.overlap_frames(overlap_s)
+    heads = decoder == "onset"
+    dev = torch.device(device)
+    net, n_mels, fe = W._window_setup(model, n_mels, heads, dev)
+    from .model import CNNRNNModelLarge
+    NS = max(1, int(streams))
+    if isinstance(net, CNNRNNModelLarge):
+        NS = min(NS, 3)
+    gw = int(group_windows) if group_windows is not None else batch * NS
+    grouper = _Grouper(gw, group_bytes, 2 if heads else 1)
+    side = [torch.cuda.Stream(device=dev) for _ in range(NS)]
+    main = torch.cuda.current_stream(dev)
+    if warm:                                     # weight packing, code objects, every stream's workspace: not part of wall_s
+        w0 = torch.zeros(batch, CH, device=dev)
+        torch.cuda.synchronize(dev)
+        for st in side:
+            with torch.cuda.stream(st):
+                m0, c0 = fe(w0, clamp=False)
+                net(m0, chunk_max_power=c0, return_all_heads=True) if heads else net(m0, chunk_max_power=c0)
+        torch.cuda.synchronize(dev)
+        del w0
+    ids = list(rec_ids)
+    fs = SR / HOP
+    res: Dict[str, object] = {"windows": 0, "slabs": 0, "notes": {}, "f1": {}, "n_notes": 0, "finite": True, "groups": [], "frames": {}}
+    if note_metrics:
+        res["note_f1"] = {}
+    held: Dict[int, torch.Tensor] = {}            # position in ids -> recording, until its group runs
+    finite_flags: List[torch.Tensor] = []
+    f1_dev: List[tuple] = []                      # per group: (ids with a reference, their rows, (R, 3) counts, (R, 4) note counts or None)
+    pending: List[tuple] = []                     # the group whose slabs are queued and whose host side is still to do
+    t0 = time.perf_counter()
+
+    def queue(group: List[int]):
+        """The group's store, zero-filled logits and slabs; the slabs go to the side streams."""
+        ys = [held.pop(k) for k in group]
+        store, offs, ns = W._store(ys)
+        Tg = [1 + n // HOP for n in ns]
+        R = len(ys)
+        outs = [torch.zeros(R, W.N_PITCH, max(Tg), dtype=torch.float32, device=dev) for _ in range(2 if heads else 1)]
+        jobs = W._jobs(ns, range(R), overlap_s)
+        events = []
+        for s0 in range(0, len(jobs), batch):
+            st = side[res["slabs"] % NS]
+            st.wait_stream(main)                 # the store and the zero fill were queued on the main stream
+            with torch.cuda.stream(st):
+                W._run_slab(net, fe, n_mels, jobs[s0:s0 + batch], store, offs, outs, heads, dev)
+                for t in [store] + outs:
+                    t.record_stream(st)
+                ev = torch.cuda.Event()
+                ev.record(st)
+            events.append(ev)
+            res["slabs"] += 1
+        res["windows"] += len(jobs)
+        rec = [ids[k] for k in group]
+        res["groups"].append(rec)
+        for i, t in zip(rec, Tg):
+            res["frames"][i] = t
+        return rec, Tg, outs, events
+
+    def finish(rec, Tg, outs, events):
+        """Notes, counts and the finite flag of one group, on the main stream behind the group's slabs."""
+        for ev in events:
+            main.wait_event(ev)
+        frame, onset = outs[0], (outs[1] if heads else None)
+        finite_flags.append(torch.isfinite(frame).all())          # (over the zero-filled buffer: padding is finite)
+        if want_notes:
+            for i, notes in zip(rec, notes_batch_device(frame, onset, threshold, onset_threshold, Tg, fs)):
+                res["notes"][i] = notes
+                res["n_notes"] += len(notes)
+                path = midi_path_of(i) if midi_path_of else None
+                if path:
+                    tr.write_midi(notes, path)
+        if reference_roll_of is None:
+            return
+        refs = [reference_roll_of(i, t) for i, t in zip(rec, Tg)]
+        if all(r is None for r in refs):
+            return
+        roll = torch.zeros_like(frame)
+        cmp = [0] * len(rec)                      # frames compared per recording; 0 = no reference, its counts are dropped
+        for r, ref in enumerate(refs):
+            if ref is not None:
+                cmp[r] = min(Tg[r], int(ref.shape[1]))
+                roll[r, :, :cmp[r]] = ref[:, :cmp[r]]
+        ln = torch.tensor(cmp, dtype=torch.int64).to(dev)
+        c = f1_counts(predict_from_logits(frame, threshold), roll, ln)
+        nc = note_match_counts(frame, roll, threshold, onset, onset_threshold, ln) if note_metrics else None
+        f1_dev.append(([i for i, ref in zip(rec, refs) if ref is not None], [r for r, ref in enumerate(refs) if ref is not None], c, nc))
+
+    def run(group: List[int]):
+        queued = queue(group)
+        if pending:
+            finish(*pending.pop())
+        pending.append(queued)
+
+    for k, i in enumerate(ids):
+        y = audio_of(i)
+        if not torch.is_tensor(y) or y.dim() != 1 or y.dtype != torch.float32 or y.device.type != "cuda":
+            raise ValueError(f"audio_of({i}) must return a 1-D float32 CUDA tensor")
+        held[k] = y
+        p = W.plan_windows(int(y.numel()), overlap_s)
+        for group in grouper.add(len(p.start), p.Tg):
+            run(group)
+    for group in grouper.flush():
+        run(group)
+    if pending:
+        finish(*pending.pop())
+    for st in side:
+        main.wait_stream(st)
+    for rec, rows, c, nc in f1_dev:
+        f1 = f1_from_counts(c)
+        for i, r in zip(rec, rows):
+            res["f1"][i] = float(f1[r])
+        if nc is not None:
+            prf = note_prf(nc)
+            for i, r in zip(rec, rows):
+                res["note_f1"][i] = (prf[r]["onset"][2], prf[r]["onset_offset"][2])
+    if finite_flags:
+        res["finite"] = bool(torch.stack(finite_flags).all())
+    torch.cuda.synchronize(dev)
+    net.raise_on_handoff_timeout(sync=False)     # a timed-out recurrence leaves NaN logits = all-zero rolls: fail loudly
+    res["wall_s"] = time.perf_counter() - t0
+    return res
+
+
 class PcmSource:
     """chunks_of for transcribe_shard when the recordings are PCM frames in (pinned) HOST memory, as a WAV file holds them:
     (frames, channels) int16 / int32 / float32 at `rate`.  Recording order is known up front, so the H2D copy of recording
@@ -210,14 +401,17 @@ class PcmSource:
             self.inflight[i] = (d, ev)
             self.cursor += 1
 
-    def __call__(self, i: int) -> torch.Tensor:
+    def recording(self, i: int) -> torch.Tensor:
+        """Recording i as 1-D float32 at 16 kHz on the device (audio_of for transcribe_shard_windows)."""
         self._prefetch(self.index[i] + self.ahead)
         d, ev = self.inflight.pop(i)
         main = torch.cuda.current_stream(self.dev)
         main.wait_event(ev)
         d.record_stream(main)
-        y = tr.resample_pcm_device(d, self.rate_of(i), SR)
-        return tr.split_into_chunks_device(y)[0]
+        return tr.resample_pcm_device(d, self.rate_of(i), SR)
+
+    def __call__(self, i: int) -> torch.Tensor:
+        return tr.split_into_chunks_device(self.recording(i))[0]
 
 
 def synthetic_corpus(n_recordings: int, hours: float, seed: int = 0):

@@ -1,0 +1,117 @@
+// mt_notes_batch: the notes of a padded batch of whole recordings, frame_logits / onset_logits [B][P][T] with lengths[b] valid frames
+// (DESIGN.md 6d "The corpus in windows").  Row (b, p) decodes exactly as mt_roll_to_notes (src_mode 0) / mt_heads_to_notes decode a
+// contiguous copy of its valid frames: the same activity expression (logit_active) and the same decode_window (note_decode.h).
+// Three launches on one stream: count (one wave64 per row), an exclusive prefix of the counts in row order (64-bit), fill (one wave64
+// per row, at row_off[row]).  Frames at or past lengths[b] are never loaded.
+#include "mt_common.h"
+#include "note_decode.h"
+
+namespace mt {
+
+constexpr int BATCH_SLAB = 16;            // 64-frame windows loaded ahead per lane: whole recordings are few, long rows, so latency rules
+constexpr int BATCH_WAVES = 4;            // waves per workgroup (one row each)
+constexpr int PREFIX_THREADS = 256;
+
+// FILL = false: counts[row] = notes of the row.  FILL = true: note k of the row goes to [row_off[row] + k]; a row without notes, or one
+// whose notes would end past `capacity`, is left alone (the host sees row_off[rows] > capacity and retries with larger buffers).
+template <bool FILL>
+__global__ __launch_bounds__(64 * BATCH_WAVES) void notes_batch_kernel(const float* __restrict__ frame, const float* __restrict__ onset,
+                                                                       float thr_f, float thr_o, const long long* __restrict__ lengths,
+                                                                       long long rows, int P, long long T, int* __restrict__ counts,
+                                                                       const long long* __restrict__ row_off, int* __restrict__ starts,
+                                                                       int* __restrict__ ends, long long capacity) {
+    const long long row = (long long)blockIdx.x * BATCH_WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // wave-uniform
+    const int lane = threadIdx.x & 63;
+    if (row >= rows) return;
+    const long long b = row / P;
+    const long long L = lengths ? min(T, max(0ll, lengths[b])) : T;
+    long long out = 0;
+    if (FILL) {
+        const int c = counts[row];
+        out = row_off[row];
+        if (c == 0 || out + c > capacity) return;
+    }
+    const float* __restrict__ xf_row = frame + (size_t)row * (size_t)T;
+    const float* __restrict__ xo_row = onset ? onset + (size_t)row * (size_t)T : nullptr;
+    int n_on = 0, n_off = 0;
+    unsigned long long o_prev = 0, open_prev = 0;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    for (long long s0 = 0; s0 < L; s0 += 64 * BATCH_SLAB) {
+        float xf[BATCH_SLAB], xo[BATCH_SLAB];
+#pragma unroll
+        for (int w = 0; w < BATCH_SLAB; ++w) {
+            const long long g = s0 + 64 * w + lane;
+            const bool in = g < L;
+            xf[w] = in ? xf_row[g] : 0.0f;
+            xo[w] = (in && xo_row) ? xo_row[g] : 0.0f;
+        }
+#pragma unroll
+        for (int w = 0; w < BATCH_SLAB; ++w) {
+            const long long g0 = s0 + 64 * w;
+            if (g0 >= L) continue;                              // (not a break: the loop stays fully unrolled, xf / xo in registers)
+            const bool in = g0 + lane < L;
+            const bool f = in && logit_active(xf[w], thr_f);
+            const bool o = xo_row ? (in && logit_active(xo[w], thr_o)) : f;
+            const WindowEvents ev = decode_window(o, f || o, lane, o_prev, open_prev);
+            if (FILL) {
+                if (ev.starts >> lane & 1ull) starts[out + n_on + __popcll(ev.starts & below)] = (int)(g0 + lane);
+                if (ev.closes >> lane & 1ull) ends[out + n_off + __popcll(ev.closes & below)] = (int)(g0 + lane);
+            }
+            n_on += __popcll(ev.starts);
+            n_off += __popcll(ev.closes);
+        }
+    }
+    if (lane == 0) {
+        if (!FILL) counts[row] = n_on;
+        else if (open_prev) ends[out + n_off] = (int)L;        // a note still open at the row's last valid frame ends at L
+    }
+}
+
+// row_off[i] = counts[0] + ... + counts[i - 1] for i in [0, rows]: one workgroup, a contiguous run of rows per thread.
+__global__ __launch_bounds__(PREFIX_THREADS) void notes_batch_prefix_kernel(const int* __restrict__ counts, long long rows,
+                                                                            long long* __restrict__ row_off) {
+    __shared__ long long part[PREFIX_THREADS];
+    const int tid = threadIdx.x;
+    const long long per = (rows + PREFIX_THREADS - 1) / PREFIX_THREADS;
+    const long long lo = min(rows, tid * per), hi = min(rows, lo + per);
+    long long s = 0;
+    for (long long i = lo; i < hi; ++i) s += counts[i];
+    part[tid] = s;
+    __syncthreads();
+    long long base = 0;
+    for (int k = 0; k < tid; ++k) base += part[k];
+    for (long long i = lo; i < hi; ++i) {
+        row_off[i] = base;
+        base += counts[i];
+    }
+    if (tid == PREFIX_THREADS - 1) row_off[rows] = base;
+}
+
+}  // namespace mt
+
+using namespace mt;
+
+extern "C" int mt_notes_batch(const float* frame_logits, const float* onset_logits, float thr_frame, float thr_onset, const long long* lengths,
+                              int B, int P, long long T, int* counts, long long* row_off, int* starts, int* ends, long long capacity,
+                              mt_stream_t stream) {
+    MT_REQUIRE(frame_logits && counts && row_off && capacity >= 0 && ((starts && ends) || capacity == 0), MT_EINVAL,
+               "mt_notes_batch: null pointer or negative capacity");
+    MT_REQUIRE(B > 0 && P > 0 && T > 0 && (long long)B * P < 2147483647ll - BATCH_WAVES && T < 2147483647ll, MT_EINVAL,
+               "mt_notes_batch: bad dims (B, P, T > 0; B * P and T below 2^31: note frames are 32-bit)");
+    MT_REQUIRE(thr_frame > 0.0f && thr_frame < 1.0f && (!onset_logits || (thr_onset > 0.0f && thr_onset < 1.0f)), MT_EINVAL,
+               "mt_notes_batch: thresholds must lie in (0, 1)");
+    hipStream_t st = (hipStream_t)stream;
+    const long long rows = (long long)B * P;
+    const dim3 grid((unsigned)((rows + BATCH_WAVES - 1) / BATCH_WAVES)), block(64 * BATCH_WAVES);
+    hipLaunchKernelGGL(notes_batch_kernel<false>, grid, block, 0, st, frame_logits, onset_logits, thr_frame, thr_onset, lengths, rows, P, T,
+                       counts, (const long long*)nullptr, (int*)nullptr, (int*)nullptr, 0ll);
+    MT_CHECK_LAUNCH();
+    hipLaunchKernelGGL(notes_batch_prefix_kernel, dim3(1), dim3(PREFIX_THREADS), 0, st, (const int*)counts, rows, row_off);
+    MT_CHECK_LAUNCH();
+    if (capacity > 0) {
+        hipLaunchKernelGGL(notes_batch_kernel<true>, grid, block, 0, st, frame_logits, onset_logits, thr_frame, thr_onset, lengths, rows, P, T,
+                           counts, (const long long*)row_off, starts, ends, capacity);
+        MT_CHECK_LAUNCH();
+    }
+    return MT_OK;
+}

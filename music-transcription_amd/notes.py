@@ -10,6 +10,8 @@
     (mt_note_sweep_counts / mt_note_sweep_list): every cell's sigmoid is evaluated once, whatever the size of the grid.
   * `note_prf` turns those counts into precision / recall / F1 on the host (0 for an empty denominator, as mir_eval).
   * `heads_to_notes_device` = transcribe.notes_from_logits_device with the onset-gated decoder (mt_heads_to_notes).
+  * `notes_batch_device` = either decoder over a padded batch of whole recordings with `lengths` (mt_notes_batch): the notes of all
+    recordings in two device-to-host copies.
 """
 from __future__ import annotations
 
@@ -219,3 +221,43 @@ def heads_to_notes_device(frame_logits: torch.Tensor, onset_logits: torch.Tensor
     s, e = starts[:total].cpu().numpy(), ends[:total].cpu().numpy()
     pitches = np.repeat(np.arange(P) + min_midi, c)
     return [(int(pp), float(a) / fs, float(b) / fs) for pp, a, b in zip(pitches, s, e)]
+
+
+def notes_batch_device(frame_logits: torch.Tensor, onset_logits: Optional[torch.Tensor] = None, threshold: float = 0.5,
+                       onset_threshold: float = 0.5, lengths=None, fs: float = FS, min_midi: int = 21) -> List[List[Tuple[int, float, float]]]:
+    """(B, P, T) frame logits of B whole recordings ON THE DEVICE, padded to T, with lengths (B,) valid frames each (None: all T) ->
+    one note list per recording: what transcribe.notes_from_logits_device (onset_logits None) or heads_to_notes_device returns on
+    that recording's rows trimmed to its length.  The padding is never read.  One launch of mt_notes_batch, one device-to-host copy
+    of the counts and offsets and one of the notes; a second launch only when the first capacity guess was short."""
+    x = _rows(frame_logits, "frame_logits")
+    on = None if onset_logits is None else _rows(onset_logits, "onset_logits")
+    if on is not None and on.shape != x.shape:
+        raise ValueError(f"frame {tuple(x.shape)} and onset {tuple(on.shape)} logits differ in shape")
+    thr = _check_threshold(threshold, "threshold")
+    othr = _check_threshold(onset_threshold, "onset_threshold") if on is not None else 0.5
+    B, P, T = x.shape
+    dev = x.device
+    ln = _lengths(lengths, B, dev)
+    rows = B * P
+    meta = torch.empty(rows + 1 + (rows + 1) // 2, dtype=torch.int64, device=dev)      # row_off (rows + 1) | counts (rows int32): one copy
+    row_off, counts = meta[:rows + 1], meta[rows + 1:].view(torch.int32)[:rows]
+    cap = max(1024, (B * T) // 16)
+    while True:
+        se = torch.empty(2, cap, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            check(lib.mt_notes_batch(ptr(x), ptr(on), thr, othr, ptr(ln), B, P, T, ptr(counts), ptr(row_off), ptr(se[0]), ptr(se[1]), cap,
+                                     _lib.stream_ptr()), "mt_notes_batch")
+        host = meta.cpu().numpy()
+        off, c = host[:rows + 1], host[rows + 1:].view(np.int32)[:rows]
+        total = int(off[rows])
+        if total <= cap:
+            break
+        cap = total
+    s, e = se[:, :total].cpu().numpy()
+    pitches = np.tile(np.arange(P) + min_midi, B)
+    out = []
+    for b in range(B):
+        lo, hi = int(off[b * P]), int(off[(b + 1) * P])
+        pp = np.repeat(pitches[b * P:(b + 1) * P], c[b * P:(b + 1) * P])
+        out.append([(int(q), float(a) / fs, float(z) / fs) for q, a, z in zip(pp, s[lo:hi], e[lo:hi])])
+    return out

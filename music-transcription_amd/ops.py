@@ -106,7 +106,12 @@ def f1_counts(pred, target, lengths: Optional[torch.Tensor] = None):
 
 def framewise_f1(pred, target, lengths=None):
     """Per-sample binary F1 with zero_division=0 (evaluate.py:369-373) -> list of floats."""
-    c = f1_counts(pred, target, lengths).cpu().tolist()
+    return f1_from_counts(f1_counts(pred, target, lengths))
+
+
+def f1_from_counts(counts) -> list:
+    """(B, 3) {TP, FP, FN} -> per-sample F1, 0 for an empty denominator."""
+    c = counts.cpu().tolist() if torch.is_tensor(counts) else counts
     return [0.0 if (2 * tp + fp + fn) == 0 else 2.0 * tp / (2 * tp + fp + fn) for tp, fp, fn in c]
 
 

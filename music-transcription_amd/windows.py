@@ -68,45 +68,72 @@ def plan_windows(n_samples: int, overlap_s: float, sr: int = SR, hop: int = HOP,
     return WindowPlan(start, own0 - start, own1 - start, Tw, Tg, O, S)
 
 
-@torch.no_grad()
-def _run_windows(model, jobs, R: int, T_dst: int, store_of, n_mels: Optional[int], batch: int, all_heads: bool, device):
-    """jobs: [(dst_row, recording key, n_samples, start frame, lo, hi)].  store_of(keys) -> (store buffer, {key: offset}) for the
-    recordings of one slab.  -> frame logits (R, 88, T_dst) [, onset logits], padding 0."""
+def _window_setup(model, n_mels: Optional[int], all_heads: bool, device):
+    """-> (net, n_mels, frontend) of a window pass; refuses all_heads for a model without the onset head."""
     from .evaluate import require_heads
     net = getattr(model, "model", model)
     if all_heads:
         require_heads(net, "all_heads=True")
     n_mels = int(net.n_mels if n_mels is None else n_mels)
-    fe = get_frontend(SR, n_mels, HOP, device)
+    return net, n_mels, get_frontend(SR, n_mels, HOP, device)
+
+
+def _run_slab(net, fe, n_mels: int, slab, buf, offs, outs, all_heads: bool, dev):
+    """One slab of window jobs on the current stream: mt_mel_db_windows_f32 on the store `buf` (offs[key] = first float of a
+    recording), one forward with the slab's chunk_max_power, one mt_stitch_windows per head into outs [(R, 88, T_dst)]."""
     Tw = 1 + WINDOW_SAMPLES // HOP
+    B = len(slab)
+    R, T_dst = int(outs[0].shape[0]), int(outs[0].shape[2])
+    rows, keys, ns, starts, lo, hi = (np.array(c) for c in zip(*slab))
+    h64 = torch.empty((2, B), dtype=torch.int64, pin_memory=True)
+    h64.copy_(torch.from_numpy(np.stack([np.array([offs[k] for k in keys.tolist()]) + HOP * starts, starts]).astype(np.int64)))
+    h32 = torch.empty((6, B), dtype=torch.int32, pin_memory=True)      # win_len, rec_end, t_keep, dst_row, keep_lo, keep_hi
+    h32.copy_(torch.from_numpy(np.stack([np.full(B, WINDOW_SAMPLES), ns - HOP * starts, np.full(B, Tw), rows, lo, hi]).astype(np.int32)))
+    with torch.cuda.device(dev):
+        d64, d32 = h64.to(dev, non_blocking=True), h32.to(dev, non_blocking=True)
+        mel = torch.empty(B, 1, n_mels, Tw, dtype=torch.float32, device=dev)
+        cmax = torch.empty(B, dtype=torch.float32, device=dev)
+        check(lib.mt_mel_db_windows_f32(ptr(fe.plan), fe.desc, ptr(buf), ptr(d64[0]), ptr(d32[0]), ptr(d32[1]), B, WINDOW_SAMPLES, Tw,
+                                        ptr(d32[2]), ptr(mel), ptr(cmax), _lib.stream_ptr()), "mt_mel_db_windows_f32")
+        if all_heads:
+            heads = net(mel, chunk_max_power=cmax, return_all_heads=True)
+            srcs = (heads["frame"], heads["onset"])
+        else:
+            srcs = (net(mel, chunk_max_power=cmax),)
+        for src, dst in zip(srcs, outs):
+            check(lib.mt_stitch_windows(ptr(src.contiguous()), B, N_PITCH, Tw, ptr(d32[3]), ptr(d64[1]), ptr(d32[4]), ptr(d32[5]),
+                                        ptr(dst), R, T_dst, _lib.stream_ptr()), "mt_stitch_windows")
+
+
+@torch.no_grad()
+def _run_windows(model, jobs, R: int, T_dst: int, store_of, n_mels: Optional[int], batch: int, all_heads: bool, device):
+    """jobs: [(dst_row, recording key, n_samples, start frame, lo, hi)].  store_of(keys) -> (store buffer, {key: offset}) for the
+    recordings of one slab.  -> frame logits (R, 88, T_dst) [, onset logits], padding 0."""
+    net, n_mels, fe = _window_setup(model, n_mels, all_heads, device)
     dev = torch.device(device)
     outs = [torch.zeros(R, N_PITCH, T_dst, dtype=torch.float32, device=dev) for _ in range(2 if all_heads else 1)]
     for s0 in range(0, len(jobs), batch):
         slab = jobs[s0:s0 + batch]
-        B = len(slab)
-        rows, keys, ns, starts, lo, hi = (np.array(c) for c in zip(*slab))
-        buf, offs = store_of(keys.tolist())
-        h64 = torch.empty((2, B), dtype=torch.int64, pin_memory=True)
-        h64.copy_(torch.from_numpy(np.stack([np.array([offs[k] for k in keys.tolist()]) + HOP * starts, starts]).astype(np.int64)))
-        h32 = torch.empty((6, B), dtype=torch.int32, pin_memory=True)      # win_len, rec_end, t_keep, dst_row, keep_lo, keep_hi
-        h32.copy_(torch.from_numpy(np.stack([np.full(B, WINDOW_SAMPLES), ns - HOP * starts, np.full(B, Tw), rows, lo, hi]).astype(np.int32)))
-        with torch.cuda.device(dev):
-            d64, d32 = h64.to(dev, non_blocking=True), h32.to(dev, non_blocking=True)
-            mel = torch.empty(B, 1, n_mels, Tw, dtype=torch.float32, device=dev)
-            cmax = torch.empty(B, dtype=torch.float32, device=dev)
-            check(lib.mt_mel_db_windows_f32(ptr(fe.plan), fe.desc, ptr(buf), ptr(d64[0]), ptr(d32[0]), ptr(d32[1]), B, WINDOW_SAMPLES, Tw,
-                                            ptr(d32[2]), ptr(mel), ptr(cmax), _lib.stream_ptr()), "mt_mel_db_windows_f32")
-            if all_heads:
-                heads = net(mel, chunk_max_power=cmax, return_all_heads=True)
-                srcs = (heads["frame"], heads["onset"])
-            else:
-                srcs = (net(mel, chunk_max_power=cmax),)
-            for src, dst in zip(srcs, outs):
-                check(lib.mt_stitch_windows(ptr(src.contiguous()), B, N_PITCH, Tw, ptr(d32[3]), ptr(d64[1]), ptr(d32[4]), ptr(d32[5]),
-                                            ptr(dst), R, T_dst, _lib.stream_ptr()), "mt_stitch_windows")
+        buf, offs = store_of([job[1] for job in slab])
+        _run_slab(net, fe, n_mels, slab, buf, offs, outs, all_heads, dev)
     if hasattr(net, "raise_on_handoff_timeout"):
         net.raise_on_handoff_timeout(sync=True)        # a timed-out recurrence would have left NaN logits: fail loudly, once per pass
     return outs
+
+
+def _store(recordings: Sequence[torch.Tensor]):
+    """The recordings side by side in one zero-padded buffer (64-float alignment and tail, as rawdata.RecordingStore) -> (buffer,
+    offsets, sample counts)."""
+    dev = recordings[0].device
+    ns = [int(y.numel()) for y in recordings]
+    offs, pos = [], 0
+    for n in ns:
+        offs.append(pos)
+        pos += -(-max(n, 1) // _ALIGN) * _ALIGN
+    store = torch.zeros(pos + _PAD, dtype=torch.float32, device=dev)
+    for y, o, n in zip(recordings, offs, ns):
+        store[o:o + n].copy_(y)
+    return store, offs, ns
 
 
 def _jobs(ns: Sequence[int], keys: Sequence, overlap_s: float):
@@ -128,14 +155,7 @@ def transcribe_windows(model, recordings: Sequence[torch.Tensor], overlap_s: flo
     dev = recordings[0].device
     if dev.type != "cuda" or any(y.dim() != 1 or y.dtype != torch.float32 or y.device != dev for y in recordings):
         raise ValueError("transcribe_windows expects 1-D float32 recordings on one CUDA device")
-    ns = [int(y.numel()) for y in recordings]
-    offs, pos = [], 0
-    for n in ns:
-        offs.append(pos)
-        pos += -(-max(n, 1) // _ALIGN) * _ALIGN
-    store = torch.zeros(pos + _PAD, dtype=torch.float32, device=dev)
-    for y, o, n in zip(recordings, offs, ns):
-        store[o:o + n].copy_(y)
+    store, offs, ns = _store(recordings)
     Tg = [1 + n // HOP for n in ns]
     outs = _run_windows(model, _jobs(ns, range(len(ns)), overlap_s), len(ns), max(Tg), lambda keys: (store, offs), n_mels, batch,
                         all_heads, dev)

@@ -2,7 +2,7 @@
 """BASELINE.json configs[4]: offline transcription of a whole corpus (MAESTRO-test sized: ~177 recordings, ~20 h),
 recordings sharded over the GPUs of one node, end-to-end wall-clock + framewise F1.
 
-    python scripts/transcribe_corpus.py [--wav-dir DIR | --synthetic 177 --hours 20] [--model CKPT.pth]
+    python scripts/transcribe_corpus.py [--wav-dir DIR | --synthetic 177 --hours 20] [--model CKPT.pth] [--overlap 2]
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 scripts/transcribe_corpus.py ...
 
 One process per GPU; recordings are assigned longest-first (LPT) so ranks finish together; there is NO data-path
@@ -11,6 +11,8 @@ per-recording F1 values at the end.  With --wav-dir, `<name>.wav` is transcribed
 ((88, T_total) {0,1}) exists, scored against it.  Without data (no MAESTRO in this image) --synthetic draws
 recording durations to the requested total, synthesises noise + decaying tones on the GPU and scores against random
 rolls: that exercises the whole path and gives throughput, the F1 is then meaningless.
+--overlap SECONDS runs whole recordings in overlapping 30 s windows on one frame grid (corpus.transcribe_shard_windows) instead
+of concatenating chunks: notes, .mid files and scores are then on the recording's own grid of 1 + n // 512 frames.
 """
 import argparse
 import json
@@ -44,6 +46,9 @@ def main():
     ap.add_argument("--batch", type=int, default=128,
                     help="chunks per forward (the recurrence interleaves up to four batch groups of 32 in one persistent launch)")
     ap.add_argument("--streams", type=int, default=4, help="forwards in flight (at most 3 for cnn_rnn_large: two recurrence launches each)")
+    ap.add_argument("--overlap", type=float, default=None,
+                    help="seconds of overlap between 30 s windows on the recording's 512-sample frame grid (0.256 .. 15.008); "
+                         "default: 30 s chunks, concatenated")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out-dir", help="directory: write <name>.mid per recording (notes extracted on the device)")
     ap.add_argument("--dump-rolls", help="directory: write <name>.roll.bits.npy (np.packbits of the (88, T_total) roll) per recording")
@@ -66,6 +71,9 @@ def main():
     import music_transcription_amd as mta
     from music_transcription_amd import transcribe as tr
     tr.check_decoder(args.decoder, model_type=args.model_type)
+    if args.overlap is not None:
+        from music_transcription_amd.windows import overlap_frames
+        overlap_frames(args.overlap)
     from music_transcription_amd.parallel import lpt_assign, gather_values
     SR, CH = 16000, 480000
 
@@ -98,6 +106,11 @@ def main():
             return tr.split_into_chunks_device(tr.load_audio_device(os.path.join(args.wav_dir, names[i] + ".wav"), SR, dev))[0]
         return synth_chunks[i]
 
+    def audio_of(i):                        # --overlap: the whole recording, 1-D
+        if args.wav_dir:
+            return tr.load_audio_device(os.path.join(args.wav_dir, names[i] + ".wav"), SR, dev)
+        return synth_chunks[i].view(-1)[:int(durations[i] * SR)]
+
     def reference_roll_of(i, T_total):
         ref_path = os.path.join(args.wav_dir, names[i] + ".roll.npy") if args.wav_dir else None
         if ref_path and os.path.exists(ref_path):
@@ -114,14 +127,20 @@ def main():
     if world > 1:
         dist.barrier()
     t0 = time.perf_counter()
-    res = corpus.transcribe_shard(model, mine, chunks_of, n_mels=args.n_mels, device=dev, batch=args.batch, streams=NS,
-                                  threshold=args.threshold, want_notes=True, reference_roll_of=reference_roll_of, midi_path_of=midi_path_of,
-                                  decoder=args.decoder, onset_threshold=args.onset_threshold, note_metrics=args.note_metrics)
+    if args.overlap is not None:
+        res = corpus.transcribe_shard_windows(model, mine, audio_of, overlap_s=args.overlap, n_mels=args.n_mels, device=dev, batch=args.batch,
+                                              streams=NS, threshold=args.threshold, want_notes=True, reference_roll_of=reference_roll_of,
+                                              midi_path_of=midi_path_of, decoder=args.decoder, onset_threshold=args.onset_threshold,
+                                              note_metrics=args.note_metrics)
+    else:
+        res = corpus.transcribe_shard(model, mine, chunks_of, n_mels=args.n_mels, device=dev, batch=args.batch, streams=NS,
+                                      threshold=args.threshold, want_notes=True, reference_roll_of=reference_roll_of, midi_path_of=midi_path_of,
+                                      decoder=args.decoder, onset_threshold=args.onset_threshold, note_metrics=args.note_metrics)
     if args.dump_rolls:                     # (debug / tests: the rolls are rebuilt from the notes -- they never left the GPU as rolls)
         os.makedirs(args.dump_rolls, exist_ok=True)
         fs = SR / 512
         for i in mine:
-            T_total = res["chunks_per_recording"][i] * 938
+            T_total = res["frames"][i] if args.overlap is not None else res["chunks_per_recording"][i] * 938
             notes = res["notes"].get(i, [])
             roll = np.zeros((88, T_total), dtype=np.uint8)
             for pch, a_, b_ in notes:
@@ -131,7 +150,8 @@ def main():
         dist.barrier()
     wall = time.perf_counter() - t0
     f1s = [res["f1"].get(i, 0.0) for i in mine]
-    n_chunks = res["chunks"]
+    unit = "windows" if args.overlap is not None else "chunks"
+    n_chunks = res[unit]
     n_notes = gather_values([rank], [float(res["n_notes"])], world)
     allf1 = gather_values(mine, f1s, len(names))
     tot_chunks = gather_values([rank], [float(n_chunks)], world)
@@ -143,7 +163,7 @@ def main():
     if rank == 0:
         print(json.dumps({**{"workload": "offline corpus transcription (BASELINE.json configs[4])", "recordings": len(names),
                           "audio_hours": round(sum(durations) / 3600.0, 2) if not args.wav_dir else None, "n_gpus": world,
-                          "chunks": int(sum(tot_chunks)), "wall_s": round(wall, 3), "chunks_per_s": round(sum(tot_chunks) / wall, 1),
+                          unit: int(sum(tot_chunks)), "wall_s": round(wall, 3), unit + "_per_s": round(sum(tot_chunks) / wall, 1),
                           "notes": int(sum(n_notes)), "mean_f1": float(np.mean(allf1)), "per_recording_f1": [float(v) for v in allf1], "model": args.model_type, "data": "wav" if args.wav_dir else "synthetic"}, **extra}))
     if world > 1:
         dist.destroy_process_group()
