@@ -454,6 +454,22 @@ int    mt_note_sweep_list(const float* frame_logits, const float* onset_logits, 
  * recording of NB*T frames per pitch; counts[p], starts / ends in the reference's note order, capacity protocol unchanged. */
 int    mt_heads_to_notes(const float* frame_logits, const float* onset_logits, float thr_frame, float thr_onset, int NB, int P, int T,
                          int* counts, int* starts, int* ends, int capacity, mt_stream_t stream);
+/* The offset-gated decoder behind the three entry points above: the onset-gated rule, and in addition a rising edge of
+ * (sigmoid(offset) > thr_offset) at frame t >= the note's start makes t the note's last frame (end t + 1).  Only edges cut -- an offset
+ * already active before the start does not -- and only onset edges open notes, so starts and the number of notes are the onset-gated
+ * decoder's and every end is <= its end; with the offset head nowhere active the notes are identical.  offset_logits has the layout of
+ * onset_logits (it may be out[2] of the Large forward); frames at or past lengths[b] are inactive for all three heads.  Each call has
+ * the contract of its namesake -- reference notes, matching, counts, chunk concatenation, note order, capacity protocol -- except that
+ * onset_logits and offset_logits must be non-NULL and all three thresholds in (0, 1): otherwise MT_EINVAL and nothing is written. */
+int    mt_note_match_counts_off(const float* frame_logits, const float* onset_logits, const float* offset_logits, float thr_frame,
+                                float thr_onset, float thr_offset, const float* ref_roll, const long long* lengths,
+                                unsigned long long* counts, int B, int P, int T, mt_stream_t stream);
+int    mt_note_match_list_off(const float* frame_logits, const float* onset_logits, const float* offset_logits, float thr_frame,
+                              float thr_onset, float thr_offset, const int* ref_on, const int* ref_off, const long long* ref_ptr,
+                              const long long* lengths, unsigned long long* counts, int B, int P, int T, mt_stream_t stream);
+int    mt_heads_to_notes_off(const float* frame_logits, const float* onset_logits, const float* offset_logits, float thr_frame,
+                             float thr_onset, float thr_offset, int NB, int P, int T, int* counts, int* starts, int* ends, int capacity,
+                             mt_stream_t stream);
 /* The notes of a padded batch of whole recordings (csrc/notes_batch.hip): row (b, p) is frame_logits[(b*P + p)*T + t]
  * (onset_logits alike, NULL = the frame decoder) and its valid frames are [0, L_b), L_b = clamp(lengths[b], 0, T) (int64, device,
  * NULL = all T).  Frames at or past L_b are inactive and never read -- the padding may hold anything, NaN included -- and a note still

@@ -27,6 +27,14 @@ from .ops import f1_counts, f1_from_counts, framewise_f1, predict_from_logits
 SR, CH, HOP = 16000, 480000, 512
 
 
+def _check_corpus_decoder(decoder: str) -> None:
+    """The corpus paths decode with the frame or the onset-gated decoder only: say so for the offset-gated one, instead of falling
+    back to the frame decoder without a word."""
+    if decoder == "onset_offset":
+        raise ValueError("decoder='onset_offset' is not available in corpus transcription (its batched note extractor reads two heads): "
+                         "use 'frame' or 'onset' here, or transcribe.transcribe_audio for the offset-gated decoder")
+
+
 @torch.no_grad()
 def transcribe_shard(model, rec_ids: Sequence[int], chunks_of: Callable[[int], torch.Tensor], *, n_mels: int, device,
                      batch: int = 128, streams: int = 3, threshold: float = 0.5, want_notes: bool = True,
@@ -39,6 +47,7 @@ def transcribe_shard(model, rec_ids: Sequence[int], chunks_of: Callable[[int], t
     the note extraction and the F1 counts (one device synchronisation at the end).  decoder="onset": notes from the onset-gated
     decoder (notes.heads_to_notes_device; cnn_rnn_large with heads only).  note_metrics=True with reference rolls: "note_f1" =
     {i: (onset F1, onset+offset F1)} against the runs of the reference roll, estimated notes from the same decoder."""
+    _check_corpus_decoder(decoder)
     tr.check_decoder(decoder, model=model)
     heads = decoder == "onset"
     dev = torch.device(device)
@@ -249,6 +258,7 @@ def transcribe_shard_windows(model, rec_ids: Sequence[int], audio_of: Callable[[
     flag; the host waits for group g's notes only after group g + 1's slabs are queued.  reference_roll_of(i, frames) -> (88, >= 1)
     roll on the recording's frame grid or None; scored over min(frames, reference frames).  Returns transcribe_shard's keys with
     "windows" for "chunks", and "groups" (lists of recording ids) and "frames" {i: 1 + n_i // 512}."""
+    _check_corpus_decoder(decoder)
     tr.check_decoder(decoder, model=model)
     W.overlap_frames(overlap_s)
     heads = decoder == "onset"

@@ -38,4 +38,22 @@ __device__ __forceinline__ WindowEvents decode_window(bool o, bool a, int lane, 
     return ev;
 }
 
+// The offset-gated decoder: the onset-gated rule with one more way to close a note.  k = the frame's offset-head
+// activity, e = its rising edge.  An edge at frame t makes t the note's last frame: open[t] = st[t] | (open[t-1] & a[t] & !e[t-1]).
+// Only edges cut (an offset still smeared over the next note's start does not), and only onset edges open a note (the rest of
+// a frame run after a cut opens nothing).  With kill = e shifted by one frame and a' = (a & ~kill) | st this is decode_window
+// on a'.  Two more carries: k_prev / e_prev = k / e of frame g0 - 1.
+__device__ __forceinline__ WindowEvents decode_window_off(bool o, bool a, bool k, int lane, unsigned long long& o_prev,
+                                                          unsigned long long& open_prev, unsigned long long& k_prev,
+                                                          unsigned long long& e_prev) {
+    const unsigned long long om = __ballot(o), km = __ballot(k);
+    const unsigned long long st = om & ~((om << 1) | o_prev);
+    const unsigned long long em = km & ~((km << 1) | k_prev);
+    const unsigned long long kill = (em << 1) | e_prev;
+    const bool a2 = (a && !(kill >> lane & 1ull)) || (st >> lane & 1ull);
+    k_prev = km >> 63;
+    e_prev = em >> 63;
+    return decode_window(o, a2, lane, o_prev, open_prev);
+}
+
 }  // namespace mt

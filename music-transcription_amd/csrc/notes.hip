@@ -4,6 +4,7 @@
 //                         mir_eval.transcription.precision_recall_f1_overlap -- one pass over the logits, only counts written;
 //   mt_note_match_list:   the same counts against a per-row note list in ticks of 100 us (the MIDI notes), which may hold re-struck keys;
 //   mt_heads_to_notes:    the onset-gated decoder with mt_roll_to_notes' output contract (main.py's note list).
+//   mt_*_off:             the three of them with the offset-gated decoder (decode_window_off): the offset head ends notes.
 // One wave64 per pitch row; it walks the row in 64-frame windows (note_decode.h), SLAB windows of loads in flight at a time.
 #include <type_traits>
 
@@ -153,10 +154,12 @@ __device__ __forceinline__ void counts_add(unsigned long long* c, int n_ref, int
 }
 
 // counts[b] += {n_ref, n_est, tp_onset, tp_onset_offset} of pitch row (b, p).  Frames at or past lengths[b] are inactive on both sides.
+// OFF: the offset-gated decoder (decode_window_off) with the offset head `offset` at thr_k; otherwise neither is read.
+template <bool OFF>
 __global__ __launch_bounds__(64 * NOTE_WAVES) void note_match_kernel(const float* __restrict__ frame, const float* __restrict__ onset,
-                                                                     float thr_f, float thr_o, const float* __restrict__ ref,
-                                                                     const long long* __restrict__ lengths, unsigned long long* __restrict__ counts,
-                                                                     int B, int P, int T) {
+                                                                     const float* __restrict__ offset, float thr_f, float thr_o, float thr_k,
+                                                                     const float* __restrict__ ref, const long long* __restrict__ lengths,
+                                                                     unsigned long long* __restrict__ counts, int B, int P, int T) {
     const int row = blockIdx.x * NOTE_WAVES + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (row >= B * P) return;
@@ -165,9 +168,9 @@ __global__ __launch_bounds__(64 * NOTE_WAVES) void note_match_kernel(const float
     const size_t base = (size_t)row * T;
     MatchState s;
     match_init(s);
-    unsigned long long o_prev = 0, open_prev = 0, r_prev = 0;
+    unsigned long long o_prev = 0, open_prev = 0, r_prev = 0, k_prev = 0, e_prev = 0;
     for (int s0 = 0; s0 < L; s0 += 64 * NOTE_SLAB) {
-        float xf[NOTE_SLAB], xo[NOTE_SLAB], xr[NOTE_SLAB];
+        float xf[NOTE_SLAB], xo[NOTE_SLAB], xr[NOTE_SLAB], xk[OFF ? NOTE_SLAB : 1];
 #pragma unroll
         for (int w = 0; w < NOTE_SLAB; ++w) {
             const int g = s0 + 64 * w + lane;
@@ -175,6 +178,7 @@ __global__ __launch_bounds__(64 * NOTE_WAVES) void note_match_kernel(const float
             xf[w] = in ? frame[base + g] : 0.0f;
             xo[w] = (in && onset) ? onset[base + g] : 0.0f;
             xr[w] = in ? ref[base + g] : 0.0f;
+            if constexpr (OFF) xk[w] = in ? offset[base + g] : 0.0f;
         }
 #pragma unroll
         for (int w = 0; w < NOTE_SLAB; ++w) {
@@ -183,7 +187,9 @@ __global__ __launch_bounds__(64 * NOTE_WAVES) void note_match_kernel(const float
             const bool in = g0 + lane < L;
             const bool f = in && logit_active(xf[w], thr_f);
             const bool o = onset ? (in && logit_active(xo[w], thr_o)) : f;
-            const WindowEvents est = decode_window(o, f || o, lane, o_prev, open_prev);
+            WindowEvents est;
+            if constexpr (OFF) est = decode_window_off(o, f || o, in && logit_active(xk[w], thr_k), lane, o_prev, open_prev, k_prev, e_prev);
+            else est = decode_window(o, f || o, lane, o_prev, open_prev);
             const unsigned long long rm = __ballot(in && xr[w] > 0.0f);
             const unsigned long long rs = rm & ~((rm << 1) | r_prev), re = ~rm & ((rm << 1) | r_prev);
             r_prev = rm >> 63;
@@ -326,10 +332,12 @@ __device__ __forceinline__ void list_finish(ListState& s, RefCursor& r, bool est
 
 // counts[b] += {n_ref, n_est, tp_onset, tp_onset_offset} of pitch row (b, p) against the notes ref_on/ref_off[ref_ptr[row] .. ref_ptr[row+1]).
 // Frames at or past L = lengths[b] are inactive; reference notes with on >= 320 L are not read and offsets are clipped to 320 L.
+// OFF as in note_match_kernel.
+template <bool OFF>
 __global__ __launch_bounds__(64 * NOTE_WAVES) void note_match_list_kernel(const float* __restrict__ frame, const float* __restrict__ onset,
-                                                                          float thr_f, float thr_o, const int* __restrict__ ref_on,
-                                                                          const int* __restrict__ ref_off, const long long* __restrict__ ref_ptr,
-                                                                          const long long* __restrict__ lengths,
+                                                                          const float* __restrict__ offset, float thr_f, float thr_o, float thr_k,
+                                                                          const int* __restrict__ ref_on, const int* __restrict__ ref_off,
+                                                                          const long long* __restrict__ ref_ptr, const long long* __restrict__ lengths,
                                                                           unsigned long long* __restrict__ counts, int B, int P, int T) {
     const int row = blockIdx.x * NOTE_WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // wave-uniform, and provably so
     const int lane = threadIdx.x & 63;
@@ -342,15 +350,16 @@ __global__ __launch_bounds__(64 * NOTE_WAVES) void note_match_list_kernel(const 
     cursor_open(r, ref_on, ref_off, ref_ptr, row, 0, lane);
     ListState s;
     list_init(s);
-    unsigned long long o_prev = 0, open_prev = 0;
+    unsigned long long o_prev = 0, open_prev = 0, k_prev = 0, e_prev = 0;
     for (int s0 = 0; s0 < L; s0 += 64 * NOTE_SLAB) {
-        float xf[NOTE_SLAB], xo[NOTE_SLAB];
+        float xf[NOTE_SLAB], xo[NOTE_SLAB], xk[OFF ? NOTE_SLAB : 1];
 #pragma unroll
         for (int w = 0; w < NOTE_SLAB; ++w) {
             const int g = s0 + 64 * w + lane;
             const bool in = g < L;
             xf[w] = in ? frame[base + g] : 0.0f;
             xo[w] = (in && onset) ? onset[base + g] : 0.0f;
+            if constexpr (OFF) xk[w] = in ? offset[base + g] : 0.0f;
         }
 #pragma unroll
         for (int w = 0; w < NOTE_SLAB; ++w) {
@@ -359,7 +368,9 @@ __global__ __launch_bounds__(64 * NOTE_WAVES) void note_match_list_kernel(const 
             const bool in = g0 + lane < L;
             const bool f = in && logit_active(xf[w], thr_f);
             const bool o = onset ? (in && logit_active(xo[w], thr_o)) : f;
-            const WindowEvents est = decode_window(o, f || o, lane, o_prev, open_prev);
+            WindowEvents est;
+            if constexpr (OFF) est = decode_window_off(o, f || o, in && logit_active(xk[w], thr_k), lane, o_prev, open_prev, k_prev, e_prev);
+            else est = decode_window(o, f || o, lane, o_prev, open_prev);
             list_window(s, r, est, g0, lane, end_tick);
         }
     }
@@ -371,10 +382,12 @@ __global__ __launch_bounds__(64 * NOTE_WAVES) void note_match_list_kernel(const 
 // ------------------------------------------------------------------------------------------------ onset-gated notes
 // The NB chunks of frame / onset [NB][P][T] are one recording of NB*T frames per pitch (as mt_roll_to_notes).  fill == 0: counts[p] =
 // notes of pitch p.  fill == 1: note k of pitch p goes to [sum of the lower pitches' counts + k], nothing when that exceeds capacity.
+// OFF: the offset-gated decoder; its carries cross chunk boundaries with the onset carry (the walk is over the concatenated frames).
+template <bool OFF>
 __global__ __launch_bounds__(64 * NOTE_WAVES) void heads_notes_kernel(const float* __restrict__ frame, const float* __restrict__ onset,
-                                                                      float thr_f, float thr_o, int NB, int P, int T, int fill,
-                                                                      int* __restrict__ counts, int* __restrict__ starts,
-                                                                      int* __restrict__ ends, int capacity) {
+                                                                      const float* __restrict__ offset, float thr_f, float thr_o, float thr_k,
+                                                                      int NB, int P, int T, int fill, int* __restrict__ counts,
+                                                                      int* __restrict__ starts, int* __restrict__ ends, int capacity) {
     const int p = blockIdx.x * NOTE_WAVES + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (p >= P) return;
@@ -385,10 +398,10 @@ __global__ __launch_bounds__(64 * NOTE_WAVES) void heads_notes_kernel(const floa
     }
     const int n = NB * T;
     int n_on = 0, n_off = 0;
-    unsigned long long o_prev = 0, open_prev = 0;
+    unsigned long long o_prev = 0, open_prev = 0, k_prev = 0, e_prev = 0;
     const unsigned long long below = (1ull << lane) - 1ull;
     for (int s0 = 0; s0 < n; s0 += 64 * NOTE_SLAB) {
-        float xf[NOTE_SLAB], xo[NOTE_SLAB];
+        float xf[NOTE_SLAB], xo[NOTE_SLAB], xk[OFF ? NOTE_SLAB : 1];
 #pragma unroll
         for (int w = 0; w < NOTE_SLAB; ++w) {
             const int g = s0 + 64 * w + lane;
@@ -396,6 +409,7 @@ __global__ __launch_bounds__(64 * NOTE_WAVES) void heads_notes_kernel(const floa
             const size_t at = ((size_t)c * P + p) * T + (g - c * T);
             xf[w] = g < n ? frame[at] : 0.0f;
             xo[w] = g < n ? onset[at] : 0.0f;
+            if constexpr (OFF) xk[w] = g < n ? offset[at] : 0.0f;
         }
 #pragma unroll
         for (int w = 0; w < NOTE_SLAB; ++w) {
@@ -404,7 +418,9 @@ __global__ __launch_bounds__(64 * NOTE_WAVES) void heads_notes_kernel(const floa
             const bool in = g0 + lane < n;
             const bool f = in && logit_active(xf[w], thr_f);
             const bool o = in && logit_active(xo[w], thr_o);
-            const WindowEvents ev = decode_window(o, f || o, lane, o_prev, open_prev);
+            WindowEvents ev;
+            if constexpr (OFF) ev = decode_window_off(o, f || o, in && logit_active(xk[w], thr_k), lane, o_prev, open_prev, k_prev, e_prev);
+            else ev = decode_window(o, f || o, lane, o_prev, open_prev);
             if (fill) {
                 if (ev.starts >> lane & 1ull) starts[out + n_on + __popcll(ev.starts & below)] = g0 + lane;
                 if (ev.closes >> lane & 1ull) ends[out + n_off + __popcll(ev.closes & below)] = g0 + lane;
@@ -601,19 +617,62 @@ __global__ __launch_bounds__(64 * SWEEP_WAVES) void note_sweep_kernel(const floa
 
 using namespace mt;
 
+// The launches behind mt_note_match_counts / mt_note_match_counts_off (OFF = the offset-gated decoder); arguments already checked.
+template <bool OFF>
+static int launch_note_match(const float* frame, const float* onset, const float* offset, float thr_f, float thr_o, float thr_k, const float* ref,
+                             const long long* lengths, unsigned long long* counts, int B, int P, int T, hipStream_t st) {
+    MT_CHECK_HIP(hipMemsetAsync(counts, 0, (size_t)B * 4 * sizeof(unsigned long long), st));
+    const int rows = B * P;
+    hipLaunchKernelGGL(note_match_kernel<OFF>, dim3((rows + NOTE_WAVES - 1) / NOTE_WAVES), dim3(64 * NOTE_WAVES), 0, st, frame, onset, offset,
+                       thr_f, thr_o, thr_k, ref, lengths, counts, B, P, T);
+    MT_CHECK_LAUNCH();
+    return MT_OK;
+}
+
+template <bool OFF>
+static int launch_note_match_list(const float* frame, const float* onset, const float* offset, float thr_f, float thr_o, float thr_k,
+                                  const int* ref_on, const int* ref_off, const long long* ref_ptr, const long long* lengths,
+                                  unsigned long long* counts, int B, int P, int T, hipStream_t st) {
+    MT_CHECK_HIP(hipMemsetAsync(counts, 0, (size_t)B * 4 * sizeof(unsigned long long), st));
+    const int rows = B * P;
+    hipLaunchKernelGGL(note_match_list_kernel<OFF>, dim3((rows + NOTE_WAVES - 1) / NOTE_WAVES), dim3(64 * NOTE_WAVES), 0, st, frame, onset, offset,
+                       thr_f, thr_o, thr_k, ref_on, ref_off, ref_ptr, lengths, counts, B, P, T);
+    MT_CHECK_LAUNCH();
+    return MT_OK;
+}
+
+template <bool OFF>
+static int launch_heads_notes(const float* frame, const float* onset, const float* offset, float thr_f, float thr_o, float thr_k, int NB, int P,
+                              int T, int* counts, int* starts, int* ends, int capacity, hipStream_t st) {
+    const dim3 grid((P + NOTE_WAVES - 1) / NOTE_WAVES), block(64 * NOTE_WAVES);
+    for (int fill = 0; fill < 2; ++fill) {                     // count, then write
+        hipLaunchKernelGGL(heads_notes_kernel<OFF>, grid, block, 0, st, frame, onset, offset, thr_f, thr_o, thr_k, NB, P, T, fill, counts, starts,
+                           ends, capacity);
+        MT_CHECK_LAUNCH();
+    }
+    return MT_OK;
+}
+
+static bool thr_ok(float t) { return t > 0.0f && t < 1.0f; }
+
 extern "C" int mt_note_match_counts(const float* frame_logits, const float* onset_logits, float thr_frame, float thr_onset, const float* ref_roll,
                                     const long long* lengths, unsigned long long* counts, int B, int P, int T, mt_stream_t stream) {
     MT_REQUIRE(frame_logits && ref_roll && counts, MT_EINVAL, "mt_note_match_counts: null pointer");
     MT_REQUIRE(B > 0 && P > 0 && T > 0 && (long long)B * P < 2147483647ll && T < (1 << 30), MT_EINVAL, "mt_note_match_counts: bad dims");
     MT_REQUIRE(thr_frame > 0.0f && thr_frame < 1.0f && (!onset_logits || (thr_onset > 0.0f && thr_onset < 1.0f)), MT_EINVAL,
                "mt_note_match_counts: thresholds must lie in (0, 1)");
-    hipStream_t st = (hipStream_t)stream;
-    MT_CHECK_HIP(hipMemsetAsync(counts, 0, (size_t)B * 4 * sizeof(unsigned long long), st));
-    const int rows = B * P;
-    hipLaunchKernelGGL(note_match_kernel, dim3((rows + NOTE_WAVES - 1) / NOTE_WAVES), dim3(64 * NOTE_WAVES), 0, st, frame_logits, onset_logits,
-                       thr_frame, thr_onset, ref_roll, lengths, counts, B, P, T);
-    MT_CHECK_LAUNCH();
-    return MT_OK;
+    return launch_note_match<false>(frame_logits, onset_logits, nullptr, thr_frame, thr_onset, 0.5f, ref_roll, lengths, counts, B, P, T,
+                                    (hipStream_t)stream);
+}
+
+extern "C" int mt_note_match_counts_off(const float* frame_logits, const float* onset_logits, const float* offset_logits, float thr_frame,
+                                        float thr_onset, float thr_offset, const float* ref_roll, const long long* lengths,
+                                        unsigned long long* counts, int B, int P, int T, mt_stream_t stream) {
+    MT_REQUIRE(frame_logits && onset_logits && offset_logits && ref_roll && counts, MT_EINVAL, "mt_note_match_counts_off: null pointer");
+    MT_REQUIRE(B > 0 && P > 0 && T > 0 && (long long)B * P < 2147483647ll && T < (1 << 30), MT_EINVAL, "mt_note_match_counts_off: bad dims");
+    MT_REQUIRE(thr_ok(thr_frame) && thr_ok(thr_onset) && thr_ok(thr_offset), MT_EINVAL, "mt_note_match_counts_off: thresholds must lie in (0, 1)");
+    return launch_note_match<true>(frame_logits, onset_logits, offset_logits, thr_frame, thr_onset, thr_offset, ref_roll, lengths, counts, B, P, T,
+                                   (hipStream_t)stream);
 }
 
 extern "C" int mt_note_match_list(const float* frame_logits, const float* onset_logits, float thr_frame, float thr_onset, const int* ref_on,
@@ -624,13 +683,20 @@ extern "C" int mt_note_match_list(const float* frame_logits, const float* onset_
                MT_EINVAL, "mt_note_match_list: bad dims (frame times must fit 31 bits of 100 us ticks)");
     MT_REQUIRE(thr_frame > 0.0f && thr_frame < 1.0f && (!onset_logits || (thr_onset > 0.0f && thr_onset < 1.0f)), MT_EINVAL,
                "mt_note_match_list: thresholds must lie in (0, 1)");
-    hipStream_t st = (hipStream_t)stream;
-    MT_CHECK_HIP(hipMemsetAsync(counts, 0, (size_t)B * 4 * sizeof(unsigned long long), st));
-    const int rows = B * P;
-    hipLaunchKernelGGL(note_match_list_kernel, dim3((rows + NOTE_WAVES - 1) / NOTE_WAVES), dim3(64 * NOTE_WAVES), 0, st, frame_logits, onset_logits,
-                       thr_frame, thr_onset, ref_on, ref_off, ref_ptr, lengths, counts, B, P, T);
-    MT_CHECK_LAUNCH();
-    return MT_OK;
+    return launch_note_match_list<false>(frame_logits, onset_logits, nullptr, thr_frame, thr_onset, 0.5f, ref_on, ref_off, ref_ptr, lengths, counts,
+                                         B, P, T, (hipStream_t)stream);
+}
+
+extern "C" int mt_note_match_list_off(const float* frame_logits, const float* onset_logits, const float* offset_logits, float thr_frame,
+                                      float thr_onset, float thr_offset, const int* ref_on, const int* ref_off, const long long* ref_ptr,
+                                      const long long* lengths, unsigned long long* counts, int B, int P, int T, mt_stream_t stream) {
+    MT_REQUIRE(frame_logits && onset_logits && offset_logits && ref_on && ref_off && ref_ptr && counts, MT_EINVAL,
+               "mt_note_match_list_off: null pointer");
+    MT_REQUIRE(B > 0 && P > 0 && T > 0 && (long long)B * P < 2147483647ll && (long long)T * TICKS_PER_FRAME < 2147483647ll - 64 * NOTE_SLAB,
+               MT_EINVAL, "mt_note_match_list_off: bad dims (frame times must fit 31 bits of 100 us ticks)");
+    MT_REQUIRE(thr_ok(thr_frame) && thr_ok(thr_onset) && thr_ok(thr_offset), MT_EINVAL, "mt_note_match_list_off: thresholds must lie in (0, 1)");
+    return launch_note_match_list<true>(frame_logits, onset_logits, offset_logits, thr_frame, thr_onset, thr_offset, ref_on, ref_off, ref_ptr,
+                                        lengths, counts, B, P, T, (hipStream_t)stream);
 }
 
 // The checks the two sweep entry points share; the thresholds end up in `thr`, which the kernel takes by value.
@@ -684,13 +750,17 @@ extern "C" int mt_heads_to_notes(const float* frame_logits, const float* onset_l
     MT_REQUIRE(NB > 0 && P > 0 && T > 0 && (long long)NB * T < 2147483647ll - 64 * NOTE_SLAB, MT_EINVAL, "mt_heads_to_notes: bad dims");
     MT_REQUIRE(thr_frame > 0.0f && thr_frame < 1.0f && thr_onset > 0.0f && thr_onset < 1.0f, MT_EINVAL,
                "mt_heads_to_notes: thresholds must lie in (0, 1)");
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((P + NOTE_WAVES - 1) / NOTE_WAVES), block(64 * NOTE_WAVES);
-    hipLaunchKernelGGL(heads_notes_kernel, grid, block, 0, st, frame_logits, onset_logits, thr_frame, thr_onset, NB, P, T, 0, counts, starts, ends,
-                       capacity);
-    MT_CHECK_LAUNCH();
-    hipLaunchKernelGGL(heads_notes_kernel, grid, block, 0, st, frame_logits, onset_logits, thr_frame, thr_onset, NB, P, T, 1, counts, starts, ends,
-                       capacity);
-    MT_CHECK_LAUNCH();
-    return MT_OK;
+    return launch_heads_notes<false>(frame_logits, onset_logits, nullptr, thr_frame, thr_onset, 0.5f, NB, P, T, counts, starts, ends, capacity,
+                                     (hipStream_t)stream);
+}
+
+extern "C" int mt_heads_to_notes_off(const float* frame_logits, const float* onset_logits, const float* offset_logits, float thr_frame,
+                                     float thr_onset, float thr_offset, int NB, int P, int T, int* counts, int* starts, int* ends, int capacity,
+                                     mt_stream_t stream) {
+    MT_REQUIRE(frame_logits && onset_logits && offset_logits && counts && starts && ends && capacity > 0, MT_EINVAL,
+               "mt_heads_to_notes_off: bad arguments");
+    MT_REQUIRE(NB > 0 && P > 0 && T > 0 && (long long)NB * T < 2147483647ll - 64 * NOTE_SLAB, MT_EINVAL, "mt_heads_to_notes_off: bad dims");
+    MT_REQUIRE(thr_ok(thr_frame) && thr_ok(thr_onset) && thr_ok(thr_offset), MT_EINVAL, "mt_heads_to_notes_off: thresholds must lie in (0, 1)");
+    return launch_heads_notes<true>(frame_logits, onset_logits, offset_logits, thr_frame, thr_onset, thr_offset, NB, P, T, counts, starts, ends,
+                                    capacity, (hipStream_t)stream);
 }

@@ -46,9 +46,12 @@ def require_heads(model, what: str) -> None:
 
 
 @torch.no_grad()
-def collect_logits(model, dataset, indices: Sequence[int], device="cuda", max_batch: int = 128, all_heads: bool = False):
+def collect_logits(model, dataset, indices: Sequence[int], device="cuda", max_batch: int = 128, all_heads: bool = False,
+                   with_offset: bool = False):
     """Forward every sample once; returns [(index, logits (88, T) on device, roll (88, T) on device)], with all_heads=True
-    [(index, frame logits, roll, onset logits)]."""
+    [(index, frame logits, roll, onset logits)] and with with_offset=True as well [(..., onset logits, offset logits)]."""
+    if with_offset and not all_heads:
+        raise ValueError("with_offset=True needs all_heads=True (the offset logits come with the onset logits)")
     if all_heads:
         require_heads(model, "collect_logits(all_heads=True)")
     by_len = defaultdict(list)
@@ -62,8 +65,9 @@ def collect_logits(model, dataset, indices: Sequence[int], device="cuda", max_ba
             mel = torch.stack([m for _, m, _ in grp]).to(device)                    # (b, 1, n_mels, T): equal T, no padding
             if all_heads:
                 heads = model(mel, return_all_heads=True)
-                for (i, _, roll), lg, on in zip(grp, heads["frame"], heads["onset"]):
-                    out.append((i, lg.contiguous(), roll.to(device).float().contiguous(), on.contiguous()))
+                for k, ((i, _, roll), lg, on) in enumerate(zip(grp, heads["frame"], heads["onset"])):
+                    item = (i, lg.contiguous(), roll.to(device).float().contiguous(), on.contiguous())
+                    out.append(item + (heads["offset"][k].contiguous(),) if with_offset else item)
             else:
                 logits = model(mel)
                 for (i, _, roll), lg in zip(grp, logits):
@@ -99,12 +103,12 @@ def f1_at_thresholds(logits_rolls, thresholds: Sequence[float]) -> np.ndarray:
     return per_sample
 
 
-def _collect(model, dataset, indices, device, window_overlap: Optional[float], all_heads: bool = False):
+def _collect(model, dataset, indices, device, window_overlap: Optional[float], all_heads: bool = False, with_offset: bool = False):
     """collect_logits, or with window_overlap (seconds) collect_logits_windows over a whole-file dataset."""
     if window_overlap is None:
-        return collect_logits(model, dataset, indices, device, all_heads=all_heads)
+        return collect_logits(model, dataset, indices, device, all_heads=all_heads, with_offset=with_offset)
     from .windows import collect_logits_windows
-    return collect_logits_windows(model, dataset, indices, window_overlap, device, all_heads=all_heads)
+    return collect_logits_windows(model, dataset, indices, window_overlap, device, all_heads=all_heads, with_offset=with_offset)
 
 
 def evaluate_dataset(model, dataset, threshold: float = 0.5, device="cuda", subset: Optional[int] = None,
@@ -124,25 +128,28 @@ NOTE_METRIC_KEYS = tuple(f"{c}_{m}" for c in ("onset", "onset_offset") for m in 
 
 def note_metrics_dataset(model, dataset, threshold: float = 0.5, onset_threshold: Optional[float] = None, device="cuda",
                          subset: Optional[int] = None, max_batch: int = 128, rank: int = 0, world: int = 1,
-                         window_overlap: Optional[float] = None, note_reference: str = "roll") -> dict:
+                         window_overlap: Optional[float] = None, note_reference: str = "roll",
+                         offset_threshold: Optional[float] = None) -> dict:
     """Note-level metrics of every sample, identical on every rank: {"mean": {key: value}, "per_sample": {key: [values]}} over
     NOTE_METRIC_KEYS (onset / onset_offset x precision / recall / f1).  onset_threshold=None: notes are the runs of
     sigmoid(frame) > threshold (the frame decoder); otherwise the onset-gated decoder with the onset head at onset_threshold.
+    offset_threshold (needs onset_threshold): the offset-gated decoder, which also ends notes where the offset head fires.
     Reference notes: note_reference="roll", the runs of the dataset's label roll; "midi", the MIDI note list of each recording
     (dataset.ref_notes: a whole-file MaestroDataset built with onset_labels="midi").  Unweighted means over samples, as
     evaluate_dataset (window_overlap too)."""
     from .notes import note_match_counts, note_match_list, note_prf
     _check_note_reference(dataset, note_reference)
+    onset, offset = onset_threshold is not None, offset_threshold is not None
+    if offset and not onset:
+        raise ValueError("offset_threshold: the offset-gated decoder needs onset_threshold as well")
     n = len(dataset) if subset is None else min(subset, len(dataset))
     mine = list(shard_range(n, rank, world))
-    onset = onset_threshold is not None
-    lr = _collect(model, dataset, mine, device, window_overlap, all_heads=onset)
+    lr = _collect(model, dataset, mine, device, window_overlap, all_heads=onset, with_offset=offset)
     vals = {k: [] for k in NOTE_METRIC_KEYS}
-    for frame, on, ref, lengths in _note_groups(lr, dataset, onset, note_reference, max_batch):
-        if note_reference == "midi":
-            counts = note_match_list(frame, ref, threshold, on, onset_threshold if onset else 0.5, lengths)
-        else:
-            counts = note_match_counts(frame, ref, threshold, on, onset_threshold if onset else 0.5, lengths)
+    match = note_match_list if note_reference == "midi" else note_match_counts
+    for frame, on, ref, lengths, off in _note_groups(lr, dataset, onset, note_reference, max_batch, offset):
+        counts = match(frame, ref, threshold, on, onset_threshold if onset else 0.5, lengths, offset_logits=off,
+                       offset_threshold=offset_threshold if offset else 0.5)
         for m in note_prf(counts):
             for c in ("onset", "onset_offset"):
                 for k, v in zip(("precision", "recall", "f1"), m[c]):
@@ -159,9 +166,9 @@ def _check_note_reference(dataset, note_reference: str) -> None:
                          "MaestroDataset(chunk_length=None, onset_labels='midi') (scripts/evaluate.py --data_source full)")
 
 
-def _note_groups(lr, dataset, onset: bool, note_reference: str, max_batch: int):
+def _note_groups(lr, dataset, onset: bool, note_reference: str, max_batch: int, offset: bool = False):
     """The collected samples in groups of max_batch, one counts pass each: (frame (b, 88, T), onset or None, reference roll or note
-    list, lengths); unequal lengths padded to the group's longest and masked by `lengths`."""
+    list, lengths, offset or None); unequal lengths padded to the group's longest and masked by `lengths`."""
     for s in range(0, len(lr), max_batch):
         grp = lr[s:s + max_batch]
         lengths = [int(x[1].shape[-1]) for x in grp]
@@ -170,7 +177,8 @@ def _note_groups(lr, dataset, onset: bool, note_reference: str, max_batch: int):
         frame = torch.stack([pad(x[1]) for x in grp])
         on = torch.stack([pad(x[3]) for x in grp]) if onset else None
         ref = dataset.ref_notes([x[0] for x in grp]) if note_reference == "midi" else torch.stack([pad(x[2]) for x in grp])
-        yield frame, on, ref, lengths
+        off = torch.stack([pad(x[4]) for x in grp]) if offset else None
+        yield frame, on, ref, lengths, off
 
 
 def tune_threshold(model, dataset, device="cuda", subset: Optional[int] = None, tune_range=(0.05, 0.95), tune_step=0.1,
@@ -246,6 +254,9 @@ def tune_note_thresholds(model, dataset, device="cuda", subset: Optional[int] = 
     -> (frame threshold, onset threshold or None, best mean F1), identical on every rank.  A candidate at or past 1 (the schedule's
     last grid point can be) decodes no note and scores 0, as it does for tune_threshold."""
     from .notes import note_prf, note_sweep_counts
+    if decoder == "onset_offset":
+        raise ValueError("tune_note_thresholds does not cover decoder='onset_offset': the threshold sweeps are not extended to the "
+                         "offset head (tune with decoder='onset', then pass offset_threshold to note_metrics_dataset)")
     if decoder not in ("onset", "frame"):
         raise ValueError(f"decoder must be 'onset' or 'frame', got {decoder!r}")
     if objective not in ("onset", "onset_offset"):
@@ -266,7 +277,7 @@ def tune_note_thresholds(model, dataset, device="cuda", subset: Optional[int] = 
         local = np.zeros((len(lr), len(fts), len(ots)))                                   # thresholds >= 1: no notes, F1 0
         at = 0
         if len(fi) and len(oj):
-            for frame, on, ref, lengths in _note_groups(lr, dataset, onset, note_reference, max_batch):
+            for frame, on, ref, lengths, _ in _note_groups(lr, dataset, onset, note_reference, max_batch):
                 counts = note_sweep_counts(frame, ref, fts[fi], on, ots[oj] if onset else None, lengths)
                 f1 = np.array([m[objective][2] for m in note_prf(counts)]).reshape(len(lengths), len(fi), len(oj))
                 local[at:at + len(lengths), fi[:, None], oj[None, :]] = f1

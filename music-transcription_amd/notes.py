@@ -10,6 +10,8 @@
     (mt_note_sweep_counts / mt_note_sweep_list): every cell's sigmoid is evaluated once, whatever the size of the grid.
   * `note_prf` turns those counts into precision / recall / F1 on the host (0 for an empty denominator, as mir_eval).
   * `heads_to_notes_device` = transcribe.notes_from_logits_device with the onset-gated decoder (mt_heads_to_notes).
+  * `offset_logits=` on the three calls above selects the offset-gated decoder: the onset-gated notes, ended where
+    the offset head fires (mt_note_match_counts_off / mt_note_match_list_off / mt_heads_to_notes_off).
   * `notes_batch_device` = either decoder over a padded batch of whole recordings with `lengths` (mt_notes_batch): the notes of all
     recordings in two device-to-host copies.
 """
@@ -44,6 +46,22 @@ def _check_threshold(t: float, name: str) -> float:
     return t
 
 
+def _needs_onset(offset_logits, onset_logits) -> None:
+    """The offset-gated decoder opens its notes at onset edges: refuse offset logits without onset logits, before anything else."""
+    if offset_logits is not None and onset_logits is None:
+        raise ValueError("offset_logits: the offset-gated decoder needs onset_logits as well")
+
+
+def _offset_head(offset_logits, offset_threshold: float, shape):
+    """The checked offset logits and threshold of the offset-gated decoder (None, 0.5 without them)."""
+    if offset_logits is None:
+        return None, 0.5
+    off = _rows(offset_logits, "offset_logits")
+    if off.shape != shape:
+        raise ValueError(f"shape mismatch: frame {tuple(shape)}, offset {tuple(off.shape)}")
+    return off, _check_threshold(offset_threshold, "offset_threshold")
+
+
 def _lengths(lengths, B: int, dev) -> Optional[torch.Tensor]:
     if lengths is None:
         return None
@@ -71,9 +89,12 @@ def _note_tables(ref_notes: Dict[str, torch.Tensor], B: int, P: int, dev):
 
 
 def note_match_counts(frame_logits: torch.Tensor, ref_roll: torch.Tensor, threshold: float = 0.5, onset_logits: Optional[torch.Tensor] = None,
-                      onset_threshold: float = 0.5, lengths=None) -> torch.Tensor:
+                      onset_threshold: float = 0.5, lengths=None, offset_logits: Optional[torch.Tensor] = None,
+                      offset_threshold: float = 0.5) -> torch.Tensor:
     """(B, P, T) frame logits (and onset logits for the onset-gated decoder) and (B, P, T) reference roll on the device -> (B, 4)
-    int64 device tensor {n_ref, n_est, tp_onset, tp_onset_offset}.  lengths (B,) = valid frames per sample (None: all T)."""
+    int64 device tensor {n_ref, n_est, tp_onset, tp_onset_offset}.  lengths (B,) = valid frames per sample (None: all T).  With
+    offset_logits (and onset_logits) the estimates come from the offset-gated decoder (mt_note_match_counts_off)."""
+    _needs_onset(offset_logits, onset_logits)
     x = _rows(frame_logits, "frame_logits")
     ref = _rows(ref_roll, "ref_roll")
     on = None if onset_logits is None else _rows(onset_logits, "onset_logits")
@@ -81,11 +102,16 @@ def note_match_counts(frame_logits: torch.Tensor, ref_roll: torch.Tensor, thresh
         raise ValueError(f"shape mismatch: frame {tuple(x.shape)}, ref {tuple(ref.shape)}, onset {None if on is None else tuple(on.shape)}")
     thr = _check_threshold(threshold, "threshold")
     othr = _check_threshold(onset_threshold, "onset_threshold") if on is not None else 0.5
+    off, kthr = _offset_head(offset_logits, offset_threshold, x.shape)
     B, P, T = x.shape
     dev = x.device
     ln = _lengths(lengths, B, dev)
     counts = torch.empty(B, 4, dtype=torch.int64, device=dev)
     with torch.cuda.device(dev):
+        if off is not None:
+            check(lib.mt_note_match_counts_off(ptr(x), ptr(on), ptr(off), thr, othr, kthr, ptr(ref), ptr(ln), ptr(counts), B, P, T,
+                                               _lib.stream_ptr()), "mt_note_match_counts_off")
+            return counts
         check(lib.mt_note_match_counts(ptr(x), ptr(on), thr, othr, ptr(ref), ptr(ln), ptr(counts), B, P, T, _lib.stream_ptr()),
               "mt_note_match_counts")
     return counts
@@ -95,23 +121,31 @@ TICKS_PER_FRAME = 320              # one frame in ticks of 100 us
 
 
 def note_match_list(frame_logits: torch.Tensor, ref_notes: Dict[str, torch.Tensor], threshold: float = 0.5,
-                    onset_logits: Optional[torch.Tensor] = None, onset_threshold: float = 0.5, lengths=None) -> torch.Tensor:
+                    onset_logits: Optional[torch.Tensor] = None, onset_threshold: float = 0.5, lengths=None,
+                    offset_logits: Optional[torch.Tensor] = None, offset_threshold: float = 0.5) -> torch.Tensor:
     """note_match_counts against a note list: ref_notes = {"on", "off"} int32 ticks of 100 us and "ptr" int64 (B * P + 1,) on the
     device, row (b, p) owning on/off[ptr[b*P + p]:ptr[b*P + p + 1]] sorted by onset (MaestroDataset.ref_notes).  An estimated
     note [s, e) in frames has times 320 s, 320 e; onsets match within 500 ticks, offsets within max(500, 0.2 reference length).
-    Notes that start at or past a sample's valid frames are not counted.  -> (B, 4) int64 {n_ref, n_est, tp_onset, tp_onset_offset}."""
+    Notes that start at or past a sample's valid frames are not counted.  -> (B, 4) int64 {n_ref, n_est, tp_onset, tp_onset_offset}.
+    With offset_logits (and onset_logits) the estimates come from the offset-gated decoder (mt_note_match_list_off)."""
+    _needs_onset(offset_logits, onset_logits)
     x = _rows(frame_logits, "frame_logits")
     on = None if onset_logits is None else _rows(onset_logits, "onset_logits")
     if on is not None and on.shape != x.shape:
         raise ValueError(f"shape mismatch: frame {tuple(x.shape)}, onset {tuple(on.shape)}")
     thr = _check_threshold(threshold, "threshold")
     othr = _check_threshold(onset_threshold, "onset_threshold") if on is not None else 0.5
+    off, kthr = _offset_head(offset_logits, offset_threshold, x.shape)
     B, P, T = x.shape
     dev = x.device
     r_on, r_off, r_ptr = _note_tables(ref_notes, B, P, dev)
     ln = _lengths(lengths, B, dev)
     counts = torch.empty(B, 4, dtype=torch.int64, device=dev)
     with torch.cuda.device(dev):
+        if off is not None:
+            check(lib.mt_note_match_list_off(ptr(x), ptr(on), ptr(off), thr, othr, kthr, ptr(r_on), ptr(r_off), ptr(r_ptr), ptr(ln), ptr(counts),
+                                             B, P, T, _lib.stream_ptr()), "mt_note_match_list_off")
+            return counts
         check(lib.mt_note_match_list(ptr(x), ptr(on), thr, othr, ptr(r_on), ptr(r_off), ptr(r_ptr), ptr(ln), ptr(counts), B, P, T,
                                      _lib.stream_ptr()), "mt_note_match_list")
     return counts
@@ -196,14 +230,18 @@ def note_prf(counts) -> List[Dict[str, Tuple[float, float, float]]]:
 
 
 def heads_to_notes_device(frame_logits: torch.Tensor, onset_logits: torch.Tensor, threshold: float = 0.5, onset_threshold: float = 0.5,
-                          fs: float = FS, min_midi: int = 21) -> List[Tuple[int, float, float]]:
+                          fs: float = FS, min_midi: int = 21, offset_logits: Optional[torch.Tensor] = None,
+                          offset_threshold: float = 0.5) -> List[Tuple[int, float, float]]:
     """(n_chunks, 88, T) frame and onset logits ON THE DEVICE -> notes of the onset-gated decoder over the chunks concatenated in
-    time, in the reference's note order (pitch-major, then time); only counts and two ints per note reach the host."""
+    time, in the reference's note order (pitch-major, then time); only counts and two ints per note reach the host.  With
+    offset_logits: the notes of the offset-gated decoder (mt_heads_to_notes_off), which end where the offset head fires."""
+    _needs_onset(offset_logits, onset_logits)
     x = _rows(frame_logits, "frame_logits")
     on = _rows(onset_logits, "onset_logits")
     if on.shape != x.shape:
         raise ValueError(f"frame {tuple(x.shape)} and onset {tuple(on.shape)} logits differ in shape")
     thr, othr = _check_threshold(threshold, "threshold"), _check_threshold(onset_threshold, "onset_threshold")
+    off, kthr = _offset_head(offset_logits, offset_threshold, x.shape)
     NB, P, T = x.shape
     dev = x.device
     counts = torch.empty(P, dtype=torch.int32, device=dev)
@@ -211,8 +249,12 @@ def heads_to_notes_device(frame_logits: torch.Tensor, onset_logits: torch.Tensor
     while True:
         starts, ends = torch.empty(cap, dtype=torch.int32, device=dev), torch.empty(cap, dtype=torch.int32, device=dev)
         with torch.cuda.device(dev):
-            check(lib.mt_heads_to_notes(ptr(x), ptr(on), thr, othr, NB, P, T, ptr(counts), ptr(starts), ptr(ends), cap, _lib.stream_ptr()),
-                  "mt_heads_to_notes")
+            if off is not None:
+                check(lib.mt_heads_to_notes_off(ptr(x), ptr(on), ptr(off), thr, othr, kthr, NB, P, T, ptr(counts), ptr(starts), ptr(ends), cap,
+                                                _lib.stream_ptr()), "mt_heads_to_notes_off")
+            else:
+                check(lib.mt_heads_to_notes(ptr(x), ptr(on), thr, othr, NB, P, T, ptr(counts), ptr(starts), ptr(ends), cap, _lib.stream_ptr()),
+                      "mt_heads_to_notes")
         c = counts.cpu().numpy()
         total = int(c.sum())
         if total <= cap:

@@ -263,45 +263,53 @@ def notes_from_logits_device(logits: torch.Tensor, threshold: float = THRESHOLD,
     return [(int(pp), float(a) / fs, float(b) / fs) for pp, a, b in zip(pitches, s, e) if b > a]
 
 
-DECODERS = ("frame", "onset")
+DECODERS = ("frame", "onset", "onset_offset")
+HEAD_DECODERS = ("onset", "onset_offset")     # they read the onset head (and the offset head) beside the frame head
 
 
 def check_decoder(decoder: str, model_type: str = None, model=None) -> None:
-    """The onset decoder reads the onset head: refuse it for a model without one, before any GPU work."""
+    """The onset and onset_offset decoders read the onset (and offset) head: refuse them for a model without heads, before any GPU work."""
     if decoder not in DECODERS:
         raise ValueError(f"decoder must be one of {DECODERS}, got {decoder!r}")
-    if decoder != "onset":
+    if decoder not in HEAD_DECODERS:
         return
     if model is not None:
         from .evaluate import require_heads
-        require_heads(model, "decoder='onset'")
+        require_heads(model, f"decoder={decoder!r}")
     elif model_type is not None and model_type.lower() not in ("cnn_rnn_large", "large"):
-        raise ValueError(f"decoder='onset' needs the onset head of cnn_rnn_large (model type {model_type!r} has none)")
+        raise ValueError(f"decoder={decoder!r} needs the onset{' and offset heads' if decoder == 'onset_offset' else ' head'} of cnn_rnn_large "
+                         f"(model type {model_type!r} has none)")
 
 
 @torch.no_grad()
 def transcribe_chunks_to_notes(model: "TranscriptionModel", chunks, threshold: float = THRESHOLD, batch: int = 128, n_mels: int = N_MELS,
-                               device: str = "cuda", decoder: str = "frame", onset_threshold: float = THRESHOLD) -> List[Tuple[int, float, float]]:
+                               device: str = "cuda", decoder: str = "frame", onset_threshold: float = THRESHOLD,
+                               offset_threshold: float = THRESHOLD) -> List[Tuple[int, float, float]]:
     """(n, 480000) waveform chunks -> notes; mel, forward, threshold, concatenation and run-length all on the GPU.  decoder="onset":
-    notes start at rising edges of the onset head and last while frame or onset is active (notes.heads_to_notes_device)."""
+    notes start at rising edges of the onset head and last while frame or onset is active (notes.heads_to_notes_device);
+    decoder="onset_offset": those notes, ended where the offset head fires."""
     check_decoder(decoder, model=model)
+    with_heads, with_offset = decoder in HEAD_DECODERS, decoder == "onset_offset"
     fe = get_frontend(SR, n_mels, HOP_LENGTH, device)
     if not torch.is_tensor(chunks):
         chunks = torch.from_numpy(np.ascontiguousarray(chunks, dtype=np.float32))
     chunks = chunks.to(device)
     net = model.model
-    outs, onsets = [], []
+    outs, onsets, offsets = [], [], []
     for i in range(0, len(chunks), batch):
         mel, cmax = fe(chunks[i:i + batch].contiguous(), clamp=False)
-        if decoder == "onset":
+        if with_heads:
             heads = net(mel, chunk_max_power=cmax, return_all_heads=True)
             outs.append(heads["frame"])
             onsets.append(heads["onset"])
+            if with_offset:
+                offsets.append(heads["offset"])
         else:
             outs.append(net(mel, chunk_max_power=cmax))
-    if decoder == "onset":
+    if with_heads:
         from .notes import heads_to_notes_device
-        notes = heads_to_notes_device(torch.cat(outs), torch.cat(onsets), threshold, onset_threshold, SR / HOP_LENGTH)
+        notes = heads_to_notes_device(torch.cat(outs), torch.cat(onsets), threshold, onset_threshold, SR / HOP_LENGTH,
+                                      offset_logits=torch.cat(offsets) if with_offset else None, offset_threshold=offset_threshold)
     else:
         notes = notes_from_logits_device(torch.cat(outs), threshold, SR / HOP_LENGTH)
     net.raise_on_handoff_timeout(sync=False)               # (the copies above synchronised with every forward)
@@ -372,20 +380,23 @@ def transcribe_chunks(model: TranscriptionModel, chunks, threshold: float = THRE
 
 @torch.no_grad()
 def transcribe_windows_to_notes(model: "TranscriptionModel", y: torch.Tensor, overlap: float, threshold: float = THRESHOLD, batch: int = 128,
-                                n_mels: int = N_MELS, decoder: str = "frame", onset_threshold: float = THRESHOLD) -> List[Tuple[int, float, float]]:
+                                n_mels: int = N_MELS, decoder: str = "frame", onset_threshold: float = THRESHOLD,
+                                offset_threshold: float = THRESHOLD) -> List[Tuple[int, float, float]]:
     """1-D device recording -> notes decoded from ONE (1, 88, 1 + n // 512) logit roll on the recording's frame grid, stitched from
     overlapping 30 s windows (windows.transcribe_windows): no per-chunk drift, no cold chunk edges inside the recording."""
     from .windows import transcribe_windows
     check_decoder(decoder, model=model)
-    heads = transcribe_windows(model, [y], overlap, batch=batch, all_heads=decoder == "onset", n_mels=n_mels)[0]
-    if decoder == "onset":
+    with_offset = decoder == "onset_offset"
+    heads = transcribe_windows(model, [y], overlap, batch=batch, all_heads=decoder in HEAD_DECODERS, n_mels=n_mels, with_offset=with_offset)[0]
+    if decoder in HEAD_DECODERS:
         from .notes import heads_to_notes_device
-        return heads_to_notes_device(heads[0][None], heads[1][None], threshold, onset_threshold, SR / HOP_LENGTH)
+        return heads_to_notes_device(heads[0][None], heads[1][None], threshold, onset_threshold, SR / HOP_LENGTH,
+                                     offset_logits=heads[2][None] if with_offset else None, offset_threshold=offset_threshold)
     return notes_from_logits_device(heads[None], threshold, SR / HOP_LENGTH)
 
 
 def transcribe_audio(audio_path: str, model_path: str, output_path=None, device=None, threshold: float = THRESHOLD, decoder: str = "frame",
-                     onset_threshold: float = THRESHOLD, overlap: float = 0.0, **model_kw):
+                     onset_threshold: float = THRESHOLD, overlap: float = 0.0, offset_threshold: float = THRESHOLD, **model_kw):
     """overlap = 0: the reference's chunk concatenation (main.py:60-100, :164-186); overlap > 0 (seconds): overlapping windows
     stitched on the recording's own frame grid (transcribe_windows_to_notes)."""
     check_decoder(decoder, model_type=model_kw.get("model_type", MODEL_TYPE))
@@ -403,12 +414,12 @@ def transcribe_audio(audio_path: str, model_path: str, output_path=None, device=
         print(f"Audio duration: {y.numel() / SR:.2f} seconds; {len(plan_windows(y.numel(), overlap).start)} windows of {CHUNK_LENGTH}s "
               f"overlapping by {overlap}s")
         notes = transcribe_windows_to_notes(model, y, overlap, threshold, n_mels=model_kw.get("n_mels", N_MELS), decoder=decoder,
-                                            onset_threshold=onset_threshold)
+                                            onset_threshold=onset_threshold, offset_threshold=offset_threshold)
     else:
         chunks, duration = split_into_chunks_device(y)
         print(f"Audio duration: {duration:.2f} seconds; {len(chunks)} chunks of {CHUNK_LENGTH}s")
         notes = transcribe_chunks_to_notes(model, chunks, threshold, n_mels=model_kw.get("n_mels", N_MELS), device=device, decoder=decoder,
-                                           onset_threshold=onset_threshold)
+                                           onset_threshold=onset_threshold, offset_threshold=offset_threshold)
     if output_path is None:
         p = Path(audio_path)
         output_path = p.parent / f"{p.stem}_transcription.mid"

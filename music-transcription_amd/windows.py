@@ -68,17 +68,19 @@ def plan_windows(n_samples: int, overlap_s: float, sr: int = SR, hop: int = HOP,
     return WindowPlan(start, own0 - start, own1 - start, Tw, Tg, O, S)
 
 
-def _window_setup(model, n_mels: Optional[int], all_heads: bool, device):
+def _window_setup(model, n_mels: Optional[int], all_heads: bool, device, with_offset: bool = False):
     """-> (net, n_mels, frontend) of a window pass; refuses all_heads for a model without the onset head."""
     from .evaluate import require_heads
     net = getattr(model, "model", model)
+    if with_offset and not all_heads:
+        raise ValueError("with_offset=True needs all_heads=True (the offset logits come with the onset logits)")
     if all_heads:
         require_heads(net, "all_heads=True")
     n_mels = int(net.n_mels if n_mels is None else n_mels)
     return net, n_mels, get_frontend(SR, n_mels, HOP, device)
 
 
-def _run_slab(net, fe, n_mels: int, slab, buf, offs, outs, all_heads: bool, dev):
+def _run_slab(net, fe, n_mels: int, slab, buf, offs, outs, all_heads: bool, dev, with_offset: bool = False):
     """One slab of window jobs on the current stream: mt_mel_db_windows_f32 on the store `buf` (offs[key] = first float of a
     recording), one forward with the slab's chunk_max_power, one mt_stitch_windows per head into outs [(R, 88, T_dst)]."""
     Tw = 1 + WINDOW_SAMPLES // HOP
@@ -97,7 +99,7 @@ def _run_slab(net, fe, n_mels: int, slab, buf, offs, outs, all_heads: bool, dev)
                                         ptr(d32[2]), ptr(mel), ptr(cmax), _lib.stream_ptr()), "mt_mel_db_windows_f32")
         if all_heads:
             heads = net(mel, chunk_max_power=cmax, return_all_heads=True)
-            srcs = (heads["frame"], heads["onset"])
+            srcs = (heads["frame"], heads["onset"]) + ((heads["offset"],) if with_offset else ())
         else:
             srcs = (net(mel, chunk_max_power=cmax),)
         for src, dst in zip(srcs, outs):
@@ -106,16 +108,17 @@ def _run_slab(net, fe, n_mels: int, slab, buf, offs, outs, all_heads: bool, dev)
 
 
 @torch.no_grad()
-def _run_windows(model, jobs, R: int, T_dst: int, store_of, n_mels: Optional[int], batch: int, all_heads: bool, device):
+def _run_windows(model, jobs, R: int, T_dst: int, store_of, n_mels: Optional[int], batch: int, all_heads: bool, device,
+                 with_offset: bool = False):
     """jobs: [(dst_row, recording key, n_samples, start frame, lo, hi)].  store_of(keys) -> (store buffer, {key: offset}) for the
-    recordings of one slab.  -> frame logits (R, 88, T_dst) [, onset logits], padding 0."""
-    net, n_mels, fe = _window_setup(model, n_mels, all_heads, device)
+    recordings of one slab.  -> frame logits (R, 88, T_dst) [, onset logits [, offset logits]], padding 0."""
+    net, n_mels, fe = _window_setup(model, n_mels, all_heads, device, with_offset)
     dev = torch.device(device)
-    outs = [torch.zeros(R, N_PITCH, T_dst, dtype=torch.float32, device=dev) for _ in range(2 if all_heads else 1)]
+    outs = [torch.zeros(R, N_PITCH, T_dst, dtype=torch.float32, device=dev) for _ in range((3 if with_offset else 2) if all_heads else 1)]
     for s0 in range(0, len(jobs), batch):
         slab = jobs[s0:s0 + batch]
         buf, offs = store_of([job[1] for job in slab])
-        _run_slab(net, fe, n_mels, slab, buf, offs, outs, all_heads, dev)
+        _run_slab(net, fe, n_mels, slab, buf, offs, outs, all_heads, dev, with_offset)
     if hasattr(net, "raise_on_handoff_timeout"):
         net.raise_on_handoff_timeout(sync=True)        # a timed-out recurrence would have left NaN logits: fail loudly, once per pass
     return outs
@@ -145,10 +148,10 @@ def _jobs(ns: Sequence[int], keys: Sequence, overlap_s: float):
 
 
 def transcribe_windows(model, recordings: Sequence[torch.Tensor], overlap_s: float, batch: int = 128, all_heads: bool = False,
-                       n_mels: Optional[int] = None) -> List:
+                       n_mels: Optional[int] = None, with_offset: bool = False) -> List:
     """1-D float32 device recordings at 16 kHz -> per recording frame logits (88, 1 + n // 512) on the recording's own frame grid
-    (the frames of one mel over the whole recording), on the device; all_heads=True: [(frame, onset)] (cnn_rnn_large with heads).
-    The windows of all recordings run in slabs of `batch`."""
+    (the frames of one mel over the whole recording), on the device; all_heads=True: [(frame, onset)] (cnn_rnn_large with heads),
+    and with with_offset=True [(frame, onset, offset)].  The windows of all recordings run in slabs of `batch`."""
     if not len(recordings):
         return []
     overlap_frames(overlap_s)
@@ -158,7 +161,7 @@ def transcribe_windows(model, recordings: Sequence[torch.Tensor], overlap_s: flo
     store, offs, ns = _store(recordings)
     Tg = [1 + n // HOP for n in ns]
     outs = _run_windows(model, _jobs(ns, range(len(ns)), overlap_s), len(ns), max(Tg), lambda keys: (store, offs), n_mels, batch,
-                        all_heads, dev)
+                        all_heads, dev, with_offset)
     res = []
     for r, t in enumerate(Tg):
         heads = [o[r] if t == o.shape[-1] else o[r, :, :t].contiguous() for o in outs]
@@ -168,9 +171,10 @@ def transcribe_windows(model, recordings: Sequence[torch.Tensor], overlap_s: flo
 
 @torch.no_grad()
 def collect_logits_windows(model, dataset, indices: Sequence[int], overlap_s: float, device="cuda", max_batch: int = 128,
-                           all_heads: bool = False):
+                           all_heads: bool = False, with_offset: bool = False):
     """evaluate.collect_logits for a whole-file MaestroDataset (chunk_length=None) through overlapping windows: the same tuples,
-    [(index, logits (88, t_keep), roll (88, t_keep)[, onset logits])] sorted by index, with the logits stitched on the recording's
+    [(index, logits (88, t_keep), roll (88, t_keep)[, onset logits[, offset logits]])] sorted by index (the offset logits with
+    all_heads=True, with_offset=True), with the logits stitched on the recording's
     grid and trimmed to the item's t_keep, and the roll the item's full-file label roll.  Reuses the dataset's recording store."""
     if getattr(dataset, "chunk_length", 0) is not None or not hasattr(dataset, "store"):
         raise ValueError("collect_logits_windows needs a whole-file MaestroDataset (chunk_length=None)")
@@ -184,7 +188,7 @@ def collect_logits_windows(model, dataset, indices: Sequence[int], overlap_s: fl
     t_keep = ds.t_keep[idx].astype(np.int64)
     T_dst = max(1 + n // HOP for n in ns)
     outs = _run_windows(model, _jobs(ns, recs, overlap_s), len(idx), T_dst, lambda keys: (ds.store.buf, ds.store.offsets(keys)),
-                        ds.n_mels, max_batch, all_heads, device)
+                        ds.n_mels, max_batch, all_heads, device, with_offset)
     # labels: mt_roll_windows in full-file mode (column n is frame n), as MaestroDataset.get_batch builds them
     B, T_roll = len(idx), max(int(t_keep.max()), 1)
     dev = torch.device(device)
@@ -198,6 +202,6 @@ def collect_logits_windows(model, dataset, indices: Sequence[int], overlap_s: fl
     for b, (i, t) in enumerate(zip(idx, t_keep.tolist())):
         item = [i, outs[0][b, :, :t].contiguous(), roll[b, :, :t].contiguous()]
         if all_heads:
-            item.append(outs[1][b, :, :t].contiguous())
+            item += [o[b, :, :t].contiguous() for o in outs[1:]]
         out.append(tuple(item))
     return out

@@ -58,10 +58,13 @@ def main():
                     help="reference notes of --note_metrics: roll = the runs of the label roll (default; pedalled and gapless re-strikes are "
                          "one note); midi = the recording's MIDI note list in 100 us ticks, pedal-extended and cut at the pitch's next onset "
                          "(needs --data_source full)")
-    ap.add_argument("--decoder", choices=["frame", "onset"], default="frame",
+    ap.add_argument("--decoder", choices=["frame", "onset", "onset_offset"], default="frame",
                     help="note decoder for --note_metrics: frame = runs of active frames (default); onset = notes start at rising edges "
-                         "of the onset head (cnn_rnn_large trained with --train_all_heads; untrained heads make it meaningless)")
-    ap.add_argument("--onset_threshold", type=float, default=0.5, help="threshold of the onset head for --decoder onset (default: 0.5)")
+                         "of the onset head; onset_offset = those notes, ended on the frame where the offset head fires (cnn_rnn_large "
+                         "trained with --train_all_heads; untrained heads make both meaningless)")
+    ap.add_argument("--onset_threshold", type=float, default=0.5,
+                    help="threshold of the onset head for --decoder onset / onset_offset (default: 0.5)")
+    ap.add_argument("--offset_threshold", type=float, default=0.5, help="threshold of the offset head for --decoder onset_offset (default: 0.5)")
     ap.add_argument("--window_overlap", type=float, default=None,
                     help="full files only: run every recording in overlapping 30 s windows (this many seconds of overlap, 0.256 to 15) "
                          "stitched on its own frame grid, instead of one recurrence over the whole file; lifts the T * hidden_size < 2^24 "
@@ -80,6 +83,9 @@ def main():
     ap.add_argument("--tune_note_objective", choices=["onset", "onset_offset"], default="onset",
                     help="the note F1 that --tune_note_thresholds maximises (default: onset)")
     args = ap.parse_args()
+    if args.tune_note_thresholds and args.decoder == "onset_offset":
+        ap.error("--tune_note_thresholds does not cover --decoder onset_offset (the threshold sweeps do not read the offset head): tune with "
+                 "--decoder onset and pass the thresholds it reports")
     say = (lambda *a, **k: None) if args.headless else print
 
     if args.note_reference == "midi" and args.data_source != "full":
@@ -92,8 +98,9 @@ def main():
     if not os.path.exists(args.model):
         print(f"Error: Model checkpoint not found: {args.model}")
         return 1
-    if args.note_metrics and args.decoder == "onset" and args.model_type not in ("cnn_rnn_large", "large"):
-        print(f"Error: --decoder onset needs the onset head of cnn_rnn_large (model_type {args.model_type} has none)")
+    heads = args.decoder in ("onset", "onset_offset")
+    if args.note_metrics and heads and args.model_type not in ("cnn_rnn_large", "large"):
+        print(f"Error: --decoder {args.decoder} needs the onset head of cnn_rnn_large (model_type {args.model_type} has none)")
         return 1
     meta_path = os.path.join(args.cache_dir, f"{args.split}_metadata.pkl")
     full = args.data_source == "full" or (args.data_source == "auto" and not os.path.exists(meta_path))
@@ -167,7 +174,8 @@ def main():
     mean_f1, per_sample = E.evaluate_dataset(model, ds, threshold, dev, subset=args.subset, rank=rank, world=world,
                                              window_overlap=args.window_overlap)
     notes = None
-    note_threshold, note_onset_threshold = threshold, (args.onset_threshold if args.decoder == "onset" else None)
+    note_threshold, note_onset_threshold = threshold, (args.onset_threshold if heads else None)
+    note_offset_threshold = args.offset_threshold if args.decoder == "onset_offset" else None
     if args.tune_note_thresholds:
         note_threshold, note_onset_threshold, tuned_note_f1 = E.tune_note_thresholds(
             model, ds, dev, subset=args.subset, decoder=args.decoder, note_reference=args.note_reference, objective=args.tune_note_objective,
@@ -178,7 +186,7 @@ def main():
     if args.note_metrics:
         notes = E.note_metrics_dataset(model, ds, note_threshold, note_onset_threshold, dev,
                                        subset=args.subset, rank=rank, world=world, window_overlap=args.window_overlap,
-                                       note_reference=args.note_reference)
+                                       note_reference=args.note_reference, offset_threshold=note_offset_threshold)
     if rank == 0:
         if args.headless:
             print(f"EVAL_MEAN_F1={mean_f1:.6f}")
@@ -199,6 +207,8 @@ def main():
                 results["note_metrics"] = {"decoder": args.decoder, "note_reference": args.note_reference,
                                            "onset_threshold": note_onset_threshold,
                                            **notes}
+                if note_offset_threshold is not None:
+                    results["note_metrics"]["offset_threshold"] = note_offset_threshold
                 if args.tune_note_thresholds:
                     results["note_metrics"].update(threshold=note_threshold, tuned_objective=args.tune_note_objective)
             os.makedirs(args.out_dir, exist_ok=True)

@@ -1,4 +1,5 @@
-"""Device time of mt_note_match_counts and mt_note_match_list (DESIGN.md "Note-level F1"), frame and onset-gated decoders, on two shapes:
+"""Device time of mt_note_match_counts and mt_note_match_list (DESIGN.md "Note-level F1"), frame, onset-gated and offset-gated decoders,
+and of mt_heads_to_notes beside mt_heads_to_notes_off, on two shapes:
 
   * chunks:     a batch of 128 chunks x 88 pitches x 938 frames (one forward's worth of 30 s chunks);
   * recordings: a padded batch of 8 whole recordings of 10-25 minutes (T up to ~47 000 frames), masked by `lengths`.
@@ -7,7 +8,9 @@ Inputs are seeded synthetic logits and rolls with note-like runs (~6 % of the ce
 timed with device events over --iters launches; GB/s counts the bytes the pass must read: the valid frames of the frame
 logits, the reference roll and (onset decoder) the onset logits.  The list matcher runs in the same process on the same logits,
 its note list being the runs of the same roll (so its counts must equal the roll matcher's); it reads the note list instead of
-the roll, and `list_over_roll` is its time over mt_note_match_counts'.
+the roll, and `list_over_roll` is its time over mt_note_match_counts'.  The offset-gated decoder ("onset_offset", the mt_*_off entry
+points) reads one array more, offset logits that mark the last active frame of every run; `over_onset` is its time over the
+onset-gated entry point's in the same run (expected about 4/3 for the roll matcher, 3/2 for the list matcher and the note lists).
 
     python tools/note_metrics_bench.py [--iters 50] [--out note_metrics.json]
 """
@@ -51,6 +54,65 @@ def make_case(B, P, T, lengths, seed, device):
     return frame.contiguous(), onset.contiguous(), ref.float().contiguous()
 
 
+def offset_logits(frame):
+    """Offset logits for `frame`: active on the last active frame of every run, with the frame logit's magnitude."""
+    import torch
+    est = frame > 0
+    last = est & ~torch.nn.functional.pad(est, (0, 1))[..., 1:]
+    return torch.where(last, frame.abs(), -frame.abs()).contiguous()
+
+
+def device_ms(fn, iters):
+    import torch
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters
+
+
+def time_offset_decoder(out, frame, onset, ref, notes, lengths, iters):
+    """The offset-gated entry points beside the onset-gated ones of `out` (same process, same logits), and the two note extractors."""
+    import torch
+    from music_transcription_amd import _lib
+    from music_transcription_amd.notes import note_match_counts, note_match_list
+    B, P, T = frame.shape
+    valid = out["valid_frames"]
+    off = offset_logits(frame)
+    for key, fn, nbytes in (("onset_offset", lambda: note_match_counts(frame, ref, 0.5, onset, 0.5, lengths, offset_logits=off), valid * P * 16),
+                            ("onset_offset_list", lambda: note_match_list(frame, notes, 0.5, onset, 0.5, lengths, offset_logits=off),
+                             valid * P * 12 + 8 * out["list_notes"])):
+        ms = device_ms(fn, iters)
+        cs = fn().sum(0).tolist()
+        base = out["onset_list" if key.endswith("_list") else "onset"]
+        out[key] = {"ms": round(ms, 4), "read_MB": round(nbytes / 1e6, 2), "GB_per_s": round(nbytes / (ms * 1e-3) / 1e9, 1),
+                    "over_onset": round(ms / base["ms"], 3), "n_ref": cs[0], "n_est": cs[1], "tp_onset": cs[2], "tp_onset_offset": cs[3]}
+        if [out[key][k] for k in ("n_ref", "n_est", "tp_onset")] != [base[k] for k in ("n_ref", "n_est", "tp_onset")]:
+            raise SystemExit(f"{out['case']} ({key}): the offset head changed more than tp_onset_offset: {out[key]} vs {base}")
+    if lengths is not None:                                    # mt_heads_to_notes takes whole chunks: the note lists are timed on the chunks case
+        return
+    counts = torch.empty(P, dtype=torch.int32, device=frame.device)
+    cap = B * P * T // 2 + 1                                   # every note has a frame and a gap of its own
+    starts, ends = torch.empty(cap, dtype=torch.int32, device=frame.device), torch.empty(cap, dtype=torch.int32, device=frame.device)
+    lib, ptr, st = _lib.lib, _lib.ptr, _lib.stream_ptr()
+    gated = lambda: _lib.check(lib.mt_heads_to_notes(ptr(frame), ptr(onset), 0.5, 0.5, B, P, T, ptr(counts), ptr(starts), ptr(ends), cap, st))
+    cut = lambda: _lib.check(lib.mt_heads_to_notes_off(ptr(frame), ptr(onset), ptr(off), 0.5, 0.5, 0.5, B, P, T, ptr(counts), ptr(starts),
+                                                       ptr(ends), cap, st))
+    for key, fn, arrays in (("heads_to_notes", gated, 2), ("heads_to_notes_off", cut, 3)):
+        ms = device_ms(fn, iters)
+        nbytes = 2 * arrays * valid * P * 4                    # a counting and a writing pass
+        out[key] = {"ms": round(ms, 4), "read_MB": round(nbytes / 1e6, 2), "GB_per_s": round(nbytes / (ms * 1e-3) / 1e9, 1),
+                    "notes": int(counts.sum())}
+    out["heads_to_notes_off"]["over_onset"] = round(out["heads_to_notes_off"]["ms"] / out["heads_to_notes"]["ms"], 3)
+    if out["heads_to_notes_off"]["notes"] != out["heads_to_notes"]["notes"]:
+        raise SystemExit(f"{out['case']}: the offset-gated note list has another number of notes: {out}")
+
+
 def roll_notes(ref):
     """The runs of the (B, P, T) roll as a note list in ticks (320 per frame) on the device: {"on", "off", "ptr"}."""
     import torch
@@ -64,22 +126,13 @@ def roll_notes(ref):
 
 
 def time_case(name, frame, onset, ref, lengths, iters):
-    import torch
     from music_transcription_amd.notes import note_match_counts, note_match_list
     B, P, T = frame.shape
     valid = B * T if lengths is None else int(sum(lengths))
     out = {"case": name, "B": B, "P": P, "T": T, "valid_frames": valid}
     for dec, on in (("frame", None), ("onset", onset)):
-        for _ in range(3):
-            c = note_match_counts(frame, ref, 0.5, on, 0.5, lengths)
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(iters):
-            note_match_counts(frame, ref, 0.5, on, 0.5, lengths)
-        e1.record()
-        torch.cuda.synchronize()
-        ms = e0.elapsed_time(e1) / iters
+        ms = device_ms(lambda: note_match_counts(frame, ref, 0.5, on, 0.5, lengths), iters)
+        c = note_match_counts(frame, ref, 0.5, on, 0.5, lengths)
         nbytes = valid * P * 4 * (3 if on is not None else 2)
         cs = c.sum(0).tolist()
         out[dec] = {"ms": round(ms, 4), "read_MB": round(nbytes / 1e6, 2), "GB_per_s": round(nbytes / (ms * 1e-3) / 1e9, 1),
@@ -87,16 +140,8 @@ def time_case(name, frame, onset, ref, lengths, iters):
     notes = roll_notes(ref)
     out["list_notes"] = int(notes["on"].numel())
     for dec, on in (("frame", None), ("onset", onset)):
-        for _ in range(3):
-            c = note_match_list(frame, notes, 0.5, on, 0.5, lengths)
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(iters):
-            note_match_list(frame, notes, 0.5, on, 0.5, lengths)
-        e1.record()
-        torch.cuda.synchronize()
-        ms = e0.elapsed_time(e1) / iters
+        ms = device_ms(lambda: note_match_list(frame, notes, 0.5, on, 0.5, lengths), iters)
+        c = note_match_list(frame, notes, 0.5, on, 0.5, lengths)
         nbytes = valid * P * 4 * (2 if on is not None else 1) + 8 * out["list_notes"]
         cs = c.sum(0).tolist()
         out[dec + "_list"] = {"ms": round(ms, 4), "read_MB": round(nbytes / 1e6, 2), "GB_per_s": round(nbytes / (ms * 1e-3) / 1e9, 1),
@@ -106,6 +151,7 @@ def time_case(name, frame, onset, ref, lengths, iters):
         if not all(same):
             raise SystemExit(f"{name} ({dec}): the list matcher's counts differ from the roll matcher's on the roll's own runs: "
                              f"{out[dec]} vs {out[dec + '_list']}")
+    time_offset_decoder(out, frame, onset, ref, notes, lengths, iters)
     return out
 
 
