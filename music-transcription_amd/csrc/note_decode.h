@@ -1,4 +1,9 @@
-// Note decoding rules shared by the kernels of notes.hip (one wave64 walks one pitch row in 64-frame windows).
+// Note decoding shared by the kernels of notes.hip and notes_batch.hip: one wave64 walks one pitch row in 64-frame windows.
+//   walk_slabs:     the row walk itself -- a slab of windows of loads in flight, then the windows one by one; frames at or past L are
+//                   never loaded.  The kernel supplies the addressing (a loader) and what it does with a window (a body);
+//   decode_step:    one window of a decoder: the heads' activity, then decode_window (frame / onset-gated) or decode_window_off
+//                   (offset-gated), the state between windows in a DecodeCarry;
+//   emit_window, emit_open_end: the count and the fill pass of a note list (mt_heads_to_notes, mt_notes_batch).
 //
 // Activity is the expression of mt_predict_threshold / note_active in post.hip, so ties break the same way everywhere.
 // Onset-gated decoder (the Onsets-and-Frames rule): a = frame-active OR onset-active; a note opens at every rising edge of
@@ -6,6 +11,8 @@
 // note (a re-struck key).  With onset := frame this is the plain run-length decoder of mt_roll_to_notes.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 namespace mt {
 
@@ -54,6 +61,74 @@ __device__ __forceinline__ WindowEvents decode_window_off(bool o, bool a, bool k
     k_prev = km >> 63;
     e_prev = em >> 63;
     return decode_window(o, a2, lane, o_prev, open_prev);
+}
+
+// The decoder's state between windows: o / open (and, offset-gated, k / e) of the frame before the window.
+struct CarryOnset { unsigned long long o_prev = 0, open_prev = 0; };
+struct CarryOffset : CarryOnset { unsigned long long k_prev = 0, e_prev = 0; };
+template <bool OFF>
+using DecodeCarry = std::conditional_t<OFF, CarryOffset, CarryOnset>;
+
+struct NoteThr { float frame, onset, offset; };   // thresholds of the three heads (offset: read by the offset-gated decoder only)
+
+// One window of a decoder.  x = the window's logits of this lane's frame, x[0] frame, x[1] onset, x[2] offset (OFF only); `in` = the
+// frame is inside the row.  Without an onset head (the frame decoder) onset := frame.
+template <bool OFF, int NCH>
+__device__ __forceinline__ WindowEvents decode_step(bool in, const float (&x)[NCH], bool has_onset, const NoteThr& thr, int lane,
+                                                    DecodeCarry<OFF>& c) {
+    static_assert(NCH >= (OFF ? 3 : 2), "frame, onset (and offset) logits");
+    const bool f = in && logit_active(x[0], thr.frame);
+    const bool o = has_onset ? (in && logit_active(x[1], thr.onset)) : f;
+    if constexpr (OFF) return decode_window_off(o, f || o, in && logit_active(x[2], thr.offset), lane, c.o_prev, c.open_prev, c.k_prev, c.e_prev);
+    else return decode_window(o, f || o, lane, c.o_prev, c.open_prev);
+}
+
+// The walk over a row of L frames (Index = int or long long), SLAB 64-frame windows at a time: first all of the slab's loads,
+// load(channel, g) for channel < NCH and every frame g < L of the slab (0 stands in past L, which is never read), then
+// body(g0, in, x) per window that starts below L, x = this lane's NCH values of frame g0 + lane and in = that frame is below L.
+// Both loops are fully unrolled, so the slab lives in registers; the loader and the body are called once per window of those loops
+// and have to end up inside them: pass lambdas marked __attribute__((always_inline)).
+template <int SLAB, int NCH, typename Index, typename Load, typename Body>
+__device__ __forceinline__ void walk_slabs(Index L, int lane, Load load, Body body) {
+    for (Index s0 = 0; s0 < L; s0 += 64 * SLAB) {
+        float x[SLAB][NCH];
+#pragma unroll
+        for (int w = 0; w < SLAB; ++w) {
+            const Index g = s0 + 64 * w + lane;
+            const bool in = g < L;                              // (one test per frame: the channels' address arithmetic is shared)
+#pragma unroll
+            for (int ch = 0; ch < NCH; ++ch) x[w][ch] = 0.0f;
+            if (in) {
+#pragma unroll
+                for (int ch = 0; ch < NCH; ++ch) x[w][ch] = load(ch, g);
+            }
+        }
+#pragma unroll
+        for (int w = 0; w < SLAB; ++w) {
+            const Index g0 = s0 + 64 * w;
+            if (g0 >= L) continue;                              // (not a break: the loop stays fully unrolled, x in registers)
+            body(g0, g0 + lane < L, x[w]);
+        }
+    }
+}
+
+// A note list's count pass (fill false) and fill pass: note k of the row starts at starts[k] and ends at ends[k], both already
+// offset to the row's first note.  n_on / n_off = starts / closes seen so far.
+template <typename Index>
+__device__ __forceinline__ void emit_window(const WindowEvents& ev, Index g0, int lane, bool fill, int* __restrict__ starts,
+                                            int* __restrict__ ends, int& n_on, int& n_off) {
+    if (fill) {
+        const unsigned long long below = (1ull << lane) - 1ull;
+        if (ev.starts >> lane & 1ull) starts[n_on + __popcll(ev.starts & below)] = (int)(g0 + lane);
+        if (ev.closes >> lane & 1ull) ends[n_off + __popcll(ev.closes & below)] = (int)(g0 + lane);
+    }
+    n_on += __popcll(ev.starts);
+    n_off += __popcll(ev.closes);
+}
+
+// A note still open after the row's last frame ends at L (one lane calls this, in the fill pass).
+__device__ __forceinline__ void emit_open_end(const CarryOnset& c, int* __restrict__ ends, int n_off, int L) {
+    if (c.open_prev) ends[n_off] = L;
 }
 
 }  // namespace mt

@@ -5,7 +5,10 @@
 //   mt_note_match_list:   the same counts against a per-row note list in ticks of 100 us (the MIDI notes), which may hold re-struck keys;
 //   mt_heads_to_notes:    the onset-gated decoder with mt_roll_to_notes' output contract (main.py's note list).
 //   mt_*_off:             the three of them with the offset-gated decoder (decode_window_off): the offset head ends notes.
-// One wave64 per pitch row; it walks the row in 64-frame windows (note_decode.h), SLAB windows of loads in flight at a time.
+// One wave64 per pitch row.  The row walk, the decode step and the note emitter are note_decode.h's (walk_slabs, decode_step,
+// emit_window); a kernel here adds its addressing, where its output goes and what it does with a window's events (match_window,
+// list_window, emit).  Two kernels walk on their own: the roll matcher (its offset-gated instance is 16 % slower on the shared walk,
+// DESIGN.md 6c; it shares decode_step) and the sweep kernel, which reads ballots from LDS, not logits.
 #include <type_traits>
 
 #include "mt_common.h"
@@ -154,7 +157,7 @@ __device__ __forceinline__ void counts_add(unsigned long long* c, int n_ref, int
 }
 
 // counts[b] += {n_ref, n_est, tp_onset, tp_onset_offset} of pitch row (b, p).  Frames at or past lengths[b] are inactive on both sides.
-// OFF: the offset-gated decoder (decode_window_off) with the offset head `offset` at thr_k; otherwise neither is read.
+// OFF: the offset-gated decoder with the offset head `offset` at thr_k; otherwise neither is read.
 template <bool OFF>
 __global__ __launch_bounds__(64 * NOTE_WAVES) void note_match_kernel(const float* __restrict__ frame, const float* __restrict__ onset,
                                                                      const float* __restrict__ offset, float thr_f, float thr_o, float thr_k,
@@ -168,7 +171,10 @@ __global__ __launch_bounds__(64 * NOTE_WAVES) void note_match_kernel(const float
     const size_t base = (size_t)row * T;
     MatchState s;
     match_init(s);
-    unsigned long long o_prev = 0, open_prev = 0, r_prev = 0, k_prev = 0, e_prev = 0;
+    const NoteThr thr{thr_f, thr_o, thr_k};
+    DecodeCarry<OFF> c;
+    unsigned long long r_prev = 0;
+    // (its own walk, not walk_slabs: on the shared walk the offset-gated instance ran its long rows 16 % slower)
     for (int s0 = 0; s0 < L; s0 += 64 * NOTE_SLAB) {
         float xf[NOTE_SLAB], xo[NOTE_SLAB], xr[NOTE_SLAB], xk[OFF ? NOTE_SLAB : 1];
 #pragma unroll
@@ -185,18 +191,15 @@ __global__ __launch_bounds__(64 * NOTE_WAVES) void note_match_kernel(const float
             const int g0 = s0 + 64 * w;
             if (g0 >= L) break;
             const bool in = g0 + lane < L;
-            const bool f = in && logit_active(xf[w], thr_f);
-            const bool o = onset ? (in && logit_active(xo[w], thr_o)) : f;
-            WindowEvents est;
-            if constexpr (OFF) est = decode_window_off(o, f || o, in && logit_active(xk[w], thr_k), lane, o_prev, open_prev, k_prev, e_prev);
-            else est = decode_window(o, f || o, lane, o_prev, open_prev);
+            const float x[3] = {xf[w], xo[w], xk[OFF ? w : 0]};
+            const WindowEvents est = decode_step<OFF>(in, x, onset != nullptr, thr, lane, c);
             const unsigned long long rm = __ballot(in && xr[w] > 0.0f);
             const unsigned long long rs = rm & ~((rm << 1) | r_prev), re = ~rm & ((rm << 1) | r_prev);
             r_prev = rm >> 63;
             match_window(s, est, rs, re, g0);
         }
     }
-    match_finish(s, open_prev != 0, r_prev != 0, L);
+    match_finish(s, c.open_prev != 0, r_prev != 0, L);
     if (lane == 0) counts_add(counts + 4 * (size_t)b, s.n_ref, s.n_est, s.tp_on, s.tp_onoff);
 }
 
@@ -346,36 +349,24 @@ __global__ __launch_bounds__(64 * NOTE_WAVES) void note_match_list_kernel(const 
     const int L = lengths ? (int)min((long long)T, max(0ll, lengths[b])) : T;
     const int end_tick = TICKS_PER_FRAME * L;
     const size_t base = (size_t)row * T;
+    constexpr int NCH = OFF ? 3 : 2;
     RefCursor r;
     cursor_open(r, ref_on, ref_off, ref_ptr, row, 0, lane);
     ListState s;
     list_init(s);
-    unsigned long long o_prev = 0, open_prev = 0, k_prev = 0, e_prev = 0;
-    for (int s0 = 0; s0 < L; s0 += 64 * NOTE_SLAB) {
-        float xf[NOTE_SLAB], xo[NOTE_SLAB], xk[OFF ? NOTE_SLAB : 1];
-#pragma unroll
-        for (int w = 0; w < NOTE_SLAB; ++w) {
-            const int g = s0 + 64 * w + lane;
-            const bool in = g < L;
-            xf[w] = in ? frame[base + g] : 0.0f;
-            xo[w] = (in && onset) ? onset[base + g] : 0.0f;
-            if constexpr (OFF) xk[w] = in ? offset[base + g] : 0.0f;
-        }
-#pragma unroll
-        for (int w = 0; w < NOTE_SLAB; ++w) {
-            const int g0 = s0 + 64 * w;
-            if (g0 >= L) break;
-            const bool in = g0 + lane < L;
-            const bool f = in && logit_active(xf[w], thr_f);
-            const bool o = onset ? (in && logit_active(xo[w], thr_o)) : f;
-            WindowEvents est;
-            if constexpr (OFF) est = decode_window_off(o, f || o, in && logit_active(xk[w], thr_k), lane, o_prev, open_prev, k_prev, e_prev);
-            else est = decode_window(o, f || o, lane, o_prev, open_prev);
-            list_window(s, r, est, g0, lane, end_tick);
-        }
-    }
+    const NoteThr thr{thr_f, thr_o, thr_k};
+    DecodeCarry<OFF> c;
+    walk_slabs<NOTE_SLAB, NCH>(
+        L, lane,
+        [&](int ch, int g) __attribute__((always_inline)) {
+            if (ch == 1) return onset ? onset[base + g] : 0.0f;
+            return (ch == 0 ? frame : offset)[base + g];
+        },
+        [&](int g0, bool in, const float(&x)[NCH]) __attribute__((always_inline)) {
+            list_window(s, r, decode_step<OFF>(in, x, onset != nullptr, thr, lane, c), g0, lane, end_tick);
+        });
     int tp_on, tp_onoff;
-    list_finish(s, r, open_prev != 0, lane, end_tick, tp_on, tp_onoff);
+    list_finish(s, r, c.open_prev != 0, lane, end_tick, tp_on, tp_onoff);
     if (lane == 0) counts_add(counts + 4 * (size_t)b, s.n_ref, s.n_est, tp_on, tp_onoff);
 }
 
@@ -397,41 +388,22 @@ __global__ __launch_bounds__(64 * NOTE_WAVES) void heads_notes_kernel(const floa
         if (out + counts[p] > capacity) return;                 // the host sees sum(counts) > capacity and retries with larger buffers
     }
     const int n = NB * T;
+    constexpr int NCH = OFF ? 3 : 2;
     int n_on = 0, n_off = 0;
-    unsigned long long o_prev = 0, open_prev = 0, k_prev = 0, e_prev = 0;
-    const unsigned long long below = (1ull << lane) - 1ull;
-    for (int s0 = 0; s0 < n; s0 += 64 * NOTE_SLAB) {
-        float xf[NOTE_SLAB], xo[NOTE_SLAB], xk[OFF ? NOTE_SLAB : 1];
-#pragma unroll
-        for (int w = 0; w < NOTE_SLAB; ++w) {
-            const int g = s0 + 64 * w + lane;
-            const int c = g / T;
-            const size_t at = ((size_t)c * P + p) * T + (g - c * T);
-            xf[w] = g < n ? frame[at] : 0.0f;
-            xo[w] = g < n ? onset[at] : 0.0f;
-            if constexpr (OFF) xk[w] = g < n ? offset[at] : 0.0f;
-        }
-#pragma unroll
-        for (int w = 0; w < NOTE_SLAB; ++w) {
-            const int g0 = s0 + 64 * w;
-            if (g0 >= n) break;
-            const bool in = g0 + lane < n;
-            const bool f = in && logit_active(xf[w], thr_f);
-            const bool o = in && logit_active(xo[w], thr_o);
-            WindowEvents ev;
-            if constexpr (OFF) ev = decode_window_off(o, f || o, in && logit_active(xk[w], thr_k), lane, o_prev, open_prev, k_prev, e_prev);
-            else ev = decode_window(o, f || o, lane, o_prev, open_prev);
-            if (fill) {
-                if (ev.starts >> lane & 1ull) starts[out + n_on + __popcll(ev.starts & below)] = g0 + lane;
-                if (ev.closes >> lane & 1ull) ends[out + n_off + __popcll(ev.closes & below)] = g0 + lane;
-            }
-            n_on += __popcll(ev.starts);
-            n_off += __popcll(ev.closes);
-        }
-    }
+    const NoteThr thr{thr_f, thr_o, thr_k};
+    DecodeCarry<OFF> c;
+    walk_slabs<NOTE_SLAB, NCH>(
+        n, lane,
+        [&](int ch, int g) __attribute__((always_inline)) {                      // frame g of the recording is frame g - k T of chunk k
+            const int k = g / T;
+            return (ch == 0 ? frame : ch == 1 ? onset : offset)[((size_t)k * P + p) * T + (g - k * T)];
+        },
+        [&](int g0, bool in, const float(&x)[NCH]) __attribute__((always_inline)) {
+            emit_window(decode_step<OFF>(in, x, true, thr, lane, c), g0, lane, fill != 0, starts + out, ends + out, n_on, n_off);
+        });
     if (lane == 0) {
         if (!fill) counts[p] = n_on;
-        else if (open_prev) ends[out + n_off] = n;
+        else emit_open_end(c, ends + out, n_off, n);
     }
 }
 
@@ -617,86 +589,82 @@ __global__ __launch_bounds__(64 * SWEEP_WAVES) void note_sweep_kernel(const floa
 
 using namespace mt;
 
-// The launches behind mt_note_match_counts / mt_note_match_counts_off (OFF = the offset-gated decoder); arguments already checked.
-template <bool OFF>
-static int launch_note_match(const float* frame, const float* onset, const float* offset, float thr_f, float thr_o, float thr_k, const float* ref,
-                             const long long* lengths, unsigned long long* counts, int B, int P, int T, hipStream_t st) {
+static bool thr_ok(float t) { return t > 0.0f && t < 1.0f; }
+
+// One checked entry per family; `who` = the calling entry point (for the message), `off` = its offset-gated form (_off), which
+// needs all three heads and thresholds.  Nothing is written before every check has passed.
+static bool thrs_ok(const NoteThr& thr, bool onset, bool off) {
+    return thr_ok(thr.frame) && (!onset || thr_ok(thr.onset)) && (!off || thr_ok(thr.offset));
+}
+
+static int note_match(const char* who, bool off, const float* frame, const float* onset, const float* offset, NoteThr thr, const float* ref,
+                      const long long* lengths, unsigned long long* counts, int B, int P, int T, mt_stream_t stream) {
+    MT_REQUIRE(frame && ref && counts && (!off || (onset && offset)), MT_EINVAL, "%s: null pointer", who);
+    MT_REQUIRE(B > 0 && P > 0 && T > 0 && (long long)B * P < 2147483647ll && T < (1 << 30), MT_EINVAL, "%s: bad dims", who);
+    MT_REQUIRE(thrs_ok(thr, onset, off), MT_EINVAL, "%s: thresholds must lie in (0, 1)", who);
+    hipStream_t st = (hipStream_t)stream;
     MT_CHECK_HIP(hipMemsetAsync(counts, 0, (size_t)B * 4 * sizeof(unsigned long long), st));
-    const int rows = B * P;
-    hipLaunchKernelGGL(note_match_kernel<OFF>, dim3((rows + NOTE_WAVES - 1) / NOTE_WAVES), dim3(64 * NOTE_WAVES), 0, st, frame, onset, offset,
-                       thr_f, thr_o, thr_k, ref, lengths, counts, B, P, T);
+    hipLaunchKernelGGL(off ? note_match_kernel<true> : note_match_kernel<false>, dim3((B * P + NOTE_WAVES - 1) / NOTE_WAVES), dim3(64 * NOTE_WAVES),
+                       0, st, frame, onset, offset, thr.frame, thr.onset, thr.offset, ref, lengths, counts, B, P, T);
     MT_CHECK_LAUNCH();
     return MT_OK;
 }
 
-template <bool OFF>
-static int launch_note_match_list(const float* frame, const float* onset, const float* offset, float thr_f, float thr_o, float thr_k,
-                                  const int* ref_on, const int* ref_off, const long long* ref_ptr, const long long* lengths,
-                                  unsigned long long* counts, int B, int P, int T, hipStream_t st) {
+static int note_match_list(const char* who, bool off, const float* frame, const float* onset, const float* offset, NoteThr thr, const int* ref_on,
+                           const int* ref_off, const long long* ref_ptr, const long long* lengths, unsigned long long* counts, int B, int P, int T,
+                           mt_stream_t stream) {
+    MT_REQUIRE(frame && ref_on && ref_off && ref_ptr && counts && (!off || (onset && offset)), MT_EINVAL, "%s: null pointer", who);
+    MT_REQUIRE(B > 0 && P > 0 && T > 0 && (long long)B * P < 2147483647ll && (long long)T * TICKS_PER_FRAME < 2147483647ll - 64 * NOTE_SLAB,
+               MT_EINVAL, "%s: bad dims (frame times must fit 31 bits of 100 us ticks)", who);
+    MT_REQUIRE(thrs_ok(thr, onset, off), MT_EINVAL, "%s: thresholds must lie in (0, 1)", who);
+    hipStream_t st = (hipStream_t)stream;
     MT_CHECK_HIP(hipMemsetAsync(counts, 0, (size_t)B * 4 * sizeof(unsigned long long), st));
-    const int rows = B * P;
-    hipLaunchKernelGGL(note_match_list_kernel<OFF>, dim3((rows + NOTE_WAVES - 1) / NOTE_WAVES), dim3(64 * NOTE_WAVES), 0, st, frame, onset, offset,
-                       thr_f, thr_o, thr_k, ref_on, ref_off, ref_ptr, lengths, counts, B, P, T);
+    hipLaunchKernelGGL(off ? note_match_list_kernel<true> : note_match_list_kernel<false>, dim3((B * P + NOTE_WAVES - 1) / NOTE_WAVES),
+                       dim3(64 * NOTE_WAVES), 0, st, frame, onset, offset, thr.frame, thr.onset, thr.offset, ref_on, ref_off, ref_ptr, lengths,
+                       counts, B, P, T);
     MT_CHECK_LAUNCH();
     return MT_OK;
 }
 
-template <bool OFF>
-static int launch_heads_notes(const float* frame, const float* onset, const float* offset, float thr_f, float thr_o, float thr_k, int NB, int P,
-                              int T, int* counts, int* starts, int* ends, int capacity, hipStream_t st) {
-    const dim3 grid((P + NOTE_WAVES - 1) / NOTE_WAVES), block(64 * NOTE_WAVES);
+static int heads_notes(const char* who, bool off, const float* frame, const float* onset, const float* offset, NoteThr thr, int NB, int P, int T,
+                       int* counts, int* starts, int* ends, int capacity, mt_stream_t stream) {
+    MT_REQUIRE(frame && onset && (!off || offset) && counts && starts && ends && capacity > 0, MT_EINVAL, "%s: bad arguments", who);
+    MT_REQUIRE(NB > 0 && P > 0 && T > 0 && (long long)NB * T < 2147483647ll - 64 * NOTE_SLAB, MT_EINVAL, "%s: bad dims", who);
+    MT_REQUIRE(thrs_ok(thr, true, off), MT_EINVAL, "%s: thresholds must lie in (0, 1)", who);
     for (int fill = 0; fill < 2; ++fill) {                     // count, then write
-        hipLaunchKernelGGL(heads_notes_kernel<OFF>, grid, block, 0, st, frame, onset, offset, thr_f, thr_o, thr_k, NB, P, T, fill, counts, starts,
-                           ends, capacity);
+        hipLaunchKernelGGL(off ? heads_notes_kernel<true> : heads_notes_kernel<false>, dim3((P + NOTE_WAVES - 1) / NOTE_WAVES), dim3(64 * NOTE_WAVES),
+                           0, (hipStream_t)stream, frame, onset, offset, thr.frame, thr.onset, thr.offset, NB, P, T, fill, counts, starts, ends,
+                           capacity);
         MT_CHECK_LAUNCH();
     }
     return MT_OK;
 }
 
-static bool thr_ok(float t) { return t > 0.0f && t < 1.0f; }
-
 extern "C" int mt_note_match_counts(const float* frame_logits, const float* onset_logits, float thr_frame, float thr_onset, const float* ref_roll,
                                     const long long* lengths, unsigned long long* counts, int B, int P, int T, mt_stream_t stream) {
-    MT_REQUIRE(frame_logits && ref_roll && counts, MT_EINVAL, "mt_note_match_counts: null pointer");
-    MT_REQUIRE(B > 0 && P > 0 && T > 0 && (long long)B * P < 2147483647ll && T < (1 << 30), MT_EINVAL, "mt_note_match_counts: bad dims");
-    MT_REQUIRE(thr_frame > 0.0f && thr_frame < 1.0f && (!onset_logits || (thr_onset > 0.0f && thr_onset < 1.0f)), MT_EINVAL,
-               "mt_note_match_counts: thresholds must lie in (0, 1)");
-    return launch_note_match<false>(frame_logits, onset_logits, nullptr, thr_frame, thr_onset, 0.5f, ref_roll, lengths, counts, B, P, T,
-                                    (hipStream_t)stream);
+    return note_match("mt_note_match_counts", false, frame_logits, onset_logits, nullptr, {thr_frame, thr_onset, 0.5f}, ref_roll, lengths, counts, B,
+                      P, T, stream);
 }
 
 extern "C" int mt_note_match_counts_off(const float* frame_logits, const float* onset_logits, const float* offset_logits, float thr_frame,
                                         float thr_onset, float thr_offset, const float* ref_roll, const long long* lengths,
                                         unsigned long long* counts, int B, int P, int T, mt_stream_t stream) {
-    MT_REQUIRE(frame_logits && onset_logits && offset_logits && ref_roll && counts, MT_EINVAL, "mt_note_match_counts_off: null pointer");
-    MT_REQUIRE(B > 0 && P > 0 && T > 0 && (long long)B * P < 2147483647ll && T < (1 << 30), MT_EINVAL, "mt_note_match_counts_off: bad dims");
-    MT_REQUIRE(thr_ok(thr_frame) && thr_ok(thr_onset) && thr_ok(thr_offset), MT_EINVAL, "mt_note_match_counts_off: thresholds must lie in (0, 1)");
-    return launch_note_match<true>(frame_logits, onset_logits, offset_logits, thr_frame, thr_onset, thr_offset, ref_roll, lengths, counts, B, P, T,
-                                   (hipStream_t)stream);
+    return note_match("mt_note_match_counts_off", true, frame_logits, onset_logits, offset_logits, {thr_frame, thr_onset, thr_offset}, ref_roll,
+                      lengths, counts, B, P, T, stream);
 }
 
 extern "C" int mt_note_match_list(const float* frame_logits, const float* onset_logits, float thr_frame, float thr_onset, const int* ref_on,
                                   const int* ref_off, const long long* ref_ptr, const long long* lengths, unsigned long long* counts, int B, int P,
                                   int T, mt_stream_t stream) {
-    MT_REQUIRE(frame_logits && ref_on && ref_off && ref_ptr && counts, MT_EINVAL, "mt_note_match_list: null pointer");
-    MT_REQUIRE(B > 0 && P > 0 && T > 0 && (long long)B * P < 2147483647ll && (long long)T * TICKS_PER_FRAME < 2147483647ll - 64 * NOTE_SLAB,
-               MT_EINVAL, "mt_note_match_list: bad dims (frame times must fit 31 bits of 100 us ticks)");
-    MT_REQUIRE(thr_frame > 0.0f && thr_frame < 1.0f && (!onset_logits || (thr_onset > 0.0f && thr_onset < 1.0f)), MT_EINVAL,
-               "mt_note_match_list: thresholds must lie in (0, 1)");
-    return launch_note_match_list<false>(frame_logits, onset_logits, nullptr, thr_frame, thr_onset, 0.5f, ref_on, ref_off, ref_ptr, lengths, counts,
-                                         B, P, T, (hipStream_t)stream);
+    return note_match_list("mt_note_match_list", false, frame_logits, onset_logits, nullptr, {thr_frame, thr_onset, 0.5f}, ref_on, ref_off, ref_ptr,
+                           lengths, counts, B, P, T, stream);
 }
 
 extern "C" int mt_note_match_list_off(const float* frame_logits, const float* onset_logits, const float* offset_logits, float thr_frame,
                                       float thr_onset, float thr_offset, const int* ref_on, const int* ref_off, const long long* ref_ptr,
                                       const long long* lengths, unsigned long long* counts, int B, int P, int T, mt_stream_t stream) {
-    MT_REQUIRE(frame_logits && onset_logits && offset_logits && ref_on && ref_off && ref_ptr && counts, MT_EINVAL,
-               "mt_note_match_list_off: null pointer");
-    MT_REQUIRE(B > 0 && P > 0 && T > 0 && (long long)B * P < 2147483647ll && (long long)T * TICKS_PER_FRAME < 2147483647ll - 64 * NOTE_SLAB,
-               MT_EINVAL, "mt_note_match_list_off: bad dims (frame times must fit 31 bits of 100 us ticks)");
-    MT_REQUIRE(thr_ok(thr_frame) && thr_ok(thr_onset) && thr_ok(thr_offset), MT_EINVAL, "mt_note_match_list_off: thresholds must lie in (0, 1)");
-    return launch_note_match_list<true>(frame_logits, onset_logits, offset_logits, thr_frame, thr_onset, thr_offset, ref_on, ref_off, ref_ptr,
-                                        lengths, counts, B, P, T, (hipStream_t)stream);
+    return note_match_list("mt_note_match_list_off", true, frame_logits, onset_logits, offset_logits, {thr_frame, thr_onset, thr_offset}, ref_on,
+                           ref_off, ref_ptr, lengths, counts, B, P, T, stream);
 }
 
 // The checks the two sweep entry points share; the thresholds end up in `thr`, which the kernel takes by value.
@@ -746,21 +714,13 @@ extern "C" int mt_note_sweep_list(const float* frame_logits, const float* onset_
 
 extern "C" int mt_heads_to_notes(const float* frame_logits, const float* onset_logits, float thr_frame, float thr_onset, int NB, int P, int T,
                                  int* counts, int* starts, int* ends, int capacity, mt_stream_t stream) {
-    MT_REQUIRE(frame_logits && onset_logits && counts && starts && ends && capacity > 0, MT_EINVAL, "mt_heads_to_notes: bad arguments");
-    MT_REQUIRE(NB > 0 && P > 0 && T > 0 && (long long)NB * T < 2147483647ll - 64 * NOTE_SLAB, MT_EINVAL, "mt_heads_to_notes: bad dims");
-    MT_REQUIRE(thr_frame > 0.0f && thr_frame < 1.0f && thr_onset > 0.0f && thr_onset < 1.0f, MT_EINVAL,
-               "mt_heads_to_notes: thresholds must lie in (0, 1)");
-    return launch_heads_notes<false>(frame_logits, onset_logits, nullptr, thr_frame, thr_onset, 0.5f, NB, P, T, counts, starts, ends, capacity,
-                                     (hipStream_t)stream);
+    return heads_notes("mt_heads_to_notes", false, frame_logits, onset_logits, nullptr, {thr_frame, thr_onset, 0.5f}, NB, P, T, counts, starts, ends,
+                       capacity, stream);
 }
 
 extern "C" int mt_heads_to_notes_off(const float* frame_logits, const float* onset_logits, const float* offset_logits, float thr_frame,
                                      float thr_onset, float thr_offset, int NB, int P, int T, int* counts, int* starts, int* ends, int capacity,
                                      mt_stream_t stream) {
-    MT_REQUIRE(frame_logits && onset_logits && offset_logits && counts && starts && ends && capacity > 0, MT_EINVAL,
-               "mt_heads_to_notes_off: bad arguments");
-    MT_REQUIRE(NB > 0 && P > 0 && T > 0 && (long long)NB * T < 2147483647ll - 64 * NOTE_SLAB, MT_EINVAL, "mt_heads_to_notes_off: bad dims");
-    MT_REQUIRE(thr_ok(thr_frame) && thr_ok(thr_onset) && thr_ok(thr_offset), MT_EINVAL, "mt_heads_to_notes_off: thresholds must lie in (0, 1)");
-    return launch_heads_notes<true>(frame_logits, onset_logits, offset_logits, thr_frame, thr_onset, thr_offset, NB, P, T, counts, starts, ends,
-                                    capacity, (hipStream_t)stream);
+    return heads_notes("mt_heads_to_notes_off", true, frame_logits, onset_logits, offset_logits, {thr_frame, thr_onset, thr_offset}, NB, P, T, counts,
+                       starts, ends, capacity, stream);
 }

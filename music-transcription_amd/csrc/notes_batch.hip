@@ -1,6 +1,7 @@
 // mt_notes_batch: the notes of a padded batch of whole recordings, frame_logits / onset_logits [B][P][T] with lengths[b] valid frames
 // (DESIGN.md 6d "The corpus in windows").  Row (b, p) decodes exactly as mt_roll_to_notes (src_mode 0) / mt_heads_to_notes decode a
-// contiguous copy of its valid frames: the same activity expression (logit_active) and the same decode_window (note_decode.h).
+// contiguous copy of its valid frames: the same walk, decode step and emitter (walk_slabs, decode_step, emit_window of note_decode.h);
+// the kernel adds 64-bit row addressing, a deeper slab and row_off as the place of a row's notes.
 // Three launches on one stream: count (one wave64 per row), an exclusive prefix of the counts in row order (64-bit), fill (one wave64
 // per row, at row_off[row]).  Frames at or past lengths[b] are never loaded.
 #include "mt_common.h"
@@ -33,37 +34,17 @@ __global__ __launch_bounds__(64 * BATCH_WAVES) void notes_batch_kernel(const flo
     }
     const float* __restrict__ xf_row = frame + (size_t)row * (size_t)T;
     const float* __restrict__ xo_row = onset ? onset + (size_t)row * (size_t)T : nullptr;
+    const NoteThr thr{thr_f, thr_o, 0.5f};
     int n_on = 0, n_off = 0;
-    unsigned long long o_prev = 0, open_prev = 0;
-    const unsigned long long below = (1ull << lane) - 1ull;
-    for (long long s0 = 0; s0 < L; s0 += 64 * BATCH_SLAB) {
-        float xf[BATCH_SLAB], xo[BATCH_SLAB];
-#pragma unroll
-        for (int w = 0; w < BATCH_SLAB; ++w) {
-            const long long g = s0 + 64 * w + lane;
-            const bool in = g < L;
-            xf[w] = in ? xf_row[g] : 0.0f;
-            xo[w] = (in && xo_row) ? xo_row[g] : 0.0f;
-        }
-#pragma unroll
-        for (int w = 0; w < BATCH_SLAB; ++w) {
-            const long long g0 = s0 + 64 * w;
-            if (g0 >= L) continue;                              // (not a break: the loop stays fully unrolled, xf / xo in registers)
-            const bool in = g0 + lane < L;
-            const bool f = in && logit_active(xf[w], thr_f);
-            const bool o = xo_row ? (in && logit_active(xo[w], thr_o)) : f;
-            const WindowEvents ev = decode_window(o, f || o, lane, o_prev, open_prev);
-            if (FILL) {
-                if (ev.starts >> lane & 1ull) starts[out + n_on + __popcll(ev.starts & below)] = (int)(g0 + lane);
-                if (ev.closes >> lane & 1ull) ends[out + n_off + __popcll(ev.closes & below)] = (int)(g0 + lane);
-            }
-            n_on += __popcll(ev.starts);
-            n_off += __popcll(ev.closes);
-        }
-    }
+    DecodeCarry<false> c;
+    walk_slabs<BATCH_SLAB, 2>(
+        L, lane, [&](int ch, long long g) __attribute__((always_inline)) { return ch == 0 ? xf_row[g] : xo_row ? xo_row[g] : 0.0f; },
+        [&](long long g0, bool in, const float(&x)[2]) __attribute__((always_inline)) {
+            emit_window(decode_step<false>(in, x, xo_row != nullptr, thr, lane, c), g0, lane, FILL, starts + out, ends + out, n_on, n_off);
+        });
     if (lane == 0) {
         if (!FILL) counts[row] = n_on;
-        else if (open_prev) ends[out + n_off] = (int)L;        // a note still open at the row's last valid frame ends at L
+        else emit_open_end(c, ends + out, n_off, (int)L);      // a note still open at the row's last valid frame ends at L
     }
 }
 

@@ -46,20 +46,28 @@ def _check_threshold(t: float, name: str) -> float:
     return t
 
 
-def _needs_onset(offset_logits, onset_logits) -> None:
-    """The offset-gated decoder opens its notes at onset edges: refuse offset logits without onset logits, before anything else."""
+def _heads(frame_logits, onset_logits, offset_logits, threshold, onset_threshold, offset_threshold, onset_required=False, ref_roll=None,
+           mismatch="shape mismatch: frame {frame}, onset {onset}"):
+    """The checked heads of a decoder call -> (x, on, off, thr, othr, kthr, ref): the contiguous (B, P, T) logits (on / off None
+    without them), their thresholds (0.5 for an absent head) and the reference roll (None without ref_roll).  The offset-gated
+    decoder opens its notes at onset edges, so offset logits without onset logits are refused before anything else; then shapes,
+    then thresholds.  `mismatch` is the calling function's own message for logits that differ in shape."""
     if offset_logits is not None and onset_logits is None:
         raise ValueError("offset_logits: the offset-gated decoder needs onset_logits as well")
-
-
-def _offset_head(offset_logits, offset_threshold: float, shape):
-    """The checked offset logits and threshold of the offset-gated decoder (None, 0.5 without them)."""
+    x = _rows(frame_logits, "frame_logits")
+    ref = None if ref_roll is None else _rows(ref_roll, "ref_roll")
+    on = _rows(onset_logits, "onset_logits") if onset_required or onset_logits is not None else None
+    if (ref is not None and ref.shape != x.shape) or (on is not None and on.shape != x.shape):
+        shapes = {"frame": tuple(x.shape), "ref": None if ref is None else tuple(ref.shape), "onset": None if on is None else tuple(on.shape)}
+        raise ValueError(mismatch.format(**shapes))
+    thr = _check_threshold(threshold, "threshold")
+    othr = _check_threshold(onset_threshold, "onset_threshold") if on is not None else 0.5
     if offset_logits is None:
-        return None, 0.5
+        return x, on, None, thr, othr, 0.5, ref
     off = _rows(offset_logits, "offset_logits")
-    if off.shape != shape:
-        raise ValueError(f"shape mismatch: frame {tuple(shape)}, offset {tuple(off.shape)}")
-    return off, _check_threshold(offset_threshold, "offset_threshold")
+    if off.shape != x.shape:
+        raise ValueError(f"shape mismatch: frame {tuple(x.shape)}, offset {tuple(off.shape)}")
+    return x, on, off, thr, othr, _check_threshold(offset_threshold, "offset_threshold"), ref
 
 
 def _lengths(lengths, B: int, dev) -> Optional[torch.Tensor]:
@@ -94,26 +102,18 @@ def note_match_counts(frame_logits: torch.Tensor, ref_roll: torch.Tensor, thresh
     """(B, P, T) frame logits (and onset logits for the onset-gated decoder) and (B, P, T) reference roll on the device -> (B, 4)
     int64 device tensor {n_ref, n_est, tp_onset, tp_onset_offset}.  lengths (B,) = valid frames per sample (None: all T).  With
     offset_logits (and onset_logits) the estimates come from the offset-gated decoder (mt_note_match_counts_off)."""
-    _needs_onset(offset_logits, onset_logits)
-    x = _rows(frame_logits, "frame_logits")
-    ref = _rows(ref_roll, "ref_roll")
-    on = None if onset_logits is None else _rows(onset_logits, "onset_logits")
-    if ref.shape != x.shape or (on is not None and on.shape != x.shape):
-        raise ValueError(f"shape mismatch: frame {tuple(x.shape)}, ref {tuple(ref.shape)}, onset {None if on is None else tuple(on.shape)}")
-    thr = _check_threshold(threshold, "threshold")
-    othr = _check_threshold(onset_threshold, "onset_threshold") if on is not None else 0.5
-    off, kthr = _offset_head(offset_logits, offset_threshold, x.shape)
+    x, on, off, thr, othr, kthr, ref = _heads(frame_logits, onset_logits, offset_logits, threshold, onset_threshold, offset_threshold,
+                                              ref_roll=ref_roll, mismatch="shape mismatch: frame {frame}, ref {ref}, onset {onset}")
     B, P, T = x.shape
     dev = x.device
     ln = _lengths(lengths, B, dev)
     counts = torch.empty(B, 4, dtype=torch.int64, device=dev)
+    rest = (ptr(ref), ptr(ln), ptr(counts), B, P, T, _lib.stream_ptr())
     with torch.cuda.device(dev):
-        if off is not None:
-            check(lib.mt_note_match_counts_off(ptr(x), ptr(on), ptr(off), thr, othr, kthr, ptr(ref), ptr(ln), ptr(counts), B, P, T,
-                                               _lib.stream_ptr()), "mt_note_match_counts_off")
-            return counts
-        check(lib.mt_note_match_counts(ptr(x), ptr(on), thr, othr, ptr(ref), ptr(ln), ptr(counts), B, P, T, _lib.stream_ptr()),
-              "mt_note_match_counts")
+        if off is None:
+            check(lib.mt_note_match_counts(ptr(x), ptr(on), thr, othr, *rest), "mt_note_match_counts")
+        else:
+            check(lib.mt_note_match_counts_off(ptr(x), ptr(on), ptr(off), thr, othr, kthr, *rest), "mt_note_match_counts_off")
     return counts
 
 
@@ -128,26 +128,18 @@ def note_match_list(frame_logits: torch.Tensor, ref_notes: Dict[str, torch.Tenso
     note [s, e) in frames has times 320 s, 320 e; onsets match within 500 ticks, offsets within max(500, 0.2 reference length).
     Notes that start at or past a sample's valid frames are not counted.  -> (B, 4) int64 {n_ref, n_est, tp_onset, tp_onset_offset}.
     With offset_logits (and onset_logits) the estimates come from the offset-gated decoder (mt_note_match_list_off)."""
-    _needs_onset(offset_logits, onset_logits)
-    x = _rows(frame_logits, "frame_logits")
-    on = None if onset_logits is None else _rows(onset_logits, "onset_logits")
-    if on is not None and on.shape != x.shape:
-        raise ValueError(f"shape mismatch: frame {tuple(x.shape)}, onset {tuple(on.shape)}")
-    thr = _check_threshold(threshold, "threshold")
-    othr = _check_threshold(onset_threshold, "onset_threshold") if on is not None else 0.5
-    off, kthr = _offset_head(offset_logits, offset_threshold, x.shape)
+    x, on, off, thr, othr, kthr, _ = _heads(frame_logits, onset_logits, offset_logits, threshold, onset_threshold, offset_threshold)
     B, P, T = x.shape
     dev = x.device
     r_on, r_off, r_ptr = _note_tables(ref_notes, B, P, dev)
     ln = _lengths(lengths, B, dev)
     counts = torch.empty(B, 4, dtype=torch.int64, device=dev)
+    rest = (ptr(r_on), ptr(r_off), ptr(r_ptr), ptr(ln), ptr(counts), B, P, T, _lib.stream_ptr())
     with torch.cuda.device(dev):
-        if off is not None:
-            check(lib.mt_note_match_list_off(ptr(x), ptr(on), ptr(off), thr, othr, kthr, ptr(r_on), ptr(r_off), ptr(r_ptr), ptr(ln), ptr(counts),
-                                             B, P, T, _lib.stream_ptr()), "mt_note_match_list_off")
-            return counts
-        check(lib.mt_note_match_list(ptr(x), ptr(on), thr, othr, ptr(r_on), ptr(r_off), ptr(r_ptr), ptr(ln), ptr(counts), B, P, T,
-                                     _lib.stream_ptr()), "mt_note_match_list")
+        if off is None:
+            check(lib.mt_note_match_list(ptr(x), ptr(on), thr, othr, *rest), "mt_note_match_list")
+        else:
+            check(lib.mt_note_match_list_off(ptr(x), ptr(on), ptr(off), thr, othr, kthr, *rest), "mt_note_match_list_off")
     return counts
 
 
@@ -235,26 +227,20 @@ def heads_to_notes_device(frame_logits: torch.Tensor, onset_logits: torch.Tensor
     """(n_chunks, 88, T) frame and onset logits ON THE DEVICE -> notes of the onset-gated decoder over the chunks concatenated in
     time, in the reference's note order (pitch-major, then time); only counts and two ints per note reach the host.  With
     offset_logits: the notes of the offset-gated decoder (mt_heads_to_notes_off), which end where the offset head fires."""
-    _needs_onset(offset_logits, onset_logits)
-    x = _rows(frame_logits, "frame_logits")
-    on = _rows(onset_logits, "onset_logits")
-    if on.shape != x.shape:
-        raise ValueError(f"frame {tuple(x.shape)} and onset {tuple(on.shape)} logits differ in shape")
-    thr, othr = _check_threshold(threshold, "threshold"), _check_threshold(onset_threshold, "onset_threshold")
-    off, kthr = _offset_head(offset_logits, offset_threshold, x.shape)
+    x, on, off, thr, othr, kthr, _ = _heads(frame_logits, onset_logits, offset_logits, threshold, onset_threshold, offset_threshold,
+                                            onset_required=True, mismatch="frame {frame} and onset {onset} logits differ in shape")
     NB, P, T = x.shape
     dev = x.device
     counts = torch.empty(P, dtype=torch.int32, device=dev)
     cap = max(1024, NB * 64)
     while True:
         starts, ends = torch.empty(cap, dtype=torch.int32, device=dev), torch.empty(cap, dtype=torch.int32, device=dev)
+        rest = (NB, P, T, ptr(counts), ptr(starts), ptr(ends), cap, _lib.stream_ptr())
         with torch.cuda.device(dev):
-            if off is not None:
-                check(lib.mt_heads_to_notes_off(ptr(x), ptr(on), ptr(off), thr, othr, kthr, NB, P, T, ptr(counts), ptr(starts), ptr(ends), cap,
-                                                _lib.stream_ptr()), "mt_heads_to_notes_off")
+            if off is None:
+                check(lib.mt_heads_to_notes(ptr(x), ptr(on), thr, othr, *rest), "mt_heads_to_notes")
             else:
-                check(lib.mt_heads_to_notes(ptr(x), ptr(on), thr, othr, NB, P, T, ptr(counts), ptr(starts), ptr(ends), cap, _lib.stream_ptr()),
-                      "mt_heads_to_notes")
+                check(lib.mt_heads_to_notes_off(ptr(x), ptr(on), ptr(off), thr, othr, kthr, *rest), "mt_heads_to_notes_off")
         c = counts.cpu().numpy()
         total = int(c.sum())
         if total <= cap:
@@ -271,12 +257,8 @@ def notes_batch_device(frame_logits: torch.Tensor, onset_logits: Optional[torch.
     one note list per recording: what transcribe.notes_from_logits_device (onset_logits None) or heads_to_notes_device returns on
     that recording's rows trimmed to its length.  The padding is never read.  One launch of mt_notes_batch, one device-to-host copy
     of the counts and offsets and one of the notes; a second launch only when the first capacity guess was short."""
-    x = _rows(frame_logits, "frame_logits")
-    on = None if onset_logits is None else _rows(onset_logits, "onset_logits")
-    if on is not None and on.shape != x.shape:
-        raise ValueError(f"frame {tuple(x.shape)} and onset {tuple(on.shape)} logits differ in shape")
-    thr = _check_threshold(threshold, "threshold")
-    othr = _check_threshold(onset_threshold, "onset_threshold") if on is not None else 0.5
+    x, on, _, thr, othr, _, _ = _heads(frame_logits, onset_logits, None, threshold, onset_threshold, 0.5,
+                                       mismatch="frame {frame} and onset {onset} logits differ in shape")
     B, P, T = x.shape
     dev = x.device
     ln = _lengths(lengths, B, dev)

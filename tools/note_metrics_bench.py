@@ -1,5 +1,5 @@
 """Device time of mt_note_match_counts and mt_note_match_list (DESIGN.md "Note-level F1"), frame, onset-gated and offset-gated decoders,
-and of mt_heads_to_notes beside mt_heads_to_notes_off, on two shapes:
+of mt_heads_to_notes beside mt_heads_to_notes_off (chunks) and of mt_notes_batch (recordings), on two shapes:
 
   * chunks:     a batch of 128 chunks x 88 pitches x 938 frames (one forward's worth of 30 s chunks);
   * recordings: a padded batch of 8 whole recordings of 10-25 minutes (T up to ~47 000 frames), masked by `lengths`.
@@ -113,6 +113,28 @@ def time_offset_decoder(out, frame, onset, ref, notes, lengths, iters):
         raise SystemExit(f"{out['case']}: the offset-gated note list has another number of notes: {out}")
 
 
+def time_notes_batch(out, frame, onset, lengths, iters):
+    """mt_notes_batch (count, prefix, fill) on the padded recordings, frame and onset-gated decoder, at a capacity that holds every note."""
+    import torch
+    from music_transcription_amd import _lib
+    B, P, T = frame.shape
+    dev = frame.device
+    ln = torch.tensor(lengths, dtype=torch.int64, device=dev)
+    counts, row_off = torch.empty(B * P, dtype=torch.int32, device=dev), torch.empty(B * P + 1, dtype=torch.int64, device=dev)
+    cap = B * P * T // 2 + 1
+    starts, ends = torch.empty(cap, dtype=torch.int32, device=dev), torch.empty(cap, dtype=torch.int32, device=dev)
+    lib, ptr, st = _lib.lib, _lib.ptr, _lib.stream_ptr()
+    for key, on in (("notes_batch_frame", None), ("notes_batch_onset", onset)):
+        fn = lambda: _lib.check(lib.mt_notes_batch(ptr(frame), ptr(on), 0.5, 0.5, ptr(ln), B, P, T, ptr(counts), ptr(row_off), ptr(starts),
+                                                   ptr(ends), cap, st))
+        ms = device_ms(fn, iters)
+        nbytes = 2 * (2 if on is not None else 1) * out["valid_frames"] * P * 4        # a counting and a writing pass
+        out[key] = {"ms": round(ms, 4), "read_MB": round(nbytes / 1e6, 2), "GB_per_s": round(nbytes / (ms * 1e-3) / 1e9, 1),
+                    "notes": int(row_off[-1])}
+        if out[key]["notes"] != out["onset" if on is not None else "frame"]["n_est"]:
+            raise SystemExit(f"{out['case']} ({key}): mt_notes_batch finds another number of notes than the matcher: {out}")
+
+
 def roll_notes(ref):
     """The runs of the (B, P, T) roll as a note list in ticks (320 per frame) on the device: {"on", "off", "ptr"}."""
     import torch
@@ -152,6 +174,8 @@ def time_case(name, frame, onset, ref, lengths, iters):
             raise SystemExit(f"{name} ({dec}): the list matcher's counts differ from the roll matcher's on the roll's own runs: "
                              f"{out[dec]} vs {out[dec + '_list']}")
     time_offset_decoder(out, frame, onset, ref, notes, lengths, iters)
+    if lengths is not None:
+        time_notes_batch(out, frame, onset, lengths, iters)
     return out
 
 
