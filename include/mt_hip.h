@@ -482,6 +482,28 @@ int    mt_heads_to_notes_off(const float* frame_logits, const float* onset_logit
 int    mt_notes_batch(const float* frame_logits, const float* onset_logits, float thr_frame, float thr_onset, const long long* lengths,
                       int B, int P, long long T, int* counts, long long* row_off, int* starts, int* ends, long long capacity,
                       mt_stream_t stream);
+/* Note cleanup in the decoders (csrc/note_decode.h clean_step, DESIGN.md 6c "Note cleanup"), two parameters in frames of 32 ms.  Per pitch row of L
+ * valid frames: inactive runs of a = f | o of at most bridge_frames (0..63) frames that have an active frame of the row directly
+ * before and after them are filled (the frame decoder fills f and takes its onsets from the result; the onset mask of the other two
+ * is untouched, so a re-struck key still splits, and an offset edge still cuts through a bridged gap); the decoder runs on that; then
+ * every note [s, e) with e - s < min_frames (1..64) is removed, however it closed, its neighbours untouched.  (1, 0) changes nothing,
+ * and is served by the cleaning kernels all the same.  Each call has the contract of its _off namesake (mt_notes_batch_clean: of
+ * mt_notes_batch) with these exceptions: offset_logits may be NULL (the onset-gated decoder; thr_offset is not read), in
+ * mt_heads_to_notes_clean onset_logits may then be NULL too (the frame decoder: mt_roll_to_notes' notes, src_mode 0); offset_logits
+ * without onset_logits, or min_frames / bridge_frames out of range: MT_EINVAL and nothing is written. */
+int    mt_note_match_counts_clean(const float* frame_logits, const float* onset_logits, const float* offset_logits, float thr_frame,
+                                  float thr_onset, float thr_offset, const float* ref_roll, const long long* lengths,
+                                  unsigned long long* counts, int B, int P, int T, int min_frames, int bridge_frames, mt_stream_t stream);
+int    mt_note_match_list_clean(const float* frame_logits, const float* onset_logits, const float* offset_logits, float thr_frame,
+                                float thr_onset, float thr_offset, const int* ref_on, const int* ref_off, const long long* ref_ptr,
+                                const long long* lengths, unsigned long long* counts, int B, int P, int T, int min_frames, int bridge_frames,
+                                mt_stream_t stream);
+int    mt_heads_to_notes_clean(const float* frame_logits, const float* onset_logits, const float* offset_logits, float thr_frame,
+                               float thr_onset, float thr_offset, int NB, int P, int T, int* counts, int* starts, int* ends, int capacity,
+                               int min_frames, int bridge_frames, mt_stream_t stream);
+int    mt_notes_batch_clean(const float* frame_logits, const float* onset_logits, float thr_frame, float thr_onset, const long long* lengths,
+                            int B, int P, long long T, int* counts, long long* row_off, int* starts, int* ends, long long capacity,
+                            int min_frames, int bridge_frames, mt_stream_t stream);
 
 /* ------------------------------------------------------------------ optimizer step (training)
  * clip_grad_norm_(max_norm) + torch.optim.Adam with coupled L2 weight decay over flat f32 buffers

@@ -2,6 +2,7 @@
 """Inference CLI with the reference's interface (main.py:290-362):
 
     python main.py audio_file model_file [-o OUT.mid] [-d {cpu,cuda}] [-t THRESHOLD] [--decoder {frame,onset,onset_offset}] [--overlap SECONDS]
+                   [--min-note-ms MS] [--bridge-gap-ms MS]
 
 Exit code 1 with a message when a file is missing or transcription fails.  The checkpoint must be a
 CNNRNNModelLarge(320, 512, 3) state_dict as in the reference (main.py:16-20); --model-type/--n-mels/
@@ -33,11 +34,23 @@ def main():
                          "places chunk k's notes 16 ms x k late because a 480000-sample chunk spans 937.5 hops but yields 938 frames). "
                          "With an overlap the windows start on the 512-sample hop and their centres are stitched on the recording's "
                          "own frame grid: no drift, and no cold network start at the chunk boundaries")
+    ap.add_argument("--min-note-ms", type=float, default=0.0,
+                    help="note cleanup in the decoder: drop every note shorter than this many milliseconds (32 ms frames; at most 2048; "
+                         "default 0 = keep all)")
+    ap.add_argument("--bridge-gap-ms", type=float, default=0.0,
+                    help="note cleanup in the decoder: a dropout of the activity no longer than this many milliseconds, with activity "
+                         "directly before and after it, does not end the note (below 2048; default 0 = none).  Gaps are bridged first, "
+                         "then short notes dropped")
     ap.add_argument("--model-type", default="cnn_rnn_large")
     ap.add_argument("--n-mels", type=int, default=320)
     ap.add_argument("--hidden-size", type=int, default=512)
     ap.add_argument("--num-layers", type=int, default=3)
     args = ap.parse_args()
+    try:
+        from music_transcription_amd.notes import cleanup_frames
+        min_note_frames, bridge_frames = cleanup_frames(args.min_note_ms, args.bridge_gap_ms)
+    except ValueError as e:
+        ap.error(str(e))
     if not os.path.exists(args.audio_file):
         print(f"Error: Audio file not found: {args.audio_file}")
         sys.exit(1)
@@ -49,7 +62,8 @@ def main():
         from music_transcription_amd.transcribe import transcribe_audio
         out = transcribe_audio(args.audio_file, args.model_file, args.output, args.device, args.threshold,
                                decoder=args.decoder, onset_threshold=args.onset_threshold, overlap=args.overlap,
-                               offset_threshold=args.offset_threshold, model_type=args.model_type, n_mels=args.n_mels, hidden_size=args.hidden_size,
+                               offset_threshold=args.offset_threshold, min_note_frames=min_note_frames, bridge_frames=bridge_frames,
+                               model_type=args.model_type, n_mels=args.n_mels, hidden_size=args.hidden_size,
                                num_layers=args.num_layers)
         print("=" * 60 + f"\nTranscription completed successfully!\nOutput: {out}\n" + "=" * 60)
     except Exception as e:

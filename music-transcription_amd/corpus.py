@@ -21,7 +21,7 @@ import torch
 from . import transcribe as tr
 from . import windows as W
 from .frontend import get_frontend
-from .notes import heads_to_notes_device, note_match_counts, note_prf, notes_batch_device
+from .notes import check_cleanup, heads_to_notes_device, note_match_counts, note_prf, notes_batch_device
 from .ops import f1_counts, f1_from_counts, framewise_f1, predict_from_logits
 
 SR, CH, HOP = 16000, 480000, 512
@@ -40,15 +40,18 @@ def transcribe_shard(model, rec_ids: Sequence[int], chunks_of: Callable[[int], t
                      batch: int = 128, streams: int = 3, threshold: float = 0.5, want_notes: bool = True,
                      reference_roll_of: Optional[Callable[[int, int], Optional[torch.Tensor]]] = None,
                      midi_path_of: Optional[Callable[[int], Optional[str]]] = None, warm: bool = True, decoder: str = "frame",
-                     onset_threshold: float = 0.5, note_metrics: bool = False) -> Dict[str, object]:
+                     onset_threshold: float = 0.5, note_metrics: bool = False, min_note_frames: int = 1,
+                     bridge_frames: int = 0) -> Dict[str, object]:
     """rec_ids: the recordings of this rank; chunks_of(i) -> (n_i, 480000) float32 CUDA tensor (decode + resample + split for
     real audio: part of the measured time; a view of resident synthetic audio otherwise).  Returns {"wall_s", "chunks",
     "notes": {i: [(pitch, start, end)]}, "f1": {i: float}, "n_notes", "finite"}; wall_s covers slab assembly, every forward,
     the note extraction and the F1 counts (one device synchronisation at the end).  decoder="onset": notes from the onset-gated
     decoder (notes.heads_to_notes_device; cnn_rnn_large with heads only).  note_metrics=True with reference rolls: "note_f1" =
-    {i: (onset F1, onset+offset F1)} against the runs of the reference roll, estimated notes from the same decoder."""
+    {i: (onset F1, onset+offset F1)} against the runs of the reference roll, estimated notes from the same decoder.
+    min_note_frames / bridge_frames: note cleanup in the decoder (DESIGN.md 6c "Note cleanup"), for the notes and for note_f1 alike."""
     _check_corpus_decoder(decoder)
     tr.check_decoder(decoder, model=model)
+    clean = dict(zip(("min_note_frames", "bridge_frames"), check_cleanup(min_note_frames, bridge_frames)))
     heads = decoder == "onset"
     dev = torch.device(device)
     net = model.model
@@ -130,7 +133,8 @@ def transcribe_shard(model, rec_ids: Sequence[int], chunks_of: Callable[[int], t
         on = (parts_on[0] if len(parts_on) == 1 else torch.cat(parts_on)) if heads else None
         finite_flags.append(torch.isfinite(lg).all())
         if want_notes:
-            notes = heads_to_notes_device(lg, on, threshold, onset_threshold, fs) if heads else tr.notes_from_logits_device(lg, threshold, fs)
+            notes = (heads_to_notes_device(lg, on, threshold, onset_threshold, fs, **clean) if heads else
+                     tr.notes_from_logits_device(lg, threshold, fs, **clean))
             res["notes"][i] = notes
             res["n_notes"] += len(notes)
             path = midi_path_of(i) if midi_path_of else None
@@ -145,7 +149,7 @@ def transcribe_shard(model, rec_ids: Sequence[int], chunks_of: Callable[[int], t
                 if note_metrics:
                     rows = lambda x: x.permute(1, 0, 2).reshape(88, -1)[:, :L].contiguous()
                     note_dev[i] = note_match_counts(rows(lg), ref[:, :L].contiguous().float(), threshold,
-                                                    rows(on) if heads else None, onset_threshold)
+                                                    rows(on) if heads else None, onset_threshold, **clean)
         del parts, parts_on, lg, on
         for k, _, _ in mine:
             slabs[k][2] -= 1
@@ -248,7 +252,7 @@ def transcribe_shard_windows(model, rec_ids: Sequence[int], audio_of: Callable[[
                              threshold: float = 0.5, decoder: str = "frame", onset_threshold: float = 0.5, want_notes: bool = True,
                              reference_roll_of: Optional[Callable[[int, int], Optional[torch.Tensor]]] = None,
                              midi_path_of: Optional[Callable[[int], Optional[str]]] = None, note_metrics: bool = False,
-                             warm: bool = True) -> Dict[str, object]:
+                             warm: bool = True, min_note_frames: int = 1, bridge_frames: int = 0) -> Dict[str, object]:
     """transcribe_shard on the window grid.  audio_of(i) -> recording i as 1-D float32 at 16 kHz on the device, any length (0 samples
     included).  Recordings are taken in rec_ids order into groups (plan_groups; group_windows defaults to batch * streams).  A group
     runs exactly the slabs of windows.transcribe_windows(model, [its recordings], overlap_s, batch, all_heads) into zero-filled
@@ -257,9 +261,11 @@ def transcribe_shard_windows(model, rec_ids: Sequence[int], audio_of: Callable[[
     = its recordings' frame counts: notes of all its recordings from one notes_batch_device call, F1 counts, note counts and a finite
     flag; the host waits for group g's notes only after group g + 1's slabs are queued.  reference_roll_of(i, frames) -> (88, >= 1)
     roll on the recording's frame grid or None; scored over min(frames, reference frames).  Returns transcribe_shard's keys with
-    "windows" for "chunks", and "groups" (lists of recording ids) and "frames" {i: 1 + n_i // 512}."""
+    "windows" for "chunks", and "groups" (lists of recording ids) and "frames" {i: 1 + n_i // 512}.  min_note_frames /
+    bridge_frames as in transcribe_shard."""
     _check_corpus_decoder(decoder)
     tr.check_decoder(decoder, model=model)
+    clean = dict(zip(("min_note_frames", "bridge_frames"), check_cleanup(min_note_frames, bridge_frames)))
     W.overlap_frames(overlap_s)
     heads = decoder == "onset"
     dev = torch.device(device)
@@ -326,7 +332,7 @@ def transcribe_shard_windows(model, rec_ids: Sequence[int], audio_of: Callable[[
         frame, onset = outs[0], (outs[1] if heads else None)
         finite_flags.append(torch.isfinite(frame).all())          # (over the zero-filled buffer: padding is finite)
         if want_notes:
-            for i, notes in zip(rec, notes_batch_device(frame, onset, threshold, onset_threshold, Tg, fs)):
+            for i, notes in zip(rec, notes_batch_device(frame, onset, threshold, onset_threshold, Tg, fs, **clean)):
                 res["notes"][i] = notes
                 res["n_notes"] += len(notes)
                 path = midi_path_of(i) if midi_path_of else None
@@ -345,7 +351,7 @@ def transcribe_shard_windows(model, rec_ids: Sequence[int], audio_of: Callable[[
                 roll[r, :, :cmp[r]] = ref[:, :cmp[r]]
         ln = torch.tensor(cmp, dtype=torch.int64).to(dev)
         c = f1_counts(predict_from_logits(frame, threshold), roll, ln)
-        nc = note_match_counts(frame, roll, threshold, onset, onset_threshold, ln) if note_metrics else None
+        nc = note_match_counts(frame, roll, threshold, onset, onset_threshold, ln, **clean) if note_metrics else None
         f1_dev.append(([i for i, ref in zip(rec, refs) if ref is not None], [r for r, ref in enumerate(refs) if ref is not None], c, nc))
 
     def run(group: List[int]):

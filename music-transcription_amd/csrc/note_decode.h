@@ -3,7 +3,9 @@
 //                   never loaded.  The kernel supplies the addressing (a loader) and what it does with a window (a body);
 //   decode_step:    one window of a decoder: the heads' activity, then decode_window (frame / onset-gated) or decode_window_off
 //                   (offset-gated), the state between windows in a DecodeCarry;
-//   emit_window, emit_open_end: the count and the fill pass of a note list (mt_heads_to_notes, mt_notes_batch).
+//   emit_window, emit_open_end: the count and the fill pass of a note list (mt_heads_to_notes, mt_notes_batch);
+//   clean_step, flush_clean:    decode_step<OFF, true>, the note cleanup of the mt_*_clean kernels (DESIGN.md 6c "Note cleanup"): short gaps of the
+//                   activity are bridged before the decoder, short notes dropped after it; events come out two windows late.
 //
 // Activity is the expression of mt_predict_threshold / note_active in post.hip, so ties break the same way everywhere.
 // Onset-gated decoder (the Onsets-and-Frames rule): a = frame-active OR onset-active; a note opens at every rising edge of
@@ -66,10 +68,69 @@ __device__ __forceinline__ WindowEvents decode_window_off(bool o, bool a, bool k
 // The decoder's state between windows: o / open (and, offset-gated, k / e) of the frame before the window.
 struct CarryOnset { unsigned long long o_prev = 0, open_prev = 0; };
 struct CarryOffset : CarryOnset { unsigned long long k_prev = 0, e_prev = 0; };
+
+// Note cleanup (DESIGN.md 6c "Note cleanup"), the two parameters in frames: inactive runs of a = f | o of at most `bridge` frames with an active
+// frame of the row directly before and after them are filled, and decoded notes shorter than `min_frames` are removed.  (1, 0) = none.
+struct NoteClean { int min_frames = 1, bridge = 0; };
+constexpr int CLEAN_MAX_MIN_FRAMES = 64, CLEAN_MAX_BRIDGE = 63;      // both stages look one 64-frame window ahead, never further
+constexpr int CLEAN_DELAY = 128;                                     // clean_step returns the events of the window two calls back
+
+// The cleanup pipeline's state on top of the decoder's, all wave-uniform.  Bridge stage: the masks of the window before the one
+// that arrives (a gap at its end is decided by the first 63 frames of the next) and gap_before = the inactive frames directly
+// before that window, capped at 64: more than any bridge, which is also how a leading run is never filled.  Drop stage: the events
+// of the window before that (a note that starts on its last frame is short iff it closes within the next 63 frames) and
+// dropped_open = the note open across the boundary into the held events has been dropped, so its close goes too.
 template <bool OFF>
-using DecodeCarry = std::conditional_t<OFF, CarryOffset, CarryOnset>;
+struct CarryClean : std::conditional_t<OFF, CarryOffset, CarryOnset> {
+    unsigned long long am = 0, om = 0, km = 0;
+    int gap_before = 64;
+    WindowEvents held = {0ull, 0ull};
+    unsigned long long dropped_open = 0;
+};
+template <bool OFF, bool CLEAN = false>
+using DecodeCarry = std::conditional_t<CLEAN, CarryClean<OFF>, std::conditional_t<OFF, CarryOffset, CarryOnset>>;
 
 struct NoteThr { float frame, onset, offset; };   // thresholds of the three heads (offset: read by the offset-gated decoder only)
+
+// One call of the cleanup pipeline: the masks am / om / km of window w arrive (a = f | o, onset, offset activity; inactive outside
+// the row), window w - 1 is bridged and decoded, and the cleaned events of window w - 2 are returned.  Neither stage changes what
+// the matchers of notes.hip rest on: bridging adds no onset edge (the onset mask is untouched; the frame decoder's edges of f' are
+// a subset of those of f) and dropping removes notes whole, so onsets of one pitch stay >= 2 frames apart and a note has ended
+// when the next one starts.
+template <bool OFF>
+__device__ __forceinline__ WindowEvents clean_step(unsigned long long am_n, unsigned long long om_n, unsigned long long km_n, bool has_onset,
+                                                   const NoteClean& cl, int lane, CarryClean<OFF>& c) {
+    const unsigned long long below = (1ull << lane) - 1ull, above = ~((2ull << lane) - 1ull);      // bits under / over this lane
+    // bridge: this lane's inactive run is next - prev - 1 frames long, prev / next = the active frames around it
+    const unsigned long long am = c.am, ab = am & below, aa = am & above;
+    const int to_prev = ab ? lane - (63 - __clzll((long long)ab)) : lane + 1 + c.gap_before;
+    const int to_next = aa ? __ffsll((long long)aa) - 1 - lane : am_n ? 63 - lane + __ffsll((long long)am_n) : 1 << 20;
+    const unsigned long long af = am | __ballot(!(am >> lane & 1ull) && to_prev + to_next - 1 <= cl.bridge);
+    c.gap_before = am ? __clzll((long long)am) : min(64, c.gap_before + 64);
+    // decode the bridged window; without an onset head o := f'
+    const bool a = af >> lane & 1ull, o = has_onset ? (c.om >> lane & 1ull) : a;
+    WindowEvents ev;
+    if constexpr (OFF) ev = decode_window_off(o, a, c.km >> lane & 1ull, lane, c.o_prev, c.open_prev, c.k_prev, c.e_prev);
+    else ev = decode_window(o, a, lane, c.o_prev, c.open_prev);
+    c.am = am_n;
+    c.om = om_n;
+    c.km = km_n;
+    // drop: a start pairs with the first close above it (in the next window: that window's first close), a close with the last
+    // start below it (none: the note open across the boundary)
+    const unsigned long long S = c.held.starts, C = c.held.closes, ca = C & above, sb = S & below;
+    const int end = ca ? __ffsll((long long)ca) - 1 : ev.closes ? 63 + __ffsll((long long)ev.closes) : 1 << 20;
+    const unsigned long long ds = __ballot((S >> lane & 1ull) && end - lane < cl.min_frames);
+    const unsigned long long dc = __ballot((C >> lane & 1ull) && (sb ? (ds >> (63 - __clzll((long long)sb)) & 1ull) : c.dropped_open) != 0ull);
+    if (S) {
+        const int top = 63 - __clzll((long long)S);                         // the last start: open across the boundary unless closed above
+        c.dropped_open = (C & ~((2ull << top) - 1ull)) ? 0ull : (ds >> top & 1ull);
+    } else if (C) {
+        c.dropped_open = 0ull;
+    }
+    const WindowEvents out = {S & ~ds, C & ~dc};
+    c.held = ev;
+    return out;
+}
 
 // One window of a decoder.  x = the window's logits of this lane's frame, x[0] frame, x[1] onset, x[2] offset (OFF only); `in` = the
 // frame is inside the row.  Without an onset head (the frame decoder) onset := frame.
@@ -81,6 +142,19 @@ __device__ __forceinline__ WindowEvents decode_step(bool in, const float (&x)[NC
     const bool o = has_onset ? (in && logit_active(x[1], thr.onset)) : f;
     if constexpr (OFF) return decode_window_off(o, f || o, in && logit_active(x[2], thr.offset), lane, c.o_prev, c.open_prev, c.k_prev, c.e_prev);
     else return decode_window(o, f || o, lane, c.o_prev, c.open_prev);
+}
+
+// decode_step<OFF, true>: the same window through the cleanup pipeline (the cleaning kernels' step; the instances above are as they
+// were).  The events are those of the window CLEAN_DELAY frames back, and flush_clean feeds the windows that bring the last ones out.
+template <bool OFF, bool CLEAN, int NCH>
+__device__ __forceinline__ WindowEvents decode_step(bool in, const float (&x)[NCH], bool has_onset, const NoteThr& thr, int lane,
+                                                    DecodeCarry<OFF, CLEAN>& c, const NoteClean& cl) {
+    static_assert(CLEAN && NCH >= (OFF ? 3 : 2), "the cleaning step: frame, onset (and offset) logits");
+    const bool f = in && logit_active(x[0], thr.frame);
+    const bool o = has_onset ? (in && logit_active(x[1], thr.onset)) : f;
+    unsigned long long km = 0;
+    if constexpr (OFF) km = __ballot(in && logit_active(x[2], thr.offset));
+    return clean_step<OFF>(__ballot(f || o), __ballot(o), km, has_onset, cl, lane, c);
 }
 
 // The walk over a row of L frames (Index = int or long long), SLAB 64-frame windows at a time: first all of the slab's loads,
@@ -129,6 +203,17 @@ __device__ __forceinline__ void emit_window(const WindowEvents& ev, Index g0, in
 // A note still open after the row's last frame ends at L (one lane calls this, in the fill pass).
 __device__ __forceinline__ void emit_open_end(const CarryOnset& c, int* __restrict__ ends, int n_off, int L) {
     if (c.open_prev) ends[n_off] = L;
+}
+
+// The end of a cleaned row: three inactive windows after the last one that holds a frame below L, fed without a load.  The
+// first closes a note still open at a multiple of 64 (otherwise frame L of the last window has), and the third brings that
+// window's events out, so a note open at L ends at exactly L, every carry is spent and nothing is left for emit_open_end.
+template <int NCH, typename Index, typename Body>
+__device__ __forceinline__ void flush_clean(Index L, Body body) {
+    const float none[NCH] = {};
+    const Index g0 = (L + 63) / 64 * 64;
+#pragma unroll 1
+    for (int w = 0; w < 3; ++w) body(g0 + 64 * w, false, none);
 }
 
 }  // namespace mt

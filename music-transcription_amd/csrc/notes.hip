@@ -5,6 +5,7 @@
 //   mt_note_match_list:   the same counts against a per-row note list in ticks of 100 us (the MIDI notes), which may hold re-struck keys;
 //   mt_heads_to_notes:    the onset-gated decoder with mt_roll_to_notes' output contract (main.py's note list).
 //   mt_*_off:             the three of them with the offset-gated decoder (decode_window_off): the offset head ends notes.
+//   mt_*_clean:           the three of them, any decoder, with note cleanup (DESIGN.md 6c "Note cleanup"): short gaps bridged, short notes dropped.
 // One wave64 per pitch row.  The row walk, the decode step and the note emitter are note_decode.h's (walk_slabs, decode_step,
 // emit_window); a kernel here adds its addressing, where its output goes and what it does with a window's events (match_window,
 // list_window, emit).  Two kernels walk on their own: the roll matcher (its offset-gated instance is 16 % slower on the shared walk,
@@ -27,7 +28,8 @@ constexpr int NOTE_WAVES = 4;             // waves per workgroup (one pitch row 
 // order, takes the earliest unmatched compatible estimate".  Edges are discovered in chain order when their later note starts;
 // onset-only edges are decided at once, onset+offset edges once both notes have ended.  An undecided edge always involves a note
 // that is still open; at most one reference and one estimate are open at a time and each has at most two edges, so a queue of
-// four edges suffices.
+// four edges suffices.  Note cleanup (clean_step) keeps both premises: bridging a gap adds no onset and dropping removes whole notes, so
+// the estimate's onsets stay >= 2 frames apart and its notes disjoint.
 struct Edge {
     int r_on, r_off, e_on, e_off;         // off = -1 while the note is open
 };
@@ -212,6 +214,8 @@ __global__ __launch_bounds__(64 * NOTE_WAVES) void note_match_kernel(const float
 // Streaming: when estimate k+1 starts at frame g, estimate k has ended, and every reference note with on < 320 g - 500 that is still
 // unread can only touch k-1 and k (an earlier start read the notes that cannot reach k).  So the state per criterion is the component
 // that holds k-1 (V, E), the loops seen at k, and the links k-1 -- k seen; a start without links closes the component.
+// Cleaned estimates (clean_step) keep both premises: their onsets are a subset of the decoder's onsets on the bridged activity, still
+// >= 2 frames apart, and estimate k has ended when k + 1 starts; their events only arrive two windows later, the cursor following them.
 constexpr int TICKS_PER_FRAME = 320;      // 512 / 16000 s in ticks of 100 us
 constexpr int ONSET_TOL = 500;            // 50 ms
 constexpr int NO_NOTE = -4096;            // on / off of "no estimate yet": compatible with no reference note (their ticks are >= 0)
@@ -407,6 +411,124 @@ __global__ __launch_bounds__(64 * NOTE_WAVES) void heads_notes_kernel(const floa
     }
 }
 
+// ------------------------------------------------------------------------------------------------ the three kernels with note cleanup
+// note_match_kernel, note_match_list_kernel and heads_notes_kernel on decode_step<OFF, true>: all of them on the shared walk, which
+// flush_clean ends.  The step hands out the events of the window CLEAN_DELAY frames back, so g0 is delayed with them, and the roll
+// matcher holds the reference's run edges back by the same two windows.  After the flush no note is open on either side.
+template <bool OFF>
+__global__ __launch_bounds__(64 * NOTE_WAVES) void note_match_clean_kernel(const float* __restrict__ frame, const float* __restrict__ onset,
+                                                                           const float* __restrict__ offset, float thr_f, float thr_o, float thr_k,
+                                                                           NoteClean cl, const float* __restrict__ ref,
+                                                                           const long long* __restrict__ lengths,
+                                                                           unsigned long long* __restrict__ counts, int B, int P, int T) {
+    const int row = blockIdx.x * NOTE_WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int lane = threadIdx.x & 63;
+    if (row >= B * P) return;
+    const int b = row / P;
+    const int L = lengths ? (int)min((long long)T, max(0ll, lengths[b])) : T;
+    const size_t base = (size_t)row * T;
+    constexpr int NCH = OFF ? 4 : 3;                            // frame, onset, (offset,) reference roll
+    MatchState s;
+    match_init(s);
+    const NoteThr thr{thr_f, thr_o, thr_k};
+    DecodeCarry<OFF, true> c;
+    unsigned long long r_prev = 0, rs1 = 0, re1 = 0, rs2 = 0, re2 = 0;      // run edges of the reference one and two windows back
+    const auto body = [&](int g0, bool in, const float(&x)[NCH]) __attribute__((always_inline)) {
+        const WindowEvents est = decode_step<OFF, true>(in, x, onset != nullptr, thr, lane, c, cl);
+        const unsigned long long rm = __ballot(in && x[NCH - 1] > 0.0f);
+        const unsigned long long rs = rm & ~((rm << 1) | r_prev), re = ~rm & ((rm << 1) | r_prev);
+        r_prev = rm >> 63;
+        match_window(s, est, rs2, re2, g0 - CLEAN_DELAY);
+        rs2 = rs1;
+        re2 = re1;
+        rs1 = rs;
+        re1 = re;
+    };
+    walk_slabs<NOTE_SLAB, NCH>(
+        L, lane,
+        [&](int ch, int g) __attribute__((always_inline)) {
+            if (ch == NCH - 1) return ref[base + g];
+            if (ch == 1) return onset ? onset[base + g] : 0.0f;
+            return (ch == 0 ? frame : offset)[base + g];
+        },
+        body);
+    flush_clean<NCH>(L, body);
+    if (lane == 0) counts_add(counts + 4 * (size_t)b, s.n_ref, s.n_est, s.tp_on, s.tp_onoff);
+}
+
+template <bool OFF>
+__global__ __launch_bounds__(64 * NOTE_WAVES) void note_match_list_clean_kernel(const float* __restrict__ frame, const float* __restrict__ onset,
+                                                                                const float* __restrict__ offset, float thr_f, float thr_o,
+                                                                                float thr_k, NoteClean cl, const int* __restrict__ ref_on,
+                                                                                const int* __restrict__ ref_off, const long long* __restrict__ ref_ptr,
+                                                                                const long long* __restrict__ lengths,
+                                                                                unsigned long long* __restrict__ counts, int B, int P, int T) {
+    const int row = blockIdx.x * NOTE_WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int lane = threadIdx.x & 63;
+    if (row >= B * P) return;
+    const int b = row / P;
+    const int L = lengths ? (int)min((long long)T, max(0ll, lengths[b])) : T;
+    const int end_tick = TICKS_PER_FRAME * L;
+    const size_t base = (size_t)row * T;
+    constexpr int NCH = OFF ? 3 : 2;
+    RefCursor r;
+    cursor_open(r, ref_on, ref_off, ref_ptr, row, 0, lane);
+    ListState s;
+    list_init(s);
+    const NoteThr thr{thr_f, thr_o, thr_k};
+    DecodeCarry<OFF, true> c;
+    const auto body = [&](int g0, bool in, const float(&x)[NCH]) __attribute__((always_inline)) {
+        list_window(s, r, decode_step<OFF, true>(in, x, onset != nullptr, thr, lane, c, cl), g0 - CLEAN_DELAY, lane, end_tick);
+    };
+    walk_slabs<NOTE_SLAB, NCH>(
+        L, lane,
+        [&](int ch, int g) __attribute__((always_inline)) {
+            if (ch == 1) return onset ? onset[base + g] : 0.0f;
+            return (ch == 0 ? frame : offset)[base + g];
+        },
+        body);
+    flush_clean<NCH>(L, body);
+    int tp_on, tp_onoff;
+    list_finish(s, r, false, lane, end_tick, tp_on, tp_onoff);
+    if (lane == 0) counts_add(counts + 4 * (size_t)b, s.n_ref, s.n_est, tp_on, tp_onoff);
+}
+
+// onset == nullptr: the frame decoder (mt_roll_to_notes' notes, cleaned).
+template <bool OFF>
+__global__ __launch_bounds__(64 * NOTE_WAVES) void heads_notes_clean_kernel(const float* __restrict__ frame, const float* __restrict__ onset,
+                                                                            const float* __restrict__ offset, float thr_f, float thr_o, float thr_k,
+                                                                            NoteClean cl, int NB, int P, int T, int fill, int* __restrict__ counts,
+                                                                            int* __restrict__ starts, int* __restrict__ ends, int capacity) {
+    const int p = blockIdx.x * NOTE_WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int lane = threadIdx.x & 63;
+    if (p >= P) return;
+    int out = 0;
+    if (fill) {
+        for (int q = 0; q < p; ++q) out += counts[q];
+        if (counts[p] == 0 || out + counts[p] > capacity) return;
+    }
+    const int n = NB * T;
+    constexpr int NCH = OFF ? 3 : 2;
+    int n_on = 0, n_off = 0;
+    const NoteThr thr{thr_f, thr_o, thr_k};
+    DecodeCarry<OFF, true> c;
+    const auto body = [&](int g0, bool in, const float(&x)[NCH]) __attribute__((always_inline)) {
+        emit_window(decode_step<OFF, true>(in, x, onset != nullptr, thr, lane, c, cl), g0 - CLEAN_DELAY, lane, fill != 0, starts + out, ends + out,
+                    n_on, n_off);
+    };
+    walk_slabs<NOTE_SLAB, NCH>(
+        n, lane,
+        [&](int ch, int g) __attribute__((always_inline)) {
+            const int k = g / T;
+            const size_t at = ((size_t)k * P + p) * T + (g - k * T);
+            if (ch == 1) return onset ? onset[at] : 0.0f;
+            return (ch == 0 ? frame : offset)[at];
+        },
+        body);
+    flush_clean<NCH>(n, body);
+    if (lane == 0 && !fill) counts[p] = n_on;
+}
+
 // ------------------------------------------------------------------------------------------------ threshold sweep
 // The counts of note_match_kernel / note_match_list_kernel for every pair (thr_f[i], thr_o[j]) of a grid, in one pass over the logits.
 // One workgroup of SWEEP_WAVES = NOTE_SLAB waves per pitch row.  Per slab of 64 * NOTE_SLAB frames, wave w loads window w of the slab
@@ -597,44 +719,69 @@ static bool thrs_ok(const NoteThr& thr, bool onset, bool off) {
     return thr_ok(thr.frame) && (!onset || thr_ok(thr.onset)) && (!off || thr_ok(thr.offset));
 }
 
+static bool clean_ok(const NoteClean* cl) {
+    return !cl || (cl->min_frames >= 1 && cl->min_frames <= CLEAN_MAX_MIN_FRAMES && cl->bridge >= 0 && cl->bridge <= CLEAN_MAX_BRIDGE);
+}
+#define MT_REQUIRE_CLEAN(cl, who)                                                                                                      \
+    MT_REQUIRE(clean_ok(cl), MT_EINVAL, "%s: needs 1 <= min_frames <= %d and 0 <= bridge_frames <= %d", who, CLEAN_MAX_MIN_FRAMES, \
+               CLEAN_MAX_BRIDGE)
+
+// cl: the cleaning kernels (the _clean entry points, whatever the two values); null: the kernels without the stage.
 static int note_match(const char* who, bool off, const float* frame, const float* onset, const float* offset, NoteThr thr, const float* ref,
-                      const long long* lengths, unsigned long long* counts, int B, int P, int T, mt_stream_t stream) {
+                      const long long* lengths, unsigned long long* counts, int B, int P, int T, mt_stream_t stream, const NoteClean* cl = nullptr) {
     MT_REQUIRE(frame && ref && counts && (!off || (onset && offset)), MT_EINVAL, "%s: null pointer", who);
+    MT_REQUIRE_CLEAN(cl, who);
     MT_REQUIRE(B > 0 && P > 0 && T > 0 && (long long)B * P < 2147483647ll && T < (1 << 30), MT_EINVAL, "%s: bad dims", who);
     MT_REQUIRE(thrs_ok(thr, onset, off), MT_EINVAL, "%s: thresholds must lie in (0, 1)", who);
     hipStream_t st = (hipStream_t)stream;
     MT_CHECK_HIP(hipMemsetAsync(counts, 0, (size_t)B * 4 * sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(off ? note_match_kernel<true> : note_match_kernel<false>, dim3((B * P + NOTE_WAVES - 1) / NOTE_WAVES), dim3(64 * NOTE_WAVES),
-                       0, st, frame, onset, offset, thr.frame, thr.onset, thr.offset, ref, lengths, counts, B, P, T);
+    const dim3 grid((B * P + NOTE_WAVES - 1) / NOTE_WAVES), block(64 * NOTE_WAVES);
+    if (cl)
+        hipLaunchKernelGGL(off ? note_match_clean_kernel<true> : note_match_clean_kernel<false>, grid, block, 0, st, frame, onset, offset, thr.frame,
+                           thr.onset, thr.offset, *cl, ref, lengths, counts, B, P, T);
+    else
+        hipLaunchKernelGGL(off ? note_match_kernel<true> : note_match_kernel<false>, grid, block, 0, st, frame, onset, offset, thr.frame, thr.onset,
+                           thr.offset, ref, lengths, counts, B, P, T);
     MT_CHECK_LAUNCH();
     return MT_OK;
 }
 
 static int note_match_list(const char* who, bool off, const float* frame, const float* onset, const float* offset, NoteThr thr, const int* ref_on,
                            const int* ref_off, const long long* ref_ptr, const long long* lengths, unsigned long long* counts, int B, int P, int T,
-                           mt_stream_t stream) {
+                           mt_stream_t stream, const NoteClean* cl = nullptr) {
     MT_REQUIRE(frame && ref_on && ref_off && ref_ptr && counts && (!off || (onset && offset)), MT_EINVAL, "%s: null pointer", who);
+    MT_REQUIRE_CLEAN(cl, who);
     MT_REQUIRE(B > 0 && P > 0 && T > 0 && (long long)B * P < 2147483647ll && (long long)T * TICKS_PER_FRAME < 2147483647ll - 64 * NOTE_SLAB,
                MT_EINVAL, "%s: bad dims (frame times must fit 31 bits of 100 us ticks)", who);
     MT_REQUIRE(thrs_ok(thr, onset, off), MT_EINVAL, "%s: thresholds must lie in (0, 1)", who);
     hipStream_t st = (hipStream_t)stream;
     MT_CHECK_HIP(hipMemsetAsync(counts, 0, (size_t)B * 4 * sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(off ? note_match_list_kernel<true> : note_match_list_kernel<false>, dim3((B * P + NOTE_WAVES - 1) / NOTE_WAVES),
-                       dim3(64 * NOTE_WAVES), 0, st, frame, onset, offset, thr.frame, thr.onset, thr.offset, ref_on, ref_off, ref_ptr, lengths,
-                       counts, B, P, T);
+    const dim3 grid((B * P + NOTE_WAVES - 1) / NOTE_WAVES), block(64 * NOTE_WAVES);
+    if (cl)
+        hipLaunchKernelGGL(off ? note_match_list_clean_kernel<true> : note_match_list_clean_kernel<false>, grid, block, 0, st, frame, onset, offset,
+                           thr.frame, thr.onset, thr.offset, *cl, ref_on, ref_off, ref_ptr, lengths, counts, B, P, T);
+    else
+        hipLaunchKernelGGL(off ? note_match_list_kernel<true> : note_match_list_kernel<false>, grid, block, 0, st, frame, onset, offset, thr.frame,
+                           thr.onset, thr.offset, ref_on, ref_off, ref_ptr, lengths, counts, B, P, T);
     MT_CHECK_LAUNCH();
     return MT_OK;
 }
 
 static int heads_notes(const char* who, bool off, const float* frame, const float* onset, const float* offset, NoteThr thr, int NB, int P, int T,
-                       int* counts, int* starts, int* ends, int capacity, mt_stream_t stream) {
-    MT_REQUIRE(frame && onset && (!off || offset) && counts && starts && ends && capacity > 0, MT_EINVAL, "%s: bad arguments", who);
+                       int* counts, int* starts, int* ends, int capacity, mt_stream_t stream, const NoteClean* cl = nullptr) {
+    // (the cleaning kernel alone decodes without an onset head: the frame decoder)
+    MT_REQUIRE(frame && (onset || (cl && !off)) && (!off || offset) && counts && starts && ends && capacity > 0, MT_EINVAL, "%s: bad arguments", who);
     MT_REQUIRE(NB > 0 && P > 0 && T > 0 && (long long)NB * T < 2147483647ll - 64 * NOTE_SLAB, MT_EINVAL, "%s: bad dims", who);
-    MT_REQUIRE(thrs_ok(thr, true, off), MT_EINVAL, "%s: thresholds must lie in (0, 1)", who);
+    MT_REQUIRE(thrs_ok(thr, onset != nullptr, off), MT_EINVAL, "%s: thresholds must lie in (0, 1)", who);
+    MT_REQUIRE_CLEAN(cl, who);
+    const dim3 grid((P + NOTE_WAVES - 1) / NOTE_WAVES), block(64 * NOTE_WAVES);
     for (int fill = 0; fill < 2; ++fill) {                     // count, then write
-        hipLaunchKernelGGL(off ? heads_notes_kernel<true> : heads_notes_kernel<false>, dim3((P + NOTE_WAVES - 1) / NOTE_WAVES), dim3(64 * NOTE_WAVES),
-                           0, (hipStream_t)stream, frame, onset, offset, thr.frame, thr.onset, thr.offset, NB, P, T, fill, counts, starts, ends,
-                           capacity);
+        if (cl)
+            hipLaunchKernelGGL(off ? heads_notes_clean_kernel<true> : heads_notes_clean_kernel<false>, grid, block, 0, (hipStream_t)stream, frame,
+                               onset, offset, thr.frame, thr.onset, thr.offset, *cl, NB, P, T, fill, counts, starts, ends, capacity);
+        else
+            hipLaunchKernelGGL(off ? heads_notes_kernel<true> : heads_notes_kernel<false>, grid, block, 0, (hipStream_t)stream, frame, onset, offset,
+                               thr.frame, thr.onset, thr.offset, NB, P, T, fill, counts, starts, ends, capacity);
         MT_CHECK_LAUNCH();
     }
     return MT_OK;
@@ -723,4 +870,31 @@ extern "C" int mt_heads_to_notes_off(const float* frame_logits, const float* ons
                                      mt_stream_t stream) {
     return heads_notes("mt_heads_to_notes_off", true, frame_logits, onset_logits, offset_logits, {thr_frame, thr_onset, thr_offset}, NB, P, T, counts,
                        starts, ends, capacity, stream);
+}
+
+// The three with note cleanup (min_frames, bridge_frames), served by the cleaning kernels whatever the two values.  offset_logits
+// null: the onset-gated decoder, or without onset_logits the frame decoder; offset_logits without onset_logits is refused.
+extern "C" int mt_note_match_counts_clean(const float* frame_logits, const float* onset_logits, const float* offset_logits, float thr_frame,
+                                          float thr_onset, float thr_offset, const float* ref_roll, const long long* lengths,
+                                          unsigned long long* counts, int B, int P, int T, int min_frames, int bridge_frames, mt_stream_t stream) {
+    const NoteClean cl{min_frames, bridge_frames};
+    return note_match("mt_note_match_counts_clean", offset_logits != nullptr, frame_logits, onset_logits, offset_logits,
+                      {thr_frame, thr_onset, offset_logits ? thr_offset : 0.5f}, ref_roll, lengths, counts, B, P, T, stream, &cl);
+}
+
+extern "C" int mt_note_match_list_clean(const float* frame_logits, const float* onset_logits, const float* offset_logits, float thr_frame,
+                                        float thr_onset, float thr_offset, const int* ref_on, const int* ref_off, const long long* ref_ptr,
+                                        const long long* lengths, unsigned long long* counts, int B, int P, int T, int min_frames,
+                                        int bridge_frames, mt_stream_t stream) {
+    const NoteClean cl{min_frames, bridge_frames};
+    return note_match_list("mt_note_match_list_clean", offset_logits != nullptr, frame_logits, onset_logits, offset_logits,
+                           {thr_frame, thr_onset, offset_logits ? thr_offset : 0.5f}, ref_on, ref_off, ref_ptr, lengths, counts, B, P, T, stream, &cl);
+}
+
+extern "C" int mt_heads_to_notes_clean(const float* frame_logits, const float* onset_logits, const float* offset_logits, float thr_frame,
+                                       float thr_onset, float thr_offset, int NB, int P, int T, int* counts, int* starts, int* ends, int capacity,
+                                       int min_frames, int bridge_frames, mt_stream_t stream) {
+    const NoteClean cl{min_frames, bridge_frames};
+    return heads_notes("mt_heads_to_notes_clean", offset_logits != nullptr, frame_logits, onset_logits, offset_logits,
+                       {thr_frame, thr_onset, offset_logits ? thr_offset : 0.5f}, NB, P, T, counts, starts, ends, capacity, stream, &cl);
 }

@@ -129,15 +129,17 @@ NOTE_METRIC_KEYS = tuple(f"{c}_{m}" for c in ("onset", "onset_offset") for m in 
 def note_metrics_dataset(model, dataset, threshold: float = 0.5, onset_threshold: Optional[float] = None, device="cuda",
                          subset: Optional[int] = None, max_batch: int = 128, rank: int = 0, world: int = 1,
                          window_overlap: Optional[float] = None, note_reference: str = "roll",
-                         offset_threshold: Optional[float] = None) -> dict:
+                         offset_threshold: Optional[float] = None, min_note_frames: int = 1, bridge_frames: int = 0) -> dict:
     """Note-level metrics of every sample, identical on every rank: {"mean": {key: value}, "per_sample": {key: [values]}} over
     NOTE_METRIC_KEYS (onset / onset_offset x precision / recall / f1).  onset_threshold=None: notes are the runs of
     sigmoid(frame) > threshold (the frame decoder); otherwise the onset-gated decoder with the onset head at onset_threshold.
     offset_threshold (needs onset_threshold): the offset-gated decoder, which also ends notes where the offset head fires.
     Reference notes: note_reference="roll", the runs of the dataset's label roll; "midi", the MIDI note list of each recording
     (dataset.ref_notes: a whole-file MaestroDataset built with onset_labels="midi").  Unweighted means over samples, as
-    evaluate_dataset (window_overlap too)."""
-    from .notes import note_match_counts, note_match_list, note_prf
+    evaluate_dataset (window_overlap too).  min_note_frames / bridge_frames: the estimates are cleaned in the decoder (DESIGN.md 6c "Note cleanup"),
+    whichever of the three it is; the result then names the two ("min_note_frames", "bridge_frames")."""
+    from .notes import check_cleanup, note_match_counts, note_match_list, note_prf
+    clean = check_cleanup(min_note_frames, bridge_frames)
     _check_note_reference(dataset, note_reference)
     onset, offset = onset_threshold is not None, offset_threshold is not None
     if offset and not onset:
@@ -149,13 +151,16 @@ def note_metrics_dataset(model, dataset, threshold: float = 0.5, onset_threshold
     match = note_match_list if note_reference == "midi" else note_match_counts
     for frame, on, ref, lengths, off in _note_groups(lr, dataset, onset, note_reference, max_batch, offset):
         counts = match(frame, ref, threshold, on, onset_threshold if onset else 0.5, lengths, offset_logits=off,
-                       offset_threshold=offset_threshold if offset else 0.5)
+                       offset_threshold=offset_threshold if offset else 0.5, min_note_frames=clean[0], bridge_frames=clean[1])
         for m in note_prf(counts):
             for c in ("onset", "onset_offset"):
                 for k, v in zip(("precision", "recall", "f1"), m[c]):
                     vals[f"{c}_{k}"].append(v)
     per = {k: gather_values(mine, v, n) for k, v in vals.items()}
-    return {"mean": {k: (float(np.mean(v)) if v else 0.0) for k, v in per.items()}, "per_sample": per}
+    out = {"mean": {k: (float(np.mean(v)) if v else 0.0) for k, v in per.items()}, "per_sample": per}
+    if clean != (1, 0):
+        out["min_note_frames"], out["bridge_frames"] = clean
+    return out
 
 
 def _check_note_reference(dataset, note_reference: str) -> None:
@@ -247,13 +252,18 @@ def search_note_thresholds(mean_f1, two_axes: bool = True, tune_range=(0.05, 0.9
 
 def tune_note_thresholds(model, dataset, device="cuda", subset: Optional[int] = None, decoder: str = "onset", note_reference: str = "roll",
                          objective: str = "onset", tune_range=(0.05, 0.95), tune_step=0.1, tune_min_step=0.01, tune_rounds=6,
-                         rank: int = 0, world: int = 1, log=print, window_overlap: Optional[float] = None, max_batch: int = 128):
+                         rank: int = 0, world: int = 1, log=print, window_overlap: Optional[float] = None, max_batch: int = 128,
+                         min_note_frames: int = 1, bridge_frames: int = 0):
     """The thresholds of the note decoder that maximise the mean note F1 (`objective`: "onset" or "onset_offset"; unweighted mean
     over samples, as note_metrics_dataset) by search_note_thresholds: decoder="onset" searches (frame, onset) pairs, "frame" the
     frame threshold alone.  The model runs once; every round is one sweep pass over each group of note_metrics_dataset.
     -> (frame threshold, onset threshold or None, best mean F1), identical on every rank.  A candidate at or past 1 (the schedule's
-    last grid point can be) decodes no note and scores 0, as it does for tune_threshold."""
-    from .notes import note_prf, note_sweep_counts
+    last grid point can be) decodes no note and scores 0, as it does for tune_threshold.  The sweep kernels do not clean notes:
+    anything but (min_note_frames, bridge_frames) = (1, 0) is refused."""
+    from .notes import check_cleanup, note_prf, note_sweep_counts
+    if check_cleanup(min_note_frames, bridge_frames) != (1, 0):
+        raise ValueError("tune_note_thresholds: the threshold sweeps do not clean notes (min_note_frames / bridge_frames): tune "
+                         "without cleanup, then evaluate with it (note_metrics_dataset(..., min_note_frames=, bridge_frames=))")
     if decoder == "onset_offset":
         raise ValueError("tune_note_thresholds does not cover decoder='onset_offset': the threshold sweeps are not extended to the "
                          "offset head (tune with decoder='onset', then pass offset_threshold to note_metrics_dataset)")

@@ -14,6 +14,9 @@
     the offset head fires (mt_note_match_counts_off / mt_note_match_list_off / mt_heads_to_notes_off).
   * `notes_batch_device` = either decoder over a padded batch of whole recordings with `lengths` (mt_notes_batch): the notes of all
     recordings in two device-to-host copies.
+  * `min_note_frames=`, `bridge_frames=` on the two matchers and the two note-list calls = note cleanup inside the decoder
+    (DESIGN.md 6c "Note cleanup"; the mt_*_clean kernels): gaps of the activity of at most bridge_frames are bridged before decoding, notes
+    shorter than min_note_frames dropped after it.  (1, 0) is no cleanup and calls exactly the entry points above.
 """
 from __future__ import annotations
 
@@ -70,6 +73,42 @@ def _heads(frame_logits, onset_logits, offset_logits, threshold, onset_threshold
     return x, on, off, thr, othr, _check_threshold(offset_threshold, "offset_threshold"), ref
 
 
+MAX_MIN_NOTE_FRAMES, MAX_BRIDGE_FRAMES = 64, 63     # CLEAN_MAX_* of csrc/note_decode.h: both stages look one 64-frame window ahead
+FRAME_MS = 1000.0 * HOP / SR                        # 32 ms
+
+
+def check_cleanup(min_note_frames=1, bridge_frames=0) -> Tuple[int, int]:
+    """The checked (min_note_frames, bridge_frames) of a decoder call; (1, 0) = no cleanup.  Raises before any GPU work."""
+    m, g = min_note_frames, bridge_frames
+    for v, name in ((m, "min_note_frames"), (g, "bridge_frames")):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{name} must be an integer number of frames, got {v!r}")
+    if not 1 <= m <= MAX_MIN_NOTE_FRAMES:
+        raise ValueError(f"min_note_frames must lie in [1, {MAX_MIN_NOTE_FRAMES}], got {m}")
+    if not 0 <= g <= MAX_BRIDGE_FRAMES:
+        raise ValueError(f"bridge_frames must lie in [0, {MAX_BRIDGE_FRAMES}], got {g}")
+    return int(m), int(g)
+
+
+def cleanup_frames(min_note_ms: float = 0.0, bridge_gap_ms: float = 0.0) -> Tuple[int, int]:
+    """Milliseconds -> (min_note_frames, bridge_frames) on the 32 ms grid, exactly: a note is dropped iff it is shorter than
+    min_note_ms (M = max(1, ceil(ms / 32))) and a gap bridged iff it is no longer than bridge_gap_ms (G = floor(ms / 32))."""
+    from fractions import Fraction
+    out = []
+    for ms, name in ((min_note_ms, "min_note_ms"), (bridge_gap_ms, "bridge_gap_ms")):
+        if isinstance(ms, bool) or not isinstance(ms, (int, float, np.integer, np.floating)) or not np.isfinite(ms) or ms < 0:
+            raise ValueError(f"{name} must be a finite number of milliseconds >= 0, got {ms!r}")
+        out.append(Fraction(ms) / Fraction(FRAME_MS))                       # (exact: a float is a fraction)
+    m, g = max(1, int(np.ceil(out[0]))), int(np.floor(out[1]))
+    if m > MAX_MIN_NOTE_FRAMES:
+        raise ValueError(f"min_note_ms must be at most {MAX_MIN_NOTE_FRAMES * FRAME_MS:g} ms ({MAX_MIN_NOTE_FRAMES} frames of "
+                         f"{FRAME_MS:g} ms), got {min_note_ms}")
+    if g > MAX_BRIDGE_FRAMES:
+        raise ValueError(f"bridge_gap_ms must be below {(MAX_BRIDGE_FRAMES + 1) * FRAME_MS:g} ms (at most {MAX_BRIDGE_FRAMES} frames of "
+                         f"{FRAME_MS:g} ms), got {bridge_gap_ms}")
+    return m, g
+
+
 def _lengths(lengths, B: int, dev) -> Optional[torch.Tensor]:
     if lengths is None:
         return None
@@ -98,10 +137,12 @@ def _note_tables(ref_notes: Dict[str, torch.Tensor], B: int, P: int, dev):
 
 def note_match_counts(frame_logits: torch.Tensor, ref_roll: torch.Tensor, threshold: float = 0.5, onset_logits: Optional[torch.Tensor] = None,
                       onset_threshold: float = 0.5, lengths=None, offset_logits: Optional[torch.Tensor] = None,
-                      offset_threshold: float = 0.5) -> torch.Tensor:
+                      offset_threshold: float = 0.5, min_note_frames: int = 1, bridge_frames: int = 0) -> torch.Tensor:
     """(B, P, T) frame logits (and onset logits for the onset-gated decoder) and (B, P, T) reference roll on the device -> (B, 4)
     int64 device tensor {n_ref, n_est, tp_onset, tp_onset_offset}.  lengths (B,) = valid frames per sample (None: all T).  With
-    offset_logits (and onset_logits) the estimates come from the offset-gated decoder (mt_note_match_counts_off)."""
+    offset_logits (and onset_logits) the estimates come from the offset-gated decoder (mt_note_match_counts_off).  With
+    (min_note_frames, bridge_frames) other than (1, 0) the estimates are cleaned in the decoder (mt_note_match_counts_clean)."""
+    clean = check_cleanup(min_note_frames, bridge_frames)
     x, on, off, thr, othr, kthr, ref = _heads(frame_logits, onset_logits, offset_logits, threshold, onset_threshold, offset_threshold,
                                               ref_roll=ref_roll, mismatch="shape mismatch: frame {frame}, ref {ref}, onset {onset}")
     B, P, T = x.shape
@@ -110,7 +151,10 @@ def note_match_counts(frame_logits: torch.Tensor, ref_roll: torch.Tensor, thresh
     counts = torch.empty(B, 4, dtype=torch.int64, device=dev)
     rest = (ptr(ref), ptr(ln), ptr(counts), B, P, T, _lib.stream_ptr())
     with torch.cuda.device(dev):
-        if off is None:
+        if clean != (1, 0):
+            check(lib.mt_note_match_counts_clean(ptr(x), ptr(on), ptr(off), thr, othr, kthr, *rest[:-1], *clean, rest[-1]),
+                  "mt_note_match_counts_clean")
+        elif off is None:
             check(lib.mt_note_match_counts(ptr(x), ptr(on), thr, othr, *rest), "mt_note_match_counts")
         else:
             check(lib.mt_note_match_counts_off(ptr(x), ptr(on), ptr(off), thr, othr, kthr, *rest), "mt_note_match_counts_off")
@@ -122,12 +166,15 @@ TICKS_PER_FRAME = 320              # one frame in ticks of 100 us
 
 def note_match_list(frame_logits: torch.Tensor, ref_notes: Dict[str, torch.Tensor], threshold: float = 0.5,
                     onset_logits: Optional[torch.Tensor] = None, onset_threshold: float = 0.5, lengths=None,
-                    offset_logits: Optional[torch.Tensor] = None, offset_threshold: float = 0.5) -> torch.Tensor:
+                    offset_logits: Optional[torch.Tensor] = None, offset_threshold: float = 0.5, min_note_frames: int = 1,
+                    bridge_frames: int = 0) -> torch.Tensor:
     """note_match_counts against a note list: ref_notes = {"on", "off"} int32 ticks of 100 us and "ptr" int64 (B * P + 1,) on the
     device, row (b, p) owning on/off[ptr[b*P + p]:ptr[b*P + p + 1]] sorted by onset (MaestroDataset.ref_notes).  An estimated
     note [s, e) in frames has times 320 s, 320 e; onsets match within 500 ticks, offsets within max(500, 0.2 reference length).
     Notes that start at or past a sample's valid frames are not counted.  -> (B, 4) int64 {n_ref, n_est, tp_onset, tp_onset_offset}.
-    With offset_logits (and onset_logits) the estimates come from the offset-gated decoder (mt_note_match_list_off)."""
+    With offset_logits (and onset_logits) the estimates come from the offset-gated decoder (mt_note_match_list_off); with
+    (min_note_frames, bridge_frames) other than (1, 0) they are cleaned in the decoder (mt_note_match_list_clean)."""
+    clean = check_cleanup(min_note_frames, bridge_frames)
     x, on, off, thr, othr, kthr, _ = _heads(frame_logits, onset_logits, offset_logits, threshold, onset_threshold, offset_threshold)
     B, P, T = x.shape
     dev = x.device
@@ -136,7 +183,10 @@ def note_match_list(frame_logits: torch.Tensor, ref_notes: Dict[str, torch.Tenso
     counts = torch.empty(B, 4, dtype=torch.int64, device=dev)
     rest = (ptr(r_on), ptr(r_off), ptr(r_ptr), ptr(ln), ptr(counts), B, P, T, _lib.stream_ptr())
     with torch.cuda.device(dev):
-        if off is None:
+        if clean != (1, 0):
+            check(lib.mt_note_match_list_clean(ptr(x), ptr(on), ptr(off), thr, othr, kthr, *rest[:-1], *clean, rest[-1]),
+                  "mt_note_match_list_clean")
+        elif off is None:
             check(lib.mt_note_match_list(ptr(x), ptr(on), thr, othr, *rest), "mt_note_match_list")
         else:
             check(lib.mt_note_match_list_off(ptr(x), ptr(on), ptr(off), thr, othr, kthr, *rest), "mt_note_match_list_off")
@@ -221,14 +271,17 @@ def note_prf(counts) -> List[Dict[str, Tuple[float, float, float]]]:
             for n_ref, n_est, tp_on, tp_onoff in c]
 
 
-def heads_to_notes_device(frame_logits: torch.Tensor, onset_logits: torch.Tensor, threshold: float = 0.5, onset_threshold: float = 0.5,
-                          fs: float = FS, min_midi: int = 21, offset_logits: Optional[torch.Tensor] = None,
-                          offset_threshold: float = 0.5) -> List[Tuple[int, float, float]]:
+def heads_to_notes_device(frame_logits: torch.Tensor, onset_logits: Optional[torch.Tensor], threshold: float = 0.5,
+                          onset_threshold: float = 0.5, fs: float = FS, min_midi: int = 21, offset_logits: Optional[torch.Tensor] = None,
+                          offset_threshold: float = 0.5, min_note_frames: int = 1, bridge_frames: int = 0) -> List[Tuple[int, float, float]]:
     """(n_chunks, 88, T) frame and onset logits ON THE DEVICE -> notes of the onset-gated decoder over the chunks concatenated in
     time, in the reference's note order (pitch-major, then time); only counts and two ints per note reach the host.  With
-    offset_logits: the notes of the offset-gated decoder (mt_heads_to_notes_off), which end where the offset head fires."""
+    offset_logits: the notes of the offset-gated decoder (mt_heads_to_notes_off), which end where the offset head fires.  With
+    (min_note_frames, bridge_frames) other than (1, 0): the cleaned notes (mt_heads_to_notes_clean), and then onset_logits may be
+    None: the frame decoder's notes, cleaned."""
+    clean = check_cleanup(min_note_frames, bridge_frames)
     x, on, off, thr, othr, kthr, _ = _heads(frame_logits, onset_logits, offset_logits, threshold, onset_threshold, offset_threshold,
-                                            onset_required=True, mismatch="frame {frame} and onset {onset} logits differ in shape")
+                                            onset_required=clean == (1, 0), mismatch="frame {frame} and onset {onset} logits differ in shape")
     NB, P, T = x.shape
     dev = x.device
     counts = torch.empty(P, dtype=torch.int32, device=dev)
@@ -237,7 +290,10 @@ def heads_to_notes_device(frame_logits: torch.Tensor, onset_logits: torch.Tensor
         starts, ends = torch.empty(cap, dtype=torch.int32, device=dev), torch.empty(cap, dtype=torch.int32, device=dev)
         rest = (NB, P, T, ptr(counts), ptr(starts), ptr(ends), cap, _lib.stream_ptr())
         with torch.cuda.device(dev):
-            if off is None:
+            if clean != (1, 0):
+                check(lib.mt_heads_to_notes_clean(ptr(x), ptr(on), ptr(off), thr, othr, kthr, *rest[:-1], *clean, rest[-1]),
+                      "mt_heads_to_notes_clean")
+            elif off is None:
                 check(lib.mt_heads_to_notes(ptr(x), ptr(on), thr, othr, *rest), "mt_heads_to_notes")
             else:
                 check(lib.mt_heads_to_notes_off(ptr(x), ptr(on), ptr(off), thr, othr, kthr, *rest), "mt_heads_to_notes_off")
@@ -252,11 +308,14 @@ def heads_to_notes_device(frame_logits: torch.Tensor, onset_logits: torch.Tensor
 
 
 def notes_batch_device(frame_logits: torch.Tensor, onset_logits: Optional[torch.Tensor] = None, threshold: float = 0.5,
-                       onset_threshold: float = 0.5, lengths=None, fs: float = FS, min_midi: int = 21) -> List[List[Tuple[int, float, float]]]:
+                       onset_threshold: float = 0.5, lengths=None, fs: float = FS, min_midi: int = 21, min_note_frames: int = 1,
+                       bridge_frames: int = 0) -> List[List[Tuple[int, float, float]]]:
     """(B, P, T) frame logits of B whole recordings ON THE DEVICE, padded to T, with lengths (B,) valid frames each (None: all T) ->
     one note list per recording: what transcribe.notes_from_logits_device (onset_logits None) or heads_to_notes_device returns on
     that recording's rows trimmed to its length.  The padding is never read.  One launch of mt_notes_batch, one device-to-host copy
-    of the counts and offsets and one of the notes; a second launch only when the first capacity guess was short."""
+    of the counts and offsets and one of the notes; a second launch only when the first capacity guess was short.  With
+    (min_note_frames, bridge_frames) other than (1, 0) the notes are cleaned in the decoder (mt_notes_batch_clean)."""
+    clean = check_cleanup(min_note_frames, bridge_frames)
     x, on, _, thr, othr, _, _ = _heads(frame_logits, onset_logits, None, threshold, onset_threshold, 0.5,
                                        mismatch="frame {frame} and onset {onset} logits differ in shape")
     B, P, T = x.shape
@@ -269,8 +328,11 @@ def notes_batch_device(frame_logits: torch.Tensor, onset_logits: Optional[torch.
     while True:
         se = torch.empty(2, cap, dtype=torch.int32, device=dev)
         with torch.cuda.device(dev):
-            check(lib.mt_notes_batch(ptr(x), ptr(on), thr, othr, ptr(ln), B, P, T, ptr(counts), ptr(row_off), ptr(se[0]), ptr(se[1]), cap,
-                                     _lib.stream_ptr()), "mt_notes_batch")
+            args = (ptr(x), ptr(on), thr, othr, ptr(ln), B, P, T, ptr(counts), ptr(row_off), ptr(se[0]), ptr(se[1]), cap)
+            if clean != (1, 0):
+                check(lib.mt_notes_batch_clean(*args, *clean, _lib.stream_ptr()), "mt_notes_batch_clean")
+            else:
+                check(lib.mt_notes_batch(*args, _lib.stream_ptr()), "mt_notes_batch")
         host = meta.cpu().numpy()
         off, c = host[:rows + 1], host[rows + 1:].view(np.int32)[:rows]
         total = int(off[rows])

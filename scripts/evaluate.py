@@ -65,6 +65,12 @@ def main():
     ap.add_argument("--onset_threshold", type=float, default=0.5,
                     help="threshold of the onset head for --decoder onset / onset_offset (default: 0.5)")
     ap.add_argument("--offset_threshold", type=float, default=0.5, help="threshold of the offset head for --decoder onset_offset (default: 0.5)")
+    ap.add_argument("--min_note_ms", type=float, default=0.0,
+                    help="with --note_metrics: note cleanup in the decoder, drop every estimated note shorter than this many milliseconds "
+                         "(32 ms frames; at most 2048; default 0 = keep all).  Not with --tune_note_thresholds: the sweeps do not clean")
+    ap.add_argument("--bridge_gap_ms", type=float, default=0.0,
+                    help="with --note_metrics: note cleanup in the decoder, a dropout of the activity no longer than this many "
+                         "milliseconds does not end the note (below 2048; default 0 = none)")
     ap.add_argument("--window_overlap", type=float, default=None,
                     help="full files only: run every recording in overlapping 30 s windows (this many seconds of overlap, 0.256 to 15) "
                          "stitched on its own frame grid, instead of one recurrence over the whole file; lifts the T * hidden_size < 2^24 "
@@ -86,6 +92,18 @@ def main():
     if args.tune_note_thresholds and args.decoder == "onset_offset":
         ap.error("--tune_note_thresholds does not cover --decoder onset_offset (the threshold sweeps do not read the offset head): tune with "
                  "--decoder onset and pass the thresholds it reports")
+    min_note_frames, bridge_frames = 1, 0
+    if args.min_note_ms or args.bridge_gap_ms:
+        if not args.note_metrics:
+            ap.error("--min_note_ms / --bridge_gap_ms clean the notes of --note_metrics and need that flag")
+        if args.tune_note_thresholds:
+            ap.error("--min_note_ms / --bridge_gap_ms cannot be combined with --tune_note_thresholds: the threshold sweeps do not clean "
+                     "notes; tune without cleanup, then evaluate with it at the thresholds reported")
+        try:
+            from music_transcription_amd.notes import cleanup_frames
+            min_note_frames, bridge_frames = cleanup_frames(args.min_note_ms, args.bridge_gap_ms)
+        except ValueError as e:
+            ap.error(str(e))
     say = (lambda *a, **k: None) if args.headless else print
 
     if args.note_reference == "midi" and args.data_source != "full":
@@ -186,7 +204,8 @@ def main():
     if args.note_metrics:
         notes = E.note_metrics_dataset(model, ds, note_threshold, note_onset_threshold, dev,
                                        subset=args.subset, rank=rank, world=world, window_overlap=args.window_overlap,
-                                       note_reference=args.note_reference, offset_threshold=note_offset_threshold)
+                                       note_reference=args.note_reference, offset_threshold=note_offset_threshold,
+                                       min_note_frames=min_note_frames, bridge_frames=bridge_frames)
     if rank == 0:
         if args.headless:
             print(f"EVAL_MEAN_F1={mean_f1:.6f}")

@@ -13,6 +13,7 @@ recording durations to the requested total, synthesises noise + decaying tones o
 rolls: that exercises the whole path and gives throughput, the F1 is then meaningless.
 --overlap SECONDS runs whole recordings in overlapping 30 s windows on one frame grid (corpus.transcribe_shard_windows) instead
 of concatenating chunks: notes, .mid files and scores are then on the recording's own grid of 1 + n // 512 frames.
+--min-note-ms / --bridge-gap-ms clean the notes inside the decoder (short gaps bridged, then short notes dropped), as main.py does.
 """
 import argparse
 import json
@@ -40,6 +41,12 @@ def main():
                     help="frame: notes are runs of active frames (default); onset: onset-gated decoder on the onset head (cnn_rnn_large "
                          "trained with --train_all_heads)")
     ap.add_argument("--onset-threshold", type=float, default=0.5, help="threshold of the onset head for --decoder onset")
+    ap.add_argument("--min-note-ms", type=float, default=0.0,
+                    help="note cleanup in the decoder: drop every note shorter than this many milliseconds (32 ms frames; at most 2048; "
+                         "default 0 = keep all); --note-metrics scores the cleaned notes")
+    ap.add_argument("--bridge-gap-ms", type=float, default=0.0,
+                    help="note cleanup in the decoder: a dropout of the activity no longer than this many milliseconds does not end the "
+                         "note (below 2048; default 0 = none)")
     ap.add_argument("--note-metrics", action="store_true",
                     help="also score notes against the runs of the reference roll (onset / onset+offset F1, mir_eval's criteria on the "
                          "32 ms grid): adds mean_note_onset_f1 / mean_note_onset_offset_f1 to the JSON line")
@@ -53,6 +60,11 @@ def main():
     ap.add_argument("--out-dir", help="directory: write <name>.mid per recording (notes extracted on the device)")
     ap.add_argument("--dump-rolls", help="directory: write <name>.roll.bits.npy (np.packbits of the (88, T_total) roll) per recording")
     args = ap.parse_args()
+    try:                                    # refused before a device is opened
+        from music_transcription_amd.notes import cleanup_frames
+        clean = dict(zip(("min_note_frames", "bridge_frames"), cleanup_frames(args.min_note_ms, args.bridge_gap_ms)))
+    except ValueError as e:
+        ap.error(str(e))
 
     import numpy as np
     import torch
@@ -131,11 +143,11 @@ def main():
         res = corpus.transcribe_shard_windows(model, mine, audio_of, overlap_s=args.overlap, n_mels=args.n_mels, device=dev, batch=args.batch,
                                               streams=NS, threshold=args.threshold, want_notes=True, reference_roll_of=reference_roll_of,
                                               midi_path_of=midi_path_of, decoder=args.decoder, onset_threshold=args.onset_threshold,
-                                              note_metrics=args.note_metrics)
+                                              note_metrics=args.note_metrics, **clean)
     else:
         res = corpus.transcribe_shard(model, mine, chunks_of, n_mels=args.n_mels, device=dev, batch=args.batch, streams=NS,
                                       threshold=args.threshold, want_notes=True, reference_roll_of=reference_roll_of, midi_path_of=midi_path_of,
-                                      decoder=args.decoder, onset_threshold=args.onset_threshold, note_metrics=args.note_metrics)
+                                      decoder=args.decoder, onset_threshold=args.onset_threshold, note_metrics=args.note_metrics, **clean)
     if args.dump_rolls:                     # (debug / tests: the rolls are rebuilt from the notes -- they never left the GPU as rolls)
         os.makedirs(args.dump_rolls, exist_ok=True)
         fs = SR / 512

@@ -1,5 +1,5 @@
 """Device time of mt_note_match_counts and mt_note_match_list (DESIGN.md "Note-level F1"), frame, onset-gated and offset-gated decoders,
-of mt_heads_to_notes beside mt_heads_to_notes_off (chunks) and of mt_notes_batch (recordings), on two shapes:
+of mt_heads_to_notes beside mt_heads_to_notes_off (chunks) and of mt_notes_batch (recordings), and of the four cleaning kernels, on two shapes:
 
   * chunks:     a batch of 128 chunks x 88 pitches x 938 frames (one forward's worth of 30 s chunks);
   * recordings: a padded batch of 8 whole recordings of 10-25 minutes (T up to ~47 000 frames), masked by `lengths`.
@@ -11,6 +11,8 @@ its note list being the runs of the same roll (so its counts must equal the roll
 the roll, and `list_over_roll` is its time over mt_note_match_counts'.  The offset-gated decoder ("onset_offset", the mt_*_off entry
 points) reads one array more, offset logits that mark the last active frame of every run; `over_onset` is its time over the
 onset-gated entry point's in the same run (expected about 4/3 for the roll matcher, 3/2 for the list matcher and the note lists).
+The four cleaning kernels (mt_*_clean, DESIGN.md 6c "Note cleanup") run last, onset-gated at (min_note_frames, bridge_frames) = CLEAN: "*_clean" beside
+its counterpart of the same run, `over_plain` = its time over the counterpart's; they read the same bytes.
 
     python tools/note_metrics_bench.py [--iters 50] [--out note_metrics.json]
 """
@@ -135,6 +137,49 @@ def time_notes_batch(out, frame, onset, lengths, iters):
             raise SystemExit(f"{out['case']} ({key}): mt_notes_batch finds another number of notes than the matcher: {out}")
 
 
+CLEAN = (2, 1)                     # drop one-frame notes, bridge one-frame gaps
+
+
+def time_clean(out, frame, onset, ref, notes, lengths, iters):
+    """The cleaning kernels beside their counterparts in `out`: the two matchers on both shapes, mt_heads_to_notes_clean on the chunks,
+    mt_notes_batch_clean on the recordings."""
+    import torch
+    from music_transcription_amd import _lib
+    from music_transcription_amd.notes import note_match_counts, note_match_list
+    B, P, T = frame.shape
+    dev = frame.device
+    kw = dict(min_note_frames=CLEAN[0], bridge_frames=CLEAN[1])
+    cases = [("onset", "onset_clean", lambda: note_match_counts(frame, ref, 0.5, onset, 0.5, lengths, **kw)),
+             ("onset_list", "onset_list_clean", lambda: note_match_list(frame, notes, 0.5, onset, 0.5, lengths, **kw))]
+    for base, key, fn in cases:
+        ms = device_ms(fn, iters)
+        cs = fn().sum(0).tolist()
+        out[key] = {"ms": round(ms, 4), "over_plain": round(ms / out[base]["ms"], 3), "n_ref": cs[0], "n_est": cs[1], "tp_onset": cs[2],
+                    "tp_onset_offset": cs[3]}
+    if out["onset_clean"]["n_est"] != out["onset_list_clean"]["n_est"] or out["onset_clean"]["n_est"] >= out["onset"]["n_est"]:
+        raise SystemExit(f"{out['case']}: the cleaning matchers disagree, or dropped nothing: {out['onset_clean']} vs {out['onset_list_clean']}")
+    cap = B * P * T // 2 + 1
+    starts, ends = torch.empty(cap, dtype=torch.int32, device=dev), torch.empty(cap, dtype=torch.int32, device=dev)
+    lib, ptr, st = _lib.lib, _lib.ptr, _lib.stream_ptr()
+    if lengths is None:
+        counts = torch.empty(P, dtype=torch.int32, device=dev)
+        base, key = "heads_to_notes", "heads_to_notes_clean"
+        fn = lambda: _lib.check(lib.mt_heads_to_notes_clean(ptr(frame), ptr(onset), None, 0.5, 0.5, 0.5, B, P, T, ptr(counts), ptr(starts),
+                                                            ptr(ends), cap, *CLEAN, st))
+        total = lambda: int(counts.sum())
+    else:
+        ln = torch.tensor(lengths, dtype=torch.int64, device=dev)
+        counts, row_off = torch.empty(B * P, dtype=torch.int32, device=dev), torch.empty(B * P + 1, dtype=torch.int64, device=dev)
+        base, key = "notes_batch_onset", "notes_batch_onset_clean"
+        fn = lambda: _lib.check(lib.mt_notes_batch_clean(ptr(frame), ptr(onset), 0.5, 0.5, ptr(ln), B, P, T, ptr(counts), ptr(row_off),
+                                                         ptr(starts), ptr(ends), cap, *CLEAN, st))
+        total = lambda: int(row_off[-1])
+    ms = device_ms(fn, iters)
+    out[key] = {"ms": round(ms, 4), "over_plain": round(ms / out[base]["ms"], 3), "notes": total()}
+    if lengths is not None and out[key]["notes"] != out["onset_clean"]["n_est"]:
+        raise SystemExit(f"{out['case']} ({key}): another number of notes than the cleaning matcher: {out}")
+
+
 def roll_notes(ref):
     """The runs of the (B, P, T) roll as a note list in ticks (320 per frame) on the device: {"on", "off", "ptr"}."""
     import torch
@@ -176,6 +221,7 @@ def time_case(name, frame, onset, ref, lengths, iters):
     time_offset_decoder(out, frame, onset, ref, notes, lengths, iters)
     if lengths is not None:
         time_notes_batch(out, frame, onset, lengths, iters)
+    time_clean(out, frame, onset, ref, notes, lengths, iters)
     return out
 
 
