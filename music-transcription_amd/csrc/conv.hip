@@ -14,13 +14,14 @@
 
 namespace mt {
 
-// ---------------------------------------------------------------- conv1 (Cin = 1, direct, fp32 VALU)
+// ---------------------------------------------------------------- conv1 (Cin = 1, direct, fp32 VALU): the bit reference
+// Not on any product path (mt_conv1_valu_bn_relu_pool_dt): the plain fmaf chain that conv1_kernel and conv12_kernel must reproduce bit for bit.
 // One thread per pooled output position (b, fo, t): 4x3 input patch, 32 channels x 2 rows x 9 taps.
 // Bandwidth-bound: reads 4 B/position of mel, writes 64 B/position (one full line per thread).
 template <int DT>
-__global__ __launch_bounds__(256) void conv1_kernel(const float* __restrict__ mel, const unsigned* __restrict__ chunk_max,
-                                                    const float* __restrict__ w /*[32][9]*/, const float* __restrict__ bias /*[32]*/,
-                                                    bf16_t* __restrict__ act1, int F, int T, int Fo) {
+__global__ __launch_bounds__(256) void conv1_valu_kernel(const float* __restrict__ mel, const unsigned* __restrict__ chunk_max,
+                                                         const float* __restrict__ w /*[32][9]*/, const float* __restrict__ bias /*[32]*/,
+                                                         bf16_t* __restrict__ act1, int F, int T, int Fo) {
     const int t = blockIdx.x * 64 + (threadIdx.x & 63);
     const int fo = blockIdx.y * 4 + (threadIdx.x >> 6);
     const int b = blockIdx.z;
@@ -65,6 +66,106 @@ __global__ __launch_bounds__(256) void conv1_kernel(const float* __restrict__ me
     uint4* dst = (uint4*)(act1 + (((size_t)b * Fo + fo) * T + t) * 32);
 #pragma unroll
     for (int i = 0; i < 4; ++i) dst[i] = make_uint4(packed[4 * i], packed[4 * i + 1], packed[4 * i + 2], packed[4 * i + 3]);
+}
+
+// ---------------------------------------------------------------- conv1 (Cin = 1) on the f32 matrix pipe
+// conv1 as an implicit GEMM on v_mfma_f32_32x32x2_f32, whose result is bit for bit the k-ordered fmaf chain D = fma(a_k, b_k, ... fma(a_0, b_0, C)):
+//   M (A operand) = the 32 output channels, folded weights, kept in registers (one VGPR per K-step);
+//   N (B operand) = 32 pooled positions;  K = the 9 taps in kh, kw order + one padding slot (5 K-steps of 2);
+//   C             = the folded bias.
+// The two pre-pool rows that MaxPool2d((2,1)) merges are two accumulators of the SAME lane (same weights, patch rows kh and kh + 1), so
+// the pool is an elementwise max of registers.  The channels sit on the accumulator's row index and the positions on its lanes (and not
+// the other way round, as in conv2) because a lane then owns 16 channels of ONE position -- 32 contiguous bytes of the channels-last
+// line, two 16-B stores to HBM or to the swizzled LDS slot -- instead of one channel of 8 positions (eight 2-B stores).  A row of the A
+// operand is channel c1_row_channel(row), chosen so that lane half h's registers 0..15 are channels 16h .. 16h + 15 in order.
+// The padding slot multiplies a weight of +0 by a patch value of -0: the product -0 added to the accumulator is the identity for every
+// value, +0 and -0 included, so the accumulator equals the 9-tap chain of conv1_valu_kernel in every bit.
+struct Conv1Frag {
+    float wa[5];      // A operand of K-step s: w[channel of row lane & 31][tap 2s + (lane >> 5)], +0 in the padding slot
+    f32x16 bias;      // C operand: register j = bias[16 (lane >> 5) + j]
+};
+__device__ __forceinline__ int c1_row_channel(int row) { return 16 * ((row >> 2) & 1) + 4 * (row >> 3) + (row & 3); }
+
+__device__ __forceinline__ Conv1Frag conv1_frag_load(const float* __restrict__ w /*[32][9]*/, const float* __restrict__ bias /*[32]*/, int lane) {
+    Conv1Frag fr;
+    const int c = c1_row_channel(lane & 31), h = lane >> 5;
+#pragma unroll
+    for (int s = 0; s < 5; ++s) fr.wa[s] = 2 * s + h < 9 ? w[c * 9 + 2 * s + h] : 0.0f;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) fr.bias[j] = bias[16 * h + j];
+    return fr;
+}
+
+// One pooled position per lane pair (lane & 31; the halves split the taps): patch(r, c) is the clamped, zero-padded mel value of patch
+// row r (0..3) and column c (0..2) of this lane's position.  Returns the lane's 16 channels (16 (lane >> 5) ..) of
+// max-pool + ReLU + 16-bit rounding, packed two per word: bytes 32 (lane >> 5) .. + 31 of the position's 64-B line.
+template <int DT, class Patch>
+__device__ __forceinline__ void conv1_mfma_position(const Conv1Frag& fr, int lane, Patch patch, unsigned (&out)[8]) {
+    const int h = lane >> 5;
+    float x0[5], x1[5];
+#pragma unroll
+    for (int s = 0; s < 5; ++s) {
+        const int k = 2 * s + h;
+        const bool pad = k >= 9;
+        const int kh = pad ? 0 : k / 3, kw = pad ? 0 : k - 3 * (k / 3);
+        const float v0 = patch(kh, kw), v1 = patch(kh + 1, kw);
+        x0[s] = pad ? -0.0f : v0;
+        x1[s] = pad ? -0.0f : v1;
+    }
+    f32x16 a0 = fr.bias, a1 = fr.bias;
+#pragma unroll
+    for (int s = 0; s < 5; ++s) {
+        a0 = __builtin_amdgcn_mfma_f32_32x32x2f32(fr.wa[s], x0[s], a0, 0, 0, 0);
+        a1 = __builtin_amdgcn_mfma_f32_32x32x2f32(fr.wa[s], x1[s], a1, 0, 0, 0);
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const float lo = fmaxf(fmaxf(a0[2 * j], a1[2 * j]), 0.0f), hi = fmaxf(fmaxf(a0[2 * j + 1], a1[2 * j + 1]), 0.0f);
+        out[j] = (unsigned)f32_to_h16<DT>(lo) | ((unsigned)f32_to_h16<DT>(hi) << 16);
+    }
+}
+
+// A wave per pooled frequency row walks blocks of 64 frames (two groups of 32 positions each), C1_TBLOCKS of them where the row is long
+// enough: its operand fragments cost 21 vector loads, which one block of 64 positions does not repay (0.78 ms per forward of 128 chunks
+// with one block per wave against the vector-ALU kernel's 0.55).  10 MFMAs of 64 cycles per 32 positions: 0.16 ms of matrix pipe per
+// forward of 128 chunks, under the 1.38 GB the kernel has to move.
+constexpr int C1_TBLOCKS = 4;
+template <int DT>
+__global__ __launch_bounds__(256) void conv1_kernel(const float* __restrict__ mel, const unsigned* __restrict__ chunk_max,
+                                                    const float* __restrict__ w /*[32][9]*/, const float* __restrict__ bias /*[32]*/,
+                                                    bf16_t* __restrict__ act1, int F, int T, int Fo) {
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int fo = blockIdx.y * 4 + wv, b = blockIdx.z;
+    if (fo >= Fo) return;                                      // (the whole wave)
+    float floor_db = -3.0e38f;
+    if (chunk_max) floor_db = 10.0f * log10f(fmaxf(__uint_as_float(chunk_max[b]), 1e-10f)) - 80.0f;
+    const float* m = mel + (size_t)b * F * T;
+    const Conv1Frag fr = conv1_frag_load(w, bias, lane);
+    const int nblk = (T + 63) >> 6;
+#pragma unroll 1
+    for (int tb = blockIdx.x; tb < nblk; tb += gridDim.x) {
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+            const int tg = tb * 64 + g * 32;
+            if (tg >= T) break;                                // (the whole wave)
+            const int t = tg + (lane & 31);
+            unsigned out[8];
+            conv1_mfma_position<DT>(fr, lane, [&](int pr, int pc) {
+                const int f = 2 * fo - 1 + pr, tt = t - 1 + pc;
+                const bool in = ((unsigned)f < (unsigned)F) & ((unsigned)tt < (unsigned)T);
+                // The load is unconditional, from a clamped address, and the value is bounded instead of selected: in the image
+                // [floor, +inf] (= the clamp), outside it [+0, +0] (= the zero padding, +0 for every finite value read).  Written as
+                // `in ? fmaxf(load, floor) : 0` the ten loads compile to ten branches with a full memory wait behind each.
+                const float v = m[(size_t)min(max(f, 0), F - 1) * T + min(max(tt, 0), T - 1)];
+                return fminf(fmaxf(v, in ? floor_db : 0.0f), in ? __builtin_inff() : 0.0f);
+            }, out);
+            if (t < T) {
+                uint4* dst = (uint4*)(act1 + (((size_t)b * Fo + fo) * T + t) * 32 + 16 * (lane >> 5));
+                dst[0] = make_uint4(out[0], out[1], out[2], out[3]);
+                dst[1] = make_uint4(out[4], out[5], out[6], out[7]);
+            }
+        }
+    }
 }
 
 // ---------------------------------------------------------------- conv2 (32 -> 64, MFMA implicit GEMM)
@@ -182,16 +283,18 @@ __global__ __launch_bounds__(256, 2) void conv2_kernel(const bf16_t* __restrict_
 // ---------------------------------------------------------------- conv1 + conv2 in one kernel (round 4)
 // conv2's input tile -- 34 rows x 18 frames x 32 channels of act1 -- is COMPUTED in the workgroup from a 70 x 20 tile of the mel
 // spectrogram instead of being read back from HBM: act1 (9.6 MB per chunk, the largest tensor of the CNN) is never written or read, and
-// conv1's launch disappears.  conv1 is vector-ALU work (576 multiply-adds per act1 position), conv2 matrix-pipe work: with two
-// workgroups per CU one's conv1 phase runs under the other's MFMAs.  The arithmetic of an act1 value is conv1_kernel's, operation for
-// operation (same folded weights, same fma order, same packed pair of pre-pool rows, same 16-bit rounding), and the tile has conv2_kernel's
-// LDS layout, so the MFMA phase and the epilogue are conv2_kernel's and X0 is bit-identical to the two-kernel path.
-// Per tile: [mel tile registers -> LDS] barrier [next tile's mel -> registers, in flight from here] [act1 tile: 612 positions over 256
-// threads] barrier [2 x (72 MFMAs per wave + epilogue)].  Halo cost: 612 act1 positions computed for 512 used (x1.2).
+// conv1's launch disappears.  The act1 phase runs on the f32 matrix pipe (conv1_mfma_position, 10 x v_mfma_f32_32x32x2_f32 per 32
+// positions: about 3 200 matrix-pipe cycles per tile and SIMD next to conv2's 4 608); as vector-ALU work (576 multiply-adds per position) it
+// cost more than the HBM round trip it saved.  The arithmetic of an act1 value is conv1_kernel's by construction (the same device
+// function), and the tile has conv2_kernel's LDS layout, so the MFMA phase and the epilogue are conv2_kernel's and X0 is bit-identical to
+// the two-kernel path.
+// Per tile: [mel tile registers -> LDS] barrier [next tile's mel -> registers, in flight from here] [act1 tile: 20 groups of 32 positions
+// over 4 waves] barrier [2 x (72 MFMAs per wave + epilogue)].  Halo cost: 612 act1 positions computed for 512 used (x1.2).
 constexpr int C12_MROWS = 2 * C2_ROWS + 2, C12_MCOLS = 20, C12_MPITCH = 21;     // mel tile: 70 rows x 20 frames, LDS pitch 21
 constexpr int C12_MEL_ELEMS = C12_MROWS * C12_MCOLS;                            // 1400
 constexpr int C12_MEL_PER_THREAD = (C12_MEL_ELEMS + 255) / 256;                 // 6
 constexpr int C12_POS = C2_ROWS * 18;                                           // 612 act1 positions per tile
+constexpr int C12_GROUPS = (C12_POS + 31) / 32;                                 // 20 MFMA groups of 32 positions
 constexpr int C12_LDS_BYTES = C2_LDS_BYTES + C12_MROWS * C12_MPITCH * 4;
 
 template <int DT>
@@ -212,6 +315,7 @@ __global__ __launch_bounds__(256, 2) void conv12_kernel(const float* __restrict_
 #pragma unroll
     for (int ks = 0; ks < 18; ++ks) wf[ks] = *(const bf16x8*)(w2 + (size_t)co * 288 + ks * 16 + h * 8);
     const int n_tiles = B * tiles_f * tiles_t;
+    const Conv1Frag c1 = conv1_frag_load(w1, b1, lane);
 
     float mreg[C12_MEL_PER_THREAD];
     auto load_mel = [&](int tile_) {
@@ -244,43 +348,28 @@ __global__ __launch_bounds__(256, 2) void conv12_kernel(const float* __restrict_
         }
         __syncthreads();                                       // (A) mel tile complete; every wave has left the previous tile's MFMA phase
         load_mel(tile + gridDim.x);                            // the next tile's values fly under this tile's work
-        // ---- act1 tile: position (row, col) <-> act1 (f1 = fb + row, t = tb + col); arithmetic = conv1_kernel
-        typedef float f2_t __attribute__((ext_vector_type(2)));
+        // ---- act1 tile: position (row, col) <-> act1 (f1 = fb + row, t = tb + col); arithmetic = conv1_kernel's (conv1_mfma_position):
+        // 20 groups of 32 positions, 5 per wave, 10 f32 MFMAs each, patch values straight from the mel tile
 #pragma unroll 1
-        for (int idx = tid; idx < C12_POS; idx += 256) {
-            const int row = idx / 18, col = idx - row * 18;
+        for (int g = wv; g < C12_GROUPS; g += 4) {
+            const int idx = g * 32 + (lane & 31);
+            const bool live = idx < C12_POS;
+            const int ic = live ? idx : C12_POS - 1;                            // (the last group's spare lanes compute a position again)
+            const int row = ic / 18, col = ic - row * 18;
+            const float* mp = ms + 2 * row * C12_MPITCH + col;
+            unsigned out[8];
+            conv1_mfma_position<DT>(c1, lane, [&](int pr, int pc) { return mp[pr * C12_MPITCH + pc]; }, out);
             const int f1 = fb + row, t = tb + col;
-            unsigned packed[16];
-            if (f1 >= 0 && f1 < F1 && t >= 0 && t < T) {
-                f2_t pp[3][3];
+            if (!(f1 >= 0 && f1 < F1 && t >= 0 && t < T)) {
 #pragma unroll
-                for (int kh = 0; kh < 3; ++kh)
-#pragma unroll
-                    for (int kw = 0; kw < 3; ++kw)
-                        pp[kh][kw] = f2_t{ms[(2 * row + kh) * C12_MPITCH + col + kw], ms[(2 * row + kh + 1) * C12_MPITCH + col + kw]};
-#pragma unroll
-                for (int c = 0; c < 32; ++c) {
-                    f2_t a = f2_t{b1[c], b1[c]};
-#pragma unroll
-                    for (int kh = 0; kh < 3; ++kh)
-#pragma unroll
-                        for (int kw = 0; kw < 3; ++kw) {
-                            const float wv_ = w1[c * 9 + kh * 3 + kw];
-                            a = __builtin_elementwise_fma(f2_t{wv_, wv_}, pp[kh][kw], a);
-                        }
-                    const float v = fmaxf(fmaxf(a.x, a.y), 0.0f);
-                    if (c & 1) packed[c >> 1] |= ((unsigned)f32_to_h16<DT>(v)) << 16;
-                    else packed[c >> 1] = f32_to_h16<DT>(v);
-                }
-            } else {
-#pragma unroll
-                for (int c = 0; c < 16; ++c) packed[c] = 0u;                    // conv2's zero padding
+                for (int j = 0; j < 8; ++j) out[j] = 0u;                        // conv2's zero padding
             }
-            char* dst = in_s + (row * C2_PITCH + col) * 64;
-            const int sw = (col >> 2) & 3;
-#pragma unroll
-            for (int sl = 0; sl < 4; ++sl)
-                *(uint4*)(dst + ((sl ^ sw) << 4)) = make_uint4(packed[4 * sl], packed[4 * sl + 1], packed[4 * sl + 2], packed[4 * sl + 3]);
+            if (live) {
+                char* dst = in_s + (row * C2_PITCH + col) * 64;
+                const int sw = (col >> 2) & 3;
+                *(uint4*)(dst + (((2 * h) ^ sw) << 4)) = make_uint4(out[0], out[1], out[2], out[3]);
+                *(uint4*)(dst + (((2 * h + 1) ^ sw) << 4)) = make_uint4(out[4], out[5], out[6], out[7]);
+            }
         }
         __syncthreads();                                       // (B) act1 tile complete
 #pragma unroll 1
@@ -332,12 +421,29 @@ extern "C" int mt_conv1_bn_relu_pool_dt(const float* mel, const float* chunk_max
     MT_REQUIRE(B > 0 && n_mels >= 2 && T > 0, MT_EINVAL, "mt_conv1_bn_relu_pool: bad dims B=%d n_mels=%d T=%d", B, n_mels, T);
     MT_REQUIRE_DT(dt, "mt_conv1_bn_relu_pool");
     const int Fo = n_mels / 2;
-    dim3 grid(cdiv(T, 64), cdiv(Fo, 4), B);
+    dim3 grid(cdiv(cdiv(T, 64), C1_TBLOCKS), cdiv(Fo, 4), B);
     if (dt == MT_DT_F16)
         hipLaunchKernelGGL(conv1_kernel<MT_DT_F16>, grid, dim3(256), 0, (hipStream_t)stream, mel, (const unsigned*)chunk_max_power, w, bias,
                            (bf16_t*)act1, n_mels, T, Fo);
     else
         hipLaunchKernelGGL(conv1_kernel<MT_DT_BF16>, grid, dim3(256), 0, (hipStream_t)stream, mel, (const unsigned*)chunk_max_power, w, bias,
+                           (bf16_t*)act1, n_mels, T, Fo);
+    MT_CHECK_LAUNCH();
+    return MT_OK;
+}
+// The vector-ALU conv1 (conv1_valu_kernel): the bit reference of the tests, not on any product path.
+extern "C" int mt_conv1_valu_bn_relu_pool_dt(const float* mel, const float* chunk_max_power, const float* w, const float* bias,
+                                             void* act1, int B, int n_mels, int T, int dt, mt_stream_t stream) {
+    MT_REQUIRE(mel && w && bias && act1, MT_EINVAL, "mt_conv1_valu_bn_relu_pool: null pointer");
+    MT_REQUIRE(B > 0 && n_mels >= 2 && T > 0, MT_EINVAL, "mt_conv1_valu_bn_relu_pool: bad dims B=%d n_mels=%d T=%d", B, n_mels, T);
+    MT_REQUIRE_DT(dt, "mt_conv1_valu_bn_relu_pool");
+    const int Fo = n_mels / 2;
+    dim3 grid(cdiv(T, 64), cdiv(Fo, 4), B);
+    if (dt == MT_DT_F16)
+        hipLaunchKernelGGL(conv1_valu_kernel<MT_DT_F16>, grid, dim3(256), 0, (hipStream_t)stream, mel, (const unsigned*)chunk_max_power, w, bias,
+                           (bf16_t*)act1, n_mels, T, Fo);
+    else
+        hipLaunchKernelGGL(conv1_valu_kernel<MT_DT_BF16>, grid, dim3(256), 0, (hipStream_t)stream, mel, (const unsigned*)chunk_max_power, w, bias,
                            (bf16_t*)act1, n_mels, T, Fo);
     MT_CHECK_LAUNCH();
     return MT_OK;
