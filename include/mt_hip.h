@@ -508,6 +508,22 @@ int    mt_heads_to_notes_clean(const float* frame_logits, const float* onset_log
 int    mt_notes_batch_clean(const float* frame_logits, const float* onset_logits, float thr_frame, float thr_onset, const long long* lengths,
                             int B, int P, long long T, int* counts, long long* row_off, int* starts, int* ends, long long capacity,
                             int min_frames, int bridge_frames, mt_stream_t stream);
+/* mt_note_match_counts_clean / mt_note_match_list_clean for a grid of every decoder parameter in one pass (DESIGN.md 6c "Decoder
+ * grid"): counts[b][i][j][k][c] (uint64 [B][Kf][Ko][Kk][Kc][4], zeroed on the stream) is bit for bit what the _clean entry point
+ * returns for (thr_frame[i], thr_onset[j], thr_offset[k], min_frames = clean[c][0], bridge_frames = clean[c][1]) on the same inputs.
+ * The threshold arrays and clean (int [Kc][2]; NULL = {{1, 0}}, then Kc must be 1) are HOST arrays, taken by value at the call (no
+ * device copy, allocation or synchronisation); any order, repeats allowed.  Every axis has 1..16 values and Kf * Ko * Kk * Kc <= 64;
+ * thresholds in (0, 1), min_frames 1..64, bridge_frames 0..63.  offset_logits == NULL: the onset-gated decoder, Kk must be 1 and
+ * thr_offset may be NULL; onset_logits == NULL as well: the frame decoder, Ko must be 1 too and thr_onset may be NULL; offset_logits
+ * without onset_logits is refused.  Every logit is read, and its sigmoid evaluated, once per launch.  Dimension limits as the
+ * single-configuration calls.  Any violation: MT_EINVAL before the first device call, nothing written. */
+int    mt_note_grid_counts(const float* frame_logits, const float* onset_logits, const float* offset_logits, const float* thr_frame, int Kf,
+                           const float* thr_onset, int Ko, const float* thr_offset, int Kk, const int* clean, int Kc, const float* ref_roll,
+                           const long long* lengths, unsigned long long* counts, int B, int P, int T, mt_stream_t stream);
+int    mt_note_grid_list(const float* frame_logits, const float* onset_logits, const float* offset_logits, const float* thr_frame, int Kf,
+                         const float* thr_onset, int Ko, const float* thr_offset, int Kk, const int* clean, int Kc, const int* ref_on,
+                         const int* ref_off, const long long* ref_ptr, const long long* lengths, unsigned long long* counts, int B, int P,
+                         int T, mt_stream_t stream);
 
 /* ------------------------------------------------------------------ optimizer step (training)
  * clip_grad_norm_(max_norm) + torch.optim.Adam with coupled L2 weight decay over flat f32 buffers

@@ -6,6 +6,8 @@
 //   mt_heads_to_notes:    the onset-gated decoder with mt_roll_to_notes' output contract (main.py's note list).
 //   mt_*_off:             the three of them with the offset-gated decoder (decode_window_off): the offset head ends notes.
 //   mt_*_clean:           the three of them, any decoder, with note cleanup (DESIGN.md 6c "Note cleanup"): short gaps bridged, short notes dropped.
+//   mt_note_sweep_*:      the two matchers for a grid of (frame, onset) thresholds in one pass; mt_note_grid_*: for a grid of every decoder
+//                         parameter -- three thresholds and the cleanup, any decoder (DESIGN.md 6c "Decoder grid").
 // One wave64 per pitch row.  The row walk, the decode step and the note emitter are note_decode.h's (walk_slabs, decode_step,
 // emit_window); a kernel here adds its addressing, where its output goes and what it does with a window's events (match_window,
 // list_window, emit).  Two kernels walk on their own: the roll matcher (its offset-gated instance is 16 % slower on the shared walk,
@@ -707,6 +709,187 @@ __global__ __launch_bounds__(64 * SWEEP_WAVES) void note_sweep_kernel(const floa
     }
 }
 
+// ------------------------------------------------------------------------------------------------ decoder grid
+// The counts of note_match_clean_kernel / note_match_list_clean_kernel for every cell (thr_f[i], thr_o[j], thr_k[k], clean[c]) of a grid,
+// in one pass over the logits (DESIGN.md 6c "Decoder grid").  The decomposition is note_sweep_kernel's: per slab wave w stages window w
+// -- one ballot per threshold and head, now the offset head too -- and then walks configurations w, w + SWEEP_WAVES, ...  Every
+// configuration runs through clean_step, whatever its cleanup ((1, 0) is the plain decoder) and whichever decoder it is (OFF: the
+// offset-gated one; onset == nullptr: the frame decoder), so the events are CLEAN_DELAY frames late as in the cleaning kernels, the
+// roll's run edges are held back two windows (across slabs: the last two windows' edges stay in LDS), and the row ends with
+// flush_clean's three empty windows, after which nothing is open.  A configuration's state between slabs, matcher and pipeline, is
+// parked in LDS whole.
+constexpr int GRID_MAX_CONFIGS = 64;
+constexpr int GRID_FLUSH = 3;             // flush_clean's windows
+constexpr int GRID_HOLD = CLEAN_DELAY / 64;                    // windows the reference's run edges are held back
+
+struct GridArgs {
+    float f[SWEEP_MAX_K], o[SWEEP_MAX_K], k[SWEEP_MAX_K];
+    int min_frames[SWEEP_MAX_K], bridge[SWEEP_MAX_K];
+};
+
+template <bool LIST, bool OFF>
+struct GridState {
+    std::conditional_t<LIST, ListState, MatchState> s;
+    int at;                               // RefCursor::at (LIST)
+    CarryClean<OFF> c;
+};
+
+template <bool LIST, bool OFF>
+__device__ __forceinline__ void grid_init(GridState<LIST, OFF>& st) {
+    if constexpr (LIST) list_init(st.s);
+    else match_init(st.s);
+    st.at = 0;
+    st.c = CarryClean<OFF>{};
+}
+
+// counts[b][i][j][k][c] += the four counts of pitch row (b, p) = blockIdx.x; i < Kf, j < Ko, k < Kk, c < Kc, Kf Ko Kk Kc <= 64.
+// LIST: against ref_on / ref_off / ref_ptr as note_match_list_clean_kernel, otherwise against the roll `ref` as note_match_clean_kernel.
+template <bool LIST, bool OFF>
+__global__ __launch_bounds__(64 * SWEEP_WAVES) void note_grid_kernel(const float* __restrict__ frame, const float* __restrict__ onset,
+                                                                     const float* __restrict__ offset, GridArgs args, int Kf, int Ko, int Kk, int Kc,
+                                                                     const float* __restrict__ ref, const int* __restrict__ ref_on,
+                                                                     const int* __restrict__ ref_off, const long long* __restrict__ ref_ptr,
+                                                                     const long long* __restrict__ lengths,
+                                                                     unsigned long long* __restrict__ counts, int P, int T) {
+    using State = GridState<LIST, OFF>;
+    constexpr int PARK = sizeof(State) / 4;
+    __shared__ unsigned long long fmask[NOTE_SLAB][SWEEP_MAX_K], omask[NOTE_SLAB][SWEEP_MAX_K];     // [window][threshold]: active lanes
+    __shared__ unsigned long long kmask[OFF ? NOTE_SLAB : 1][SWEEP_MAX_K];
+    // roll: the windows' activity; their run starts / ends at [GRID_HOLD + window], before them those of the last slab's last windows
+    __shared__ unsigned long long rmask[NOTE_SLAB], rstart[GRID_HOLD + NOTE_SLAB], rend[GRID_HOLD + NOTE_SLAB];
+    __shared__ int parked[GRID_MAX_CONFIGS][PARK];
+    __shared__ float thr_f[SWEEP_MAX_K], thr_o[SWEEP_MAX_K], thr_k[SWEEP_MAX_K];
+    __shared__ int cl_min[SWEEP_MAX_K], cl_bridge[SWEEP_MAX_K];
+    const int row = blockIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int lane = threadIdx.x & 63;
+    const int b = row / P;
+    const int L = lengths ? (int)min((long long)T, max(0ll, lengths[b])) : T;
+    if (L <= 0) return;                                        // no frame: no estimate, and no reference note starts below frame 0
+    const int end_tick = TICKS_PER_FRAME * L;
+    const size_t base = (size_t)row * T;
+    const int n_cfg = Kf * Ko * Kk * Kc;
+    float xf, xo, xk = 0.0f, xr = 0.0f, xb = 0.0f;             // this wave's window: frame, onset, offset, roll, roll one frame before it
+    const auto load = [&](int s0) {
+        const int g0 = s0 + 64 * wave, g = g0 + lane;
+        const bool in = g < L;
+        xf = in ? frame[base + g] : 0.0f;
+        xo = (in && onset) ? onset[base + g] : 0.0f;
+        if constexpr (OFF) xk = in ? offset[base + g] : 0.0f;
+        if (!LIST) {
+            xr = in ? ref[base + g] : 0.0f;
+            xb = (g0 > 0 && g0 <= L) ? ref[base + g0 - 1] : 0.0f;
+        }
+    };
+    load(0);
+#pragma unroll
+    for (int k = 0; k < SWEEP_MAX_K; ++k)
+        if ((int)threadIdx.x == k) {
+            thr_f[k] = args.f[k];
+            thr_o[k] = args.o[k];
+            thr_k[k] = args.k[k];
+            cl_min[k] = args.min_frames[k];
+            cl_bridge[k] = args.bridge[k];
+        }
+    __syncthreads();
+    for (int s0 = 0; s0 < L; s0 += 64 * NOTE_SLAB) {
+        const bool last = s0 + 64 * NOTE_SLAB >= L;
+        {                                                      // stage window `wave` of the slab
+            const bool in = s0 + 64 * wave + lane < L;
+            const float sf = logit_sigmoid(xf), so = logit_sigmoid(xo);
+#pragma unroll
+            for (int i = 0; i < SWEEP_MAX_K; ++i)
+                if (i < Kf) {
+                    const unsigned long long m = __ballot(in && sf > thr_f[i]);
+                    if (lane == 0) fmask[wave][i] = m;
+                }
+            if (onset) {
+#pragma unroll
+                for (int j = 0; j < SWEEP_MAX_K; ++j)
+                    if (j < Ko) {
+                        const unsigned long long m = __ballot(in && so > thr_o[j]);
+                        if (lane == 0) omask[wave][j] = m;
+                    }
+            }
+            if constexpr (OFF) {
+                const float sk = logit_sigmoid(xk);
+#pragma unroll
+                for (int k = 0; k < SWEEP_MAX_K; ++k)
+                    if (k < Kk) {
+                        const unsigned long long m = __ballot(in && sk > thr_k[k]);
+                        if (lane == 0) kmask[wave][k] = m;
+                    }
+            }
+            if (!LIST) {
+                const unsigned long long rm = __ballot(in && xr > 0.0f);
+                const unsigned long long r_prev = __ballot(xb > 0.0f) ? 1ull : 0ull;
+                if (lane == 0) {
+                    if (wave >= NOTE_SLAB - GRID_HOLD) {       // this window's edges of the slab before stay for the first windows of this one
+                        rstart[wave - (NOTE_SLAB - GRID_HOLD)] = s0 ? rstart[GRID_HOLD + wave] : 0ull;
+                        rend[wave - (NOTE_SLAB - GRID_HOLD)] = s0 ? rend[GRID_HOLD + wave] : 0ull;
+                    }
+                    rmask[wave] = rm;
+                    rstart[GRID_HOLD + wave] = rm & ~((rm << 1) | r_prev);
+                    rend[GRID_HOLD + wave] = ~rm & ((rm << 1) | r_prev);
+                }
+            }
+        }
+        if (!last) load(s0 + 64 * NOTE_SLAB);
+        __syncthreads();
+        const int n_win = min(NOTE_SLAB, (L - s0 + 63) >> 6);                  // windows of the slab that hold a frame below L
+        const int n_pos = last ? n_win + GRID_FLUSH : NOTE_SLAB;               // the row ends with flush_clean's empty windows
+        for (int cfg = wave; cfg < n_cfg; cfg += SWEEP_WAVES) {
+            const int ij = cfg / (Kk * Kc), kc = cfg - ij * (Kk * Kc);
+            const int i = ij / Ko, j = ij - i * Ko, k = kc / Kc, ci = kc - k * Kc;
+            const NoteClean cl{__builtin_amdgcn_readfirstlane(cl_min[ci]), __builtin_amdgcn_readfirstlane(cl_bridge[ci])};
+            State st;
+            if (s0 == 0) grid_init(st);
+            else unpark(st, parked[cfg]);
+            RefCursor r;
+            if constexpr (LIST) cursor_open(r, ref_on, ref_off, ref_ptr, row, st.at, lane);
+#pragma unroll 1
+            for (int pos = 0; pos < n_pos; ++pos) {
+                unsigned long long am = 0, om = 0, km = 0;
+                if (pos < n_win) {
+                    const unsigned long long fm = uniform64(fmask[pos][i]);
+                    om = onset ? uniform64(omask[pos][j]) : fm;
+                    am = fm | om;
+                    if constexpr (OFF) km = uniform64(kmask[pos][k]);
+                }
+                const WindowEvents est = clean_step<OFF>(am, om, km, onset != nullptr, cl, lane, st.c);
+                const int g0 = s0 + 64 * pos - CLEAN_DELAY;
+                if constexpr (LIST) {
+                    list_window(st.s, r, est, g0, lane, end_tick);
+                } else {
+                    const int q = pos - GRID_HOLD;             // the window whose run edges the matcher sees now
+                    unsigned long long rs = 0, re = 0;
+                    if (q < n_win) {
+                        rs = uniform64(rstart[GRID_HOLD + q]);
+                        re = uniform64(rend[GRID_HOLD + q]);
+                    } else if (q == n_win) {                   // the first empty window: a run up to the last frame of a full window ends here
+                        re = uniform64(rmask[n_win - 1]) >> 63;
+                    }
+                    match_window(st.s, est, rs, re, g0);
+                }
+            }
+            if (!last) {
+                if constexpr (LIST) st.at = r.at;
+                park(st, parked[cfg], lane);
+            } else {
+                unsigned long long* c = counts + 4 * ((size_t)b * n_cfg + cfg);
+                if constexpr (LIST) {
+                    int tp_on, tp_onoff;
+                    list_finish(st.s, r, false, lane, end_tick, tp_on, tp_onoff);
+                    if (lane == 0) counts_add(c, st.s.n_ref, st.s.n_est, tp_on, tp_onoff);
+                } else {
+                    if (lane == 0) counts_add(c, st.s.n_ref, st.s.n_est, st.s.tp_on, st.s.tp_onoff);
+                }
+            }
+        }
+        if (!last) __syncthreads();                            // the next slab's masks replace these
+    }
+}
+
 }  // namespace mt
 
 using namespace mt;
@@ -857,6 +1040,73 @@ extern "C" int mt_note_sweep_list(const float* frame_logits, const float* onset_
                        (const float*)nullptr, ref_on, ref_off, ref_ptr, lengths, counts, P, T);
     MT_CHECK_LAUNCH();
     return MT_OK;
+}
+
+// The checks the two grid entry points share; thresholds and cleanups end up in `a`, which the kernel takes by value.
+static int grid_arguments(const char* who, const float* frame, const float* onset, const float* offset, const float* thr_frame, int Kf,
+                          const float* thr_onset, int Ko, const float* thr_offset, int Kk, const int* clean, int Kc, GridArgs& a) {
+    MT_REQUIRE(frame, MT_EINVAL, "%s: null pointer", who);
+    MT_REQUIRE(onset || !offset, MT_EINVAL, "%s: offset_logits without onset_logits (the offset-gated decoder opens its notes at onset edges)", who);
+    MT_REQUIRE(thr_frame && (thr_onset || !onset) && (thr_offset || !offset), MT_EINVAL, "%s: null threshold array", who);
+    const auto axis_ok = [](int K) { return K >= 1 && K <= SWEEP_MAX_K; };
+    MT_REQUIRE(axis_ok(Kf) && axis_ok(Ko) && axis_ok(Kk) && axis_ok(Kc) && Kf * Ko * Kk * Kc <= GRID_MAX_CONFIGS, MT_EINVAL,
+               "%s: needs 1 <= Kf, Ko, Kk, Kc <= %d and Kf * Ko * Kk * Kc <= %d, got %d, %d, %d, %d", who, SWEEP_MAX_K, GRID_MAX_CONFIGS, Kf, Ko,
+               Kk, Kc);
+    MT_REQUIRE(onset || Ko == 1, MT_EINVAL, "%s: without onset logits (the frame decoder) Ko must be 1, got %d", who, Ko);
+    MT_REQUIRE(offset || Kk == 1, MT_EINVAL, "%s: without offset logits Kk must be 1, got %d", who, Kk);
+    MT_REQUIRE(clean || Kc == 1, MT_EINVAL, "%s: without a cleanup array (no cleanup: {1, 0}) Kc must be 1, got %d", who, Kc);
+    for (int n = 0; n < SWEEP_MAX_K; ++n) {
+        a.f[n] = n < Kf ? thr_frame[n] : 0.5f;
+        a.o[n] = (onset && n < Ko) ? thr_onset[n] : 0.5f;
+        a.k[n] = (offset && n < Kk) ? thr_offset[n] : 0.5f;
+        MT_REQUIRE(thr_ok(a.f[n]) && thr_ok(a.o[n]) && thr_ok(a.k[n]), MT_EINVAL, "%s: thresholds must lie in (0, 1)", who);
+        const NoteClean cl{(clean && n < Kc) ? clean[2 * n] : 1, (clean && n < Kc) ? clean[2 * n + 1] : 0};
+        MT_REQUIRE_CLEAN(&cl, who);
+        a.min_frames[n] = cl.min_frames;
+        a.bridge[n] = cl.bridge;
+    }
+    return MT_OK;
+}
+
+template <bool LIST>
+static int note_grid(const char* who, const float* frame, const float* onset, const float* offset, const GridArgs& a, int Kf, int Ko, int Kk, int Kc,
+                     const float* ref, const int* ref_on, const int* ref_off, const long long* ref_ptr, const long long* lengths,
+                     unsigned long long* counts, int B, int P, int T, mt_stream_t stream) {
+    hipStream_t st = (hipStream_t)stream;
+    MT_CHECK_HIP(hipMemsetAsync(counts, 0, (size_t)B * Kf * Ko * Kk * Kc * 4 * sizeof(unsigned long long), st));
+    const auto kernel = offset ? note_grid_kernel<LIST, true> : note_grid_kernel<LIST, false>;
+    hipLaunchKernelGGL(kernel, dim3(B * P), dim3(64 * SWEEP_WAVES), 0, st, frame, onset, offset, a, Kf, Ko, Kk, Kc, ref, ref_on, ref_off, ref_ptr,
+                       lengths, counts, P, T);
+    MT_CHECK_LAUNCH();
+    return MT_OK;
+}
+
+extern "C" int mt_note_grid_counts(const float* frame_logits, const float* onset_logits, const float* offset_logits, const float* thr_frame, int Kf,
+                                   const float* thr_onset, int Ko, const float* thr_offset, int Kk, const int* clean, int Kc, const float* ref_roll,
+                                   const long long* lengths, unsigned long long* counts, int B, int P, int T, mt_stream_t stream) {
+    MT_REQUIRE(ref_roll && counts, MT_EINVAL, "mt_note_grid_counts: null pointer");
+    MT_REQUIRE(B > 0 && P > 0 && T > 0 && (long long)B * P < 2147483647ll && T < (1 << 30), MT_EINVAL, "mt_note_grid_counts: bad dims");
+    GridArgs a;
+    if (const int rc = grid_arguments("mt_note_grid_counts", frame_logits, onset_logits, offset_logits, thr_frame, Kf, thr_onset, Ko, thr_offset, Kk,
+                                      clean, Kc, a))
+        return rc;
+    return note_grid<false>("mt_note_grid_counts", frame_logits, onset_logits, offset_logits, a, Kf, Ko, Kk, Kc, ref_roll, nullptr, nullptr, nullptr,
+                            lengths, counts, B, P, T, stream);
+}
+
+extern "C" int mt_note_grid_list(const float* frame_logits, const float* onset_logits, const float* offset_logits, const float* thr_frame, int Kf,
+                                 const float* thr_onset, int Ko, const float* thr_offset, int Kk, const int* clean, int Kc, const int* ref_on,
+                                 const int* ref_off, const long long* ref_ptr, const long long* lengths, unsigned long long* counts, int B, int P,
+                                 int T, mt_stream_t stream) {
+    MT_REQUIRE(ref_on && ref_off && ref_ptr && counts, MT_EINVAL, "mt_note_grid_list: null pointer");
+    MT_REQUIRE(B > 0 && P > 0 && T > 0 && (long long)B * P < 2147483647ll && (long long)T * TICKS_PER_FRAME < 2147483647ll - 64 * NOTE_SLAB,
+               MT_EINVAL, "mt_note_grid_list: bad dims (frame times must fit 31 bits of 100 us ticks)");
+    GridArgs a;
+    if (const int rc = grid_arguments("mt_note_grid_list", frame_logits, onset_logits, offset_logits, thr_frame, Kf, thr_onset, Ko, thr_offset, Kk,
+                                      clean, Kc, a))
+        return rc;
+    return note_grid<true>("mt_note_grid_list", frame_logits, onset_logits, offset_logits, a, Kf, Ko, Kk, Kc, nullptr, ref_on, ref_off, ref_ptr,
+                           lengths, counts, B, P, T, stream);
 }
 
 extern "C" int mt_heads_to_notes(const float* frame_logits, const float* onset_logits, float thr_frame, float thr_onset, int NB, int P, int T,

@@ -13,6 +13,9 @@
   * `tune_note_thresholds` = tune_threshold's schedule on note F1, over the frame threshold and (onset-gated decoder) the onset
     threshold at once: the model runs once, every round is one sweep pass per group (notes.note_sweep_counts: each cell's sigmoid is
     evaluated once for the whole grid).  `search_note_thresholds` is the search alone, on any callable.
+  * `tune_note_decoder` = the same schedule over every parameter of the note decoder at once, whichever of the three decoders it
+    is: up to three thresholds (frame, onset, offset) times a list of note-cleanup candidates, one grid pass per group and round
+    (notes.note_grid_counts).  `search_note_decoder` is the search alone.
   * `window_overlap` (seconds, whole-file datasets): every recording runs in overlapping 30 s windows stitched on its own
     frame grid (windows.collect_logits_windows) instead of one recurrence over the whole file;
   * recordings / chunks shard over ranks with no data-path collective (parallel.py); per-sample F1 values are
@@ -297,3 +300,94 @@ def tune_note_thresholds(model, dataset, device="cuda", subset: Optional[int] = 
         return np.asarray(allv).reshape(n, len(fts), len(ots)).mean(axis=0) if n else np.zeros((len(fts), len(ots)))
 
     return search_note_thresholds(mean_f1, onset, tune_range, tune_step, tune_min_step, tune_rounds, log)
+
+
+def search_note_decoder(mean_f1, n_axes: int = 3, n_clean: int = 1, tune_range=(0.05, 0.95), tune_step=0.1, tune_min_step=0.01,
+                        tune_rounds=6, log=None):
+    """search_note_thresholds' schedule on 1-3 threshold axes (frame; frame, onset; frame, onset, offset) times a fixed list of
+    n_clean cleanup candidates that is part of every round (no GPU in here).  mean_f1(frame_ths, onset_ths, offset_ths) ->
+    (Kf, Ko, Kk, n_clean) array of the objective; an axis past n_axes is passed as None and has one cell.  A round's candidates on
+    each axis are np.arange(min, max + step / 2, step); cells are visited frame-major, then onset, then offset, then cleanup in
+    the given order, and replace the best only on strict improvement, starting from all thresholds at 0.5 and cleanup 0 at -1; the
+    next window on each axis is best +- 2 step clipped to [0.01, 0.99]; the step halves, and the search ends when it falls below
+    tune_min_step or after tune_rounds.  -> (frame, onset or None, offset or None thresholds, cleanup index, best value)."""
+    if n_axes not in (1, 2, 3):
+        raise ValueError(f"n_axes must be 1, 2 or 3, got {n_axes!r}")
+    if n_clean < 1:
+        raise ValueError(f"n_clean must be at least 1, got {n_clean!r}")
+    names = ("frame", "onset", "offset")[:n_axes]
+    lo, hi = [tune_range[0]] * n_axes, [tune_range[1]] * n_axes
+    step = tune_step
+    best_t, best_c, best = [0.5] * n_axes, 0, -1.0
+    for rnd in range(1, tune_rounds + 1):
+        grids = [np.arange(lo[a], hi[a] + step / 2, step) for a in range(n_axes)]
+        shape = tuple(len(g) for g in grids) + (1,) * (3 - n_axes) + (n_clean,)
+        means = np.asarray(mean_f1(*(grids + [None] * (3 - n_axes))), dtype=np.float64).reshape(shape)
+        for idx in np.ndindex(*shape):                                       # C order: frame-major, ..., cleanup last
+            if means[idx] > best:
+                best, best_c = float(means[idx]), idx[3]
+                best_t = [float(grids[a][idx[a]]) for a in range(n_axes)]
+        if log:
+            log(f"=== Round {rnd}/{tune_rounds} | " + " ".join(f"{n}=[{lo[a]:.4f}, {hi[a]:.4f}]" for a, n in enumerate(names))
+                + f" step={step:.4f} -> " + " ".join(f"{n}_t={best_t[a]:.4f}" for a, n in enumerate(names))
+                + f" cleanup={best_c} f1={best:.6f}")
+        for a in range(n_axes):
+            lo[a], hi[a] = max(0.01, best_t[a] - 2 * step), min(0.99, best_t[a] + 2 * step)
+        step = step / 2
+        if step < tune_min_step:
+            break
+    thr = best_t + [None] * (3 - n_axes)
+    return thr[0], thr[1], thr[2], best_c, best
+
+
+NOTE_DECODER_AXES = {"frame": 1, "onset": 2, "onset_offset": 3}
+
+
+def tune_note_decoder(model, dataset, device="cuda", subset: Optional[int] = None, decoder: str = "onset", note_reference: str = "roll",
+                      objective: str = "onset", cleanups=((1, 0),), tune_range=(0.05, 0.95), tune_step=0.1, tune_min_step=0.01,
+                      tune_rounds=6, rank: int = 0, world: int = 1, log=print, window_overlap: Optional[float] = None, max_batch: int = 128):
+    """Every parameter of the note decoder at once, for the best mean note F1 (`objective`: "onset" or "onset_offset"; unweighted
+    mean over samples, as note_metrics_dataset) by search_note_decoder: the thresholds of the heads that `decoder` reads ("frame":
+    frame; "onset": frame, onset; "onset_offset": frame, onset, offset) times the candidates `cleanups`, a list of
+    (min_note_frames, bridge_frames) pairs that takes part in every round.  The model runs once; every round is one
+    notes.note_grid_counts call over each group of note_metrics_dataset, so each cell is what the single-configuration kernels count.
+    -> (frame threshold, onset threshold or None, offset threshold or None, (min_note_frames, bridge_frames), best mean F1),
+    identical on every rank.  A candidate threshold at or past 1 decodes no note and scores 0, as in tune_note_thresholds."""
+    from .notes import check_cleanup, note_grid_counts, note_prf
+    if decoder not in NOTE_DECODER_AXES:
+        raise ValueError(f"decoder must be 'frame', 'onset' or 'onset_offset', got {decoder!r}")
+    if objective not in ("onset", "onset_offset"):
+        raise ValueError(f"objective must be 'onset' or 'onset_offset', got {objective!r}")
+    cleanups = [check_cleanup(*c) for c in cleanups]
+    if not cleanups:
+        raise ValueError("cleanups: expected at least one (min_note_frames, bridge_frames) pair")
+    _check_note_reference(dataset, note_reference)
+    n_axes = NOTE_DECODER_AXES[decoder]
+    onset, offset = n_axes >= 2, n_axes >= 3
+    n = len(dataset) if subset is None else min(subset, len(dataset))
+    mine = list(shard_range(n, rank, world))
+    lr = _collect(model, dataset, mine, device, window_overlap, all_heads=onset, with_offset=offset)      # the only forward passes
+
+    def mean_f1(fts, ots, kts):
+        axes = [np.asarray(t, dtype=np.float64) if t is not None else np.full(1, 0.5) for t in (fts, ots, kts)]
+        if any((t <= 0.0).any() for t in axes):
+            raise ValueError("tune_note_decoder: candidate thresholds must be positive (tune_range)")
+        below = [np.flatnonzero(np.float32(t) < 1.0) for t in axes]
+        shape = tuple(len(t) for t in axes) + (len(cleanups),)
+        K = int(np.prod(shape))
+        local = np.zeros((len(lr),) + shape)                                               # thresholds >= 1: no notes, F1 0
+        at = 0
+        if all(len(v) for v in below):
+            fi, oj, kk = below
+            for frame, on, ref, lengths, off in _note_groups(lr, dataset, onset, note_reference, max_batch, offset):
+                counts = note_grid_counts(frame, ref, axes[0][fi], on, axes[1][oj] if onset else None, off, axes[2][kk] if offset else None,
+                                          cleanups, lengths)
+                f1 = np.array([m[objective][2] for m in note_prf(counts)]).reshape(len(lengths), len(fi), len(oj), len(kk), len(cleanups))
+                local[at:at + len(lengths), fi[:, None, None], oj[None, :, None], kk[None, None, :]] = f1
+                at += len(lengths)
+        flat_idx = [i * K + k for i in mine for k in range(K)]
+        allv = gather_values(flat_idx, local.reshape(-1).tolist(), n * K)
+        return np.asarray(allv).reshape((n,) + shape).mean(axis=0) if n else np.zeros(shape)
+
+    thr, othr, kthr, c, best = search_note_decoder(mean_f1, n_axes, len(cleanups), tune_range, tune_step, tune_min_step, tune_rounds, log)
+    return thr, othr, kthr, cleanups[c], best

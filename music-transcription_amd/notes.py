@@ -8,6 +8,8 @@
     which re-struck keys are notes of their own: mir_eval's criteria in integers, a maximum matching per criterion.
   * `note_sweep_counts` = either of them for a whole grid of (frame, onset) thresholds in one pass over the logits
     (mt_note_sweep_counts / mt_note_sweep_list): every cell's sigmoid is evaluated once, whatever the size of the grid.
+  * `note_grid_counts` = either of them for a grid of every decoder parameter -- frame, onset and offset thresholds times a list of
+    cleanup pairs, any of the three decoders -- in one pass over the logits (mt_note_grid_counts / mt_note_grid_list).
   * `note_prf` turns those counts into precision / recall / F1 on the host (0 for an empty denominator, as mir_eval).
   * `heads_to_notes_device` = transcribe.notes_from_logits_device with the onset-gated decoder (mt_heads_to_notes).
   * `offset_logits=` on the three calls above selects the offset-gated decoder: the onset-gated notes, ended where
@@ -253,6 +255,75 @@ def note_sweep_counts(frame_logits: torch.Tensor, ref, thresholds, onset_logits:
                                                    _lib.stream_ptr()), "mt_note_sweep_counts")
                 if not whole:
                     out[:, i0:i0 + len(a), j0:j0 + len(b)] = c
+    return out
+
+
+GRID_MAX_K, GRID_MAX_CONFIGS = 16, 64              # mt_note_grid_*: values per axis, configurations per call
+
+
+def note_grid_counts(frame_logits: torch.Tensor, ref, thresholds, onset_logits: Optional[torch.Tensor] = None, onset_thresholds=None,
+                     offset_logits: Optional[torch.Tensor] = None, offset_thresholds=None, cleanups=None, lengths=None) -> torch.Tensor:
+    """note_match_counts (ref = a (B, P, T) roll) or note_match_list (ref = the {"on", "off", "ptr"} note list) at every cell of
+    `thresholds` x `onset_thresholds` x `offset_thresholds` x `cleanups` -> (B, Kf, Ko, Kk, Kc, 4) int64 device tensor; [b, i, j, k, c]
+    is exactly what the single call returns at (thresholds[i], onset_thresholds[j], offset_thresholds[k]) with (min_note_frames,
+    bridge_frames) = cleanups[c] (mt_note_grid_counts / mt_note_grid_list).  cleanups: a list of (min_note_frames, bridge_frames)
+    pairs as check_cleanup takes them, None = [(1, 0)].  Without offset logits (the onset-gated decoder) Kk = 1 and offset_thresholds
+    is not read; without onset logits either (the frame decoder) Ko = 1 as well.  The logits are read, and their sigmoids evaluated,
+    once per call of the kernel; a grid past its limits (16 per axis, 64 configurations) is cut into several calls here and pasted
+    together.  With a roll nothing synchronises (a note list's ptr table is checked with one small read-back, as in note_match_list)."""
+    if offset_logits is not None and onset_logits is None:
+        raise ValueError("offset_logits: the offset-gated decoder needs onset_logits as well")
+    x = _rows(frame_logits, "frame_logits")
+    heads = {}
+    for name, lg, ths in (("onset", onset_logits, onset_thresholds), ("offset", offset_logits, offset_thresholds)):
+        if lg is None:
+            heads[name] = (None, np.full(1, 0.5, np.float32))
+            continue
+        h = _rows(lg, f"{name}_logits")
+        if h.shape != x.shape:
+            raise ValueError(f"shape mismatch: frame {tuple(x.shape)}, {name} {tuple(h.shape)}")
+        if ths is None:
+            raise ValueError(f"{name}_thresholds: needed with {name}_logits")
+        heads[name] = (h, _threshold_array(ths, f"{name}_thresholds"))
+    (on, to), (off, tk) = heads["onset"], heads["offset"]
+    tf = _threshold_array(thresholds, "thresholds")
+    pairs = [(1, 0)] if cleanups is None else [check_cleanup(*c) for c in cleanups]
+    if not pairs:
+        raise ValueError("cleanups: expected a non-empty list of (min_note_frames, bridge_frames) pairs")
+    cl = np.asarray(pairs, dtype=np.int32).reshape(-1, 2)
+    B, P, T = x.shape
+    dev = x.device
+    as_list = isinstance(ref, dict)
+    if as_list:
+        r_on, r_off, r_ptr = _note_tables(ref, B, P, dev)
+    else:
+        roll = _rows(ref, "ref_roll")
+        if roll.shape != x.shape:
+            raise ValueError(f"shape mismatch: frame {tuple(x.shape)}, ref {tuple(roll.shape)}")
+    ln = _lengths(lengths, B, dev)
+    Kf, Ko, Kk, Kc = len(tf), len(to), len(tk), len(cl)
+    out = torch.empty(B, Kf, Ko, Kk, Kc, 4, dtype=torch.int64, device=dev)
+    kc = min(Kc, GRID_MAX_K)                                 # tiles of kf x ko x kk x kc <= 64, the inner axes as wide as they go
+    kk = min(Kk, GRID_MAX_K, GRID_MAX_CONFIGS // kc)
+    ko = min(Ko, GRID_MAX_K, GRID_MAX_CONFIGS // (kc * kk))
+    kf = min(Kf, GRID_MAX_K, GRID_MAX_CONFIGS // (kc * kk * ko))
+    with torch.cuda.device(dev):
+        for i0 in range(0, Kf, kf):
+            for j0 in range(0, Ko, ko):
+                for k0 in range(0, Kk, kk):
+                    for c0 in range(0, Kc, kc):
+                        a, b, k, c = (np.ascontiguousarray(v) for v in (tf[i0:i0 + kf], to[j0:j0 + ko], tk[k0:k0 + kk], cl[c0:c0 + kc]))
+                        whole = (len(a), len(b), len(k), len(c)) == (Kf, Ko, Kk, Kc)
+                        t = out if whole else torch.empty(B, len(a), len(b), len(k), len(c), 4, dtype=torch.int64, device=dev)
+                        axes = (ptr(x), ptr(on), ptr(off), a.ctypes.data, len(a), b.ctypes.data if on is not None else None, len(b),
+                                k.ctypes.data if off is not None else None, len(k), c.ctypes.data, len(c))
+                        if as_list:
+                            check(lib.mt_note_grid_list(*axes, ptr(r_on), ptr(r_off), ptr(r_ptr), ptr(ln), ptr(t), B, P, T, _lib.stream_ptr()),
+                                  "mt_note_grid_list")
+                        else:
+                            check(lib.mt_note_grid_counts(*axes, ptr(roll), ptr(ln), ptr(t), B, P, T, _lib.stream_ptr()), "mt_note_grid_counts")
+                        if not whole:
+                            out[:, i0:i0 + len(a), j0:j0 + len(b), k0:k0 + len(k), c0:c0 + len(c)] = t
     return out
 
 

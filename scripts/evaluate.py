@@ -19,6 +19,9 @@ naming it.  `--window_overlap SECONDS` instead runs every recording in overlappi
 against the MIDI note list of each recording, in which a re-struck key is a note of its own, instead of the runs of the label roll.
 `--note_metrics --tune_note_thresholds` first chooses the note decoder's thresholds for the best mean note F1 (one model run, one
 sweep pass over the logits per group and round: evaluate.tune_note_thresholds) and reports the note metrics at those.
+`--note_metrics --tune_note_decoder [--tune_min_note_ms 0 64 ...] [--tune_bridge_gap_ms 0 32 ...]` chooses every parameter of the
+decoder together, with any --decoder: its thresholds (frame; onset; offset) and the note cleanup out of the product of the two lists
+(evaluate.tune_note_decoder: one model run, one grid pass per group and round), and reports the note metrics at that configuration.
 MIDI / plot outputs, background mode and the results browser are out of scope.
 """
 import argparse
@@ -88,7 +91,32 @@ def main():
                          "--threshold / --tune_threshold")
     ap.add_argument("--tune_note_objective", choices=["onset", "onset_offset"], default="onset",
                     help="the note F1 that --tune_note_thresholds maximises (default: onset)")
+    ap.add_argument("--tune_note_decoder", action="store_true",
+                    help="with --note_metrics: choose every parameter of the note decoder together for the best mean note F1 "
+                         "(--tune_note_objective), with any --decoder: the thresholds of the heads it reads (frame; onset; offset) and the "
+                         "note cleanup out of --tune_min_note_ms x --tune_bridge_gap_ms, by the schedule of --tune_threshold, one model run; "
+                         "headless adds EVAL_NOTE_THRESHOLD= (EVAL_NOTE_ONSET_THRESHOLD=, EVAL_NOTE_OFFSET_THRESHOLD=), "
+                         "EVAL_NOTE_MIN_NOTE_MS= and EVAL_NOTE_BRIDGE_GAP_MS=.  Not with --tune_note_thresholds, --min_note_ms or "
+                         "--bridge_gap_ms")
+    ap.add_argument("--tune_min_note_ms", type=float, nargs="+", default=[0.0],
+                    help="--tune_note_decoder: the candidates for --min_note_ms (default: 0)")
+    ap.add_argument("--tune_bridge_gap_ms", type=float, nargs="+", default=[0.0],
+                    help="--tune_note_decoder: the candidates for --bridge_gap_ms (default: 0); every pair of the two lists is tried")
     args = ap.parse_args()
+    tune_cleanups = None
+    if args.tune_note_decoder:
+        if args.tune_note_thresholds:
+            ap.error("--tune_note_decoder cannot be combined with --tune_note_thresholds: it tunes the thresholds itself")
+        if args.min_note_ms or args.bridge_gap_ms:
+            ap.error("--tune_note_decoder cannot be combined with --min_note_ms / --bridge_gap_ms: it chooses the cleanup itself, out of "
+                     "--tune_min_note_ms x --tune_bridge_gap_ms")
+        try:
+            from music_transcription_amd.notes import cleanup_frames
+            tune_cleanups = [(m, g, cleanup_frames(m, g)) for m in args.tune_min_note_ms for g in args.tune_bridge_gap_ms]     # min-note-major
+        except ValueError as e:
+            ap.error(str(e))
+    elif args.tune_min_note_ms != [0.0] or args.tune_bridge_gap_ms != [0.0]:
+        ap.error("--tune_min_note_ms / --tune_bridge_gap_ms are the cleanup candidates of --tune_note_decoder and need that flag")
     if args.tune_note_thresholds and args.decoder == "onset_offset":
         ap.error("--tune_note_thresholds does not cover --decoder onset_offset (the threshold sweeps do not read the offset head): tune with "
                  "--decoder onset and pass the thresholds it reports")
@@ -112,6 +140,9 @@ def main():
         return 1
     if args.tune_note_thresholds and not args.note_metrics:
         print("Error: --tune_note_thresholds tunes the thresholds of --note_metrics and needs that flag")
+        return 1
+    if args.tune_note_decoder and not args.note_metrics:
+        print("Error: --tune_note_decoder tunes the decoder of --note_metrics and needs that flag")
         return 1
     if not os.path.exists(args.model):
         print(f"Error: Model checkpoint not found: {args.model}")
@@ -201,6 +232,19 @@ def main():
             rank=rank, world=world, log=say if rank == 0 else None, window_overlap=args.window_overlap)
         say(f"Best note thresholds: frame {note_threshold:.4f}" + ("" if note_onset_threshold is None else f", onset {note_onset_threshold:.4f}")
             + f" (mean {args.tune_note_objective} note F1 {tuned_note_f1:.6f})")
+    note_min_ms = note_gap_ms = None
+    if args.tune_note_decoder:
+        note_threshold, note_onset_threshold, note_offset_threshold, tuned_clean, tuned_note_f1 = E.tune_note_decoder(
+            model, ds, dev, subset=args.subset, decoder=args.decoder, note_reference=args.note_reference, objective=args.tune_note_objective,
+            cleanups=[c for _, _, c in tune_cleanups], tune_range=tuple(args.tune_range), tune_step=args.tune_step,
+            tune_min_step=args.tune_min_step, tune_rounds=args.tune_rounds, rank=rank, world=world, log=say if rank == 0 else None,
+            window_overlap=args.window_overlap)
+        # (the first candidate with the chosen frames: different milliseconds can round to one pair, and the search keeps the first)
+        note_min_ms, note_gap_ms = next((m, g) for m, g, c in tune_cleanups if c == tuned_clean)
+        min_note_frames, bridge_frames = tuned_clean
+        say(f"Best note decoder: frame {note_threshold:.4f}" + ("" if note_onset_threshold is None else f", onset {note_onset_threshold:.4f}")
+            + ("" if note_offset_threshold is None else f", offset {note_offset_threshold:.4f}")
+            + f", min note {note_min_ms:g} ms, bridged gap {note_gap_ms:g} ms (mean {args.tune_note_objective} note F1 {tuned_note_f1:.6f})")
     if args.note_metrics:
         notes = E.note_metrics_dataset(model, ds, note_threshold, note_onset_threshold, dev,
                                        subset=args.subset, rank=rank, world=world, window_overlap=args.window_overlap,
@@ -212,10 +256,15 @@ def main():
             if notes is not None:
                 print(f"EVAL_NOTE_ONSET_F1={notes['mean']['onset_f1']:.6f}")
                 print(f"EVAL_NOTE_ONSET_OFFSET_F1={notes['mean']['onset_offset_f1']:.6f}")
-                if args.tune_note_thresholds:
+                if args.tune_note_thresholds or args.tune_note_decoder:
                     print(f"EVAL_NOTE_THRESHOLD={note_threshold:.4f}")
                     if note_onset_threshold is not None:
                         print(f"EVAL_NOTE_ONSET_THRESHOLD={note_onset_threshold:.4f}")
+                if args.tune_note_decoder:
+                    if note_offset_threshold is not None:
+                        print(f"EVAL_NOTE_OFFSET_THRESHOLD={note_offset_threshold:.4f}")
+                    print(f"EVAL_NOTE_MIN_NOTE_MS={note_min_ms:g}")
+                    print(f"EVAL_NOTE_BRIDGE_GAP_MS={note_gap_ms:g}")
         else:
             print(f"\nMean framewise F1 over {len(per_sample)} samples at threshold {threshold:.4f}: {mean_f1:.6f}")
             results = {"mean_f1": mean_f1, "threshold": threshold, "per_sample_f1": per_sample, "split": args.split,
@@ -228,8 +277,10 @@ def main():
                                            **notes}
                 if note_offset_threshold is not None:
                     results["note_metrics"]["offset_threshold"] = note_offset_threshold
-                if args.tune_note_thresholds:
+                if args.tune_note_thresholds or args.tune_note_decoder:
                     results["note_metrics"].update(threshold=note_threshold, tuned_objective=args.tune_note_objective)
+                if args.tune_note_decoder:
+                    results["note_metrics"].update(min_note_ms=note_min_ms, bridge_gap_ms=note_gap_ms)
             os.makedirs(args.out_dir, exist_ok=True)
             with open(os.path.join(args.out_dir, "results.json"), "w") as f:
                 json.dump(results, f)
