@@ -508,6 +508,22 @@ int    mt_heads_to_notes_clean(const float* frame_logits, const float* onset_log
 int    mt_notes_batch_clean(const float* frame_logits, const float* onset_logits, float thr_frame, float thr_onset, const long long* lengths,
                             int B, int P, long long T, int* counts, long long* row_off, int* starts, int* ends, long long capacity,
                             int min_frames, int bridge_frames, mt_stream_t stream);
+/* Frame smoothing (csrc/smooth.hip, DESIGN.md 6c "Frame smoothing"): per pitch row, the Viterbi path of a two-state (off / on) HMM over
+ * the frame head, written as logits.  Evidence q_t = rint(clamp(x_t - logit(thr), -64, 64) * 64), forced to q_t >= 1 where the frame is
+ * active as mt_predict_threshold has it and to q_t <= 0 where it is not; a = rint(64 * on_penalty), b = rint(64 * off_penalty); the
+ * path s maximises sum s_t q_t - a #(0->1) - b #(1->0) over the row's valid frames (a tie from on goes to off, from off stays off).
+ * out[t] = s_t ? +64.0f : -64.0f, so every consumer of frame logits reads the path at any threshold in [1e-6, 1 - 1e-6].  With both
+ * penalties 0 the path is the thresholded activity, bit for bit.
+ *   mt_frame_smooth:        a padded batch [B][P][T], valid frames [0, L_b), L_b = clamp(lengths[b], 0, T) (int64, device, NULL = all
+ *                           T), 64-bit row addressing as mt_notes_batch.  Frames at or past L_b are neither read nor written.
+ *   mt_frame_smooth_chunks: the NB chunks [NB][P][T] as one row of NB * T frames per pitch, as mt_heads_to_notes walks them.
+ * out may be frame_logits itself (in place: a frame is read before anything is stored at its place); any other overlap of the two
+ * buffers, a threshold outside (0, 1), a penalty outside [0, 64] (NaN included), a null pointer or bad dims: MT_EINVAL, no launch.
+ * One launch on `stream`; no workspace, synchronisation, allocation or copy. */
+int    mt_frame_smooth(const float* frame_logits, float* out, float thr, float on_penalty, float off_penalty, const long long* lengths,
+                       int B, int P, long long T, mt_stream_t stream);
+int    mt_frame_smooth_chunks(const float* frame_logits, float* out, float thr, float on_penalty, float off_penalty, int NB, int P, int T,
+                              mt_stream_t stream);
 /* mt_note_match_counts_clean / mt_note_match_list_clean for a grid of every decoder parameter in one pass (DESIGN.md 6c "Decoder
  * grid"): counts[b][i][j][k][c] (uint64 [B][Kf][Ko][Kk][Kc][4], zeroed on the stream) is bit for bit what the _clean entry point
  * returns for (thr_frame[i], thr_onset[j], thr_offset[k], min_frames = clean[c][0], bridge_frames = clean[c][1]) on the same inputs.

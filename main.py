@@ -2,7 +2,7 @@
 """Inference CLI with the reference's interface (main.py:290-362):
 
     python main.py audio_file model_file [-o OUT.mid] [-d {cpu,cuda}] [-t THRESHOLD] [--decoder {frame,onset,onset_offset}] [--overlap SECONDS]
-                   [--min-note-ms MS] [--bridge-gap-ms MS]
+                   [--min-note-ms MS] [--bridge-gap-ms MS] [--smooth-on LOGITS] [--smooth-off LOGITS]
 
 Exit code 1 with a message when a file is missing or transcription fails.  The checkpoint must be a
 CNNRNNModelLarge(320, 512, 3) state_dict as in the reference (main.py:16-20); --model-type/--n-mels/
@@ -41,14 +41,23 @@ def main():
                     help="note cleanup in the decoder: a dropout of the activity no longer than this many milliseconds, with activity "
                          "directly before and after it, does not end the note (below 2048; default 0 = none).  Gaps are bridged first, "
                          "then short notes dropped")
+    ap.add_argument("--smooth-on", type=float, default=0.0,
+                    help="frame smoothing before the decoder: per pitch, the frame head is replaced by the best path of a two-state "
+                         "(off / on) HMM whose evidence is logit - logit(threshold) per frame; switching a pitch on costs this many "
+                         "logits (0 to 64; default 0).  A blip survives only if its evidence pays for switching on and off again")
+    ap.add_argument("--smooth-off", type=float, default=0.0,
+                    help="frame smoothing: the cost in logits of switching a pitch off (0 to 64; default 0).  A dropout is bridged only "
+                         "if its counter-evidence is smaller than --smooth-on + --smooth-off.  Both 0 = no smoothing.  Chunks and "
+                         "--overlap alike; the onset and offset heads are not smoothed; note cleanup then sees the smoothed activity")
     ap.add_argument("--model-type", default="cnn_rnn_large")
     ap.add_argument("--n-mels", type=int, default=320)
     ap.add_argument("--hidden-size", type=int, default=512)
     ap.add_argument("--num-layers", type=int, default=3)
     args = ap.parse_args()
     try:
-        from music_transcription_amd.notes import cleanup_frames
+        from music_transcription_amd.notes import check_smoothing, cleanup_frames
         min_note_frames, bridge_frames = cleanup_frames(args.min_note_ms, args.bridge_gap_ms)
+        smooth_on, smooth_off = check_smoothing(args.smooth_on, args.smooth_off)
     except ValueError as e:
         ap.error(str(e))
     if not os.path.exists(args.audio_file):
@@ -63,6 +72,7 @@ def main():
         out = transcribe_audio(args.audio_file, args.model_file, args.output, args.device, args.threshold,
                                decoder=args.decoder, onset_threshold=args.onset_threshold, overlap=args.overlap,
                                offset_threshold=args.offset_threshold, min_note_frames=min_note_frames, bridge_frames=bridge_frames,
+                               smooth_on=smooth_on, smooth_off=smooth_off,
                                model_type=args.model_type, n_mels=args.n_mels, hidden_size=args.hidden_size,
                                num_layers=args.num_layers)
         print("=" * 60 + f"\nTranscription completed successfully!\nOutput: {out}\n" + "=" * 60)

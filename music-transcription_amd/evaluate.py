@@ -132,7 +132,8 @@ NOTE_METRIC_KEYS = tuple(f"{c}_{m}" for c in ("onset", "onset_offset") for m in 
 def note_metrics_dataset(model, dataset, threshold: float = 0.5, onset_threshold: Optional[float] = None, device="cuda",
                          subset: Optional[int] = None, max_batch: int = 128, rank: int = 0, world: int = 1,
                          window_overlap: Optional[float] = None, note_reference: str = "roll",
-                         offset_threshold: Optional[float] = None, min_note_frames: int = 1, bridge_frames: int = 0) -> dict:
+                         offset_threshold: Optional[float] = None, min_note_frames: int = 1, bridge_frames: int = 0,
+                         smooth_on: float = 0.0, smooth_off: float = 0.0) -> dict:
     """Note-level metrics of every sample, identical on every rank: {"mean": {key: value}, "per_sample": {key: [values]}} over
     NOTE_METRIC_KEYS (onset / onset_offset x precision / recall / f1).  onset_threshold=None: notes are the runs of
     sigmoid(frame) > threshold (the frame decoder); otherwise the onset-gated decoder with the onset head at onset_threshold.
@@ -140,9 +141,11 @@ def note_metrics_dataset(model, dataset, threshold: float = 0.5, onset_threshold
     Reference notes: note_reference="roll", the runs of the dataset's label roll; "midi", the MIDI note list of each recording
     (dataset.ref_notes: a whole-file MaestroDataset built with onset_labels="midi").  Unweighted means over samples, as
     evaluate_dataset (window_overlap too).  min_note_frames / bridge_frames: the estimates are cleaned in the decoder (DESIGN.md 6c "Note cleanup"),
-    whichever of the three it is; the result then names the two ("min_note_frames", "bridge_frames")."""
-    from .notes import check_cleanup, note_match_counts, note_match_list, note_prf
+    whichever of the three it is; the result then names the two ("min_note_frames", "bridge_frames").  smooth_on / smooth_off: the frame
+    head is smoothed before the decoder (DESIGN.md 6c "Frame smoothing"); the result then names those two as well."""
+    from .notes import check_cleanup, check_smoothing, note_match_counts, note_match_list, note_prf
     clean = check_cleanup(min_note_frames, bridge_frames)
+    smooth = check_smoothing(smooth_on, smooth_off)
     _check_note_reference(dataset, note_reference)
     onset, offset = onset_threshold is not None, offset_threshold is not None
     if offset and not onset:
@@ -154,7 +157,8 @@ def note_metrics_dataset(model, dataset, threshold: float = 0.5, onset_threshold
     match = note_match_list if note_reference == "midi" else note_match_counts
     for frame, on, ref, lengths, off in _note_groups(lr, dataset, onset, note_reference, max_batch, offset):
         counts = match(frame, ref, threshold, on, onset_threshold if onset else 0.5, lengths, offset_logits=off,
-                       offset_threshold=offset_threshold if offset else 0.5, min_note_frames=clean[0], bridge_frames=clean[1])
+                       offset_threshold=offset_threshold if offset else 0.5, min_note_frames=clean[0], bridge_frames=clean[1],
+                       smooth_on=smooth[0], smooth_off=smooth[1])
         for m in note_prf(counts):
             for c in ("onset", "onset_offset"):
                 for k, v in zip(("precision", "recall", "f1"), m[c]):
@@ -163,7 +167,17 @@ def note_metrics_dataset(model, dataset, threshold: float = 0.5, onset_threshold
     out = {"mean": {k: (float(np.mean(v)) if v else 0.0) for k, v in per.items()}, "per_sample": per}
     if clean != (1, 0):
         out["min_note_frames"], out["bridge_frames"] = clean
+    if smooth != (0.0, 0.0):
+        out["smooth_on"], out["smooth_off"] = smooth
     return out
+
+
+def _refuse_smoothing(who: str, smooth_on, smooth_off) -> None:
+    """The tuners search thresholds (and cleanup) on the raw frame head: frame smoothing is refused, before any GPU work."""
+    from .notes import check_smoothing
+    if check_smoothing(smooth_on, smooth_off) != (0.0, 0.0):
+        raise ValueError(f"{who}: the tuners do not smooth the frame head (smooth_on / smooth_off): tune without smoothing, then evaluate "
+                         "with it (note_metrics_dataset(..., smooth_on=, smooth_off=))")
 
 
 def _check_note_reference(dataset, note_reference: str) -> None:
@@ -190,9 +204,12 @@ def _note_groups(lr, dataset, onset: bool, note_reference: str, max_batch: int, 
 
 
 def tune_threshold(model, dataset, device="cuda", subset: Optional[int] = None, tune_range=(0.05, 0.95), tune_step=0.1,
-                   tune_min_step=0.01, tune_rounds=6, rank: int = 0, world: int = 1, log=print, window_overlap: Optional[float] = None):
+                   tune_min_step=0.01, tune_rounds=6, rank: int = 0, world: int = 1, log=print, window_overlap: Optional[float] = None,
+                   smooth_on: float = 0.0, smooth_off: float = 0.0):
     """Coarse-to-fine search of evaluate.py:556-618 (same candidate grids, same strict-improvement rule, same window
-    and stopping rule); returns (best_threshold, best_mean_f1).  window_overlap: as evaluate_dataset."""
+    and stopping rule); returns (best_threshold, best_mean_f1).  window_overlap: as evaluate_dataset.  Frame smoothing
+    (smooth_on, smooth_off) other than (0, 0) is refused."""
+    _refuse_smoothing("tune_threshold", smooth_on, smooth_off)
     n = len(dataset) if subset is None else min(subset, len(dataset))
     mine = list(shard_range(n, rank, world))
     lr = _collect(model, dataset, mine, device, window_overlap)          # the only forward passes
@@ -256,14 +273,15 @@ def search_note_thresholds(mean_f1, two_axes: bool = True, tune_range=(0.05, 0.9
 def tune_note_thresholds(model, dataset, device="cuda", subset: Optional[int] = None, decoder: str = "onset", note_reference: str = "roll",
                          objective: str = "onset", tune_range=(0.05, 0.95), tune_step=0.1, tune_min_step=0.01, tune_rounds=6,
                          rank: int = 0, world: int = 1, log=print, window_overlap: Optional[float] = None, max_batch: int = 128,
-                         min_note_frames: int = 1, bridge_frames: int = 0):
+                         min_note_frames: int = 1, bridge_frames: int = 0, smooth_on: float = 0.0, smooth_off: float = 0.0):
     """The thresholds of the note decoder that maximise the mean note F1 (`objective`: "onset" or "onset_offset"; unweighted mean
     over samples, as note_metrics_dataset) by search_note_thresholds: decoder="onset" searches (frame, onset) pairs, "frame" the
     frame threshold alone.  The model runs once; every round is one sweep pass over each group of note_metrics_dataset.
     -> (frame threshold, onset threshold or None, best mean F1), identical on every rank.  A candidate at or past 1 (the schedule's
     last grid point can be) decodes no note and scores 0, as it does for tune_threshold.  The sweep kernels do not clean notes:
-    anything but (min_note_frames, bridge_frames) = (1, 0) is refused."""
+    anything but (min_note_frames, bridge_frames) = (1, 0) is refused, and so is frame smoothing (smooth_on, smooth_off) other than (0, 0)."""
     from .notes import check_cleanup, note_prf, note_sweep_counts
+    _refuse_smoothing("tune_note_thresholds", smooth_on, smooth_off)
     if check_cleanup(min_note_frames, bridge_frames) != (1, 0):
         raise ValueError("tune_note_thresholds: the threshold sweeps do not clean notes (min_note_frames / bridge_frames): tune "
                          "without cleanup, then evaluate with it (note_metrics_dataset(..., min_note_frames=, bridge_frames=))")
@@ -345,15 +363,18 @@ NOTE_DECODER_AXES = {"frame": 1, "onset": 2, "onset_offset": 3}
 
 def tune_note_decoder(model, dataset, device="cuda", subset: Optional[int] = None, decoder: str = "onset", note_reference: str = "roll",
                       objective: str = "onset", cleanups=((1, 0),), tune_range=(0.05, 0.95), tune_step=0.1, tune_min_step=0.01,
-                      tune_rounds=6, rank: int = 0, world: int = 1, log=print, window_overlap: Optional[float] = None, max_batch: int = 128):
+                      tune_rounds=6, rank: int = 0, world: int = 1, log=print, window_overlap: Optional[float] = None, max_batch: int = 128,
+                      smooth_on: float = 0.0, smooth_off: float = 0.0):
     """Every parameter of the note decoder at once, for the best mean note F1 (`objective`: "onset" or "onset_offset"; unweighted
     mean over samples, as note_metrics_dataset) by search_note_decoder: the thresholds of the heads that `decoder` reads ("frame":
     frame; "onset": frame, onset; "onset_offset": frame, onset, offset) times the candidates `cleanups`, a list of
     (min_note_frames, bridge_frames) pairs that takes part in every round.  The model runs once; every round is one
     notes.note_grid_counts call over each group of note_metrics_dataset, so each cell is what the single-configuration kernels count.
     -> (frame threshold, onset threshold or None, offset threshold or None, (min_note_frames, bridge_frames), best mean F1),
-    identical on every rank.  A candidate threshold at or past 1 decodes no note and scores 0, as in tune_note_thresholds."""
+    identical on every rank.  A candidate threshold at or past 1 decodes no note and scores 0, as in tune_note_thresholds.  Frame
+    smoothing (smooth_on, smooth_off) other than (0, 0) is refused: tuning the penalties is not part of the grid."""
     from .notes import check_cleanup, note_grid_counts, note_prf
+    _refuse_smoothing("tune_note_decoder", smooth_on, smooth_off)
     if decoder not in NOTE_DECODER_AXES:
         raise ValueError(f"decoder must be 'frame', 'onset' or 'onset_offset', got {decoder!r}")
     if objective not in ("onset", "onset_offset"):

@@ -19,6 +19,10 @@
   * `min_note_frames=`, `bridge_frames=` on the two matchers and the two note-list calls = note cleanup inside the decoder
     (DESIGN.md 6c "Note cleanup"; the mt_*_clean kernels): gaps of the activity of at most bridge_frames are bridged before decoding, notes
     shorter than min_note_frames dropped after it.  (1, 0) is no cleanup and calls exactly the entry points above.
+  * `smooth_frame_logits` = the frame head of every pitch row replaced by the Viterbi path of a two-state HMM, as logits of +-64
+    (DESIGN.md 6c "Frame smoothing"; mt_frame_smooth / mt_frame_smooth_chunks).  `smooth_on=`, `smooth_off=` (switching penalties in
+    logits) on the two matchers and the two note-list calls smooth the frame head first and then proceed as above; the onset and
+    offset heads are edge detectors and stay as they are.  (0, 0) is no smoothing and launches nothing.
 """
 from __future__ import annotations
 
@@ -111,6 +115,20 @@ def cleanup_frames(min_note_ms: float = 0.0, bridge_gap_ms: float = 0.0) -> Tupl
     return m, g
 
 
+MAX_SMOOTH_PENALTY = 64.0                           # logits; csrc/smooth.hip counts evidence in steps of 1/64 logit, capped at +-64 logits
+
+
+def check_smoothing(smooth_on=0.0, smooth_off=0.0) -> Tuple[float, float]:
+    """The checked (smooth_on, smooth_off) of a decoder call: the penalties, in logits, that the frame smoothing charges for switching
+    a pitch on and off; (0, 0) = no smoothing.  Raises before any GPU work."""
+    out = []
+    for v, name in ((smooth_on, "smooth_on"), (smooth_off, "smooth_off")):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0.0 <= float(np.float32(v)) <= MAX_SMOOTH_PENALTY:
+            raise ValueError(f"{name} must be a penalty of 0 to {MAX_SMOOTH_PENALTY:g} logits, got {v!r}")
+        out.append(float(np.float32(v)))
+    return out[0], out[1]
+
+
 def _lengths(lengths, B: int, dev) -> Optional[torch.Tensor]:
     if lengths is None:
         return None
@@ -118,6 +136,38 @@ def _lengths(lengths, B: int, dev) -> Optional[torch.Tensor]:
     if ln.numel() != B:
         raise ValueError(f"lengths has {ln.numel()} entries for a batch of {B}")
     return ln
+
+
+def _smoothed(x: torch.Tensor, thr: float, smooth: Tuple[float, float], ln: Optional[torch.Tensor], chunks: bool) -> torch.Tensor:
+    """The checked, contiguous (B, P, T) frame logits x smoothed into a new tensor; frames at or past a row's length are not written
+    (they hold x's values when there are lengths)."""
+    B, P, T = x.shape
+    out = torch.empty_like(x) if ln is None else x.clone()
+    with torch.cuda.device(x.device):
+        if chunks:
+            check(lib.mt_frame_smooth_chunks(ptr(x), ptr(out), thr, *smooth, B, P, T, _lib.stream_ptr()), "mt_frame_smooth_chunks")
+        else:
+            check(lib.mt_frame_smooth(ptr(x), ptr(out), thr, *smooth, ptr(ln), B, P, T, _lib.stream_ptr()), "mt_frame_smooth")
+    return out
+
+
+def smooth_frame_logits(frame_logits: torch.Tensor, threshold: float = 0.5, on_penalty: float = 0.0, off_penalty: float = 0.0, lengths=None,
+                        chunks: bool = False) -> torch.Tensor:
+    """(B, P, T) or (P, T) frame logits ON THE DEVICE -> a float tensor of the same shape that holds, per pitch row, the Viterbi path
+    of a two-state (off / on) HMM as logits: +64 where the path is on, -64 where it is off (DESIGN.md 6c "Frame smoothing").  The
+    evidence of a frame is its logit minus logit(threshold); switching on costs on_penalty, switching off off_penalty (logits, 0 to
+    64), so a blip survives only if its evidence pays for both and a dropout is bridged only if its counter-evidence is smaller than
+    both.  Every consumer of frame logits reads the path from the result at any threshold.  lengths (B,): valid frames per row of the
+    batch (None: all T); frames past them keep the input's values.  chunks=True: the B chunks are one recording of B * T frames per
+    pitch, as heads_to_notes_device concatenates them (no lengths then).  (0, 0) returns frame_logits itself and launches nothing."""
+    smooth = check_smoothing(on_penalty, off_penalty)
+    thr = _check_threshold(threshold, "threshold")
+    if chunks and lengths is not None:
+        raise ValueError("lengths: chunks=True concatenates whole chunks, which have no lengths")
+    if smooth == (0.0, 0.0):
+        return frame_logits
+    x = _rows(frame_logits, "frame_logits")
+    return _smoothed(x, thr, smooth, _lengths(lengths, x.shape[0], x.device), chunks).reshape(frame_logits.shape)
 
 
 def _note_tables(ref_notes: Dict[str, torch.Tensor], B: int, P: int, dev):
@@ -139,17 +189,22 @@ def _note_tables(ref_notes: Dict[str, torch.Tensor], B: int, P: int, dev):
 
 def note_match_counts(frame_logits: torch.Tensor, ref_roll: torch.Tensor, threshold: float = 0.5, onset_logits: Optional[torch.Tensor] = None,
                       onset_threshold: float = 0.5, lengths=None, offset_logits: Optional[torch.Tensor] = None,
-                      offset_threshold: float = 0.5, min_note_frames: int = 1, bridge_frames: int = 0) -> torch.Tensor:
+                      offset_threshold: float = 0.5, min_note_frames: int = 1, bridge_frames: int = 0, smooth_on: float = 0.0,
+                      smooth_off: float = 0.0) -> torch.Tensor:
     """(B, P, T) frame logits (and onset logits for the onset-gated decoder) and (B, P, T) reference roll on the device -> (B, 4)
     int64 device tensor {n_ref, n_est, tp_onset, tp_onset_offset}.  lengths (B,) = valid frames per sample (None: all T).  With
     offset_logits (and onset_logits) the estimates come from the offset-gated decoder (mt_note_match_counts_off).  With
-    (min_note_frames, bridge_frames) other than (1, 0) the estimates are cleaned in the decoder (mt_note_match_counts_clean)."""
+    (min_note_frames, bridge_frames) other than (1, 0) the estimates are cleaned in the decoder (mt_note_match_counts_clean).  With
+    (smooth_on, smooth_off) other than (0, 0) the frame head is smoothed first (smooth_frame_logits, over the same lengths)."""
     clean = check_cleanup(min_note_frames, bridge_frames)
+    smooth = check_smoothing(smooth_on, smooth_off)
     x, on, off, thr, othr, kthr, ref = _heads(frame_logits, onset_logits, offset_logits, threshold, onset_threshold, offset_threshold,
                                               ref_roll=ref_roll, mismatch="shape mismatch: frame {frame}, ref {ref}, onset {onset}")
     B, P, T = x.shape
     dev = x.device
     ln = _lengths(lengths, B, dev)
+    if smooth != (0.0, 0.0):
+        x = _smoothed(x, thr, smooth, ln, False)
     counts = torch.empty(B, 4, dtype=torch.int64, device=dev)
     rest = (ptr(ref), ptr(ln), ptr(counts), B, P, T, _lib.stream_ptr())
     with torch.cuda.device(dev):
@@ -169,19 +224,23 @@ TICKS_PER_FRAME = 320              # one frame in ticks of 100 us
 def note_match_list(frame_logits: torch.Tensor, ref_notes: Dict[str, torch.Tensor], threshold: float = 0.5,
                     onset_logits: Optional[torch.Tensor] = None, onset_threshold: float = 0.5, lengths=None,
                     offset_logits: Optional[torch.Tensor] = None, offset_threshold: float = 0.5, min_note_frames: int = 1,
-                    bridge_frames: int = 0) -> torch.Tensor:
+                    bridge_frames: int = 0, smooth_on: float = 0.0, smooth_off: float = 0.0) -> torch.Tensor:
     """note_match_counts against a note list: ref_notes = {"on", "off"} int32 ticks of 100 us and "ptr" int64 (B * P + 1,) on the
     device, row (b, p) owning on/off[ptr[b*P + p]:ptr[b*P + p + 1]] sorted by onset (MaestroDataset.ref_notes).  An estimated
     note [s, e) in frames has times 320 s, 320 e; onsets match within 500 ticks, offsets within max(500, 0.2 reference length).
     Notes that start at or past a sample's valid frames are not counted.  -> (B, 4) int64 {n_ref, n_est, tp_onset, tp_onset_offset}.
     With offset_logits (and onset_logits) the estimates come from the offset-gated decoder (mt_note_match_list_off); with
-    (min_note_frames, bridge_frames) other than (1, 0) they are cleaned in the decoder (mt_note_match_list_clean)."""
+    (min_note_frames, bridge_frames) other than (1, 0) they are cleaned in the decoder (mt_note_match_list_clean); with
+    (smooth_on, smooth_off) other than (0, 0) the frame head is smoothed first (smooth_frame_logits, over the same lengths)."""
     clean = check_cleanup(min_note_frames, bridge_frames)
+    smooth = check_smoothing(smooth_on, smooth_off)
     x, on, off, thr, othr, kthr, _ = _heads(frame_logits, onset_logits, offset_logits, threshold, onset_threshold, offset_threshold)
     B, P, T = x.shape
     dev = x.device
     r_on, r_off, r_ptr = _note_tables(ref_notes, B, P, dev)
     ln = _lengths(lengths, B, dev)
+    if smooth != (0.0, 0.0):
+        x = _smoothed(x, thr, smooth, ln, False)
     counts = torch.empty(B, 4, dtype=torch.int64, device=dev)
     rest = (ptr(r_on), ptr(r_off), ptr(r_ptr), ptr(ln), ptr(counts), B, P, T, _lib.stream_ptr())
     with torch.cuda.device(dev):
@@ -344,17 +403,22 @@ def note_prf(counts) -> List[Dict[str, Tuple[float, float, float]]]:
 
 def heads_to_notes_device(frame_logits: torch.Tensor, onset_logits: Optional[torch.Tensor], threshold: float = 0.5,
                           onset_threshold: float = 0.5, fs: float = FS, min_midi: int = 21, offset_logits: Optional[torch.Tensor] = None,
-                          offset_threshold: float = 0.5, min_note_frames: int = 1, bridge_frames: int = 0) -> List[Tuple[int, float, float]]:
+                          offset_threshold: float = 0.5, min_note_frames: int = 1, bridge_frames: int = 0, smooth_on: float = 0.0,
+                          smooth_off: float = 0.0) -> List[Tuple[int, float, float]]:
     """(n_chunks, 88, T) frame and onset logits ON THE DEVICE -> notes of the onset-gated decoder over the chunks concatenated in
     time, in the reference's note order (pitch-major, then time); only counts and two ints per note reach the host.  With
     offset_logits: the notes of the offset-gated decoder (mt_heads_to_notes_off), which end where the offset head fires.  With
     (min_note_frames, bridge_frames) other than (1, 0): the cleaned notes (mt_heads_to_notes_clean), and then onset_logits may be
-    None: the frame decoder's notes, cleaned."""
+    None: the frame decoder's notes, cleaned.  With (smooth_on, smooth_off) other than (0, 0) the frame head is smoothed first, over
+    the chunks concatenated in time (smooth_frame_logits, chunks=True)."""
     clean = check_cleanup(min_note_frames, bridge_frames)
+    smooth = check_smoothing(smooth_on, smooth_off)
     x, on, off, thr, othr, kthr, _ = _heads(frame_logits, onset_logits, offset_logits, threshold, onset_threshold, offset_threshold,
                                             onset_required=clean == (1, 0), mismatch="frame {frame} and onset {onset} logits differ in shape")
     NB, P, T = x.shape
     dev = x.device
+    if smooth != (0.0, 0.0):
+        x = _smoothed(x, thr, smooth, None, True)
     counts = torch.empty(P, dtype=torch.int32, device=dev)
     cap = max(1024, NB * 64)
     while True:
@@ -380,18 +444,22 @@ def heads_to_notes_device(frame_logits: torch.Tensor, onset_logits: Optional[tor
 
 def notes_batch_device(frame_logits: torch.Tensor, onset_logits: Optional[torch.Tensor] = None, threshold: float = 0.5,
                        onset_threshold: float = 0.5, lengths=None, fs: float = FS, min_midi: int = 21, min_note_frames: int = 1,
-                       bridge_frames: int = 0) -> List[List[Tuple[int, float, float]]]:
+                       bridge_frames: int = 0, smooth_on: float = 0.0, smooth_off: float = 0.0) -> List[List[Tuple[int, float, float]]]:
     """(B, P, T) frame logits of B whole recordings ON THE DEVICE, padded to T, with lengths (B,) valid frames each (None: all T) ->
     one note list per recording: what transcribe.notes_from_logits_device (onset_logits None) or heads_to_notes_device returns on
     that recording's rows trimmed to its length.  The padding is never read.  One launch of mt_notes_batch, one device-to-host copy
     of the counts and offsets and one of the notes; a second launch only when the first capacity guess was short.  With
-    (min_note_frames, bridge_frames) other than (1, 0) the notes are cleaned in the decoder (mt_notes_batch_clean)."""
+    (min_note_frames, bridge_frames) other than (1, 0) the notes are cleaned in the decoder (mt_notes_batch_clean).  With
+    (smooth_on, smooth_off) other than (0, 0) the frame head is smoothed first (smooth_frame_logits, over the same lengths)."""
     clean = check_cleanup(min_note_frames, bridge_frames)
+    smooth = check_smoothing(smooth_on, smooth_off)
     x, on, _, thr, othr, _, _ = _heads(frame_logits, onset_logits, None, threshold, onset_threshold, 0.5,
                                        mismatch="frame {frame} and onset {onset} logits differ in shape")
     B, P, T = x.shape
     dev = x.device
     ln = _lengths(lengths, B, dev)
+    if smooth != (0.0, 0.0):
+        x = _smoothed(x, thr, smooth, ln, False)
     rows = B * P
     meta = torch.empty(rows + 1 + (rows + 1) // 2, dtype=torch.int64, device=dev)      # row_off (rows + 1) | counts (rows int32): one copy
     row_off, counts = meta[:rows + 1], meta[rows + 1:].view(torch.int32)[:rows]

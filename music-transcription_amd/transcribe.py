@@ -237,16 +237,23 @@ def pianoroll_to_notes(roll: np.ndarray, fs: float, min_midi: int = 21) -> List[
 
 
 def notes_from_logits_device(logits: torch.Tensor, threshold: float = THRESHOLD, fs: float = SR / HOP_LENGTH, min_midi: int = 21,
-                             is_roll: bool = False, min_note_frames: int = 1, bridge_frames: int = 0) -> List[Tuple[int, float, float]]:
+                             is_roll: bool = False, min_note_frames: int = 1, bridge_frames: int = 0, smooth_on: float = 0.0,
+                             smooth_off: float = 0.0) -> List[Tuple[int, float, float]]:
     """(n_chunks, 88, T) logits (or {0,1} roll values with is_roll=True) ON THE DEVICE -> notes, without the roll ever
     leaving the GPU: threshold + combine_piano_rolls + the run-length of pianoroll_to_midi (main.py:153-226) in
     mt_roll_to_notes; only 88 counts and two ints per note are copied to the host.  With (min_note_frames, bridge_frames) other than
     (1, 0): the same notes with short gaps bridged and short notes dropped in the decoder (notes.heads_to_notes_device without an
-    onset head; logits only)."""
-    from .notes import check_cleanup, heads_to_notes_device
+    onset head; logits only).  With (smooth_on, smooth_off) other than (0, 0): the logits are smoothed first, over the chunks
+    concatenated in time (notes.smooth_frame_logits; logits only), and decoded as above."""
+    from .notes import check_cleanup, check_smoothing, heads_to_notes_device, smooth_frame_logits
     clean = check_cleanup(min_note_frames, bridge_frames)
+    smooth = check_smoothing(smooth_on, smooth_off)
+    if smooth != (0.0, 0.0) and is_roll:
+        raise ValueError("frame smoothing reads logits: is_roll=True is not supported with smooth_on / smooth_off")
     if not logits.is_cuda:
         raise RuntimeError("notes_from_logits_device expects a CUDA tensor")
+    if smooth != (0.0, 0.0):
+        logits = smooth_frame_logits(logits, threshold, *smooth, chunks=True)
     if clean != (1, 0):
         if is_roll:
             raise ValueError("note cleanup decodes logits: is_roll=True is not supported with min_note_frames / bridge_frames")
@@ -293,14 +300,16 @@ def check_decoder(decoder: str, model_type: str = None, model=None) -> None:
 def transcribe_chunks_to_notes(model: "TranscriptionModel", chunks, threshold: float = THRESHOLD, batch: int = 128, n_mels: int = N_MELS,
                                device: str = "cuda", decoder: str = "frame", onset_threshold: float = THRESHOLD,
                                offset_threshold: float = THRESHOLD, min_note_frames: int = 1,
-                               bridge_frames: int = 0) -> List[Tuple[int, float, float]]:
+                               bridge_frames: int = 0, smooth_on: float = 0.0, smooth_off: float = 0.0) -> List[Tuple[int, float, float]]:
     """(n, 480000) waveform chunks -> notes; mel, forward, threshold, concatenation and run-length all on the GPU.  decoder="onset":
     notes start at rising edges of the onset head and last while frame or onset is active (notes.heads_to_notes_device);
     decoder="onset_offset": those notes, ended where the offset head fires.  min_note_frames / bridge_frames: note
-    cleanup in the decoder, any of the three (DESIGN.md 6c "Note cleanup")."""
-    from .notes import check_cleanup
+    cleanup in the decoder, any of the three (DESIGN.md 6c "Note cleanup").  smooth_on / smooth_off: the frame head is smoothed before
+    any of the three decodes it (DESIGN.md 6c "Frame smoothing")."""
+    from .notes import check_cleanup, check_smoothing
     check_decoder(decoder, model=model)
     clean = check_cleanup(min_note_frames, bridge_frames)
+    smooth = check_smoothing(smooth_on, smooth_off)
     with_heads, with_offset = decoder in HEAD_DECODERS, decoder == "onset_offset"
     fe = get_frontend(SR, n_mels, HOP_LENGTH, device)
     if not torch.is_tensor(chunks):
@@ -322,9 +331,10 @@ def transcribe_chunks_to_notes(model: "TranscriptionModel", chunks, threshold: f
         from .notes import heads_to_notes_device
         notes = heads_to_notes_device(torch.cat(outs), torch.cat(onsets), threshold, onset_threshold, SR / HOP_LENGTH,
                                       offset_logits=torch.cat(offsets) if with_offset else None, offset_threshold=offset_threshold,
-                                      min_note_frames=clean[0], bridge_frames=clean[1])
+                                      min_note_frames=clean[0], bridge_frames=clean[1], smooth_on=smooth[0], smooth_off=smooth[1])
     else:
-        notes = notes_from_logits_device(torch.cat(outs), threshold, SR / HOP_LENGTH, min_note_frames=clean[0], bridge_frames=clean[1])
+        notes = notes_from_logits_device(torch.cat(outs), threshold, SR / HOP_LENGTH, min_note_frames=clean[0], bridge_frames=clean[1],
+                                         smooth_on=smooth[0], smooth_off=smooth[1])
     net.raise_on_handoff_timeout(sync=False)               # (the copies above synchronised with every forward)
     return notes
 
@@ -395,32 +405,37 @@ def transcribe_chunks(model: TranscriptionModel, chunks, threshold: float = THRE
 def transcribe_windows_to_notes(model: "TranscriptionModel", y: torch.Tensor, overlap: float, threshold: float = THRESHOLD, batch: int = 128,
                                 n_mels: int = N_MELS, decoder: str = "frame", onset_threshold: float = THRESHOLD,
                                 offset_threshold: float = THRESHOLD, min_note_frames: int = 1,
-                                bridge_frames: int = 0) -> List[Tuple[int, float, float]]:
+                                bridge_frames: int = 0, smooth_on: float = 0.0, smooth_off: float = 0.0) -> List[Tuple[int, float, float]]:
     """1-D device recording -> notes decoded from ONE (1, 88, 1 + n // 512) logit roll on the recording's frame grid, stitched from
     overlapping 30 s windows (windows.transcribe_windows): no per-chunk drift, no cold chunk edges inside the recording.
-    min_note_frames / bridge_frames: note cleanup in the decoder (DESIGN.md 6c "Note cleanup")."""
-    from .notes import check_cleanup
+    min_note_frames / bridge_frames: note cleanup in the decoder (DESIGN.md 6c "Note cleanup"); smooth_on / smooth_off: the frame head
+    is smoothed first (DESIGN.md 6c "Frame smoothing")."""
+    from .notes import check_cleanup, check_smoothing
     from .windows import transcribe_windows
     check_decoder(decoder, model=model)
     clean = check_cleanup(min_note_frames, bridge_frames)
+    smooth = check_smoothing(smooth_on, smooth_off)
     with_offset = decoder == "onset_offset"
     heads = transcribe_windows(model, [y], overlap, batch=batch, all_heads=decoder in HEAD_DECODERS, n_mels=n_mels, with_offset=with_offset)[0]
     if decoder in HEAD_DECODERS:
         from .notes import heads_to_notes_device
         return heads_to_notes_device(heads[0][None], heads[1][None], threshold, onset_threshold, SR / HOP_LENGTH,
                                      offset_logits=heads[2][None] if with_offset else None, offset_threshold=offset_threshold,
-                                     min_note_frames=clean[0], bridge_frames=clean[1])
-    return notes_from_logits_device(heads[None], threshold, SR / HOP_LENGTH, min_note_frames=clean[0], bridge_frames=clean[1])
+                                     min_note_frames=clean[0], bridge_frames=clean[1], smooth_on=smooth[0], smooth_off=smooth[1])
+    return notes_from_logits_device(heads[None], threshold, SR / HOP_LENGTH, min_note_frames=clean[0], bridge_frames=clean[1],
+                                    smooth_on=smooth[0], smooth_off=smooth[1])
 
 
 def transcribe_audio(audio_path: str, model_path: str, output_path=None, device=None, threshold: float = THRESHOLD, decoder: str = "frame",
                      onset_threshold: float = THRESHOLD, overlap: float = 0.0, offset_threshold: float = THRESHOLD, min_note_frames: int = 1,
-                     bridge_frames: int = 0, **model_kw):
+                     bridge_frames: int = 0, smooth_on: float = 0.0, smooth_off: float = 0.0, **model_kw):
     """overlap = 0: the reference's chunk concatenation (main.py:60-100, :164-186); overlap > 0 (seconds): overlapping windows
-    stitched on the recording's own frame grid (transcribe_windows_to_notes)."""
-    from .notes import check_cleanup
+    stitched on the recording's own frame grid (transcribe_windows_to_notes).  smooth_on / smooth_off: frame smoothing before the
+    decoder, in either mode (DESIGN.md 6c "Frame smoothing")."""
+    from .notes import check_cleanup, check_smoothing
     check_decoder(decoder, model_type=model_kw.get("model_type", MODEL_TYPE))
     clean = check_cleanup(min_note_frames, bridge_frames)    # refused before any GPU work, like the decoder
+    smooth = check_smoothing(smooth_on, smooth_off)
     if overlap:
         from .windows import overlap_frames
         overlap_frames(overlap)                          # refuse an out-of-range overlap before any GPU work
@@ -436,13 +451,13 @@ def transcribe_audio(audio_path: str, model_path: str, output_path=None, device=
               f"overlapping by {overlap}s")
         notes = transcribe_windows_to_notes(model, y, overlap, threshold, n_mels=model_kw.get("n_mels", N_MELS), decoder=decoder,
                                             onset_threshold=onset_threshold, offset_threshold=offset_threshold, min_note_frames=clean[0],
-                                            bridge_frames=clean[1])
+                                            bridge_frames=clean[1], smooth_on=smooth[0], smooth_off=smooth[1])
     else:
         chunks, duration = split_into_chunks_device(y)
         print(f"Audio duration: {duration:.2f} seconds; {len(chunks)} chunks of {CHUNK_LENGTH}s")
         notes = transcribe_chunks_to_notes(model, chunks, threshold, n_mels=model_kw.get("n_mels", N_MELS), device=device, decoder=decoder,
                                            onset_threshold=onset_threshold, offset_threshold=offset_threshold, min_note_frames=clean[0],
-                                            bridge_frames=clean[1])
+                                           bridge_frames=clean[1], smooth_on=smooth[0], smooth_off=smooth[1])
     if output_path is None:
         p = Path(audio_path)
         output_path = p.parent / f"{p.stem}_transcription.mid"

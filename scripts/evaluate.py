@@ -22,6 +22,8 @@ sweep pass over the logits per group and round: evaluate.tune_note_thresholds) a
 `--note_metrics --tune_note_decoder [--tune_min_note_ms 0 64 ...] [--tune_bridge_gap_ms 0 32 ...]` chooses every parameter of the
 decoder together, with any --decoder: its thresholds (frame; onset; offset) and the note cleanup out of the product of the two lists
 (evaluate.tune_note_decoder: one model run, one grid pass per group and round), and reports the note metrics at that configuration.
+`--note_metrics --smooth_on X --smooth_off Y` smooths the frame head with a two-state HMM per pitch before the notes are decoded
+(notes.smooth_frame_logits); the framewise F1 stays that of the raw threshold, and none of the tuners takes smoothing.
 MIDI / plot outputs, background mode and the results browser are out of scope.
 """
 import argparse
@@ -74,6 +76,14 @@ def main():
     ap.add_argument("--bridge_gap_ms", type=float, default=0.0,
                     help="with --note_metrics: note cleanup in the decoder, a dropout of the activity no longer than this many "
                          "milliseconds does not end the note (below 2048; default 0 = none)")
+    ap.add_argument("--smooth_on", type=float, default=0.0,
+                    help="with --note_metrics: frame smoothing before the note decoder, the cost in logits of switching a pitch on in the "
+                         "two-state HMM that replaces the frame head by its best path (0 to 64; default 0).  The framewise F1 printed "
+                         "beside the note F1 stays that of the raw threshold.  Not with --tune_threshold, --tune_note_thresholds or "
+                         "--tune_note_decoder: the tuners do not smooth")
+    ap.add_argument("--smooth_off", type=float, default=0.0,
+                    help="with --note_metrics: frame smoothing, the cost in logits of switching a pitch off (0 to 64; default 0 = with "
+                         "--smooth_on 0, no smoothing)")
     ap.add_argument("--window_overlap", type=float, default=None,
                     help="full files only: run every recording in overlapping 30 s windows (this many seconds of overlap, 0.256 to 15) "
                          "stitched on its own frame grid, instead of one recurrence over the whole file; lifts the T * hidden_size < 2^24 "
@@ -130,6 +140,19 @@ def main():
         try:
             from music_transcription_amd.notes import cleanup_frames
             min_note_frames, bridge_frames = cleanup_frames(args.min_note_ms, args.bridge_gap_ms)
+        except ValueError as e:
+            ap.error(str(e))
+    smooth_on = smooth_off = 0.0
+    if args.smooth_on or args.smooth_off:
+        if not args.note_metrics:
+            ap.error("--smooth_on / --smooth_off smooth the frame head for the notes of --note_metrics and need that flag")
+        for flag in ("tune_threshold", "tune_note_thresholds", "tune_note_decoder"):
+            if getattr(args, flag):
+                ap.error(f"--smooth_on / --smooth_off cannot be combined with --{flag}: the tuners do not smooth; tune without smoothing, "
+                         "then evaluate with it at the values reported")
+        try:
+            from music_transcription_amd.notes import check_smoothing
+            smooth_on, smooth_off = check_smoothing(args.smooth_on, args.smooth_off)
         except ValueError as e:
             ap.error(str(e))
     say = (lambda *a, **k: None) if args.headless else print
@@ -249,7 +272,8 @@ def main():
         notes = E.note_metrics_dataset(model, ds, note_threshold, note_onset_threshold, dev,
                                        subset=args.subset, rank=rank, world=world, window_overlap=args.window_overlap,
                                        note_reference=args.note_reference, offset_threshold=note_offset_threshold,
-                                       min_note_frames=min_note_frames, bridge_frames=bridge_frames)
+                                       min_note_frames=min_note_frames, bridge_frames=bridge_frames, smooth_on=smooth_on,
+                                       smooth_off=smooth_off)
     if rank == 0:
         if args.headless:
             print(f"EVAL_MEAN_F1={mean_f1:.6f}")
