@@ -4,8 +4,10 @@
 //   decode_step:    one window of a decoder: the heads' activity, then decode_window (frame / onset-gated) or decode_window_off
 //                   (offset-gated), the state between windows in a DecodeCarry;
 //   emit_window, emit_open_end: the count and the fill pass of a note list (mt_heads_to_notes, mt_notes_batch);
-//   clean_step, flush_clean:    decode_step<OFF, true>, the note cleanup of the mt_*_clean kernels (DESIGN.md 6c "Note cleanup"): short gaps of the
-//                   activity are bridged before the decoder, short notes dropped after it; events come out two windows late.
+//   clean_step:     the note cleanup of the mt_*_clean entry points (DESIGN.md 6c "Note cleanup"): short gaps of the activity are
+//                   bridged before the decoder, short notes dropped after it; events come out two windows late.
+// A kernel is written once for both modes, generic over CLEAN: decode_step<OFF, CLEAN> with a DecodeCarry<OFF, CLEAN>, the events'
+// window at g0 - decode_delay<CLEAN>, flush_clean<CLEAN> after the walk, and then the row's end as without cleanup.
 //
 // Activity is the expression of mt_predict_threshold / note_active in post.hip, so ties break the same way everywhere.
 // Onset-gated decoder (the Onsets-and-Frames rule): a = frame-active OR onset-active; a note opens at every rising edge of
@@ -74,6 +76,16 @@ struct CarryOffset : CarryOnset { unsigned long long k_prev = 0, e_prev = 0; };
 struct NoteClean { int min_frames = 1, bridge = 0; };
 constexpr int CLEAN_MAX_MIN_FRAMES = 64, CLEAN_MAX_BRIDGE = 63;      // both stages look one 64-frame window ahead, never further
 constexpr int CLEAN_DELAY = 128;                                     // clean_step returns the events of the window two calls back
+template <bool CLEAN>
+constexpr int decode_delay = CLEAN ? CLEAN_DELAY : 0;                // frames by which decode_step<OFF, CLEAN>'s events trail its window
+
+// The host's check of an entry point's cleanup; null = an entry point without the stage.
+inline bool clean_ok(const NoteClean* cl) {
+    return !cl || (cl->min_frames >= 1 && cl->min_frames <= CLEAN_MAX_MIN_FRAMES && cl->bridge >= 0 && cl->bridge <= CLEAN_MAX_BRIDGE);
+}
+#define MT_REQUIRE_CLEAN(cl, who)                                                                                                      \
+    MT_REQUIRE(mt::clean_ok(cl), MT_EINVAL, "%s: needs 1 <= min_frames <= %d and 0 <= bridge_frames <= %d", who, mt::CLEAN_MAX_MIN_FRAMES, \
+               mt::CLEAN_MAX_BRIDGE)
 
 // The cleanup pipeline's state on top of the decoder's, all wave-uniform.  Bridge stage: the masks of the window before the one
 // that arrives (a gap at its end is decided by the first 63 frames of the next) and gap_before = the inactive frames directly
@@ -133,28 +145,20 @@ __device__ __forceinline__ WindowEvents clean_step(unsigned long long am_n, unsi
 }
 
 // One window of a decoder.  x = the window's logits of this lane's frame, x[0] frame, x[1] onset, x[2] offset (OFF only); `in` = the
-// frame is inside the row.  Without an onset head (the frame decoder) onset := frame.
-template <bool OFF, int NCH>
-__device__ __forceinline__ WindowEvents decode_step(bool in, const float (&x)[NCH], bool has_onset, const NoteThr& thr, int lane,
-                                                    DecodeCarry<OFF>& c) {
+// frame is inside the row.  Without an onset head (the frame decoder) onset := frame.  CLEAN: the same window through the cleanup
+// pipeline, so the events are those of the window decode_delay<CLEAN> frames back and flush_clean feeds the windows that bring the
+// last ones out; otherwise cl is not read.
+template <bool OFF, bool CLEAN, int NCH>
+__device__ __forceinline__ WindowEvents decode_step(bool in, const float (&x)[NCH], bool has_onset, const NoteThr& thr, const NoteClean& cl,
+                                                    int lane, DecodeCarry<OFF, CLEAN>& c) {
     static_assert(NCH >= (OFF ? 3 : 2), "frame, onset (and offset) logits");
     const bool f = in && logit_active(x[0], thr.frame);
     const bool o = has_onset ? (in && logit_active(x[1], thr.onset)) : f;
-    if constexpr (OFF) return decode_window_off(o, f || o, in && logit_active(x[2], thr.offset), lane, c.o_prev, c.open_prev, c.k_prev, c.e_prev);
+    bool k = false;
+    if constexpr (OFF) k = in && logit_active(x[2], thr.offset);
+    if constexpr (CLEAN) return clean_step<OFF>(__ballot(f || o), __ballot(o), OFF ? __ballot(k) : 0ull, has_onset, cl, lane, c);
+    else if constexpr (OFF) return decode_window_off(o, f || o, k, lane, c.o_prev, c.open_prev, c.k_prev, c.e_prev);
     else return decode_window(o, f || o, lane, c.o_prev, c.open_prev);
-}
-
-// decode_step<OFF, true>: the same window through the cleanup pipeline (the cleaning kernels' step; the instances above are as they
-// were).  The events are those of the window CLEAN_DELAY frames back, and flush_clean feeds the windows that bring the last ones out.
-template <bool OFF, bool CLEAN, int NCH>
-__device__ __forceinline__ WindowEvents decode_step(bool in, const float (&x)[NCH], bool has_onset, const NoteThr& thr, int lane,
-                                                    DecodeCarry<OFF, CLEAN>& c, const NoteClean& cl) {
-    static_assert(CLEAN && NCH >= (OFF ? 3 : 2), "the cleaning step: frame, onset (and offset) logits");
-    const bool f = in && logit_active(x[0], thr.frame);
-    const bool o = has_onset ? (in && logit_active(x[1], thr.onset)) : f;
-    unsigned long long km = 0;
-    if constexpr (OFF) km = __ballot(in && logit_active(x[2], thr.offset));
-    return clean_step<OFF>(__ballot(f || o), __ballot(o), km, has_onset, cl, lane, c);
 }
 
 // The walk over a row of L frames (Index = int or long long), SLAB 64-frame windows at a time: first all of the slab's loads,
@@ -205,15 +209,18 @@ __device__ __forceinline__ void emit_open_end(const CarryOnset& c, int* __restri
     if (c.open_prev) ends[n_off] = L;
 }
 
-// The end of a cleaned row: three inactive windows after the last one that holds a frame below L, fed without a load.  The
-// first closes a note still open at a multiple of 64 (otherwise frame L of the last window has), and the third brings that
-// window's events out, so a note open at L ends at exactly L, every carry is spent and nothing is left for emit_open_end.
-template <int NCH, typename Index, typename Body>
+// The end of a cleaned row (nothing without CLEAN): three inactive windows after the last one that holds a frame below L, fed
+// without a load.  The first closes a note still open at a multiple of 64 (otherwise frame L of the last window has), and the third
+// brings that window's events out, so a note open at L ends at exactly L and every carry is spent: open_prev is 0, and what a
+// kernel does for a note open at the row's end (emit_open_end, match_finish, list_finish) finds none.
+template <bool CLEAN, int NCH, typename Index, typename Body>
 __device__ __forceinline__ void flush_clean(Index L, Body body) {
-    const float none[NCH] = {};
-    const Index g0 = (L + 63) / 64 * 64;
+    if constexpr (CLEAN) {
+        const float none[NCH] = {};
+        const Index g0 = (L + 63) / 64 * 64;
 #pragma unroll 1
-    for (int w = 0; w < 3; ++w) body(g0 + 64 * w, false, none);
+        for (int w = 0; w < 3; ++w) body(g0 + 64 * w, false, none);
+    }
 }
 
 }  // namespace mt

@@ -5,13 +5,15 @@
 //   mt_note_match_list:   the same counts against a per-row note list in ticks of 100 us (the MIDI notes), which may hold re-struck keys;
 //   mt_heads_to_notes:    the onset-gated decoder with mt_roll_to_notes' output contract (main.py's note list).
 //   mt_*_off:             the three of them with the offset-gated decoder (decode_window_off): the offset head ends notes.
-//   mt_*_clean:           the three of them, any decoder, with note cleanup (DESIGN.md 6c "Note cleanup"): short gaps bridged, short notes dropped.
+//   mt_*_clean:           the three of them, any decoder, with note cleanup (DESIGN.md 6c "Note cleanup"): short gaps bridged, short notes
+//                         dropped.  Each family is one kernel template <OFF, CLEAN>: four instances, chosen by the entry point.
 //   mt_note_sweep_*:      the two matchers for a grid of (frame, onset) thresholds in one pass; mt_note_grid_*: for a grid of every decoder
 //                         parameter -- three thresholds and the cleanup, any decoder (DESIGN.md 6c "Decoder grid").
-// One wave64 per pitch row.  The row walk, the decode step and the note emitter are note_decode.h's (walk_slabs, decode_step,
-// emit_window); a kernel here adds its addressing, where its output goes and what it does with a window's events (match_window,
-// list_window, emit).  Two kernels walk on their own: the roll matcher (its offset-gated instance is 16 % slower on the shared walk,
-// DESIGN.md 6c; it shares decode_step) and the sweep kernel, which reads ballots from LDS, not logits.
+// One wave64 per pitch row.  The row walk, the decode step with or without cleanup, the row's end and the note emitter are
+// note_decode.h's (walk_slabs, decode_step, flush_clean, emit_window); a kernel here adds its addressing, where its output goes and
+// what it does with a window's events (match_window, list_window, emit).  Two kernels walk on their own: the roll matcher without
+// cleanup (its offset-gated instance is 16 % slower on the shared walk; the window's body is the cleaning instances')
+// and the sweep kernel, which reads ballots from LDS, not logits.
 #include <type_traits>
 
 #include "mt_common.h"
@@ -21,6 +23,14 @@ namespace mt {
 
 constexpr int NOTE_SLAB = 8;              // 64-frame windows loaded ahead per lane: 3 x 8 loads in flight per wave
 constexpr int NOTE_WAVES = 4;             // waves per workgroup (one pitch row each)
+
+// This wave's index in its workgroup.  UNIFORM: provably wave-uniform, so the row and what hangs on it live in scalar registers.  The
+// roll matcher and the note emitter without cleanup do without it: their time follows the register allocation it changes.
+template <bool UNIFORM>
+__device__ __forceinline__ int wave_in_block() {
+    const int w = threadIdx.x >> 6;
+    return UNIFORM ? __builtin_amdgcn_readfirstlane(w) : w;
+}
 
 // ------------------------------------------------------------------------------------------------ matching
 // Within one pitch both note lists are disjoint runs, so onsets of one list are >= 2 frames apart and every note has at most two
@@ -161,49 +171,74 @@ __device__ __forceinline__ void counts_add(unsigned long long* c, int n_ref, int
 }
 
 // counts[b] += {n_ref, n_est, tp_onset, tp_onset_offset} of pitch row (b, p).  Frames at or past lengths[b] are inactive on both sides.
-// OFF: the offset-gated decoder with the offset head `offset` at thr_k; otherwise neither is read.
-template <bool OFF>
+// OFF: the offset-gated decoder with the offset head `offset` at thr_k; otherwise neither is read.  CLEAN: note cleanup by cl (DESIGN.md
+// 6c "Note cleanup"); otherwise cl is not read.  This holds for every decoding kernel of this file.
+template <bool OFF, bool CLEAN>
 __global__ __launch_bounds__(64 * NOTE_WAVES) void note_match_kernel(const float* __restrict__ frame, const float* __restrict__ onset,
                                                                      const float* __restrict__ offset, float thr_f, float thr_o, float thr_k,
-                                                                     const float* __restrict__ ref, const long long* __restrict__ lengths,
+                                                                     NoteClean cl, const float* __restrict__ ref,
+                                                                     const long long* __restrict__ lengths,
                                                                      unsigned long long* __restrict__ counts, int B, int P, int T) {
-    const int row = blockIdx.x * NOTE_WAVES + (threadIdx.x >> 6);
+    const int row = blockIdx.x * NOTE_WAVES + wave_in_block<CLEAN>();
     const int lane = threadIdx.x & 63;
     if (row >= B * P) return;
     const int b = row / P;
     const int L = lengths ? (int)min((long long)T, max(0ll, lengths[b])) : T;
     const size_t base = (size_t)row * T;
+    constexpr int NCH = OFF ? 4 : 3, ROLL = NCH - 1;            // frame, onset, (offset,) reference roll
+    constexpr int HOLD = decode_delay<CLEAN> / 64;              // the estimate's events come this many windows late: so do the roll's
     MatchState s;
     match_init(s);
     const NoteThr thr{thr_f, thr_o, thr_k};
-    DecodeCarry<OFF> c;
-    unsigned long long r_prev = 0;
-    // (its own walk, not walk_slabs: on the shared walk the offset-gated instance ran its long rows 16 % slower)
-    for (int s0 = 0; s0 < L; s0 += 64 * NOTE_SLAB) {
-        float xf[NOTE_SLAB], xo[NOTE_SLAB], xr[NOTE_SLAB], xk[OFF ? NOTE_SLAB : 1];
+    DecodeCarry<OFF, CLEAN> c;
+    unsigned long long r_prev = 0, rs[HOLD + 1] = {}, re[HOLD + 1] = {};      // run edges of the reference, [0] = HOLD windows back
+    // one window, for either walk: x = frame, onset, (offset,) roll of this lane's frame
+    const auto window = [&](int g0, bool in, const float(&x)[NCH]) __attribute__((always_inline)) {
+        const WindowEvents est = decode_step<OFF, CLEAN>(in, x, onset != nullptr, thr, cl, lane, c);
+        const unsigned long long rm = __ballot(in && x[ROLL] > 0.0f);
+        rs[HOLD] = rm & ~((rm << 1) | r_prev);
+        re[HOLD] = ~rm & ((rm << 1) | r_prev);
+        r_prev = rm >> 63;
+        match_window(s, est, rs[0], re[0], g0 - decode_delay<CLEAN>);
 #pragma unroll
-        for (int w = 0; w < NOTE_SLAB; ++w) {
-            const int g = s0 + 64 * w + lane;
-            const bool in = g < L;
-            xf[w] = in ? frame[base + g] : 0.0f;
-            xo[w] = (in && onset) ? onset[base + g] : 0.0f;
-            xr[w] = in ? ref[base + g] : 0.0f;
-            if constexpr (OFF) xk[w] = in ? offset[base + g] : 0.0f;
+        for (int k = 0; k < HOLD; ++k) {
+            rs[k] = rs[k + 1];
+            re[k] = re[k + 1];
         }
+    };
+    if constexpr (CLEAN) {
+        const auto load = [&](int ch, int g) __attribute__((always_inline)) {
+            if (ch == ROLL) return ref[base + g];
+            if (ch == 1) return onset ? onset[base + g] : 0.0f;
+            return (ch == 0 ? frame : offset)[base + g];
+        };
+        walk_slabs<NOTE_SLAB, NCH>(L, lane, load, window);
+        flush_clean<CLEAN, NCH>(L, window);
+    } else {
+        // (its own walk, not walk_slabs: on the shared walk the offset-gated instance ran its long rows 16 % slower)
+        for (int s0 = 0; s0 < L; s0 += 64 * NOTE_SLAB) {
+            float xf[NOTE_SLAB], xo[NOTE_SLAB], xr[NOTE_SLAB], xk[OFF ? NOTE_SLAB : 1];
 #pragma unroll
-        for (int w = 0; w < NOTE_SLAB; ++w) {
-            const int g0 = s0 + 64 * w;
-            if (g0 >= L) break;
-            const bool in = g0 + lane < L;
-            const float x[3] = {xf[w], xo[w], xk[OFF ? w : 0]};
-            const WindowEvents est = decode_step<OFF>(in, x, onset != nullptr, thr, lane, c);
-            const unsigned long long rm = __ballot(in && xr[w] > 0.0f);
-            const unsigned long long rs = rm & ~((rm << 1) | r_prev), re = ~rm & ((rm << 1) | r_prev);
-            r_prev = rm >> 63;
-            match_window(s, est, rs, re, g0);
+            for (int w = 0; w < NOTE_SLAB; ++w) {
+                const int g = s0 + 64 * w + lane;
+                const bool in = g < L;
+                xf[w] = in ? frame[base + g] : 0.0f;
+                xo[w] = (in && onset) ? onset[base + g] : 0.0f;
+                xr[w] = in ? ref[base + g] : 0.0f;
+                if constexpr (OFF) xk[w] = in ? offset[base + g] : 0.0f;
+            }
+#pragma unroll
+            for (int w = 0; w < NOTE_SLAB; ++w) {
+                const int g0 = s0 + 64 * w;
+                if (g0 >= L) break;
+                float x[NCH] = {xf[w], xo[w]};
+                if constexpr (OFF) x[2] = xk[w];
+                x[ROLL] = xr[w];
+                window(g0, g0 + lane < L, x);
+            }
         }
     }
-    match_finish(s, c.open_prev != 0, r_prev != 0, L);
+    match_finish(s, c.open_prev != 0, r_prev != 0, L);         // (after the flush neither side is open)
     if (lane == 0) counts_add(counts + 4 * (size_t)b, s.n_ref, s.n_est, s.tp_on, s.tp_onoff);
 }
 
@@ -341,14 +376,15 @@ __device__ __forceinline__ void list_finish(ListState& s, RefCursor& r, bool est
 
 // counts[b] += {n_ref, n_est, tp_onset, tp_onset_offset} of pitch row (b, p) against the notes ref_on/ref_off[ref_ptr[row] .. ref_ptr[row+1]).
 // Frames at or past L = lengths[b] are inactive; reference notes with on >= 320 L are not read and offsets are clipped to 320 L.
-// OFF as in note_match_kernel.
-template <bool OFF>
+// OFF, CLEAN as in note_match_kernel; the cursor follows the delayed events by itself.
+template <bool OFF, bool CLEAN>
 __global__ __launch_bounds__(64 * NOTE_WAVES) void note_match_list_kernel(const float* __restrict__ frame, const float* __restrict__ onset,
                                                                           const float* __restrict__ offset, float thr_f, float thr_o, float thr_k,
-                                                                          const int* __restrict__ ref_on, const int* __restrict__ ref_off,
-                                                                          const long long* __restrict__ ref_ptr, const long long* __restrict__ lengths,
+                                                                          NoteClean cl, const int* __restrict__ ref_on,
+                                                                          const int* __restrict__ ref_off, const long long* __restrict__ ref_ptr,
+                                                                          const long long* __restrict__ lengths,
                                                                           unsigned long long* __restrict__ counts, int B, int P, int T) {
-    const int row = blockIdx.x * NOTE_WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // wave-uniform, and provably so
+    const int row = blockIdx.x * NOTE_WAVES + wave_in_block<true>();
     const int lane = threadIdx.x & 63;
     if (row >= B * P) return;
     const int b = row / P;
@@ -361,16 +397,18 @@ __global__ __launch_bounds__(64 * NOTE_WAVES) void note_match_list_kernel(const 
     ListState s;
     list_init(s);
     const NoteThr thr{thr_f, thr_o, thr_k};
-    DecodeCarry<OFF> c;
+    DecodeCarry<OFF, CLEAN> c;
+    const auto window = [&](int g0, bool in, const float(&x)[NCH]) __attribute__((always_inline)) {
+        list_window(s, r, decode_step<OFF, CLEAN>(in, x, onset != nullptr, thr, cl, lane, c), g0 - decode_delay<CLEAN>, lane, end_tick);
+    };
     walk_slabs<NOTE_SLAB, NCH>(
         L, lane,
         [&](int ch, int g) __attribute__((always_inline)) {
             if (ch == 1) return onset ? onset[base + g] : 0.0f;
             return (ch == 0 ? frame : offset)[base + g];
         },
-        [&](int g0, bool in, const float(&x)[NCH]) __attribute__((always_inline)) {
-            list_window(s, r, decode_step<OFF>(in, x, onset != nullptr, thr, lane, c), g0, lane, end_tick);
-        });
+        window);
+    flush_clean<CLEAN, NCH>(L, window);
     int tp_on, tp_onoff;
     list_finish(s, r, c.open_prev != 0, lane, end_tick, tp_on, tp_onoff);
     if (lane == 0) counts_add(counts + 4 * (size_t)b, s.n_ref, s.n_est, tp_on, tp_onoff);
@@ -380,155 +418,46 @@ __global__ __launch_bounds__(64 * NOTE_WAVES) void note_match_list_kernel(const 
 // The NB chunks of frame / onset [NB][P][T] are one recording of NB*T frames per pitch (as mt_roll_to_notes).  fill == 0: counts[p] =
 // notes of pitch p.  fill == 1: note k of pitch p goes to [sum of the lower pitches' counts + k], nothing when that exceeds capacity.
 // OFF: the offset-gated decoder; its carries cross chunk boundaries with the onset carry (the walk is over the concatenated frames).
-template <bool OFF>
+// CLEAN as in note_match_kernel.  The cleaning instances alone take onset == nullptr (the frame decoder: mt_roll_to_notes' notes,
+// cleaned) and skip a pitch without notes in the fill pass; the host refuses a null onset head for the others.
+template <bool OFF, bool CLEAN>
 __global__ __launch_bounds__(64 * NOTE_WAVES) void heads_notes_kernel(const float* __restrict__ frame, const float* __restrict__ onset,
                                                                       const float* __restrict__ offset, float thr_f, float thr_o, float thr_k,
-                                                                      int NB, int P, int T, int fill, int* __restrict__ counts,
+                                                                      NoteClean cl, int NB, int P, int T, int fill, int* __restrict__ counts,
                                                                       int* __restrict__ starts, int* __restrict__ ends, int capacity) {
-    const int p = blockIdx.x * NOTE_WAVES + (threadIdx.x >> 6);
+    const int p = blockIdx.x * NOTE_WAVES + wave_in_block<CLEAN>();
     const int lane = threadIdx.x & 63;
     if (p >= P) return;
     int out = 0;
     if (fill) {
         for (int q = 0; q < p; ++q) out += counts[q];
+        if (CLEAN && counts[p] == 0) return;
         if (out + counts[p] > capacity) return;                 // the host sees sum(counts) > capacity and retries with larger buffers
     }
     const int n = NB * T;
     constexpr int NCH = OFF ? 3 : 2;
+    const bool has_onset = !CLEAN || onset != nullptr;
     int n_on = 0, n_off = 0;
     const NoteThr thr{thr_f, thr_o, thr_k};
-    DecodeCarry<OFF> c;
+    DecodeCarry<OFF, CLEAN> c;
+    const auto window = [&](int g0, bool in, const float(&x)[NCH]) __attribute__((always_inline)) {
+        emit_window(decode_step<OFF, CLEAN>(in, x, has_onset, thr, cl, lane, c), g0 - decode_delay<CLEAN>, lane, fill != 0, starts + out,
+                    ends + out, n_on, n_off);
+    };
     walk_slabs<NOTE_SLAB, NCH>(
         n, lane,
         [&](int ch, int g) __attribute__((always_inline)) {                      // frame g of the recording is frame g - k T of chunk k
             const int k = g / T;
-            return (ch == 0 ? frame : ch == 1 ? onset : offset)[((size_t)k * P + p) * T + (g - k * T)];
+            const size_t at = ((size_t)k * P + p) * T + (g - k * T);
+            if (ch == 1) return has_onset ? onset[at] : 0.0f;
+            return (ch == 0 ? frame : offset)[at];
         },
-        [&](int g0, bool in, const float(&x)[NCH]) __attribute__((always_inline)) {
-            emit_window(decode_step<OFF>(in, x, true, thr, lane, c), g0, lane, fill != 0, starts + out, ends + out, n_on, n_off);
-        });
+        window);
+    flush_clean<CLEAN, NCH>(n, window);
     if (lane == 0) {
         if (!fill) counts[p] = n_on;
         else emit_open_end(c, ends + out, n_off, n);
     }
-}
-
-// ------------------------------------------------------------------------------------------------ the three kernels with note cleanup
-// note_match_kernel, note_match_list_kernel and heads_notes_kernel on decode_step<OFF, true>: all of them on the shared walk, which
-// flush_clean ends.  The step hands out the events of the window CLEAN_DELAY frames back, so g0 is delayed with them, and the roll
-// matcher holds the reference's run edges back by the same two windows.  After the flush no note is open on either side.
-template <bool OFF>
-__global__ __launch_bounds__(64 * NOTE_WAVES) void note_match_clean_kernel(const float* __restrict__ frame, const float* __restrict__ onset,
-                                                                           const float* __restrict__ offset, float thr_f, float thr_o, float thr_k,
-                                                                           NoteClean cl, const float* __restrict__ ref,
-                                                                           const long long* __restrict__ lengths,
-                                                                           unsigned long long* __restrict__ counts, int B, int P, int T) {
-    const int row = blockIdx.x * NOTE_WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int lane = threadIdx.x & 63;
-    if (row >= B * P) return;
-    const int b = row / P;
-    const int L = lengths ? (int)min((long long)T, max(0ll, lengths[b])) : T;
-    const size_t base = (size_t)row * T;
-    constexpr int NCH = OFF ? 4 : 3;                            // frame, onset, (offset,) reference roll
-    MatchState s;
-    match_init(s);
-    const NoteThr thr{thr_f, thr_o, thr_k};
-    DecodeCarry<OFF, true> c;
-    unsigned long long r_prev = 0, rs1 = 0, re1 = 0, rs2 = 0, re2 = 0;      // run edges of the reference one and two windows back
-    const auto body = [&](int g0, bool in, const float(&x)[NCH]) __attribute__((always_inline)) {
-        const WindowEvents est = decode_step<OFF, true>(in, x, onset != nullptr, thr, lane, c, cl);
-        const unsigned long long rm = __ballot(in && x[NCH - 1] > 0.0f);
-        const unsigned long long rs = rm & ~((rm << 1) | r_prev), re = ~rm & ((rm << 1) | r_prev);
-        r_prev = rm >> 63;
-        match_window(s, est, rs2, re2, g0 - CLEAN_DELAY);
-        rs2 = rs1;
-        re2 = re1;
-        rs1 = rs;
-        re1 = re;
-    };
-    walk_slabs<NOTE_SLAB, NCH>(
-        L, lane,
-        [&](int ch, int g) __attribute__((always_inline)) {
-            if (ch == NCH - 1) return ref[base + g];
-            if (ch == 1) return onset ? onset[base + g] : 0.0f;
-            return (ch == 0 ? frame : offset)[base + g];
-        },
-        body);
-    flush_clean<NCH>(L, body);
-    if (lane == 0) counts_add(counts + 4 * (size_t)b, s.n_ref, s.n_est, s.tp_on, s.tp_onoff);
-}
-
-template <bool OFF>
-__global__ __launch_bounds__(64 * NOTE_WAVES) void note_match_list_clean_kernel(const float* __restrict__ frame, const float* __restrict__ onset,
-                                                                                const float* __restrict__ offset, float thr_f, float thr_o,
-                                                                                float thr_k, NoteClean cl, const int* __restrict__ ref_on,
-                                                                                const int* __restrict__ ref_off, const long long* __restrict__ ref_ptr,
-                                                                                const long long* __restrict__ lengths,
-                                                                                unsigned long long* __restrict__ counts, int B, int P, int T) {
-    const int row = blockIdx.x * NOTE_WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int lane = threadIdx.x & 63;
-    if (row >= B * P) return;
-    const int b = row / P;
-    const int L = lengths ? (int)min((long long)T, max(0ll, lengths[b])) : T;
-    const int end_tick = TICKS_PER_FRAME * L;
-    const size_t base = (size_t)row * T;
-    constexpr int NCH = OFF ? 3 : 2;
-    RefCursor r;
-    cursor_open(r, ref_on, ref_off, ref_ptr, row, 0, lane);
-    ListState s;
-    list_init(s);
-    const NoteThr thr{thr_f, thr_o, thr_k};
-    DecodeCarry<OFF, true> c;
-    const auto body = [&](int g0, bool in, const float(&x)[NCH]) __attribute__((always_inline)) {
-        list_window(s, r, decode_step<OFF, true>(in, x, onset != nullptr, thr, lane, c, cl), g0 - CLEAN_DELAY, lane, end_tick);
-    };
-    walk_slabs<NOTE_SLAB, NCH>(
-        L, lane,
-        [&](int ch, int g) __attribute__((always_inline)) {
-            if (ch == 1) return onset ? onset[base + g] : 0.0f;
-            return (ch == 0 ? frame : offset)[base + g];
-        },
-        body);
-    flush_clean<NCH>(L, body);
-    int tp_on, tp_onoff;
-    list_finish(s, r, false, lane, end_tick, tp_on, tp_onoff);
-    if (lane == 0) counts_add(counts + 4 * (size_t)b, s.n_ref, s.n_est, tp_on, tp_onoff);
-}
-
-// onset == nullptr: the frame decoder (mt_roll_to_notes' notes, cleaned).
-template <bool OFF>
-__global__ __launch_bounds__(64 * NOTE_WAVES) void heads_notes_clean_kernel(const float* __restrict__ frame, const float* __restrict__ onset,
-                                                                            const float* __restrict__ offset, float thr_f, float thr_o, float thr_k,
-                                                                            NoteClean cl, int NB, int P, int T, int fill, int* __restrict__ counts,
-                                                                            int* __restrict__ starts, int* __restrict__ ends, int capacity) {
-    const int p = blockIdx.x * NOTE_WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int lane = threadIdx.x & 63;
-    if (p >= P) return;
-    int out = 0;
-    if (fill) {
-        for (int q = 0; q < p; ++q) out += counts[q];
-        if (counts[p] == 0 || out + counts[p] > capacity) return;
-    }
-    const int n = NB * T;
-    constexpr int NCH = OFF ? 3 : 2;
-    int n_on = 0, n_off = 0;
-    const NoteThr thr{thr_f, thr_o, thr_k};
-    DecodeCarry<OFF, true> c;
-    const auto body = [&](int g0, bool in, const float(&x)[NCH]) __attribute__((always_inline)) {
-        emit_window(decode_step<OFF, true>(in, x, onset != nullptr, thr, lane, c, cl), g0 - CLEAN_DELAY, lane, fill != 0, starts + out, ends + out,
-                    n_on, n_off);
-    };
-    walk_slabs<NOTE_SLAB, NCH>(
-        n, lane,
-        [&](int ch, int g) __attribute__((always_inline)) {
-            const int k = g / T;
-            const size_t at = ((size_t)k * P + p) * T + (g - k * T);
-            if (ch == 1) return onset ? onset[at] : 0.0f;
-            return (ch == 0 ? frame : offset)[at];
-        },
-        body);
-    flush_clean<NCH>(n, body);
-    if (lane == 0 && !fill) counts[p] = n_on;
 }
 
 // ------------------------------------------------------------------------------------------------ threshold sweep
@@ -710,11 +639,11 @@ __global__ __launch_bounds__(64 * SWEEP_WAVES) void note_sweep_kernel(const floa
 }
 
 // ------------------------------------------------------------------------------------------------ decoder grid
-// The counts of note_match_clean_kernel / note_match_list_clean_kernel for every cell (thr_f[i], thr_o[j], thr_k[k], clean[c]) of a grid,
+// The counts of the cleaning note_match_kernel / note_match_list_kernel for every cell (thr_f[i], thr_o[j], thr_k[k], clean[c]) of a grid,
 // in one pass over the logits (DESIGN.md 6c "Decoder grid").  The decomposition is note_sweep_kernel's: per slab wave w stages window w
 // -- one ballot per threshold and head, now the offset head too -- and then walks configurations w, w + SWEEP_WAVES, ...  Every
 // configuration runs through clean_step, whatever its cleanup ((1, 0) is the plain decoder) and whichever decoder it is (OFF: the
-// offset-gated one; onset == nullptr: the frame decoder), so the events are CLEAN_DELAY frames late as in the cleaning kernels, the
+// offset-gated one; onset == nullptr: the frame decoder), so the events are CLEAN_DELAY frames late as in the cleaning instances, the
 // roll's run edges are held back two windows (across slabs: the last two windows' edges stay in LDS), and the row ends with
 // flush_clean's three empty windows, after which nothing is open.  A configuration's state between slabs, matcher and pipeline, is
 // parked in LDS whole.
@@ -743,7 +672,7 @@ __device__ __forceinline__ void grid_init(GridState<LIST, OFF>& st) {
 }
 
 // counts[b][i][j][k][c] += the four counts of pitch row (b, p) = blockIdx.x; i < Kf, j < Ko, k < Kk, c < Kc, Kf Ko Kk Kc <= 64.
-// LIST: against ref_on / ref_off / ref_ptr as note_match_list_clean_kernel, otherwise against the roll `ref` as note_match_clean_kernel.
+// LIST: against ref_on / ref_off / ref_ptr as note_match_list_kernel, otherwise against the roll `ref` as note_match_kernel, CLEAN both.
 template <bool LIST, bool OFF>
 __global__ __launch_bounds__(64 * SWEEP_WAVES) void note_grid_kernel(const float* __restrict__ frame, const float* __restrict__ onset,
                                                                      const float* __restrict__ offset, GridArgs args, int Kf, int Ko, int Kk, int Kc,
@@ -902,14 +831,11 @@ static bool thrs_ok(const NoteThr& thr, bool onset, bool off) {
     return thr_ok(thr.frame) && (!onset || thr_ok(thr.onset)) && (!off || thr_ok(thr.offset));
 }
 
-static bool clean_ok(const NoteClean* cl) {
-    return !cl || (cl->min_frames >= 1 && cl->min_frames <= CLEAN_MAX_MIN_FRAMES && cl->bridge >= 0 && cl->bridge <= CLEAN_MAX_BRIDGE);
-}
-#define MT_REQUIRE_CLEAN(cl, who)                                                                                                      \
-    MT_REQUIRE(clean_ok(cl), MT_EINVAL, "%s: needs 1 <= min_frames <= %d and 0 <= bridge_frames <= %d", who, CLEAN_MAX_MIN_FRAMES, \
-               CLEAN_MAX_BRIDGE)
+// The instance of a decoding kernel template <OFF, CLEAN> that serves an entry point.
+#define NOTE_INSTANCE(kernel, off, clean) \
+    ((clean) ? ((off) ? kernel<true, true> : kernel<false, true>) : ((off) ? kernel<true, false> : kernel<false, false>))
 
-// cl: the cleaning kernels (the _clean entry points, whatever the two values); null: the kernels without the stage.
+// cl: the cleaning instances (the _clean entry points, whatever the two values); null: the instances without the stage.
 static int note_match(const char* who, bool off, const float* frame, const float* onset, const float* offset, NoteThr thr, const float* ref,
                       const long long* lengths, unsigned long long* counts, int B, int P, int T, mt_stream_t stream, const NoteClean* cl = nullptr) {
     MT_REQUIRE(frame && ref && counts && (!off || (onset && offset)), MT_EINVAL, "%s: null pointer", who);
@@ -919,12 +845,9 @@ static int note_match(const char* who, bool off, const float* frame, const float
     hipStream_t st = (hipStream_t)stream;
     MT_CHECK_HIP(hipMemsetAsync(counts, 0, (size_t)B * 4 * sizeof(unsigned long long), st));
     const dim3 grid((B * P + NOTE_WAVES - 1) / NOTE_WAVES), block(64 * NOTE_WAVES);
-    if (cl)
-        hipLaunchKernelGGL(off ? note_match_clean_kernel<true> : note_match_clean_kernel<false>, grid, block, 0, st, frame, onset, offset, thr.frame,
-                           thr.onset, thr.offset, *cl, ref, lengths, counts, B, P, T);
-    else
-        hipLaunchKernelGGL(off ? note_match_kernel<true> : note_match_kernel<false>, grid, block, 0, st, frame, onset, offset, thr.frame, thr.onset,
-                           thr.offset, ref, lengths, counts, B, P, T);
+    const auto kernel = NOTE_INSTANCE(note_match_kernel, off, cl != nullptr);
+    hipLaunchKernelGGL(kernel, grid, block, 0, st, frame, onset, offset, thr.frame, thr.onset, thr.offset,
+                       cl ? *cl : NoteClean{}, ref, lengths, counts, B, P, T);
     MT_CHECK_LAUNCH();
     return MT_OK;
 }
@@ -940,31 +863,25 @@ static int note_match_list(const char* who, bool off, const float* frame, const 
     hipStream_t st = (hipStream_t)stream;
     MT_CHECK_HIP(hipMemsetAsync(counts, 0, (size_t)B * 4 * sizeof(unsigned long long), st));
     const dim3 grid((B * P + NOTE_WAVES - 1) / NOTE_WAVES), block(64 * NOTE_WAVES);
-    if (cl)
-        hipLaunchKernelGGL(off ? note_match_list_clean_kernel<true> : note_match_list_clean_kernel<false>, grid, block, 0, st, frame, onset, offset,
-                           thr.frame, thr.onset, thr.offset, *cl, ref_on, ref_off, ref_ptr, lengths, counts, B, P, T);
-    else
-        hipLaunchKernelGGL(off ? note_match_list_kernel<true> : note_match_list_kernel<false>, grid, block, 0, st, frame, onset, offset, thr.frame,
-                           thr.onset, thr.offset, ref_on, ref_off, ref_ptr, lengths, counts, B, P, T);
+    const auto kernel = NOTE_INSTANCE(note_match_list_kernel, off, cl != nullptr);
+    hipLaunchKernelGGL(kernel, grid, block, 0, st, frame, onset, offset, thr.frame, thr.onset, thr.offset,
+                       cl ? *cl : NoteClean{}, ref_on, ref_off, ref_ptr, lengths, counts, B, P, T);
     MT_CHECK_LAUNCH();
     return MT_OK;
 }
 
 static int heads_notes(const char* who, bool off, const float* frame, const float* onset, const float* offset, NoteThr thr, int NB, int P, int T,
                        int* counts, int* starts, int* ends, int capacity, mt_stream_t stream, const NoteClean* cl = nullptr) {
-    // (the cleaning kernel alone decodes without an onset head: the frame decoder)
+    // (the cleaning instances alone decode without an onset head: the frame decoder)
     MT_REQUIRE(frame && (onset || (cl && !off)) && (!off || offset) && counts && starts && ends && capacity > 0, MT_EINVAL, "%s: bad arguments", who);
     MT_REQUIRE(NB > 0 && P > 0 && T > 0 && (long long)NB * T < 2147483647ll - 64 * NOTE_SLAB, MT_EINVAL, "%s: bad dims", who);
     MT_REQUIRE(thrs_ok(thr, onset != nullptr, off), MT_EINVAL, "%s: thresholds must lie in (0, 1)", who);
     MT_REQUIRE_CLEAN(cl, who);
     const dim3 grid((P + NOTE_WAVES - 1) / NOTE_WAVES), block(64 * NOTE_WAVES);
+    const auto kernel = NOTE_INSTANCE(heads_notes_kernel, off, cl != nullptr);
     for (int fill = 0; fill < 2; ++fill) {                     // count, then write
-        if (cl)
-            hipLaunchKernelGGL(off ? heads_notes_clean_kernel<true> : heads_notes_clean_kernel<false>, grid, block, 0, (hipStream_t)stream, frame,
-                               onset, offset, thr.frame, thr.onset, thr.offset, *cl, NB, P, T, fill, counts, starts, ends, capacity);
-        else
-            hipLaunchKernelGGL(off ? heads_notes_kernel<true> : heads_notes_kernel<false>, grid, block, 0, (hipStream_t)stream, frame, onset, offset,
-                               thr.frame, thr.onset, thr.offset, NB, P, T, fill, counts, starts, ends, capacity);
+        hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)stream, frame, onset, offset, thr.frame,
+                           thr.onset, thr.offset, cl ? *cl : NoteClean{}, NB, P, T, fill, counts, starts, ends, capacity);
         MT_CHECK_LAUNCH();
     }
     return MT_OK;

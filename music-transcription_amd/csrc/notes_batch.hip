@@ -4,7 +4,7 @@
 // the kernel adds 64-bit row addressing, a deeper slab and row_off as the place of a row's notes.
 // Three launches on one stream: count (one wave64 per row), an exclusive prefix of the counts in row order (64-bit), fill (one wave64
 // per row, at row_off[row]).  Frames at or past lengths[b] are never loaded.
-// mt_notes_batch_clean: the same with note cleanup (DESIGN.md 6c "Note cleanup") -- decode_step<false, true>, the row ended by flush_clean.
+// mt_notes_batch_clean: the same with note cleanup (DESIGN.md 6c "Note cleanup") -- the CLEAN instances of the same kernel template.
 #include "mt_common.h"
 #include "note_decode.h"
 
@@ -16,12 +16,14 @@ constexpr int PREFIX_THREADS = 256;
 
 // FILL = false: counts[row] = notes of the row.  FILL = true: note k of the row goes to [row_off[row] + k]; a row without notes, or one
 // whose notes would end past `capacity`, is left alone (the host sees row_off[rows] > capacity and retries with larger buffers).
-template <bool FILL>
+// CLEAN: note cleanup by cl -- a window's events arrive decode_delay frames late and the flush closes a note open at L; otherwise
+// cl is not read.
+template <bool FILL, bool CLEAN>
 __global__ __launch_bounds__(64 * BATCH_WAVES) void notes_batch_kernel(const float* __restrict__ frame, const float* __restrict__ onset,
-                                                                       float thr_f, float thr_o, const long long* __restrict__ lengths,
-                                                                       long long rows, int P, long long T, int* __restrict__ counts,
-                                                                       const long long* __restrict__ row_off, int* __restrict__ starts,
-                                                                       int* __restrict__ ends, long long capacity) {
+                                                                       float thr_f, float thr_o, NoteClean cl,
+                                                                       const long long* __restrict__ lengths, long long rows, int P, long long T,
+                                                                       int* __restrict__ counts, const long long* __restrict__ row_off,
+                                                                       int* __restrict__ starts, int* __restrict__ ends, long long capacity) {
     const long long row = (long long)blockIdx.x * BATCH_WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // wave-uniform
     const int lane = threadIdx.x & 63;
     if (row >= rows) return;
@@ -37,49 +39,18 @@ __global__ __launch_bounds__(64 * BATCH_WAVES) void notes_batch_kernel(const flo
     const float* __restrict__ xo_row = onset ? onset + (size_t)row * (size_t)T : nullptr;
     const NoteThr thr{thr_f, thr_o, 0.5f};
     int n_on = 0, n_off = 0;
-    DecodeCarry<false> c;
+    DecodeCarry<false, CLEAN> c;
+    const auto window = [&](long long g0, bool in, const float(&x)[2]) __attribute__((always_inline)) {
+        emit_window(decode_step<false, CLEAN>(in, x, xo_row != nullptr, thr, cl, lane, c), g0 - decode_delay<CLEAN>, lane, FILL, starts + out,
+                    ends + out, n_on, n_off);
+    };
     walk_slabs<BATCH_SLAB, 2>(
-        L, lane, [&](int ch, long long g) __attribute__((always_inline)) { return ch == 0 ? xf_row[g] : xo_row ? xo_row[g] : 0.0f; },
-        [&](long long g0, bool in, const float(&x)[2]) __attribute__((always_inline)) {
-            emit_window(decode_step<false>(in, x, xo_row != nullptr, thr, lane, c), g0, lane, FILL, starts + out, ends + out, n_on, n_off);
-        });
+        L, lane, [&](int ch, long long g) __attribute__((always_inline)) { return ch == 0 ? xf_row[g] : xo_row ? xo_row[g] : 0.0f; }, window);
+    flush_clean<CLEAN, 2>(L, window);
     if (lane == 0) {
         if (!FILL) counts[row] = n_on;
         else emit_open_end(c, ends + out, n_off, (int)L);      // a note still open at the row's last valid frame ends at L
     }
-}
-
-// notes_batch_kernel with note cleanup: the events of a window arrive CLEAN_DELAY frames late and the flush closes a note open at L.
-template <bool FILL>
-__global__ __launch_bounds__(64 * BATCH_WAVES) void notes_batch_clean_kernel(const float* __restrict__ frame, const float* __restrict__ onset,
-                                                                             float thr_f, float thr_o, NoteClean cl,
-                                                                             const long long* __restrict__ lengths, long long rows, int P, long long T,
-                                                                             int* __restrict__ counts, const long long* __restrict__ row_off,
-                                                                             int* __restrict__ starts, int* __restrict__ ends, long long capacity) {
-    const long long row = (long long)blockIdx.x * BATCH_WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // wave-uniform
-    const int lane = threadIdx.x & 63;
-    if (row >= rows) return;
-    const long long b = row / P;
-    const long long L = lengths ? min(T, max(0ll, lengths[b])) : T;
-    long long out = 0;
-    if (FILL) {
-        const int c = counts[row];
-        out = row_off[row];
-        if (c == 0 || out + c > capacity) return;
-    }
-    const float* __restrict__ xf_row = frame + (size_t)row * (size_t)T;
-    const float* __restrict__ xo_row = onset ? onset + (size_t)row * (size_t)T : nullptr;
-    const NoteThr thr{thr_f, thr_o, 0.5f};
-    int n_on = 0, n_off = 0;
-    DecodeCarry<false, true> c;
-    const auto body = [&](long long g0, bool in, const float(&x)[2]) __attribute__((always_inline)) {
-        emit_window(decode_step<false, true>(in, x, xo_row != nullptr, thr, lane, c, cl), g0 - CLEAN_DELAY, lane, FILL, starts + out, ends + out,
-                    n_on, n_off);
-    };
-    walk_slabs<BATCH_SLAB, 2>(
-        L, lane, [&](int ch, long long g) __attribute__((always_inline)) { return ch == 0 ? xf_row[g] : xo_row ? xo_row[g] : 0.0f; }, body);
-    flush_clean<2>(L, body);
-    if (lane == 0 && !FILL) counts[row] = n_on;
 }
 
 // row_off[i] = counts[0] + ... + counts[i - 1] for i in [0, rows]: one workgroup, a contiguous run of rows per thread.
@@ -106,7 +77,7 @@ __global__ __launch_bounds__(PREFIX_THREADS) void notes_batch_prefix_kernel(cons
 
 using namespace mt;
 
-// cl: the cleaning kernel (mt_notes_batch_clean, whatever the two values); null: the kernel without the stage.
+// cl: the cleaning instances (mt_notes_batch_clean, whatever the two values); null: the instances without the stage.
 static int notes_batch(const char* who, const float* frame_logits, const float* onset_logits, float thr_frame, float thr_onset,
                        const long long* lengths, int B, int P, long long T, int* counts, long long* row_off, int* starts, int* ends,
                        long long capacity, mt_stream_t stream, const NoteClean* cl) {
@@ -116,27 +87,21 @@ static int notes_batch(const char* who, const float* frame_logits, const float* 
                "%s: bad dims (B, P, T > 0; B * P and T below 2^31: note frames are 32-bit)", who);
     MT_REQUIRE(thr_frame > 0.0f && thr_frame < 1.0f && (!onset_logits || (thr_onset > 0.0f && thr_onset < 1.0f)), MT_EINVAL,
                "%s: thresholds must lie in (0, 1)", who);
-    MT_REQUIRE(!cl || (cl->min_frames >= 1 && cl->min_frames <= CLEAN_MAX_MIN_FRAMES && cl->bridge >= 0 && cl->bridge <= CLEAN_MAX_BRIDGE), MT_EINVAL,
-               "%s: needs 1 <= min_frames <= %d and 0 <= bridge_frames <= %d", who, CLEAN_MAX_MIN_FRAMES, CLEAN_MAX_BRIDGE);
+    MT_REQUIRE_CLEAN(cl, who);
     hipStream_t st = (hipStream_t)stream;
     const long long rows = (long long)B * P;
     const dim3 grid((unsigned)((rows + BATCH_WAVES - 1) / BATCH_WAVES)), block(64 * BATCH_WAVES);
-    if (cl)
-        hipLaunchKernelGGL(notes_batch_clean_kernel<false>, grid, block, 0, st, frame_logits, onset_logits, thr_frame, thr_onset, *cl, lengths, rows,
-                           P, T, counts, (const long long*)nullptr, (int*)nullptr, (int*)nullptr, 0ll);
-    else
-        hipLaunchKernelGGL(notes_batch_kernel<false>, grid, block, 0, st, frame_logits, onset_logits, thr_frame, thr_onset, lengths, rows, P, T,
-                           counts, (const long long*)nullptr, (int*)nullptr, (int*)nullptr, 0ll);
+    const auto count = cl ? notes_batch_kernel<false, true> : notes_batch_kernel<false, false>;
+    const auto fill = cl ? notes_batch_kernel<true, true> : notes_batch_kernel<true, false>;
+    const NoteClean clean = cl ? *cl : NoteClean{};
+    hipLaunchKernelGGL(count, grid, block, 0, st, frame_logits, onset_logits, thr_frame, thr_onset, clean, lengths, rows, P, T, counts,
+                       (const long long*)nullptr, (int*)nullptr, (int*)nullptr, 0ll);
     MT_CHECK_LAUNCH();
     hipLaunchKernelGGL(notes_batch_prefix_kernel, dim3(1), dim3(PREFIX_THREADS), 0, st, (const int*)counts, rows, row_off);
     MT_CHECK_LAUNCH();
     if (capacity > 0) {
-        if (cl)
-            hipLaunchKernelGGL(notes_batch_clean_kernel<true>, grid, block, 0, st, frame_logits, onset_logits, thr_frame, thr_onset, *cl, lengths,
-                               rows, P, T, counts, (const long long*)row_off, starts, ends, capacity);
-        else
-            hipLaunchKernelGGL(notes_batch_kernel<true>, grid, block, 0, st, frame_logits, onset_logits, thr_frame, thr_onset, lengths, rows, P, T,
-                               counts, (const long long*)row_off, starts, ends, capacity);
+        hipLaunchKernelGGL(fill, grid, block, 0, st, frame_logits, onset_logits, thr_frame, thr_onset, clean, lengths, rows, P, T, counts,
+                           (const long long*)row_off, starts, ends, capacity);
         MT_CHECK_LAUNCH();
     }
     return MT_OK;

@@ -129,6 +129,21 @@ def check_smoothing(smooth_on=0.0, smooth_off=0.0) -> Tuple[float, float]:
     return out[0], out[1]
 
 
+def _decode(family: str, clean: Tuple[int, int], x, on, off, thrs, rest, offset_head: bool = True) -> None:
+    """Call the entry point of `family` (mt_note_match_counts, mt_note_match_list, mt_heads_to_notes, mt_notes_batch) that serves a
+    decoder call: `family` itself or, with offset logits, `family`_off at no cleanup (1, 0), `family`_clean otherwise.  thrs = the
+    (frame, onset, offset) thresholds, rest = the arguments after the heads and thresholds, the stream last (the cleanup goes before
+    it).  offset_head=False: a family without an offset head, whose _clean takes two heads as well."""
+    two, three = (ptr(x), ptr(on), *thrs[:2]), (ptr(x), ptr(on), ptr(off), *thrs)
+    if clean != (1, 0):
+        name, args = family + "_clean", (*(three if offset_head else two), *rest[:-1], *clean, rest[-1])
+    elif off is None:
+        name, args = family, (*two, *rest)
+    else:
+        name, args = family + "_off", (*three, *rest)
+    check(getattr(lib, name)(*args), name)
+
+
 def _lengths(lengths, B: int, dev) -> Optional[torch.Tensor]:
     if lengths is None:
         return None
@@ -206,15 +221,8 @@ def note_match_counts(frame_logits: torch.Tensor, ref_roll: torch.Tensor, thresh
     if smooth != (0.0, 0.0):
         x = _smoothed(x, thr, smooth, ln, False)
     counts = torch.empty(B, 4, dtype=torch.int64, device=dev)
-    rest = (ptr(ref), ptr(ln), ptr(counts), B, P, T, _lib.stream_ptr())
     with torch.cuda.device(dev):
-        if clean != (1, 0):
-            check(lib.mt_note_match_counts_clean(ptr(x), ptr(on), ptr(off), thr, othr, kthr, *rest[:-1], *clean, rest[-1]),
-                  "mt_note_match_counts_clean")
-        elif off is None:
-            check(lib.mt_note_match_counts(ptr(x), ptr(on), thr, othr, *rest), "mt_note_match_counts")
-        else:
-            check(lib.mt_note_match_counts_off(ptr(x), ptr(on), ptr(off), thr, othr, kthr, *rest), "mt_note_match_counts_off")
+        _decode("mt_note_match_counts", clean, x, on, off, (thr, othr, kthr), (ptr(ref), ptr(ln), ptr(counts), B, P, T, _lib.stream_ptr()))
     return counts
 
 
@@ -242,15 +250,9 @@ def note_match_list(frame_logits: torch.Tensor, ref_notes: Dict[str, torch.Tenso
     if smooth != (0.0, 0.0):
         x = _smoothed(x, thr, smooth, ln, False)
     counts = torch.empty(B, 4, dtype=torch.int64, device=dev)
-    rest = (ptr(r_on), ptr(r_off), ptr(r_ptr), ptr(ln), ptr(counts), B, P, T, _lib.stream_ptr())
     with torch.cuda.device(dev):
-        if clean != (1, 0):
-            check(lib.mt_note_match_list_clean(ptr(x), ptr(on), ptr(off), thr, othr, kthr, *rest[:-1], *clean, rest[-1]),
-                  "mt_note_match_list_clean")
-        elif off is None:
-            check(lib.mt_note_match_list(ptr(x), ptr(on), thr, othr, *rest), "mt_note_match_list")
-        else:
-            check(lib.mt_note_match_list_off(ptr(x), ptr(on), ptr(off), thr, othr, kthr, *rest), "mt_note_match_list_off")
+        _decode("mt_note_match_list", clean, x, on, off, (thr, othr, kthr),
+                (ptr(r_on), ptr(r_off), ptr(r_ptr), ptr(ln), ptr(counts), B, P, T, _lib.stream_ptr()))
     return counts
 
 
@@ -423,15 +425,9 @@ def heads_to_notes_device(frame_logits: torch.Tensor, onset_logits: Optional[tor
     cap = max(1024, NB * 64)
     while True:
         starts, ends = torch.empty(cap, dtype=torch.int32, device=dev), torch.empty(cap, dtype=torch.int32, device=dev)
-        rest = (NB, P, T, ptr(counts), ptr(starts), ptr(ends), cap, _lib.stream_ptr())
         with torch.cuda.device(dev):
-            if clean != (1, 0):
-                check(lib.mt_heads_to_notes_clean(ptr(x), ptr(on), ptr(off), thr, othr, kthr, *rest[:-1], *clean, rest[-1]),
-                      "mt_heads_to_notes_clean")
-            elif off is None:
-                check(lib.mt_heads_to_notes(ptr(x), ptr(on), thr, othr, *rest), "mt_heads_to_notes")
-            else:
-                check(lib.mt_heads_to_notes_off(ptr(x), ptr(on), ptr(off), thr, othr, kthr, *rest), "mt_heads_to_notes_off")
+            _decode("mt_heads_to_notes", clean, x, on, off, (thr, othr, kthr),
+                    (NB, P, T, ptr(counts), ptr(starts), ptr(ends), cap, _lib.stream_ptr()))
         c = counts.cpu().numpy()
         total = int(c.sum())
         if total <= cap:
@@ -467,11 +463,8 @@ def notes_batch_device(frame_logits: torch.Tensor, onset_logits: Optional[torch.
     while True:
         se = torch.empty(2, cap, dtype=torch.int32, device=dev)
         with torch.cuda.device(dev):
-            args = (ptr(x), ptr(on), thr, othr, ptr(ln), B, P, T, ptr(counts), ptr(row_off), ptr(se[0]), ptr(se[1]), cap)
-            if clean != (1, 0):
-                check(lib.mt_notes_batch_clean(*args, *clean, _lib.stream_ptr()), "mt_notes_batch_clean")
-            else:
-                check(lib.mt_notes_batch(*args, _lib.stream_ptr()), "mt_notes_batch")
+            _decode("mt_notes_batch", clean, x, on, None, (thr, othr, 0.5),
+                    (ptr(ln), B, P, T, ptr(counts), ptr(row_off), ptr(se[0]), ptr(se[1]), cap, _lib.stream_ptr()), offset_head=False)
         host = meta.cpu().numpy()
         off, c = host[:rows + 1], host[rows + 1:].view(np.int32)[:rows]
         total = int(off[rows])
