@@ -1,7 +1,8 @@
 """The LSTM layout movers of csrc/lstm.hip and csrc/lstm_bwd.hip, one by one through the C ABI: mt_lstm_unpack_f32, mt_lstm_relayout_dt /
-_ex / _bf16, mt_lstm_relayout_train, mt_lstm_dh_relayout and mt_lstm_hprev_t.  Exact comparisons only, and nothing here runs a recurrence:
-every input image is built by tests/lstm_layout_ref.py (numpy; tests/test_post_optim_ref_cpu.py checks it index by index against the
-formulas of include/mt_hip.h) from random finite f16 bit patterns that are all distinct while there are enough of them, so a misplaced
+_ex / _bf16, mt_lstm_relayout_train, mt_lstm_dh_relayout, mt_lstm_hprev_t and mt_lstm_dg_unpack.  Exact comparisons only, and nothing here runs a
+recurrence: every input image is built by tests/lstm_layout_ref.py (numpy; tests/test_post_optim_ref_cpu.py checks it index by index against the
+formulas of include/mt_hip.h; the dgx image of mt_lstm_dg_unpack by tests/lstm_rec_ref.py, checked by tests/test_lstm_rec_ref_cpu.py) from random
+finite f16 bit patterns that are all distinct while there are enough of them, so a misplaced
 element cannot equal the right one.  Batch slots >= B of an input image hold NaN; every output lies in a sentinel-filled buffer (0x7FC1 for
 16-bit words, an f32 NaN pattern for floats) between two guard bands with spare rows behind it, and is compared whole: what the contract
 does not write must still hold the sentinel.
@@ -17,6 +18,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import lstm_layout_ref as L  # noqa: E402
+import lstm_rec_ref as R  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -242,3 +244,38 @@ def test_hprev_t_exact(mta, B, T, H):
         assert HT.guards_ok() and np.array_equal(HT.bits(), want.reshape(-1)), ld
         if T == 1:
             assert (HT.bits().reshape(2, rpd, ld)[:, :H, :B] == 0).all()
+
+
+# ================================================================== mt_lstm_dg_unpack
+def _dg_unpack(lib, st, dgx, B, T, H, ldg, ldt, want_g, want_t):
+    rows_g, rows_t = T * B + SPARE_ROWS, 8 * H + SPARE_ROWS
+    dG = _Out(rows_g * ldg, 2) if want_g else None
+    dGT = _Out(rows_t * ldt, 2) if want_t else None
+    _ok(lib.mt_lstm_dg_unpack(dgx.data_ptr(), dG.ptr if dG else None, ldg, dGT.ptr if dGT else None, ldt, B, T, H, st))
+    torch.cuda.synchronize()
+    for o in (dG, dGT):
+        assert o is None or o.guards_ok()
+    return (dG.bits().reshape(rows_g, ldg) if dG else None), (dGT.bits().reshape(rows_t, ldt) if dGT else None)
+
+
+@pytest.mark.parametrize("B,T,H", [(1, 3, 16), (5, 2, 48), (16, 2, 96), (33, 2, 272), (40, 1, 16)])
+def test_dg_unpack_exact(mta, B, T, H):
+    """dG[(t B + b) ldg + d 4H + p H + j] and dGT[(d 4H + p H + j) ldt + t B + b] are the bf16 words of the dgx image, bit for bit; the dG-only and
+    dGT-only calls (how training calls it) write what the both-outputs call writes; columns >= 8H / >= T B and the spare rows keep their sentinel.
+    ldg = 8H takes the 16-byte pieces (H = 16, 48, 272: a last workgroup with 16 of its 32 units live), ldg = 8H + 4 the per-element path; ldt a
+    multiple of 8 the 16-byte columns when B is a multiple of 8 (B = 16; B = 40: a ragged second group of 8), odd ldt the per-element path"""
+    lib, st = _lib()
+    bits = L.distinct_f16_bits((B, T, 2, 4, H), 500 + B + 7 * T + H)                # any 16-bit patterns: the kernel only moves them
+    dgx = _dev(R.encode_dgx(bits, PAD16))
+    want_g = bits.transpose(1, 0, 2, 3, 4).reshape(T * B, 8 * H)                     # row t B + b, column d 4H + p H + j
+    for ldg in (8 * H, 8 * H + 4):
+        for ldt in (_roundup(T * B, 8) + 8, T * B + 3):
+            full_g = np.full((T * B + SPARE_ROWS, ldg), SENT16, dtype=np.uint16)
+            full_g[:T * B, :8 * H] = want_g
+            full_t = np.full((8 * H + SPARE_ROWS, ldt), SENT16, dtype=np.uint16)
+            full_t[:8 * H, :T * B] = want_g.T
+            dG, dGT = _dg_unpack(lib, st, dgx, B, T, H, ldg, ldt, True, True)
+            assert np.array_equal(dG, full_g) and np.array_equal(dGT, full_t), (ldg, ldt)
+            only_g, none_t = _dg_unpack(lib, st, dgx, B, T, H, ldg, ldt, True, False)
+            none_g, only_t = _dg_unpack(lib, st, dgx, B, T, H, ldg, ldt, False, True)
+            assert none_t is None and none_g is None and np.array_equal(only_g, dG) and np.array_equal(only_t, dGT), (ldg, ldt)
