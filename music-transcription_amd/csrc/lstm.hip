@@ -47,12 +47,10 @@
 // L2 -- shipped as "mode 2" through round 2.  With the interleaved batch groups below the agent-scope kernel beats it at every
 // schedule bench.py reports (7.45k against 6.75k chunks/s at its own best case, one batch per forward on three streams), so it
 // was removed in round 3 together with its placement census.)
-#include "mt_common.h"
+#include "lstm_handoff.h"
 #include <stdlib.h>
 
 namespace mt {
-
-constexpr int LSTM_SPIN_LIMIT_TICKS = 200000000;   // 2 s of the 100 MHz s_memrealtime clock
 
 struct LstmArgs {
     const float* gx;      // [NG][T][2][NKB][4][8][32]
@@ -75,15 +73,10 @@ struct LstmArgs {
     int sleep_first, sleep_retry;
 };
 
-__device__ __forceinline__ void sleep64(int n) {
-    for (int i = 0; i < n; ++i) __builtin_amdgcn_s_sleep(1);
-}
-
 // v_exp_f32 + v_rcp_f32 (1 ulp each): absolute error ~1e-7, saturate cleanly for |x| large
 __device__ __forceinline__ float sigmoidf_(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
 // tanh(x) = 2 sigmoid(2x) - 1
 __device__ __forceinline__ float tanhf_(float x) { return fmaf(2.0f, __builtin_amdgcn_rcpf(1.0f + __expf(-2.0f * x)), -1.0f); }
-constexpr int OOB_OFF = 0x7FFFFF00;           // a buffer offset beyond every resource here: such loads return 0, such stores are dropped
 constexpr unsigned H_POISON = 0xFFFFFFFFu;   // never the bit pattern of a hidden state (|h| < 1)
 constexpr int PAYLOAD_POLL_SLEEP = 10;       // s_sleep units (64 clocks) before a step's first payload poll: 8..14 measured equal, 24+ slower
 constexpr int PAYLOAD_POLL_SLEEP_BUSY = 18;  // inference with OTHER persistent launches pending on the GPU (forwards in flight on other streams: their kernels share the CUs
@@ -112,7 +105,6 @@ __device__ unsigned long long mt_lstm_diag[1024][8];
 // (vm_wait<N>: at most N younger requests may still be out; loads return in order).  `vm_settle` ties a register to the wait
 // that precedes it in program order (volatile asm statements keep their order), so no consumer can be scheduled above the wait.
 typedef __attribute__((__vector_size__(4 * sizeof(int)))) int i32x4_t;
-typedef __attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned u32x4_t;
 __device__ __forceinline__ i32x4_t raw_rsrc(const void* p, unsigned bytes) {
     const unsigned long long a = (unsigned long long)p;
     i32x4_t r;
@@ -122,11 +114,11 @@ __device__ __forceinline__ i32x4_t raw_rsrc(const void* p, unsigned bytes) {
     r[3] = 0x00020000;
     return r;
 }
-__device__ __forceinline__ void asm_load_b128_sc1(u32x4_t& dst, int voff, i32x4_t rsrc) {
+__device__ __forceinline__ void asm_load_b128_sc1(u32x4& dst, int voff, i32x4_t rsrc) {
     asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen sc1" : "=v"(dst) : "v"(voff), "s"(rsrc));
 }
 template <int N> __device__ __forceinline__ void vm_wait() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N)); }
-__device__ __forceinline__ void vm_settle(u32x4_t& v) { asm volatile("" : "+v"(v)); }
+__device__ __forceinline__ void vm_settle(u32x4& v) { asm volatile("" : "+v"(v)); }
 
 // XP = true: the layer's INPUT PROJECTION is fused in (layers fed by another LSTM layer): no gx buffer (0.5 GB written by a
 // GEMM and read back here), no projection GEMM, no re-layout pass between the layers.  x_t is read as MFMA B operands
@@ -256,7 +248,6 @@ __global__ __launch_bounds__(XP ? 256 : 320, XP ? 1 : (NKSW > 8 ? 2 : 4)) void l
     // NG > 1: the h gather of the NEXT (step, group) slot is issued right behind this slot's MFMAs, so that its round trip through
     // the memory system runs under this slot's reduce / cell / publish phases (the slot that published those bytes lies ngh - 1
     // slots back: they have usually landed; if not, the poison check sends the wave into the ordinary re-issue loop)
-    typedef __attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned u32x4;
     u32x4 hq[NKSW];
     const bool pf = NG > 1 && ngh > 1;
     int ring = 0;                                     // gring slot of the current (step, group) slot
@@ -269,7 +260,6 @@ __global__ __launch_bounds__(XP ? 256 : 320, XP ? 1 : (NKSW > 8 ? 2 : 4)) void l
         const int g = gbase + gi;
         const int Bg = min(32, a.B - g * 32);                           // valid batch rows of this group
         float& c = cst[gi];
-        const float* gx_g = a.gx + (size_t)g * gd_blocks * 1024;
         char* hx_g = (char*)a.hx + (size_t)g * gd_blocks * 512;
         // buffer resource over this group's hx (all t, both d): offsets stay < 2^31
         const __amdgpu_buffer_rsrc_t hrsrc = __builtin_amdgcn_make_buffer_rsrc(hx_g, 0, (int)(gd_blocks * 512), 0x00020000);
@@ -278,8 +268,7 @@ __global__ __launch_bounds__(XP ? 256 : 320, XP ? 1 : (NKSW > 8 ? 2 : 4)) void l
 
         // XP: x_t = the previous layer's h of step t, both directions (2H features), as MFMA B operands straight from its
         // hx images (plain loads: that buffer is complete)
-        typedef __attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned u32x4_;
-        u32x4_ xr[NKSX];
+        u32x4 xr[NKSX];
         if (XP) {
 #pragma unroll
             for (int i = 0; i < NKSX; ++i) {
@@ -554,7 +543,6 @@ __global__ __launch_bounds__(320, 4) void lstm_rec16_kernel(LstmArgs a) {
     if (tid < 128) ((unsigned*)&hs[0][0])[tid] = 0u;                      // (rows >= 16 stay zero)
     __syncthreads();
 
-    typedef __attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned u32x4;
     int ring = 0;
     for (int s = 0; s < T; ++s) {
         const int t = d ? (T - 1 - s) : s;
@@ -693,56 +681,38 @@ __global__ void lstm_unpack_kernel(const f16_t* __restrict__ hx, float* __restri
     }
 }
 
-int persistent_admit(const void* kernel, int block, size_t smem, int nwg, hipStream_t st, const char* who);   // residency.hip
-int persistent_mark(hipStream_t st);
-int persistent_cancel(hipStream_t st);
-// (a launch that fails after its admission gives the reserved CUs back)
-#define MT_CHECK_LAUNCH_OR_CANCEL()                                                                 \
-    do {                                                                                            \
-        hipError_t e_ = hipGetLastError();                                                          \
-        if (e_ != hipSuccess) {                                                                     \
-            mt::persistent_cancel(st);                                                              \
-            mt::set_error("%s:%d: persistent launch -> %s", __FILE__, __LINE__, hipGetErrorString(e_)); \
-            return MT_EHIP;                                                                         \
-        }                                                                                           \
-    } while (0)
+// plain inference with several batch groups: up to 4 groups interleaved inside one set of workgroups (see NG above)
+// (H > 512, NKSW > 8: a workgroup's W_hh slice takes 64 registers per lane and the interleaved variants would spill: one group per
+// workgroup -- those variants are not even built)
+template <int NKSW, bool G16>
+static int launch_rec_plain(const LstmArgs& a, int ngroups, hipStream_t st) {
+    const dim3 one_set(a.H >> 3, 2, 1);
+    if constexpr (NKSW <= 8) {
+        if (ngroups == 2) return persistent_launch(lstm_rec_kernel<NKSW, false, false, 2, G16>, one_set, 320, a, st, "mt_lstm_bidir_fwd");
+        if (ngroups == 3) return persistent_launch(lstm_rec_kernel<NKSW, false, false, 3, G16>, one_set, 320, a, st, "mt_lstm_bidir_fwd");
+        if (ngroups > 3) return persistent_launch(lstm_rec_kernel<NKSW, false, false, 4, G16>, dim3(a.H >> 3, 2, cdiv(ngroups, 4)), 320, a, st, "mt_lstm_bidir_fwd");
+    }
+    return persistent_launch(lstm_rec_kernel<NKSW, false, false, 1, G16>, dim3(a.H >> 3, 2, ngroups), 320, a, st, "mt_lstm_bidir_fwd");
+}
 
-// every workgroup of a persistent launch must be resident: admission check first (fails fast), completion event behind it
-#define MT_PERSISTENT_LAUNCH_N(kernel, grid, nthreads, who)                                                       \
-    do {                                                                                                          \
-        const dim3 g_ = (grid);                                                                                   \
-        int rc_ = persistent_admit((const void*)(kernel), (nthreads), 0, (int)(g_.x * g_.y * g_.z), st, who);     \
-        if (rc_ != MT_OK) return rc_;                                                                             \
-        hipLaunchKernelGGL((kernel), g_, dim3(nthreads), 0, st, a);                                               \
-        MT_CHECK_LAUNCH_OR_CANCEL();                                                                              \
-        if ((rc_ = persistent_mark(st)) != MT_OK) return rc_;                                                     \
-    } while (0)
-#define MT_PERSISTENT_LAUNCH(kernel, grid, who) MT_PERSISTENT_LAUNCH_N(kernel, grid, 256, who)
-
+// NKSW > 8 (H > 512) is a compile-time fact: no 16-column kernel, no fused projection, no interleaving -- only kernels that can be
+// launched are instantiated.  Block size: 256 for XP (no loader wave), 320 for everything else.
 template <int NKSW>
 static int launch_rec(const LstmArgs& a, int ngroups, bool g16, hipStream_t st) {
-    // B <= 16 (one batch group, at most 16 live columns): the 16-column kernel (MT_LSTM_C16=0 keeps the 32-column one)
-    static const bool c16 = !(getenv("MT_LSTM_C16") && atoi(getenv("MT_LSTM_C16")) == 0);
-    constexpr int NK16 = (NKSW + 1) / 2;                       // 32-wide k-steps per wave
-    if (c16 && !a.w_ihx && a.B <= 16 && ngroups == 1 && NKSW <= 8) {
-        if (a.cx) MT_PERSISTENT_LAUNCH_N((lstm_rec16_kernel<NK16, true, false>), dim3(a.H >> 3, 2, 1), 320, "mt_lstm_bidir_fwd_train");
-        else if (g16) MT_PERSISTENT_LAUNCH_N((lstm_rec16_kernel<NK16, false, true>), dim3(a.H >> 3, 2, 1), 320, "mt_lstm_bidir_fwd");
-        else MT_PERSISTENT_LAUNCH_N((lstm_rec16_kernel<NK16, false, false>), dim3(a.H >> 3, 2, 1), 320, "mt_lstm_bidir_fwd");
-        return MT_OK;
-    }
-    if (a.w_ihx) MT_PERSISTENT_LAUNCH((lstm_rec_kernel<NKSW, false, true>), dim3(a.H >> 3, 2, ngroups), "mt_lstm_bidir_fwd_xproj");
-    else if (a.cx) MT_PERSISTENT_LAUNCH_N((lstm_rec_kernel<NKSW, true, false>), dim3(a.H >> 3, 2, ngroups), 320, "mt_lstm_bidir_fwd_train");
-    // (H > 512: a workgroup's W_hh slice takes 64 registers per lane and the interleaved variants would spill: one group per workgroup)
-    // inference with several batch groups: up to 4 groups interleaved inside one set of workgroups (see NG above)
-#define MT_REC_PLAIN(G16_)                                                                                                              \
-    if (ngroups == 1 || NKSW > 8) MT_PERSISTENT_LAUNCH_N((lstm_rec_kernel<NKSW, false, false, 1, G16_>), dim3(a.H >> 3, 2, ngroups), 320, "mt_lstm_bidir_fwd"); \
-    else if (ngroups == 2) MT_PERSISTENT_LAUNCH_N((lstm_rec_kernel<NKSW, false, false, 2, G16_>), dim3(a.H >> 3, 2, 1), 320, "mt_lstm_bidir_fwd");       \
-    else if (ngroups == 3) MT_PERSISTENT_LAUNCH_N((lstm_rec_kernel<NKSW, false, false, 3, G16_>), dim3(a.H >> 3, 2, 1), 320, "mt_lstm_bidir_fwd");       \
-    else MT_PERSISTENT_LAUNCH_N((lstm_rec_kernel<NKSW, false, false, 4, G16_>), dim3(a.H >> 3, 2, cdiv(ngroups, 4)), 320, "mt_lstm_bidir_fwd");
-    else if (g16) { MT_REC_PLAIN(true) }
-    else { MT_REC_PLAIN(false) }
-#undef MT_REC_PLAIN
-    return MT_OK;
+    const dim3 per_group(a.H >> 3, 2, ngroups);
+    if constexpr (NKSW <= 8) {
+        // B <= 16 (one batch group, at most 16 live columns): the 16-column kernel (MT_LSTM_C16=0 keeps the 32-column one)
+        static const bool c16 = !(getenv("MT_LSTM_C16") && atoi(getenv("MT_LSTM_C16")) == 0);
+        constexpr int NK16 = (NKSW + 1) / 2;                       // 32-wide k-steps per wave
+        if (c16 && !a.w_ihx && a.B <= 16 && ngroups == 1) {
+            if (a.cx) return persistent_launch(lstm_rec16_kernel<NK16, true, false>, per_group, 320, a, st, "mt_lstm_bidir_fwd_train");
+            if (g16) return persistent_launch(lstm_rec16_kernel<NK16, false, true>, per_group, 320, a, st, "mt_lstm_bidir_fwd");
+            return persistent_launch(lstm_rec16_kernel<NK16, false, false>, per_group, 320, a, st, "mt_lstm_bidir_fwd");
+        }
+        if (a.w_ihx) return persistent_launch(lstm_rec_kernel<NKSW, false, true>, per_group, 256, a, st, "mt_lstm_bidir_fwd_xproj");
+    }                                  // (NKSW > 8 with w_ihx: refused by mt_lstm_bidir_fwd_xproj, H <= 512)
+    if (a.cx) return persistent_launch(lstm_rec_kernel<NKSW, true, false>, per_group, 320, a, st, "mt_lstm_bidir_fwd_train");
+    return g16 ? launch_rec_plain<NKSW, true>(a, ngroups, st) : launch_rec_plain<NKSW, false>(a, ngroups, st);
 }
 
 }  // namespace mt

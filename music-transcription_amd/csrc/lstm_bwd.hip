@@ -32,12 +32,11 @@
 // empty batch columns: 3.1 -> 2.6 ms per layer (CNNRNNModel training step 21.4 -> 19.6 ms).
 // Its per-phase clock (same tool, B = 16): sleep + gather 1.55 us (0.36 failed polls per step), fetch issue + cell math + image write 0.33,
 // barrier 0.36, LDS read + 16 MFMAs (16x16x32) + publish 0.43, dgx store 0.10: 2.77 us per step, 1.22 of them the workgroup's own work.
-#include "mt_common.h"
+#include "lstm_handoff.h"
 #include <stdlib.h>
 
 namespace mt {
 
-constexpr int BPTT_SPIN_LIMIT_TICKS = 200000000;   // 2 s of the 100 MHz s_memrealtime clock
 constexpr unsigned DG_POISON = 0xFFFFFFFFu;        // two bf16 NaNs with all-ones payload: f32_to_bf16 never produces it
 
 struct LstmBwdArgs {
@@ -259,7 +258,7 @@ __global__ __launch_bounds__(512) void lstm_bptt_kernel(LstmBwdArgs a) {
                 if ((it & 255u) == 255u) {
                     const long long now = __builtin_amdgcn_s_memrealtime();
                     if (t1 == 0) t1 = now;
-                    else if (now - t1 > BPTT_SPIN_LIMIT_TICKS) {
+                    else if (now - t1 > LSTM_SPIN_LIMIT_TICKS) {
                         if (lane == 0) {
                             __hip_atomic_store(a.status, 0x40000000u + (unsigned)s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                             abort_s = 1;
@@ -524,21 +523,6 @@ __global__ void dlogits_pack_kernel(const float* __restrict__ dl, bf16_t* __rest
 
 }  // namespace mt
 
-namespace mt {
-int persistent_admit(const void* kernel, int block, size_t smem, int nwg, hipStream_t st, const char* who);   // residency.hip
-int persistent_mark(hipStream_t st);
-int persistent_cancel(hipStream_t st);
-// (a launch that fails after its admission gives the reserved CUs back)
-#define MT_CHECK_LAUNCH_OR_CANCEL()                                                                 \
-    do {                                                                                            \
-        hipError_t e_ = hipGetLastError();                                                          \
-        if (e_ != hipSuccess) {                                                                     \
-            mt::persistent_cancel(st);                                                              \
-            mt::set_error("%s:%d: persistent launch -> %s", __FILE__, __LINE__, hipGetErrorString(e_)); \
-            return MT_EHIP;                                                                         \
-        }                                                                                           \
-    } while (0)
-}
 using namespace mt;
 
 #ifdef MT_BPTT_DIAG
@@ -583,16 +567,9 @@ extern "C" int mt_lstm_bidir_bwd_ex(const float* gates, const float* cx, const f
     MT_REQUIRE(NW * 2 * NG <= 256, MT_EUNSUPPORTED, "mt_lstm_bidir_bwd: %d workgroups must be co-resident (<= 256 CUs)", NW * 2 * NG);
     // every workgroup of this persistent launch must be resident: admission check (residency.hip), completion event behind it
     const bool one = B <= 16;                              // one cell per thread (see lstm_bptt_kernel)
-    const void* kern = NW <= 8 ? (one ? (const void*)lstm_bptt_kernel<1, true> : (const void*)lstm_bptt_kernel<1, false>)
-                               : (one ? (const void*)lstm_bptt_kernel<2, true> : (const void*)lstm_bptt_kernel<2, false>);
-    int rc = persistent_admit(kern, 512, 0, NW * 2 * NG, st, "mt_lstm_bidir_bwd");
-    if (rc != MT_OK) return rc;
-    if (NW <= 8 && one) hipLaunchKernelGGL((lstm_bptt_kernel<1, true>), grid, dim3(512), 0, st, a);
-    else if (NW <= 8) hipLaunchKernelGGL((lstm_bptt_kernel<1, false>), grid, dim3(512), 0, st, a);
-    else if (one) hipLaunchKernelGGL((lstm_bptt_kernel<2, true>), grid, dim3(512), 0, st, a);
-    else hipLaunchKernelGGL((lstm_bptt_kernel<2, false>), grid, dim3(512), 0, st, a);
-    MT_CHECK_LAUNCH_OR_CANCEL();
-    return persistent_mark(st);
+    void (*const kern)(LstmBwdArgs) = NW <= 8 ? (one ? lstm_bptt_kernel<1, true> : lstm_bptt_kernel<1, false>)
+                                              : (one ? lstm_bptt_kernel<2, true> : lstm_bptt_kernel<2, false>);
+    return persistent_launch(kern, grid, 512, a, st, "mt_lstm_bidir_bwd");
 }
 
 extern "C" int mt_lstm_bidir_bwd(const float* gates, const float* cx, const float* dh, const float* w_hh, void* dgx, void* part_ws,

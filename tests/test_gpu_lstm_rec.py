@@ -28,7 +28,7 @@ f16 / stored bf16 value landing on the other side of a rounding boundary), never
       rounding boundary.  A gate whose reference is all zero (f at T = 1: c_prev = 0) must be exactly zero.  bwd (16, 1, 9) reproduces the
       kernel-rounded model bit for bit.
 
-What is launched (read against launch_rec, lstm_fwd_impl, mt_lstm_bidir_bwd_ex).  NKSW = ceil(H / 64) rounded up to 1, 2, 4, 8 or 16: H = 16, 48 -> 1; 96, 128 -> 2; 208, 256 -> 4
+What is launched (read against launch_rec / launch_rec_plain, lstm_fwd_impl, mt_lstm_bidir_bwd_ex).  NKSW = ceil(H / 64) rounded up to 1, 2, 4, 8 or 16: H = 16, 48 -> 1; 96, 128 -> 2; 208, 256 -> 4
 (208 ragged); 272 (ragged), 512 -> 8; 528 -> 16.
   forward   B <= 16 and NKSW <= 8: lstm_rec16_kernel plain / G16 / TRAIN;  B = 17 .. 32: lstm_rec_kernel NG = 1 (plain, G16, TRAIN);
             B = 33, 70, 100: NG = 2, 3, 4 interleaved in one set of workgroups, B = 130: 4 + 1 groups in grid.z = 2 with a ragged last group;

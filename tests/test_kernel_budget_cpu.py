@@ -16,6 +16,50 @@ def _alloc(n):
     return (n + 7) // 8 * 8
 
 
+def _resources(src, out):
+    """compile one file of csrc for gfx950 to assembly; {symbol: value} of the compiler's num_vgpr / num_agpr / private_seg_size lines"""
+    subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-I" + os.path.join(ROOT, "include"), "-S", "--cuda-device-only",
+                    os.path.join(CSRC, src), "-o", str(out)], check=True, capture_output=True, timeout=900)
+    txt = out.read_text()
+    return tuple({m.group(1): int(m.group(2)) for m in re.finditer(r"\.set (\S+)\.%s, (\d+)" % f, txt)}
+                 for f in ("num_vgpr", "num_agpr", "private_seg_size"))
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
+def test_only_launchable_recurrence_kernels_are_built_and_none_spills(tmp_path):
+    """The dispatch (launch_rec in csrc/lstm.hip, mt_lstm_bidir_bwd_ex in csrc/lstm_bwd.hip) instantiates exactly the kernels it can
+    launch, and none of them has a private segment.  NKSW = 1, 2, 4, 8 (H <= 512): fused projection, train, and plain inference with
+    NG = 1..4 interleaved groups x {f32, f16} gx; NKSW = 16 (H > 512): train and plain NG = 1 only (no interleaving, no fused
+    projection, no 16-column kernel).  The 16-column kernel: NK = ceil(NKSW / 2) = 1, 2, 4 x {plain, f16 gx, train}.  The backward:
+    TPW = 1, 2 x {two cells, one cell per thread}."""
+    b = lambda v: "Lb%dE" % int(v)
+    rec = set()
+    for nksw in (1, 2, 4, 8, 16):
+        rec.add((nksw, True, False, 1, False))                                        # TRAIN
+        if nksw <= 8:
+            rec.add((nksw, False, True, 1, False))                                    # XP
+        for ng in ((1, 2, 3, 4) if nksw <= 8 else (1,)):
+            for g16 in (False, True):
+                rec.add((nksw, False, False, ng, g16))
+    want = {"_ZN2mt15lstm_rec_kernelILi%dE%s%sLi%dE%sEEvNS_8LstmArgsE" % (n, b(tr), b(xp), ng, b(g)) for n, tr, xp, ng, g in rec}
+    assert len(want) == 43
+    rec16 = {"_ZN2mt17lstm_rec16_kernelILi%dE%s%sEEvNS_8LstmArgsE" % (nk, b(tr), b(g)) for nk in (1, 2, 4)
+             for tr, g in ((False, False), (False, True), (True, False))}
+    assert len(rec16) == 9
+    bptt = {"_ZN2mt16lstm_bptt_kernelILi%dE%sEEvNS_11LstmBwdArgsE" % (tpw, b(one)) for tpw in (1, 2) for one in (False, True)}
+    want |= rec16 | bptt
+    v, a, scratch = {}, {}, {}
+    for i, src in enumerate(("lstm.hip", "lstm_bwd.hip")):
+        for have, new in zip((v, a, scratch), _resources(src, tmp_path / ("%d.s" % i))):
+            have.update(new)
+    pat = re.compile(r"lstm_(rec|rec16|bptt)_kernel")
+    got = {k for k in v if pat.search(k)}
+    assert got == want, (sorted(got - want), sorted(want - got))
+    for k in sorted(want):
+        assert k in a and k in scratch, k
+        assert scratch[k] == 0, (k, scratch[k], v[k], a[k])
+
+
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
 def test_three_recurrence_workgroups_fit_a_cu(tmp_path):
     """A plain recurrence workgroup is five waves (4 compute + the gx loader).  At 128 registers a SIMD holds 4 waves, a CU 16:
