@@ -114,8 +114,22 @@ __device__ __forceinline__ i32x4_t raw_rsrc(const void* p, unsigned bytes) {
     r[3] = 0x00020000;
     return r;
 }
-__device__ __forceinline__ void asm_load_b128_sc1(u32x4& dst, int voff, i32x4_t rsrc) {
-    asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen sc1" : "=v"(dst) : "v"(voff), "s"(rsrc));
+template <int OFF> __device__ __forceinline__ void asm_load_b128_sc1(u32x4& dst, int voff, i32x4_t rsrc) {
+    asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen offset:%3 sc1" : "=v"(dst) : "v"(voff), "s"(rsrc), "n"(OFF));
+}
+// the NKSW loads of one h gather.  K-step i of the wave lies i KB behind the lane's offset `voff` into the (step, direction) image
+// that `rsrc` covers: the first 4 KB go into the instruction's immediate offset, the rest into a second address register -- two
+// registers per gather, not one per k-step.
+template <int NKSW, int I = 0> __device__ __forceinline__ void asm_gather_sc1(u32x4 (&hq)[NKSW], int voff, i32x4_t rsrc) {
+    if constexpr (I < NKSW) {
+        asm_load_b128_sc1<(I & 3) * 1024>(hq[I], voff + (I >> 2) * 4096, rsrc);
+        asm_gather_sc1<NKSW, I + 1>(hq, voff, rsrc);
+    }
+}
+// the low word of s_memrealtime (wraps after 43 s, far beyond the spin limit), never 0, as a value the compiler knows to be wave-uniform:
+// the spin clock is then scalar arithmetic throughout (a 64-bit signed compare would go through the vector ALU and its registers)
+__device__ __forceinline__ unsigned spin_clock() {
+    return (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)__builtin_amdgcn_s_memrealtime()) | 1u;
 }
 template <int N> __device__ __forceinline__ void vm_wait() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N)); }
 __device__ __forceinline__ void vm_settle(u32x4& v) { asm volatile("" : "+v"(v)); }
@@ -136,8 +150,13 @@ template <int NKSW, bool TRAIN = false, bool XP = false, int NG = 1, bool G16 = 
 // 4 waves per SIMD): a workgroup is five waves, so three workgroups share a CU (43 CUs per launch at H = 512) and the GEMMs of
 // other forwards in flight get the rest of the chip -- capped at two or one per CU the default schedule loses 15 %
 // (tests/test_kernel_budget_cpu.py pins the bound).
+// FOUR per CU is a measured dead end (profiles/lstm_pack4_*.txt): bound to 96 registers (5 waves per SIMD, 32 CUs per
+// launch) the f16-gx instances compile without scratch, but a launch under load runs 5.45 instead of 4.75 ms, the GEMMs gain nothing from
+// the 11 CUs, and the default schedule loses 3 %.  The bound stays at 4 waves per SIMD, where these instances take about 100 registers.
 __global__ __launch_bounds__(XP ? 256 : 320, XP ? 1 : (NKSW > 8 ? 2 : 4)) void lstm_rec_kernel(LstmArgs a) {
     __shared__ __attribute__((aligned(16))) float red[4][64][20];       // [k-slice wave][lane][16 regs + pad]: 80-B lane stride, conflict-free b128
+    // (NG > 1: the four pad words of red[wv][lane] are thread (wv, lane)'s own -- they hold its cell state of every batch group between that
+    //  group's slots, read beside the partial sums and written back behind the cell update: NG registers less across the whole step)
     __shared__ __attribute__((aligned(16))) f16_t hs[32][8];           // [batch][unit]
     // Without the fused projection the workgroup has a FIFTH wave that does nothing but bring the gate pre-activations in: the 4-KB
     // gx block of every (step, group) slot goes from HBM straight into this ring by LDS-DMA, GX_RING - 1 slots ahead of its use.
@@ -147,7 +166,7 @@ __global__ __launch_bounds__(XP ? 256 : 320, XP ? 1 : (NKSW > 8 ? 2 : 4)) void l
     constexpr int GX_DMA = G16 ? 2 : 4;               // DMA instructions (1 KB each) per slot
     __shared__ __attribute__((aligned(16))) float gring[GX_RING][XP ? 4 : (G16 ? 512 : 1024)];      // (G16: 1024 f16 per slot)
     __shared__ int abort_s;
-    const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
+    const int tid = threadIdx.x, wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;   // (the wave index as a scalar: what depends on it alone stays out of the VGPRs)
     const int H = a.H, T = a.T, nkb = H >> 3, nks = H >> 4;
     const int kb = blockIdx.x, d = blockIdx.y, gbase = blockIdx.z * NG + a.g0;
     const int ngh = min(NG, a.g0 + a.ngl - gbase);   // batch groups this workgroup carries
@@ -229,9 +248,12 @@ __global__ __launch_bounds__(XP ? 256 : 320, XP ? 1 : (NKSW > 8 ? 2 : 4)) void l
 
     // this thread's cell: unit jl = 2*wv + hh of the workgroup, batch row b
     const int jl = 2 * wv + hh;
-    float cst[NG];                                   // cell state, one per batch group
+    float cst[NG];                                   // cell state, one per batch group (NG > 1: at home in LDS, see `red`)
 #pragma unroll
-    for (int gi = 0; gi < NG; ++gi) cst[gi] = 0.0f;
+    for (int gi = 0; gi < NG; ++gi) {
+        cst[gi] = 0.0f;
+        if (NG > 1) red[wv][lane][16 + gi] = 0.0f;
+    }
     float bias4[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     if (XP) {
 #pragma unroll
@@ -250,7 +272,9 @@ __global__ __launch_bounds__(XP ? 256 : 320, XP ? 1 : (NKSW > 8 ? 2 : 4)) void l
     // slots back: they have usually landed; if not, the poison check sends the wave into the ordinary re-issue loop)
     u32x4 hq[NKSW];
     const bool pf = NG > 1 && ngh > 1;
-    int ring = 0;                                     // gring slot of the current (step, group) slot
+    int gvoff = wv * (NKSW * 1024) + lane * 16;         // this lane's 16 bytes of the wave's first k-step inside a (step, direction) image of hx
+    asm volatile("" : "+v"(gvoff));                     // (opaque: the k-steps' constants are ADDED to it and land in the loads' immediate offsets)
+    int ring = 0;                                    // gring slot of the current (step, group) slot
     for (int s = 0; s < T; ++s) {
         const int t = d ? (T - 1 - s) : s;
         const int tprev = d ? (t + 1) : (t - 1);
@@ -259,7 +283,7 @@ __global__ __launch_bounds__(XP ? 256 : 320, XP ? 1 : (NKSW > 8 ? 2 : 4)) void l
         if (gi >= ngh) continue;                                        // (uniform over the workgroup)
         const int g = gbase + gi;
         const int Bg = min(32, a.B - g * 32);                           // valid batch rows of this group
-        float& c = cst[gi];
+        float& c = cst[NG > 1 ? 0 : gi];
         char* hx_g = (char*)a.hx + (size_t)g * gd_blocks * 512;
         // buffer resource over this group's hx (all t, both d): offsets stay < 2^31
         const __amdgpu_buffer_rsrc_t hrsrc = __builtin_amdgcn_make_buffer_rsrc(hx_g, 0, (int)(gd_blocks * 512), 0x00020000);
@@ -277,16 +301,12 @@ __global__ __launch_bounds__(XP ? 256 : 320, XP ? 1 : (NKSW > 8 ? 2 : 4)) void l
             }
         }
         float gxv[4];                                               // the loader wave's gx block (landed one barrier ago)
+        const int ring_cur = ring;
         if (XP) {
 #pragma unroll
             for (int pp = 0; pp < 4; ++pp) gxv[pp] = bias4[pp];
         } else if (G16) {
-            unsigned short raw[4];                                  // (all four reads first, then the conversions)
-#pragma unroll
-            for (int pp = 0; pp < 4; ++pp) raw[pp] = ((const unsigned short*)gring[ring])[pp * 256 + jl * 32 + b];
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int pp = 0; pp < 4; ++pp) gxv[pp] = (float)__builtin_bit_cast(f16_t, raw[pp]);
+            // f16 gx: read behind the reduce barrier, beside the partial sums (below) -- four registers less across the gather and the MFMAs
         } else {
 #pragma unroll
             for (int pp = 0; pp < 4; ++pp) gxv[pp] = gring[ring][pp * 256 + jl * 32 + b];
@@ -311,16 +331,19 @@ __global__ __launch_bounds__(XP ? 256 : 320, XP ? 1 : (NKSW > 8 ? 2 : 4)) void l
             }
             // ---- gather h_{t-1} (one 16-B sc1 load per lane per k-step) and run the f16 MFMA chain (f32 accumulate).
             //      A word still holding the poison pattern means its store has not landed: redo (rare, bounded).
-            const int hbase = ((tprev * 2 + d) * nkb) * 512 + lane * 16;
-            long long t1 = 0;
-            const i32x4_t hr = raw_rsrc(hx_g, (unsigned)(gd_blocks * 512));
+            //      The gather reads through a buffer over the (tprev, d) image alone (nks k-steps of 1 KB): a k-step beyond nks is out of
+            //      its range and returns 0 without a per-k-step address select, and the lane's offset `gvoff` is the same in every step.
+            const char* himg = hx_g + (size_t)((tprev * 2 + d) * nkb) * 512;
+            unsigned t1 = 0;
+            int gave_up = 0;                             // 1: the abort word was raised elsewhere, 2: this wave's spin ran out
+            const i32x4_t hr = raw_rsrc(himg, (unsigned)(nkb * 512));
+            const __amdgpu_buffer_rsrc_t hr1 = __builtin_amdgcn_make_buffer_rsrc((void*)himg, 0, nkb * 512, 0x00020000);
             for (unsigned it = 0;; ++it) {
                 if (!pf || it > 0) {
+                    if constexpr (NG > 1) asm_gather_sc1<NKSW>(hq, gvoff, hr);
+                    else {
 #pragma unroll
-                    for (int i = 0; i < NKSW; ++i) {
-                        const int ks = wv * NKSW + i;
-                        if (NG > 1) asm_load_b128_sc1(hq[i], (ks < nks) ? hbase + ks * 1024 : OOB_OFF, hr);
-                        else hq[i] = __builtin_amdgcn_raw_buffer_load_b128(hrsrc, (ks < nks) ? hbase + ks * 1024 : OOB_OFF, 0, 16 /*sc1*/);
+                        for (int i = 0; i < NKSW; ++i) hq[i] = __builtin_amdgcn_raw_buffer_load_b128(hr1, gvoff + i * 1024, 0, 16 /*sc1*/);
                     }
                 }
                 if (NG > 1) {
@@ -357,21 +380,24 @@ __global__ __launch_bounds__(XP ? 256 : 320, XP ? 1 : (NKSW > 8 ? 2 : 4)) void l
 #pragma unroll
                 for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
                 sleep64(a.sleep_retry);
-                if ((it & 63u) == 63u && __hip_atomic_load(a.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
-                    if (lane == 0) abort_s = 1;          // another workgroup gave up: leave with it
+                // (the abort word is read into a scalar: the loop's exits are wave-uniform, so its counter and its clock live in SGPRs)
+                if ((it & 63u) == 63u && __builtin_amdgcn_readfirstlane((int)__hip_atomic_load(a.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != 0) {
+                    gave_up = 1;                         // another workgroup gave up: leave with it
                     break;
                 }
                 if ((it & 255u) == 255u) {
-                    const long long now = __builtin_amdgcn_s_memrealtime();
+                    const unsigned now = spin_clock();
                     if (t1 == 0) t1 = now;
-                    else if (now - t1 > LSTM_SPIN_LIMIT_TICKS) {
-                        if (lane == 0) {
-                            __hip_atomic_store(a.status, 0x40000000u + (unsigned)s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            abort_s = 1;
-                        }
+                    else if (now - t1 > (unsigned)LSTM_SPIN_LIMIT_TICKS) {
+                        gave_up = 2;
                         break;
                     }
                 }
+            }
+            // (what one lane does about it stands behind the loop: nothing in the loop diverges, and nothing of it lives in a VGPR)
+            if (gave_up && lane == 0) {
+                if (gave_up == 2) __hip_atomic_store(a.status, 0x40000000u + (unsigned)s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                abort_s = 1;
             }
         }
         // ---- request the next slot's h: (s, gi + 1), or (s + 1, first group)
@@ -380,13 +406,8 @@ __global__ __launch_bounds__(XP ? 256 : 320, XP ? 1 : (NKSW > 8 ? 2 : 4)) void l
         if (pf) {
             if (sn > 0 && sn < T) {
                 const int tpn = d ? (T - sn) : (sn - 1);                // the step before sn, as a time index
-                const i32x4_t nr = raw_rsrc((char*)a.hx + (size_t)gn * gd_blocks * 512, (unsigned)(gd_blocks * 512));
-                const int nbase = ((tpn * 2 + d) * nkb) * 512 + lane * 16;
-#pragma unroll
-                for (int i = 0; i < NKSW; ++i) {
-                    const int ks = wv * NKSW + i;
-                    asm_load_b128_sc1(hq[i], (ks < nks) ? nbase + ks * 1024 : OOB_OFF, nr);
-                }
+                const i32x4_t nr = raw_rsrc((char*)a.hx + ((size_t)gn * gd_blocks + (size_t)((tpn * 2 + d) * nkb)) * 512, (unsigned)(nkb * 512));
+                asm_gather_sc1<NKSW>(hq, gvoff, nr);
             }
         }
 #ifdef MT_LSTM_DIAG
@@ -405,6 +426,15 @@ __global__ __launch_bounds__(XP ? 256 : 320, XP ? 1 : (NKSW > 8 ? 2 : 4)) void l
         }
         float pre[4];
         {
+            if (G16 && !XP) {
+                // (the slot's ring entry stays until the loader's next request, which lies behind this slot's publish barrier)
+                unsigned short raw[4];                              // (all four reads first, then the conversions)
+#pragma unroll
+                for (int pp = 0; pp < 4; ++pp) raw[pp] = ((const unsigned short*)gring[ring_cur])[pp * 256 + jl * 32 + b];
+#pragma unroll
+                for (int pp = 0; pp < 4; ++pp) gxv[pp] = (float)__builtin_bit_cast(f16_t, raw[pp]);
+            }
+            if (NG > 1) c = red[wv][lane][16 + gi];
             const f32x4 r0 = *(const f32x4*)(&red[0][lane][4 * wv]), r1 = *(const f32x4*)(&red[1][lane][4 * wv]);
             const f32x4 r2 = *(const f32x4*)(&red[2][lane][4 * wv]), r3 = *(const f32x4*)(&red[3][lane][4 * wv]);
 #pragma unroll
@@ -415,6 +445,7 @@ __global__ __launch_bounds__(XP ? 256 : 320, XP ? 1 : (NKSW > 8 ? 2 : 4)) void l
         const float ig = sigmoidf_(pre[0]), fg = sigmoidf_(pre[1]), gg = tanhf_(pre[2]), og = sigmoidf_(pre[3]);
         c = fmaf(fg, c, ig * gg);
         const float hval = og * tanhf_(c);
+        if (NG > 1) red[wv][lane][16 + gi] = c;
         if (TRAIN && b < Bg) {                          // saved for the backward pass (off the critical path: fire and forget)
             float* go = a.gates_out + (size_t)g * gd_blocks * 1024 + (((size_t)t * 2 + d) * nkb + kb) * 1024 + jl * 32 + b;
             go[0] = ig; go[256] = fg; go[512] = gg; go[768] = og;
@@ -431,10 +462,10 @@ __global__ __launch_bounds__(XP ? 256 : 320, XP ? 1 : (NKSW > 8 ? 2 : 4)) void l
         hs[b][jl] = (f16_t)hval;
         DIAG_STAMP(5);
         __syncthreads();                                          // pieces assembled; every wave is done with `red`
-        if (wv == 0) {
+        if (wv == 0 && lane < 32) {                                // (wave 0 issues this store whatever its lanes do: see the hand-counted wait)
             const u32x4 piece = *(const u32x4*)(&hs[b][0]);
             const int hoff = ((t * 2 + d) * nkb) * 512 + (kb >> 1) * 1024 + ((kb & 1) * 32 + b) * 16;
-            __builtin_amdgcn_raw_buffer_store_b128(piece, hrsrc, lane < 32 ? hoff : OOB_OFF, 0, 16 /*sc1: write-through*/);
+            __builtin_amdgcn_raw_buffer_store_b128(piece, hrsrc, hoff, 0, 16 /*sc1: write-through*/);
             // NO drain and no flag: a consumer that gets ahead of the payload sees the poison pattern in the words that have not
             // landed and redoes its loads (every word is written exactly once by one store, so it is either poison or final).
         }
