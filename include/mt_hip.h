@@ -540,6 +540,30 @@ int    mt_note_grid_list(const float* frame_logits, const float* onset_logits, c
                          const float* thr_onset, int Ko, const float* thr_offset, int Kk, const int* clean, int Kc, const int* ref_on,
                          const int* ref_off, const long long* ref_ptr, const long long* lengths, unsigned long long* counts, int B, int P,
                          int T, mt_stream_t stream);
+/* Frame smoothing inside the decoder grid (DESIGN.md 6c "Smoothing in the decoder grid").
+ *   mt_frame_smooth_paths: the Viterbi paths of mt_frame_smooth for K candidates (thr[k], on_penalty[k], off_penalty[k]) in one launch,
+ *     as bit masks: bit l of paths[k][row][w] (uint64 [K][B * P][W], W = (T + 63) / 64, device) is 1 iff mt_frame_smooth at candidate k
+ *     writes +64 at frame 64 w + l of that row.  Every word is written; bits at or past a row's length are 0 (a row of length 0: all
+ *     zeros).  thr, on_penalty, off_penalty: HOST arrays of K entries, 1 <= K <= 16, taken by value at the call.  work: device scratch of
+ *     the same size as paths, contents unspecified afterwards.  paths, work and frame_logits must not overlap.  lengths as
+ *     mt_frame_smooth; B * P below 2^21, T below 2^31.  A null pointer, K outside 1..16, a threshold outside (0, 1), a penalty outside
+ *     [0, 64] (NaN included), bad dims or overlapping buffers: MT_EINVAL, no launch, nothing written.  With both penalties 0 the path
+ *     is the thresholded activity, bit for bit.  One launch on `stream`; no synchronisation, allocation or copy.
+ *   mt_note_grid_counts_paths / mt_note_grid_list_paths: mt_note_grid_counts / mt_note_grid_list with a frame axis of Kf such
+ *     candidates in place of Kf thresholds: counts[b][i][j][k][c] is what the grid gives when the frame head's activity at frame t of
+ *     row r is bit t % 64 of paths[i][r][t / 64] (uint64 [Kf][B * P][(T + 63) / 64], device).  No frame logits are read.  Limits,
+ *     the other arguments and the refusals are those of mt_note_grid_counts / mt_note_grid_list. */
+int    mt_frame_smooth_paths(const float* frame_logits, const float* thr, const float* on_penalty, const float* off_penalty, int K,
+                             const long long* lengths, int B, int P, long long T, unsigned long long* paths, unsigned long long* work,
+                             mt_stream_t stream);
+int    mt_note_grid_counts_paths(const unsigned long long* paths, int Kf, const float* onset_logits, const float* offset_logits,
+                                 const float* thr_onset, int Ko, const float* thr_offset, int Kk, const int* clean, int Kc,
+                                 const float* ref_roll, const long long* lengths, unsigned long long* counts, int B, int P, int T,
+                                 mt_stream_t stream);
+int    mt_note_grid_list_paths(const unsigned long long* paths, int Kf, const float* onset_logits, const float* offset_logits,
+                               const float* thr_onset, int Ko, const float* thr_offset, int Kk, const int* clean, int Kc, const int* ref_on,
+                               const int* ref_off, const long long* ref_ptr, const long long* lengths, unsigned long long* counts, int B,
+                               int P, int T, mt_stream_t stream);
 
 /* ------------------------------------------------------------------ optimizer step (training)
  * clip_grad_norm_(max_norm) + torch.optim.Adam with coupled L2 weight decay over flat f32 buffers

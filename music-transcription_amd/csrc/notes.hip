@@ -647,6 +647,11 @@ __global__ __launch_bounds__(64 * SWEEP_WAVES) void note_sweep_kernel(const floa
 // roll's run edges are held back two windows (across slabs: the last two windows' edges stay in LDS), and the row ends with
 // flush_clean's three empty windows, after which nothing is open.  A configuration's state between slabs, matcher and pipeline, is
 // parked in LDS whole.
+// PATHS (the mt_note_grid_*_paths entry points; DESIGN.md 6c "Smoothing in the decoder grid"): entry i of the frame axis is not a threshold
+// but candidate i of mt_frame_smooth_paths' packed Viterbi paths [Kf][rows][W], whose word of a window is the mask a threshold ballot
+// would have built: lane i < Kf loads candidate i's word of the wave's window, no frame logit is read and no frame sigmoid evaluated;
+// everything after the staging step is the same code.  The body is one function for both; the two __global__ names keep the
+// instances apart.
 constexpr int GRID_MAX_CONFIGS = 64;
 constexpr int GRID_FLUSH = 3;             // flush_clean's windows
 constexpr int GRID_HOLD = CLEAN_DELAY / 64;                    // windows the reference's run edges are held back
@@ -673,13 +678,12 @@ __device__ __forceinline__ void grid_init(GridState<LIST, OFF>& st) {
 
 // counts[b][i][j][k][c] += the four counts of pitch row (b, p) = blockIdx.x; i < Kf, j < Ko, k < Kk, c < Kc, Kf Ko Kk Kc <= 64.
 // LIST: against ref_on / ref_off / ref_ptr as note_match_list_kernel, otherwise against the roll `ref` as note_match_kernel, CLEAN both.
-template <bool LIST, bool OFF>
-__global__ __launch_bounds__(64 * SWEEP_WAVES) void note_grid_kernel(const float* __restrict__ frame, const float* __restrict__ onset,
-                                                                     const float* __restrict__ offset, GridArgs args, int Kf, int Ko, int Kk, int Kc,
-                                                                     const float* __restrict__ ref, const int* __restrict__ ref_on,
-                                                                     const int* __restrict__ ref_off, const long long* __restrict__ ref_ptr,
-                                                                     const long long* __restrict__ lengths,
-                                                                     unsigned long long* __restrict__ counts, int P, int T) {
+template <bool LIST, bool OFF, bool PATHS>
+__device__ __forceinline__ void note_grid_rows(const float* __restrict__ frame, const unsigned long long* __restrict__ paths,
+                                               const float* __restrict__ onset, const float* __restrict__ offset, const GridArgs& sh, int Kf,
+                                               int Ko, int Kk, int Kc, const float* __restrict__ ref, const int* __restrict__ ref_on,
+                                               const int* __restrict__ ref_off, const long long* __restrict__ ref_ptr,
+                                               const long long* __restrict__ lengths, unsigned long long* __restrict__ counts, int P, int T) {
     using State = GridState<LIST, OFF>;
     constexpr int PARK = sizeof(State) / 4;
     __shared__ unsigned long long fmask[NOTE_SLAB][SWEEP_MAX_K], omask[NOTE_SLAB][SWEEP_MAX_K];     // [window][threshold]: active lanes
@@ -687,8 +691,8 @@ __global__ __launch_bounds__(64 * SWEEP_WAVES) void note_grid_kernel(const float
     // roll: the windows' activity; their run starts / ends at [GRID_HOLD + window], before them those of the last slab's last windows
     __shared__ unsigned long long rmask[NOTE_SLAB], rstart[GRID_HOLD + NOTE_SLAB], rend[GRID_HOLD + NOTE_SLAB];
     __shared__ int parked[GRID_MAX_CONFIGS][PARK];
-    __shared__ float thr_f[SWEEP_MAX_K], thr_o[SWEEP_MAX_K], thr_k[SWEEP_MAX_K];
-    __shared__ int cl_min[SWEEP_MAX_K], cl_bridge[SWEEP_MAX_K];
+    const float(&thr_f)[SWEEP_MAX_K] = sh.f, (&thr_o)[SWEEP_MAX_K] = sh.o, (&thr_k)[SWEEP_MAX_K] = sh.k;
+    const int(&cl_min)[SWEEP_MAX_K] = sh.min_frames, (&cl_bridge)[SWEEP_MAX_K] = sh.bridge;
     const int row = blockIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int lane = threadIdx.x & 63;
@@ -698,11 +702,14 @@ __global__ __launch_bounds__(64 * SWEEP_WAVES) void note_grid_kernel(const float
     const int end_tick = TICKS_PER_FRAME * L;
     const size_t base = (size_t)row * T;
     const int n_cfg = Kf * Ko * Kk * Kc;
-    float xf, xo, xk = 0.0f, xr = 0.0f, xb = 0.0f;             // this wave's window: frame, onset, offset, roll, roll one frame before it
+    float xf = 0.0f, xo, xk = 0.0f, xr = 0.0f, xb = 0.0f;      // this wave's window: frame, onset, offset, roll, roll one frame before it
+    unsigned long long xp = 0;                                 // PATHS: lane i < Kf holds candidate i's word of this wave's window
+    const size_t W = ((size_t)T + 63) >> 6;
     const auto load = [&](int s0) {
         const int g0 = s0 + 64 * wave, g = g0 + lane;
         const bool in = g < L;
-        xf = in ? frame[base + g] : 0.0f;
+        if constexpr (PATHS) xp = (lane < Kf && g0 < L) ? paths[((size_t)lane * gridDim.x + (size_t)row) * W + (size_t)(g0 >> 6)] : 0ull;
+        else xf = in ? frame[base + g] : 0.0f;
         xo = (in && onset) ? onset[base + g] : 0.0f;
         if constexpr (OFF) xk = in ? offset[base + g] : 0.0f;
         if (!LIST) {
@@ -711,27 +718,24 @@ __global__ __launch_bounds__(64 * SWEEP_WAVES) void note_grid_kernel(const float
         }
     };
     load(0);
-#pragma unroll
-    for (int k = 0; k < SWEEP_MAX_K; ++k)
-        if ((int)threadIdx.x == k) {
-            thr_f[k] = args.f[k];
-            thr_o[k] = args.o[k];
-            thr_k[k] = args.k[k];
-            cl_min[k] = args.min_frames[k];
-            cl_bridge[k] = args.bridge[k];
-        }
-    __syncthreads();
+    __syncthreads();                                           // sh: the kernel's arguments, staged by its first lines
     for (int s0 = 0; s0 < L; s0 += 64 * NOTE_SLAB) {
         const bool last = s0 + 64 * NOTE_SLAB >= L;
         {                                                      // stage window `wave` of the slab
             const bool in = s0 + 64 * wave + lane < L;
-            const float sf = logit_sigmoid(xf), so = logit_sigmoid(xo);
+            const float so = logit_sigmoid(xo);
+            if constexpr (PATHS) {
+                const unsigned long long inside = __ballot(in);
+                if (lane < Kf) fmask[wave][lane] = xp & inside;
+            } else {
+                const float sf = logit_sigmoid(xf);
 #pragma unroll
-            for (int i = 0; i < SWEEP_MAX_K; ++i)
-                if (i < Kf) {
-                    const unsigned long long m = __ballot(in && sf > thr_f[i]);
-                    if (lane == 0) fmask[wave][i] = m;
-                }
+                for (int i = 0; i < SWEEP_MAX_K; ++i)
+                    if (i < Kf) {
+                        const unsigned long long m = __ballot(in && sf > thr_f[i]);
+                        if (lane == 0) fmask[wave][i] = m;
+                    }
+            }
             if (onset) {
 #pragma unroll
                 for (int j = 0; j < SWEEP_MAX_K; ++j)
@@ -817,6 +821,43 @@ __global__ __launch_bounds__(64 * SWEEP_WAVES) void note_grid_kernel(const float
         }
         if (!last) __syncthreads();                            // the next slab's masks replace these
     }
+}
+
+// A kernel's by-value arguments into its LDS copy `sh` (in the kernel itself, with constant indices: they stay scalar loads of the
+// argument segment and nothing goes through scratch).
+#define GRID_STAGE_ARGS(sh, args)                         \
+    _Pragma("unroll") for (int n = 0; n < SWEEP_MAX_K; ++n) \
+        if ((int)threadIdx.x == n) {                      \
+            sh.f[n] = args.f[n];                          \
+            sh.o[n] = args.o[n];                          \
+            sh.k[n] = args.k[n];                          \
+            sh.min_frames[n] = args.min_frames[n];        \
+            sh.bridge[n] = args.bridge[n];                \
+        }
+
+template <bool LIST, bool OFF>
+__global__ __launch_bounds__(64 * SWEEP_WAVES) void note_grid_kernel(const float* __restrict__ frame, const float* __restrict__ onset,
+                                                                     const float* __restrict__ offset, GridArgs args, int Kf, int Ko, int Kk, int Kc,
+                                                                     const float* __restrict__ ref, const int* __restrict__ ref_on,
+                                                                     const int* __restrict__ ref_off, const long long* __restrict__ ref_ptr,
+                                                                     const long long* __restrict__ lengths,
+                                                                     unsigned long long* __restrict__ counts, int P, int T) {
+    __shared__ GridArgs sh;
+    GRID_STAGE_ARGS(sh, args)
+    note_grid_rows<LIST, OFF, false>(frame, nullptr, onset, offset, sh, Kf, Ko, Kk, Kc, ref, ref_on, ref_off, ref_ptr, lengths, counts, P, T);
+}
+
+template <bool LIST, bool OFF>
+__global__ __launch_bounds__(64 * SWEEP_WAVES) void note_paths_grid_kernel(const unsigned long long* __restrict__ paths,
+                                                                           const float* __restrict__ onset, const float* __restrict__ offset,
+                                                                           GridArgs args, int Kf, int Ko, int Kk, int Kc,
+                                                                           const float* __restrict__ ref, const int* __restrict__ ref_on,
+                                                                           const int* __restrict__ ref_off, const long long* __restrict__ ref_ptr,
+                                                                           const long long* __restrict__ lengths,
+                                                                           unsigned long long* __restrict__ counts, int P, int T) {
+    __shared__ GridArgs sh;
+    GRID_STAGE_ARGS(sh, args)
+    note_grid_rows<LIST, OFF, true>(nullptr, paths, onset, offset, sh, Kf, Ko, Kk, Kc, ref, ref_on, ref_off, ref_ptr, lengths, counts, P, T);
 }
 
 }  // namespace mt
@@ -960,11 +1001,13 @@ extern "C" int mt_note_sweep_list(const float* frame_logits, const float* onset_
 }
 
 // The checks the two grid entry points share; thresholds and cleanups end up in `a`, which the kernel takes by value.
-static int grid_arguments(const char* who, const float* frame, const float* onset, const float* offset, const float* thr_frame, int Kf,
-                          const float* thr_onset, int Ko, const float* thr_offset, int Kk, const int* clean, int Kc, GridArgs& a) {
+// paths: the frame axis is Kf candidates of packed paths (`frame` points at them) and has no thresholds.
+static int grid_arguments(const char* who, const void* frame, const float* onset, const float* offset, const float* thr_frame, int Kf,
+                          const float* thr_onset, int Ko, const float* thr_offset, int Kk, const int* clean, int Kc, GridArgs& a,
+                          bool paths = false) {
     MT_REQUIRE(frame, MT_EINVAL, "%s: null pointer", who);
     MT_REQUIRE(onset || !offset, MT_EINVAL, "%s: offset_logits without onset_logits (the offset-gated decoder opens its notes at onset edges)", who);
-    MT_REQUIRE(thr_frame && (thr_onset || !onset) && (thr_offset || !offset), MT_EINVAL, "%s: null threshold array", who);
+    MT_REQUIRE((thr_frame || paths) && (thr_onset || !onset) && (thr_offset || !offset), MT_EINVAL, "%s: null threshold array", who);
     const auto axis_ok = [](int K) { return K >= 1 && K <= SWEEP_MAX_K; };
     MT_REQUIRE(axis_ok(Kf) && axis_ok(Ko) && axis_ok(Kk) && axis_ok(Kc) && Kf * Ko * Kk * Kc <= GRID_MAX_CONFIGS, MT_EINVAL,
                "%s: needs 1 <= Kf, Ko, Kk, Kc <= %d and Kf * Ko * Kk * Kc <= %d, got %d, %d, %d, %d", who, SWEEP_MAX_K, GRID_MAX_CONFIGS, Kf, Ko,
@@ -973,7 +1016,7 @@ static int grid_arguments(const char* who, const float* frame, const float* onse
     MT_REQUIRE(offset || Kk == 1, MT_EINVAL, "%s: without offset logits Kk must be 1, got %d", who, Kk);
     MT_REQUIRE(clean || Kc == 1, MT_EINVAL, "%s: without a cleanup array (no cleanup: {1, 0}) Kc must be 1, got %d", who, Kc);
     for (int n = 0; n < SWEEP_MAX_K; ++n) {
-        a.f[n] = n < Kf ? thr_frame[n] : 0.5f;
+        a.f[n] = (!paths && n < Kf) ? thr_frame[n] : 0.5f;
         a.o[n] = (onset && n < Ko) ? thr_onset[n] : 0.5f;
         a.k[n] = (offset && n < Kk) ? thr_offset[n] : 0.5f;
         MT_REQUIRE(thr_ok(a.f[n]) && thr_ok(a.o[n]) && thr_ok(a.k[n]), MT_EINVAL, "%s: thresholds must lie in (0, 1)", who);
@@ -985,45 +1028,86 @@ static int grid_arguments(const char* who, const float* frame, const float* onse
     return MT_OK;
 }
 
+// Exactly one of frame (logits) and paths (packed paths, the _paths entry points) is given.
 template <bool LIST>
-static int note_grid(const char* who, const float* frame, const float* onset, const float* offset, const GridArgs& a, int Kf, int Ko, int Kk, int Kc,
-                     const float* ref, const int* ref_on, const int* ref_off, const long long* ref_ptr, const long long* lengths,
-                     unsigned long long* counts, int B, int P, int T, mt_stream_t stream) {
+static int note_grid(const char* who, const float* frame, const unsigned long long* paths, const float* onset, const float* offset,
+                     const GridArgs& a, int Kf, int Ko, int Kk, int Kc, const float* ref, const int* ref_on, const int* ref_off,
+                     const long long* ref_ptr, const long long* lengths, unsigned long long* counts, int B, int P, int T, mt_stream_t stream) {
     hipStream_t st = (hipStream_t)stream;
     MT_CHECK_HIP(hipMemsetAsync(counts, 0, (size_t)B * Kf * Ko * Kk * Kc * 4 * sizeof(unsigned long long), st));
-    const auto kernel = offset ? note_grid_kernel<LIST, true> : note_grid_kernel<LIST, false>;
-    hipLaunchKernelGGL(kernel, dim3(B * P), dim3(64 * SWEEP_WAVES), 0, st, frame, onset, offset, a, Kf, Ko, Kk, Kc, ref, ref_on, ref_off, ref_ptr,
-                       lengths, counts, P, T);
+    const dim3 grid(B * P), block(64 * SWEEP_WAVES);
+    if (paths) {
+        const auto kernel = offset ? note_paths_grid_kernel<LIST, true> : note_paths_grid_kernel<LIST, false>;
+        hipLaunchKernelGGL(kernel, grid, block, 0, st, paths, onset, offset, a, Kf, Ko, Kk, Kc, ref, ref_on, ref_off, ref_ptr, lengths, counts, P, T);
+    } else {
+        const auto kernel = offset ? note_grid_kernel<LIST, true> : note_grid_kernel<LIST, false>;
+        hipLaunchKernelGGL(kernel, grid, block, 0, st, frame, onset, offset, a, Kf, Ko, Kk, Kc, ref, ref_on, ref_off, ref_ptr, lengths, counts, P, T);
+    }
     MT_CHECK_LAUNCH();
     return MT_OK;
+}
+
+// The two reference kinds of the grid, from logits (paths == nullptr) or from packed paths (frame_logits == nullptr).
+static int note_grid_counts(const char* who, const float* frame_logits, const unsigned long long* paths, const float* onset_logits,
+                            const float* offset_logits, const float* thr_frame, int Kf, const float* thr_onset, int Ko, const float* thr_offset,
+                            int Kk, const int* clean, int Kc, const float* ref_roll, const long long* lengths, unsigned long long* counts, int B,
+                            int P, int T, mt_stream_t stream) {
+    MT_REQUIRE(ref_roll && counts, MT_EINVAL, "%s: null pointer", who);
+    MT_REQUIRE(B > 0 && P > 0 && T > 0 && (long long)B * P < 2147483647ll && T < (1 << 30), MT_EINVAL, "%s: bad dims", who);
+    GridArgs a;
+    if (const int rc = grid_arguments(who, paths ? (const void*)paths : (const void*)frame_logits, onset_logits, offset_logits, thr_frame, Kf,
+                                      thr_onset, Ko, thr_offset, Kk, clean, Kc, a, paths != nullptr))
+        return rc;
+    return note_grid<false>(who, frame_logits, paths, onset_logits, offset_logits, a, Kf, Ko, Kk, Kc, ref_roll, nullptr, nullptr, nullptr, lengths,
+                            counts, B, P, T, stream);
+}
+
+static int note_grid_list(const char* who, const float* frame_logits, const unsigned long long* paths, const float* onset_logits,
+                          const float* offset_logits, const float* thr_frame, int Kf, const float* thr_onset, int Ko, const float* thr_offset,
+                          int Kk, const int* clean, int Kc, const int* ref_on, const int* ref_off, const long long* ref_ptr,
+                          const long long* lengths, unsigned long long* counts, int B, int P, int T, mt_stream_t stream) {
+    MT_REQUIRE(ref_on && ref_off && ref_ptr && counts, MT_EINVAL, "%s: null pointer", who);
+    MT_REQUIRE(B > 0 && P > 0 && T > 0 && (long long)B * P < 2147483647ll && (long long)T * TICKS_PER_FRAME < 2147483647ll - 64 * NOTE_SLAB,
+               MT_EINVAL, "%s: bad dims (frame times must fit 31 bits of 100 us ticks)", who);
+    GridArgs a;
+    if (const int rc = grid_arguments(who, paths ? (const void*)paths : (const void*)frame_logits, onset_logits, offset_logits, thr_frame, Kf,
+                                      thr_onset, Ko, thr_offset, Kk, clean, Kc, a, paths != nullptr))
+        return rc;
+    return note_grid<true>(who, frame_logits, paths, onset_logits, offset_logits, a, Kf, Ko, Kk, Kc, nullptr, ref_on, ref_off, ref_ptr, lengths,
+                           counts, B, P, T, stream);
 }
 
 extern "C" int mt_note_grid_counts(const float* frame_logits, const float* onset_logits, const float* offset_logits, const float* thr_frame, int Kf,
                                    const float* thr_onset, int Ko, const float* thr_offset, int Kk, const int* clean, int Kc, const float* ref_roll,
                                    const long long* lengths, unsigned long long* counts, int B, int P, int T, mt_stream_t stream) {
-    MT_REQUIRE(ref_roll && counts, MT_EINVAL, "mt_note_grid_counts: null pointer");
-    MT_REQUIRE(B > 0 && P > 0 && T > 0 && (long long)B * P < 2147483647ll && T < (1 << 30), MT_EINVAL, "mt_note_grid_counts: bad dims");
-    GridArgs a;
-    if (const int rc = grid_arguments("mt_note_grid_counts", frame_logits, onset_logits, offset_logits, thr_frame, Kf, thr_onset, Ko, thr_offset, Kk,
-                                      clean, Kc, a))
-        return rc;
-    return note_grid<false>("mt_note_grid_counts", frame_logits, onset_logits, offset_logits, a, Kf, Ko, Kk, Kc, ref_roll, nullptr, nullptr, nullptr,
-                            lengths, counts, B, P, T, stream);
+    return note_grid_counts("mt_note_grid_counts", frame_logits, nullptr, onset_logits, offset_logits, thr_frame, Kf, thr_onset, Ko, thr_offset, Kk,
+                            clean, Kc, ref_roll, lengths, counts, B, P, T, stream);
 }
 
 extern "C" int mt_note_grid_list(const float* frame_logits, const float* onset_logits, const float* offset_logits, const float* thr_frame, int Kf,
                                  const float* thr_onset, int Ko, const float* thr_offset, int Kk, const int* clean, int Kc, const int* ref_on,
                                  const int* ref_off, const long long* ref_ptr, const long long* lengths, unsigned long long* counts, int B, int P,
                                  int T, mt_stream_t stream) {
-    MT_REQUIRE(ref_on && ref_off && ref_ptr && counts, MT_EINVAL, "mt_note_grid_list: null pointer");
-    MT_REQUIRE(B > 0 && P > 0 && T > 0 && (long long)B * P < 2147483647ll && (long long)T * TICKS_PER_FRAME < 2147483647ll - 64 * NOTE_SLAB,
-               MT_EINVAL, "mt_note_grid_list: bad dims (frame times must fit 31 bits of 100 us ticks)");
-    GridArgs a;
-    if (const int rc = grid_arguments("mt_note_grid_list", frame_logits, onset_logits, offset_logits, thr_frame, Kf, thr_onset, Ko, thr_offset, Kk,
-                                      clean, Kc, a))
-        return rc;
-    return note_grid<true>("mt_note_grid_list", frame_logits, onset_logits, offset_logits, a, Kf, Ko, Kk, Kc, nullptr, ref_on, ref_off, ref_ptr,
-                           lengths, counts, B, P, T, stream);
+    return note_grid_list("mt_note_grid_list", frame_logits, nullptr, onset_logits, offset_logits, thr_frame, Kf, thr_onset, Ko, thr_offset, Kk,
+                          clean, Kc, ref_on, ref_off, ref_ptr, lengths, counts, B, P, T, stream);
+}
+
+extern "C" int mt_note_grid_counts_paths(const unsigned long long* paths, int Kf, const float* onset_logits, const float* offset_logits,
+                                         const float* thr_onset, int Ko, const float* thr_offset, int Kk, const int* clean, int Kc,
+                                         const float* ref_roll, const long long* lengths, unsigned long long* counts, int B, int P, int T,
+                                         mt_stream_t stream) {
+    MT_REQUIRE(paths, MT_EINVAL, "mt_note_grid_counts_paths: null pointer");
+    return note_grid_counts("mt_note_grid_counts_paths", nullptr, paths, onset_logits, offset_logits, nullptr, Kf, thr_onset, Ko, thr_offset, Kk,
+                            clean, Kc, ref_roll, lengths, counts, B, P, T, stream);
+}
+
+extern "C" int mt_note_grid_list_paths(const unsigned long long* paths, int Kf, const float* onset_logits, const float* offset_logits,
+                                       const float* thr_onset, int Ko, const float* thr_offset, int Kk, const int* clean, int Kc, const int* ref_on,
+                                       const int* ref_off, const long long* ref_ptr, const long long* lengths, unsigned long long* counts, int B,
+                                       int P, int T, mt_stream_t stream) {
+    MT_REQUIRE(paths, MT_EINVAL, "mt_note_grid_list_paths: null pointer");
+    return note_grid_list("mt_note_grid_list_paths", nullptr, paths, onset_logits, offset_logits, nullptr, Kf, thr_onset, Ko, thr_offset, Kk, clean,
+                          Kc, ref_on, ref_off, ref_ptr, lengths, counts, B, P, T, stream);
 }
 
 extern "C" int mt_heads_to_notes(const float* frame_logits, const float* onset_logits, float thr_frame, float thr_onset, int NB, int P, int T,

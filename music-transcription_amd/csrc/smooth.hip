@@ -16,6 +16,23 @@
 // Int32 bounds: |q| <= 4096, so a frame's (c, lo, hi) lie within +-8192; a composition keeps lo / hi inside the later function's
 // [lo, hi] (within +-8192) and |c| <= 64 * 4096 = 2^18; a lane past L holds the identity (0, -2^30, 2^30), which only ever follows the
 // row's frames, so the largest intermediate is 2^30 + 2^18 < 2^31.  |d| <= 8192 throughout.
+//
+// mt_frame_smooth_paths: the same paths for up to 16 candidates (thr, on, off) at once, written as bit masks, one 64-bit word per
+// 64-frame window (DESIGN.md 6c "Smoothing in the decoder grid"): what the decoder grid reads in place of a threshold ballot.  One
+// workgroup per row, one wave64 per candidate, so the candidates' loads of the same logits meet in the compute unit's cache.
+//   forward   as above, with q from the candidate's threshold and a, b from its penalties, but nothing is stored per frame: a window
+//             leaves two words, Hi = ballot(d > b) and Dec = Hi | ballot(d <= -a), the row's last frame made decisive (Hi = d > 0).
+//             Lane j keeps the pair of window 64 m + j of the current block of 64 windows, and after the block every lane stores
+//             its own pair: Hi to paths, Dec to work, consecutive lanes to consecutive words.
+//   backward  over the blocks in reverse, 64 windows per step.  Lane j loads back the pair it stored itself (program order again:
+//             no traffic between lanes through memory).  Two ballots say which windows of the block hold a decisive frame and
+//             whether the lowest one of each is Hi; lane j's carry-in is that bit of the nearest such window above it in the
+//             block, else the carry of the block above (0 above the row, as `next`).  The lane then resolves its word alone: an
+//             undecided bit takes the lowest decisive bit above it, else the carry-in -- on the bit-reversed words that is the carry
+//             chain of one 64-bit addition (generate = Hi, propagate = ~Dec) -- masks the bits past L and stores the word to paths.
+// The arithmetic per frame is frame_smooth_kernel's, so the int32 bounds above hold unchanged: |q| <= 4096, a frame's (c, lo, hi)
+// within +-8192, |c| <= 2^18 after a window, the identity's 2^30 only ever after the row's frames, |d| <= 8192.  Words: W = ceil(T / 64)
+// per row and candidate, every one of them written (zeros past the row's last window).
 #include <math.h>
 
 #include "mt_common.h"
@@ -126,21 +143,117 @@ __global__ __launch_bounds__(64 * SMOOTH_WAVES) void frame_smooth_kernel(const f
     }
 }
 
+constexpr int SMOOTH_MAX_K = 16;           // candidates per mt_frame_smooth_paths call: one wave each, 1024 threads per workgroup
+
+struct PathArgs {                          // per candidate: threshold, its logit, the penalties in grid steps
+    float thr[SMOOTH_MAX_K], c[SMOOTH_MAX_K];
+    int a[SMOOTH_MAX_K], b[SMOOTH_MAX_K];
+};
+
+// paths / work [K][rows][W] words, rows = B * P = gridDim.x rows of a padded batch [B][P][T] with lengths; the wave is the candidate.
+__global__ __launch_bounds__(64 * SMOOTH_MAX_K) void frame_smooth_paths_kernel(const float* __restrict__ x, PathArgs args,
+                                                                               const long long* __restrict__ lengths, int P, long long T,
+                                                                               long long W, unsigned long long* __restrict__ paths,
+                                                                               unsigned long long* __restrict__ work) {
+    const long long row = blockIdx.x, rows = gridDim.x;
+    const int k = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));      // wave-uniform
+    const int lane = threadIdx.x & 63;
+    float thr = 0.5f, c = 0.0f;
+    int a = 0, b = 0;
+#pragma unroll
+    for (int i = 0; i < SMOOTH_MAX_K; ++i)                                      // (constant indices: the arguments stay in scalar registers)
+        if (k == i) {
+            thr = args.thr[i];
+            c = args.c[i];
+            a = args.a[i];
+            b = args.b[i];
+        }
+    const long long L = lengths ? min(T, max(0ll, lengths[row / P])) : T;
+    const long long n_win = (L + 63) >> 6, n_blocks = (n_win + 63) >> 6;        // windows that hold a frame; blocks of 64 windows
+    const float* xr = x + (size_t)row * (size_t)T;
+    unsigned long long* pk = paths + ((size_t)k * (size_t)rows + (size_t)row) * (size_t)W;
+    unsigned long long* wk = work + ((size_t)k * (size_t)rows + (size_t)row) * (size_t)W;
+    // forward: Hi and Dec of every window, lane j holding those of window j of the block
+    int d_prev = 0;
+    unsigned long long my_hi = 0, my_dec = 0;
+    walk_slabs<SMOOTH_SLAB, 1>(
+        L, lane, [&](int, long long g) __attribute__((always_inline)) { return xr[g]; },
+        [&](long long g0, bool in, const float(&v)[1]) __attribute__((always_inline)) {
+            ClampAdd f = {0, -SMOOTH_FAR, SMOOTH_FAR};
+            if (in) {
+                const int q = quantise(v[0], thr, c);
+                f = {q, q - a, q + b};
+            }
+            f = scan_wave(f);
+            const int d = clampi(d_prev + f.c, f.lo, f.hi);
+            d_prev = __builtin_amdgcn_readlane(d, 63);                          // (lanes past L hold the identity: d of frame L - 1)
+            unsigned long long hi = __ballot(in && d > b), dec = hi | __ballot(in && d <= -a);
+            if (L - g0 <= 64) {                                                 // the row's last frame is decisive: on iff d > 0
+                const unsigned long long last = 1ull << (int)(L - 1 - g0);
+                hi = d_prev > 0 ? hi | last : hi & ~last;
+                dec |= last;
+            }
+            const long long m = g0 >> 6;
+            const int j = (int)(m & 63);
+            if (lane == j) {
+                my_hi = hi;
+                my_dec = dec;
+            }
+            if (j == 63 || m == n_win - 1) {                                    // the block is complete, or the row is
+                const long long w = m - j + lane;
+                if (w < W) {                                                    // (words of the block past the row's last window: zeros)
+                    pk[w] = my_hi;
+                    wk[w] = my_dec;
+                }
+                my_hi = my_dec = 0;
+            }
+        });
+    // backward: 64 windows per step, blocks in reverse
+    unsigned long long carry = 0;                                               // the state below which the block above begins (none: 0)
+    for (long long blk = n_blocks - 1; blk >= 0; --blk) {
+        const long long w = blk * 64 + lane;
+        const bool have = w < n_win;
+        const unsigned long long hi = have ? pk[w] : 0ull, dec = have ? wk[w] : 0ull;
+        const bool low_hi = dec != 0ull && (hi >> (__ffsll((long long)dec) - 1) & 1ull) != 0ull;
+        const unsigned long long has = __ballot(dec != 0ull), lows = __ballot(low_hi);
+        const unsigned long long above = has & ~((2ull << lane) - 1ull);        // windows over this lane's that hold a decisive frame
+        const unsigned long long cin = above ? lows >> (__ffsll((long long)above) - 1) & 1ull : carry;
+        if (has) carry = lows >> (__ffsll((long long)has) - 1) & 1ull;
+        // bit-reversed, "the lowest decisive bit above" is "the highest below": the carry into each bit of (~dec | hi) + hi + cin
+        const unsigned long long dr = __brevll(dec), hr = __brevll(hi);
+        const unsigned long long into = (((~dr | hr) + hr + cin) ^ ~dr);
+        unsigned long long word = __brevll(hr | (~dr & into));
+        const long long left = L - (w << 6);                                    // the row's frames from this word's first on
+        if (left < 64) word &= (1ull << (int)max(left, 0ll)) - 1ull;
+        if (have) pk[w] = word;
+    }
+    for (long long w = n_blocks * 64 + lane; w < W; w += 64) pk[w] = 0ull;      // rows shorter than T: every word is written
+}
+
 }  // namespace mt
 
 using namespace mt;
+
+// The checks of a threshold and a pair of penalties, and what the kernels take of them: c = logit(thr), a, b in grid steps.
+static int smooth_candidate(const char* who, float thr, float on_penalty, float off_penalty, float& c, int& a, int& b) {
+    MT_REQUIRE(thr > 0.0f && thr < 1.0f, MT_EINVAL, "%s: the threshold must lie in (0, 1)", who);
+    MT_REQUIRE(on_penalty >= 0.0f && on_penalty <= 64.0f && off_penalty >= 0.0f && off_penalty <= 64.0f, MT_EINVAL,
+               "%s: on_penalty and off_penalty must lie in [0, 64] logits", who);
+    c = (float)log((double)thr / (1.0 - (double)thr));
+    a = (int)rintf(on_penalty * (float)SMOOTH_GRID);
+    b = (int)rintf(off_penalty * (float)SMOOTH_GRID);
+    return MT_OK;
+}
 
 // The checks and the launch the two entry points share.  n = floats of either buffer.
 template <bool CHUNKS, typename Index>
 static int frame_smooth(const char* who, const float* x, float* y, float thr, float on_penalty, float off_penalty, const long long* lengths,
                         long long rows, int P, Index T, Index NBT, size_t n, mt_stream_t stream) {
-    MT_REQUIRE(thr > 0.0f && thr < 1.0f, MT_EINVAL, "%s: the threshold must lie in (0, 1)", who);
-    MT_REQUIRE(on_penalty >= 0.0f && on_penalty <= 64.0f && off_penalty >= 0.0f && off_penalty <= 64.0f, MT_EINVAL,
-               "%s: on_penalty and off_penalty must lie in [0, 64] logits", who);
+    float c;
+    int a, b;
+    if (const int rc = smooth_candidate(who, thr, on_penalty, off_penalty, c, a, b)) return rc;
     const uintptr_t xa = (uintptr_t)x, ya = (uintptr_t)y, bytes = n * sizeof(float);
     MT_REQUIRE(xa == ya || xa + bytes <= ya || ya + bytes <= xa, MT_EINVAL, "%s: out must be frame_logits itself or not overlap it", who);
-    const float c = (float)log((double)thr / (1.0 - (double)thr));
-    const int a = (int)rintf(on_penalty * (float)SMOOTH_GRID), b = (int)rintf(off_penalty * (float)SMOOTH_GRID);
     const dim3 grid((unsigned)((rows + SMOOTH_WAVES - 1) / SMOOTH_WAVES)), block(64 * SMOOTH_WAVES);
     hipLaunchKernelGGL((frame_smooth_kernel<CHUNKS, Index>), grid, block, 0, (hipStream_t)stream, x, y, thr, c, a, b, lengths, rows, P, T, NBT);
     MT_CHECK_LAUNCH();
@@ -163,4 +276,30 @@ extern "C" int mt_frame_smooth_chunks(const float* frame_logits, float* out, flo
                "mt_frame_smooth_chunks: bad dims (NB, P, T > 0; NB * T below 2^31)");
     return frame_smooth<true, int>("mt_frame_smooth_chunks", frame_logits, out, thr, on_penalty, off_penalty, nullptr, (long long)P, P, T, NB * T,
                                    (size_t)NB * (size_t)P * (size_t)T, stream);
+}
+
+extern "C" int mt_frame_smooth_paths(const float* frame_logits, const float* thr, const float* on_penalty, const float* off_penalty, int K,
+                                     const long long* lengths, int B, int P, long long T, unsigned long long* paths, unsigned long long* work,
+                                     mt_stream_t stream) {
+    const char* who = "mt_frame_smooth_paths";
+    MT_REQUIRE(frame_logits && thr && on_penalty && off_penalty && paths && work, MT_EINVAL, "%s: null pointer", who);
+    MT_REQUIRE(K >= 1 && K <= SMOOTH_MAX_K, MT_EINVAL, "%s: needs 1 <= K <= %d candidates, got %d", who, SMOOTH_MAX_K, K);
+    // (one workgroup of 64 K threads per row: the launch's threads stay below 2^32)
+    MT_REQUIRE(B > 0 && P > 0 && T > 0 && (long long)B * P < (1ll << 21) && T < 2147483647ll, MT_EINVAL,
+               "%s: bad dims (B, P, T > 0; B * P below 2^21, T below 2^31)", who);
+    PathArgs args = {};
+    for (int k = 0; k < K; ++k) {
+        args.thr[k] = thr[k];
+        if (const int rc = smooth_candidate(who, thr[k], on_penalty[k], off_penalty[k], args.c[k], args.a[k], args.b[k])) return rc;
+    }
+    const long long rows = (long long)B * P, W = (T + 63) / 64;
+    const uintptr_t xa = (uintptr_t)frame_logits, pa = (uintptr_t)paths, wa = (uintptr_t)work;
+    const uintptr_t xn = (size_t)rows * (size_t)T * sizeof(float), wn = (size_t)K * (size_t)rows * (size_t)W * sizeof(unsigned long long);
+    const auto apart = [](uintptr_t p, uintptr_t pn, uintptr_t q, uintptr_t qn) { return p + pn <= q || q + qn <= p; };
+    MT_REQUIRE(apart(pa, wn, wa, wn) && apart(pa, wn, xa, xn) && apart(wa, wn, xa, xn), MT_EINVAL,
+               "%s: paths, work and frame_logits must not overlap", who);
+    hipLaunchKernelGGL(frame_smooth_paths_kernel, dim3((unsigned)rows), dim3(64 * K), 0, (hipStream_t)stream, frame_logits, args, lengths, P, T, W,
+                       paths, work);
+    MT_CHECK_LAUNCH();
+    return MT_OK;
 }

@@ -15,7 +15,8 @@
     evaluated once for the whole grid).  `search_note_thresholds` is the search alone, on any callable.
   * `tune_note_decoder` = the same schedule over every parameter of the note decoder at once, whichever of the three decoders it
     is: up to three thresholds (frame, onset, offset) times a list of note-cleanup candidates, one grid pass per group and round
-    (notes.note_grid_counts).  `search_note_decoder` is the search alone.
+    (notes.note_grid_counts).  `search_note_decoder` is the search alone.  `smoothings=` adds a list of frame-smoothing penalty
+    pairs to the candidates of every round: the discrete axis of the search is then cleanups x smoothings.
   * `window_overlap` (seconds, whole-file datasets): every recording runs in overlapping 30 s windows stitched on its own
     frame grid (windows.collect_logits_windows) instead of one recurrence over the whole file;
   * recordings / chunks shard over ranks with no data-path collective (parallel.py); per-sample F1 values are
@@ -361,20 +362,43 @@ def search_note_decoder(mean_f1, n_axes: int = 3, n_clean: int = 1, tune_range=(
 NOTE_DECODER_AXES = {"frame": 1, "onset": 2, "onset_offset": 3}
 
 
+def decoder_candidate(index: int, cleanups: Sequence, smoothings: Sequence):
+    """Entry `index` of the tuner's discrete axis cleanups x smoothings, cleanup-major -> (cleanup, smoothing)."""
+    if not 0 <= index < len(cleanups) * len(smoothings):
+        raise ValueError(f"index {index} outside {len(cleanups)} x {len(smoothings)} candidates")
+    return cleanups[index // len(smoothings)], smoothings[index % len(smoothings)]
+
+
+def fold_smoothings(f1: np.ndarray) -> np.ndarray:
+    """(n, Kf, Ks, Ko, Kk, Kc) values as notes.note_grid_counts(smoothings=...) orders them -> (n, Kf, Ko, Kk, Kc * Ks), the last
+    axis cleanup-major: what search_note_decoder takes with n_clean = Kc * Ks and decoder_candidate reads back."""
+    n, Kf, Ks, Ko, Kk, Kc = f1.shape
+    return np.ascontiguousarray(np.transpose(f1, (0, 1, 3, 4, 5, 2))).reshape(n, Kf, Ko, Kk, Kc * Ks)
+
+
 def tune_note_decoder(model, dataset, device="cuda", subset: Optional[int] = None, decoder: str = "onset", note_reference: str = "roll",
                       objective: str = "onset", cleanups=((1, 0),), tune_range=(0.05, 0.95), tune_step=0.1, tune_min_step=0.01,
                       tune_rounds=6, rank: int = 0, world: int = 1, log=print, window_overlap: Optional[float] = None, max_batch: int = 128,
-                      smooth_on: float = 0.0, smooth_off: float = 0.0):
+                      smooth_on: float = 0.0, smooth_off: float = 0.0, smoothings=None):
     """Every parameter of the note decoder at once, for the best mean note F1 (`objective`: "onset" or "onset_offset"; unweighted
     mean over samples, as note_metrics_dataset) by search_note_decoder: the thresholds of the heads that `decoder` reads ("frame":
     frame; "onset": frame, onset; "onset_offset": frame, onset, offset) times the candidates `cleanups`, a list of
     (min_note_frames, bridge_frames) pairs that takes part in every round.  The model runs once; every round is one
     notes.note_grid_counts call over each group of note_metrics_dataset, so each cell is what the single-configuration kernels count.
     -> (frame threshold, onset threshold or None, offset threshold or None, (min_note_frames, bridge_frames), best mean F1),
-    identical on every rank.  A candidate threshold at or past 1 decodes no note and scores 0, as in tune_note_thresholds.  Frame
-    smoothing (smooth_on, smooth_off) other than (0, 0) is refused: tuning the penalties is not part of the grid."""
-    from .notes import check_cleanup, note_grid_counts, note_prf
-    _refuse_smoothing("tune_note_decoder", smooth_on, smooth_off)
+    identical on every rank.  A candidate threshold at or past 1 decodes no note and scores 0, as in tune_note_thresholds.
+    smoothings: a list of (smooth_on, smooth_off) frame-smoothing candidates (DESIGN.md 6c "Smoothing in the decoder grid") that takes
+    part in every round as `cleanups` does: the search's discrete axis is cleanups x smoothings, cleanup-major, every round still one
+    note_grid_counts call per group, and the result is (frame threshold, onset threshold or None, offset threshold or None,
+    (min_note_frames, bridge_frames), (smooth_on, smooth_off), best mean F1).  A single smoothing (smooth_on, smooth_off) other than
+    (0, 0) is refused either way: the penalties are tuned through `smoothings`, not fixed beside the search."""
+    from .notes import _smoothing_list, check_cleanup, check_smoothing, note_grid_counts, note_prf
+    if smoothings is None:
+        _refuse_smoothing("tune_note_decoder", smooth_on, smooth_off)
+    else:
+        if check_smoothing(smooth_on, smooth_off) != (0.0, 0.0):
+            raise ValueError("tune_note_decoder: smooth_on / smooth_off cannot be combined with smoothings: the candidates are `smoothings`")
+        smoothings = _smoothing_list(smoothings)
     if decoder not in NOTE_DECODER_AXES:
         raise ValueError(f"decoder must be 'frame', 'onset' or 'onset_offset', got {decoder!r}")
     if objective not in ("onset", "onset_offset"):
@@ -394,7 +418,8 @@ def tune_note_decoder(model, dataset, device="cuda", subset: Optional[int] = Non
         if any((t <= 0.0).any() for t in axes):
             raise ValueError("tune_note_decoder: candidate thresholds must be positive (tune_range)")
         below = [np.flatnonzero(np.float32(t) < 1.0) for t in axes]
-        shape = tuple(len(t) for t in axes) + (len(cleanups),)
+        n_disc = len(cleanups) * (1 if smoothings is None else len(smoothings))
+        shape = tuple(len(t) for t in axes) + (n_disc,)
         K = int(np.prod(shape))
         local = np.zeros((len(lr),) + shape)                                               # thresholds >= 1: no notes, F1 0
         at = 0
@@ -402,13 +427,22 @@ def tune_note_decoder(model, dataset, device="cuda", subset: Optional[int] = Non
             fi, oj, kk = below
             for frame, on, ref, lengths, off in _note_groups(lr, dataset, onset, note_reference, max_batch, offset):
                 counts = note_grid_counts(frame, ref, axes[0][fi], on, axes[1][oj] if onset else None, off, axes[2][kk] if offset else None,
-                                          cleanups, lengths)
-                f1 = np.array([m[objective][2] for m in note_prf(counts)]).reshape(len(lengths), len(fi), len(oj), len(kk), len(cleanups))
+                                          cleanups, lengths, smoothings=smoothings)
+                f1 = np.array([m[objective][2] for m in note_prf(counts)])
+                if smoothings is None:
+                    f1 = f1.reshape(len(lengths), len(fi), len(oj), len(kk), len(cleanups))
+                else:
+                    f1 = fold_smoothings(f1.reshape(len(lengths), len(fi), len(smoothings), len(oj), len(kk), len(cleanups)))
                 local[at:at + len(lengths), fi[:, None, None], oj[None, :, None], kk[None, None, :]] = f1
                 at += len(lengths)
         flat_idx = [i * K + k for i in mine for k in range(K)]
         allv = gather_values(flat_idx, local.reshape(-1).tolist(), n * K)
         return np.asarray(allv).reshape((n,) + shape).mean(axis=0) if n else np.zeros(shape)
 
-    thr, othr, kthr, c, best = search_note_decoder(mean_f1, n_axes, len(cleanups), tune_range, tune_step, tune_min_step, tune_rounds, log)
-    return thr, othr, kthr, cleanups[c], best
+    if smoothings is None:
+        thr, othr, kthr, c, best = search_note_decoder(mean_f1, n_axes, len(cleanups), tune_range, tune_step, tune_min_step, tune_rounds, log)
+        return thr, othr, kthr, cleanups[c], best
+    thr, othr, kthr, d, best = search_note_decoder(mean_f1, n_axes, len(cleanups) * len(smoothings), tune_range, tune_step, tune_min_step,
+                                                   tune_rounds, log)
+    clean, smooth = decoder_candidate(d, cleanups, smoothings)
+    return thr, othr, kthr, clean, smooth, best

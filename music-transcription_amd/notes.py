@@ -23,10 +23,14 @@
     (DESIGN.md 6c "Frame smoothing"; mt_frame_smooth / mt_frame_smooth_chunks).  `smooth_on=`, `smooth_off=` (switching penalties in
     logits) on the two matchers and the two note-list calls smooth the frame head first and then proceed as above; the onset and
     offset heads are edge detectors and stay as they are.  (0, 0) is no smoothing and launches nothing.
+  * `smooth_frame_paths` = those paths for up to 16 (threshold, on, off) candidates per launch, packed 64 frames to a word
+    (mt_frame_smooth_paths), and `smoothings=` on `note_grid_counts` = a list of penalty pairs as one more axis of the grid, which
+    then reads such words as its frame axis (mt_note_grid_counts_paths / mt_note_grid_list_paths; DESIGN.md 6c "Smoothing in the
+    decoder grid").
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -185,6 +189,52 @@ def smooth_frame_logits(frame_logits: torch.Tensor, threshold: float = 0.5, on_p
     return _smoothed(x, thr, smooth, _lengths(lengths, x.shape[0], x.device), chunks).reshape(frame_logits.shape)
 
 
+SMOOTH_MAX_K = 16                                   # mt_frame_smooth_paths: candidates per call
+
+
+def _smoothing_list(smoothings) -> List[Tuple[float, float]]:
+    """The checked, non-empty list of (on, off) penalty pairs of a smoothing axis."""
+    try:
+        pairs = [tuple(s) for s in smoothings]
+    except TypeError:
+        raise ValueError(f"smoothings: expected a list of (smooth_on, smooth_off) pairs, got {smoothings!r}") from None
+    if not pairs or any(len(s) != 2 for s in pairs):
+        raise ValueError("smoothings: expected a non-empty list of (smooth_on, smooth_off) pairs")
+    return [check_smoothing(*s) for s in pairs]
+
+
+def _paths(x: torch.Tensor, thr: np.ndarray, pairs: Sequence[Tuple[float, float]], ln: Optional[torch.Tensor]) -> torch.Tensor:
+    """mt_frame_smooth_paths on checked arguments: x contiguous (B, P, T), thr float32 (K,), K = len(pairs) <= 16 -> (K, B, P, W) int64."""
+    B, P, T = x.shape
+    K = len(pairs)
+    out = torch.empty(2, K, B, P, (T + 63) // 64, dtype=torch.int64, device=x.device)          # paths | the kernel's scratch
+    thr = np.ascontiguousarray(thr, dtype=np.float32)
+    on, off = (np.ascontiguousarray([s[i] for s in pairs], dtype=np.float32) for i in (0, 1))
+    with torch.cuda.device(x.device):
+        check(lib.mt_frame_smooth_paths(ptr(x), thr.ctypes.data, on.ctypes.data, off.ctypes.data, K, ptr(ln), B, P, T, ptr(out[0]), ptr(out[1]),
+                                        _lib.stream_ptr()), "mt_frame_smooth_paths")
+    return out[0]
+
+
+def smooth_frame_paths(frame_logits: torch.Tensor, thresholds, smoothings, lengths=None) -> torch.Tensor:
+    """(B, P, T) or (P, T) frame logits ON THE DEVICE -> (K, B, P, W) int64 device tensor, W = ceil(T / 64): the Viterbi paths of
+    smooth_frame_logits for K candidates at once, packed 64 frames to a word (mt_frame_smooth_paths; DESIGN.md 6c "Smoothing in the
+    decoder grid").  Bit l of [k, b, p, w] is 1 iff smooth_frame_logits at (thresholds[k], *smoothings[k]) is +64 at frame 64 w + l;
+    bits at or past a sample's length are 0.  smoothings: a list of (on, off) penalty pairs as check_smoothing takes them; thresholds:
+    one value for all of them or one value per pair.  (0, 0) goes through the kernel as any other pair: its path is the thresholded
+    activity.  More than 16 candidates are cut into several launches.  The kernel's scratch (as large as the result) is allocated here."""
+    pairs = _smoothing_list(smoothings)
+    thr = _threshold_array(thresholds, "thresholds")
+    if len(thr) == 1:
+        thr = np.repeat(thr, len(pairs))
+    if len(thr) != len(pairs):
+        raise ValueError(f"thresholds: expected one value or one per pair of smoothings, got {len(thr)} for {len(pairs)}")
+    x = _rows(frame_logits, "frame_logits")
+    ln = _lengths(lengths, x.shape[0], x.device)
+    tiles = [_paths(x, thr[k0:k0 + SMOOTH_MAX_K], pairs[k0:k0 + SMOOTH_MAX_K], ln) for k0 in range(0, len(pairs), SMOOTH_MAX_K)]
+    return tiles[0] if len(tiles) == 1 else torch.cat(tiles)
+
+
 def _note_tables(ref_notes: Dict[str, torch.Tensor], B: int, P: int, dev):
     """The checked, contiguous (on, off, ptr) of a note list for B x P rows."""
     r_on, r_off, r_ptr = (ref_notes[k] for k in ("on", "off", "ptr"))
@@ -323,7 +373,8 @@ GRID_MAX_K, GRID_MAX_CONFIGS = 16, 64              # mt_note_grid_*: values per 
 
 
 def note_grid_counts(frame_logits: torch.Tensor, ref, thresholds, onset_logits: Optional[torch.Tensor] = None, onset_thresholds=None,
-                     offset_logits: Optional[torch.Tensor] = None, offset_thresholds=None, cleanups=None, lengths=None) -> torch.Tensor:
+                     offset_logits: Optional[torch.Tensor] = None, offset_thresholds=None, cleanups=None, lengths=None,
+                     smoothings=None) -> torch.Tensor:
     """note_match_counts (ref = a (B, P, T) roll) or note_match_list (ref = the {"on", "off", "ptr"} note list) at every cell of
     `thresholds` x `onset_thresholds` x `offset_thresholds` x `cleanups` -> (B, Kf, Ko, Kk, Kc, 4) int64 device tensor; [b, i, j, k, c]
     is exactly what the single call returns at (thresholds[i], onset_thresholds[j], offset_thresholds[k]) with (min_note_frames,
@@ -331,7 +382,13 @@ def note_grid_counts(frame_logits: torch.Tensor, ref, thresholds, onset_logits: 
     pairs as check_cleanup takes them, None = [(1, 0)].  Without offset logits (the onset-gated decoder) Kk = 1 and offset_thresholds
     is not read; without onset logits either (the frame decoder) Ko = 1 as well.  The logits are read, and their sigmoids evaluated,
     once per call of the kernel; a grid past its limits (16 per axis, 64 configurations) is cut into several calls here and pasted
-    together.  With a roll nothing synchronises (a note list's ptr table is checked with one small read-back, as in note_match_list)."""
+    together.  With a roll nothing synchronises (a note list's ptr table is checked with one small read-back, as in note_match_list).
+    smoothings: a non-empty list of (smooth_on, smooth_off) pairs as check_smoothing takes them adds an axis Ks after the frame axis ->
+    (B, Kf, Ks, Ko, Kk, Kc, 4); [b, i, s, j, k, c] is exactly what the single call returns with smooth_on, smooth_off = smoothings[s] as
+    well.  The Kf * Ks frame candidates are cut into tiles of at most 16; per tile one mt_frame_smooth_paths launch packs their Viterbi
+    paths into bit masks (smooth_frame_paths), which mt_note_grid_counts_paths / mt_note_grid_list_paths read as their frame axis in
+    place of thresholds (DESIGN.md 6c "Smoothing in the decoder grid").  (0, 0) goes the same way: its path is the threshold's
+    activity.  None: no such axis, and the calls above."""
     if offset_logits is not None and onset_logits is None:
         raise ValueError("offset_logits: the offset-gated decoder needs onset_logits as well")
     x = _rows(frame_logits, "frame_logits")
@@ -348,6 +405,7 @@ def note_grid_counts(frame_logits: torch.Tensor, ref, thresholds, onset_logits: 
         heads[name] = (h, _threshold_array(ths, f"{name}_thresholds"))
     (on, to), (off, tk) = heads["onset"], heads["offset"]
     tf = _threshold_array(thresholds, "thresholds")
+    smooth = None if smoothings is None else _smoothing_list(smoothings)
     pairs = [(1, 0)] if cleanups is None else [check_cleanup(*c) for c in cleanups]
     if not pairs:
         raise ValueError("cleanups: expected a non-empty list of (min_note_frames, bridge_frames) pairs")
@@ -362,30 +420,50 @@ def note_grid_counts(frame_logits: torch.Tensor, ref, thresholds, onset_logits: 
         if roll.shape != x.shape:
             raise ValueError(f"shape mismatch: frame {tuple(x.shape)}, ref {tuple(roll.shape)}")
     ln = _lengths(lengths, B, dev)
-    Kf, Ko, Kk, Kc = len(tf), len(to), len(tk), len(cl)
-    out = torch.empty(B, Kf, Ko, Kk, Kc, 4, dtype=torch.int64, device=dev)
+    Ko, Kk, Kc = len(to), len(tk), len(cl)
     kc = min(Kc, GRID_MAX_K)                                 # tiles of kf x ko x kk x kc <= 64, the inner axes as wide as they go
     kk = min(Kk, GRID_MAX_K, GRID_MAX_CONFIGS // kc)
     ko = min(Ko, GRID_MAX_K, GRID_MAX_CONFIGS // (kc * kk))
-    kf = min(Kf, GRID_MAX_K, GRID_MAX_CONFIGS // (kc * kk * ko))
-    with torch.cuda.device(dev):
+
+    def tiles(out, head):
+        """Fill out (B, Kf, Ko, Kk, Kc, 4) tile by tile; head(i0, n) = the arguments of entries i0 .. i0 + n of the frame axis (those
+        before thr_onset) and the suffix of the entry points that take them."""
+        Kf = out.shape[1]
+        kf = min(Kf, GRID_MAX_K, GRID_MAX_CONFIGS // (kc * kk * ko))
         for i0 in range(0, Kf, kf):
             for j0 in range(0, Ko, ko):
                 for k0 in range(0, Kk, kk):
                     for c0 in range(0, Kc, kc):
-                        a, b, k, c = (np.ascontiguousarray(v) for v in (tf[i0:i0 + kf], to[j0:j0 + ko], tk[k0:k0 + kk], cl[c0:c0 + kc]))
-                        whole = (len(a), len(b), len(k), len(c)) == (Kf, Ko, Kk, Kc)
-                        t = out if whole else torch.empty(B, len(a), len(b), len(k), len(c), 4, dtype=torch.int64, device=dev)
-                        axes = (ptr(x), ptr(on), ptr(off), a.ctypes.data, len(a), b.ctypes.data if on is not None else None, len(b),
-                                k.ctypes.data if off is not None else None, len(k), c.ctypes.data, len(c))
+                        n = min(kf, Kf - i0)
+                        b, k, c = (np.ascontiguousarray(v) for v in (to[j0:j0 + ko], tk[k0:k0 + kk], cl[c0:c0 + kc]))
+                        whole = (n, len(b), len(k), len(c)) == (Kf, Ko, Kk, Kc) and out.is_contiguous()
+                        t = out if whole else torch.empty(B, n, len(b), len(k), len(c), 4, dtype=torch.int64, device=dev)
+                        first, suffix = head(i0, n)
+                        axes = (*first, b.ctypes.data if on is not None else None, len(b), k.ctypes.data if off is not None else None, len(k),
+                                c.ctypes.data, len(c))
                         if as_list:
-                            check(lib.mt_note_grid_list(*axes, ptr(r_on), ptr(r_off), ptr(r_ptr), ptr(ln), ptr(t), B, P, T, _lib.stream_ptr()),
-                                  "mt_note_grid_list")
+                            name = "mt_note_grid_list" + suffix
+                            check(getattr(lib, name)(*axes, ptr(r_on), ptr(r_off), ptr(r_ptr), ptr(ln), ptr(t), B, P, T, _lib.stream_ptr()), name)
                         else:
-                            check(lib.mt_note_grid_counts(*axes, ptr(roll), ptr(ln), ptr(t), B, P, T, _lib.stream_ptr()), "mt_note_grid_counts")
+                            name = "mt_note_grid_counts" + suffix
+                            check(getattr(lib, name)(*axes, ptr(roll), ptr(ln), ptr(t), B, P, T, _lib.stream_ptr()), name)
                         if not whole:
-                            out[:, i0:i0 + len(a), j0:j0 + len(b), k0:k0 + len(k), c0:c0 + len(c)] = t
-    return out
+                            out[:, i0:i0 + n, j0:j0 + len(b), k0:k0 + len(k), c0:c0 + len(c)] = t
+
+    with torch.cuda.device(dev):
+        if smooth is None:
+            out = torch.empty(B, len(tf), Ko, Kk, Kc, 4, dtype=torch.int64, device=dev)
+
+            tiles(out, lambda i0, n: ((ptr(x), ptr(on), ptr(off), tf[i0:].ctypes.data, n), ""))         # (tf: contiguous float32)
+            return out
+        Ks = len(smooth)
+        cand_thr = np.repeat(tf, Ks)                         # candidate i * Ks + s = (thresholds[i], smoothings[s]): frame-major
+        cand = smooth * len(tf)
+        out = torch.empty(B, len(cand), Ko, Kk, Kc, 4, dtype=torch.int64, device=dev)
+        for q0 in range(0, len(cand), SMOOTH_MAX_K):
+            paths = _paths(x, cand_thr[q0:q0 + SMOOTH_MAX_K], cand[q0:q0 + SMOOTH_MAX_K], ln)
+            tiles(out[:, q0:q0 + len(paths)], lambda i0, n: ((ptr(paths[i0:i0 + n]), n, ptr(on), ptr(off)), "_paths"))
+    return out.reshape(B, len(tf), Ks, Ko, Kk, Kc, 4)
 
 
 def _prf(tp: int, n_ref: int, n_est: int) -> Tuple[float, float, float]:

@@ -23,7 +23,10 @@ sweep pass over the logits per group and round: evaluate.tune_note_thresholds) a
 decoder together, with any --decoder: its thresholds (frame; onset; offset) and the note cleanup out of the product of the two lists
 (evaluate.tune_note_decoder: one model run, one grid pass per group and round), and reports the note metrics at that configuration.
 `--note_metrics --smooth_on X --smooth_off Y` smooths the frame head with a two-state HMM per pitch before the notes are decoded
-(notes.smooth_frame_logits); the framewise F1 stays that of the raw threshold, and none of the tuners takes smoothing.
+(notes.smooth_frame_logits); the framewise F1 stays that of the raw threshold, and no tuner takes a fixed smoothing.
+`--tune_note_decoder --tune_smooth_on 0 1 2 --tune_smooth_off 0 1 2` tunes the two penalties with everything else: every pair of the
+two lists is one more candidate of each round's grid (one packed-path launch per group and tile of 16 frame candidates), and the
+note metrics are reported at the chosen pair.
 MIDI / plot outputs, background mode and the results browser are out of scope.
 """
 import argparse
@@ -112,8 +115,14 @@ def main():
                     help="--tune_note_decoder: the candidates for --min_note_ms (default: 0)")
     ap.add_argument("--tune_bridge_gap_ms", type=float, nargs="+", default=[0.0],
                     help="--tune_note_decoder: the candidates for --bridge_gap_ms (default: 0); every pair of the two lists is tried")
+    ap.add_argument("--tune_smooth_on", type=float, nargs="+", default=[0.0],
+                    help="--tune_note_decoder: the candidates for --smooth_on, in logits (default: 0); headless adds EVAL_NOTE_SMOOTH_ON= "
+                         "and EVAL_NOTE_SMOOTH_OFF= when either list is given")
+    ap.add_argument("--tune_smooth_off", type=float, nargs="+", default=[0.0],
+                    help="--tune_note_decoder: the candidates for --smooth_off (default: 0); every pair of the two lists is tried, with "
+                         "every cleanup pair, in every round")
     args = ap.parse_args()
-    tune_cleanups = None
+    tune_cleanups = tune_smoothings = None
     if args.tune_note_decoder:
         if args.tune_note_thresholds:
             ap.error("--tune_note_decoder cannot be combined with --tune_note_thresholds: it tunes the thresholds itself")
@@ -123,10 +132,15 @@ def main():
         try:
             from music_transcription_amd.notes import cleanup_frames
             tune_cleanups = [(m, g, cleanup_frames(m, g)) for m in args.tune_min_note_ms for g in args.tune_bridge_gap_ms]     # min-note-major
+            if args.tune_smooth_on != [0.0] or args.tune_smooth_off != [0.0]:
+                from music_transcription_amd.notes import check_smoothing
+                tune_smoothings = [check_smoothing(a, b) for a in args.tune_smooth_on for b in args.tune_smooth_off]             # on-major
         except ValueError as e:
             ap.error(str(e))
     elif args.tune_min_note_ms != [0.0] or args.tune_bridge_gap_ms != [0.0]:
         ap.error("--tune_min_note_ms / --tune_bridge_gap_ms are the cleanup candidates of --tune_note_decoder and need that flag")
+    elif args.tune_smooth_on != [0.0] or args.tune_smooth_off != [0.0]:
+        ap.error("--tune_smooth_on / --tune_smooth_off are the smoothing candidates of --tune_note_decoder and need that flag")
     if args.tune_note_thresholds and args.decoder == "onset_offset":
         ap.error("--tune_note_thresholds does not cover --decoder onset_offset (the threshold sweeps do not read the offset head): tune with "
                  "--decoder onset and pass the thresholds it reports")
@@ -257,17 +271,23 @@ def main():
             + f" (mean {args.tune_note_objective} note F1 {tuned_note_f1:.6f})")
     note_min_ms = note_gap_ms = None
     if args.tune_note_decoder:
-        note_threshold, note_onset_threshold, note_offset_threshold, tuned_clean, tuned_note_f1 = E.tune_note_decoder(
+        tuned = E.tune_note_decoder(
             model, ds, dev, subset=args.subset, decoder=args.decoder, note_reference=args.note_reference, objective=args.tune_note_objective,
             cleanups=[c for _, _, c in tune_cleanups], tune_range=tuple(args.tune_range), tune_step=args.tune_step,
             tune_min_step=args.tune_min_step, tune_rounds=args.tune_rounds, rank=rank, world=world, log=say if rank == 0 else None,
-            window_overlap=args.window_overlap)
+            window_overlap=args.window_overlap, smoothings=tune_smoothings)
+        note_threshold, note_onset_threshold, note_offset_threshold, tuned_clean = tuned[:4]
+        tuned_note_f1 = tuned[-1]
+        if tune_smoothings is not None:                    # the note metrics below are those at the chosen penalties
+            smooth_on, smooth_off = tuned[4]
         # (the first candidate with the chosen frames: different milliseconds can round to one pair, and the search keeps the first)
         note_min_ms, note_gap_ms = next((m, g) for m, g, c in tune_cleanups if c == tuned_clean)
         min_note_frames, bridge_frames = tuned_clean
         say(f"Best note decoder: frame {note_threshold:.4f}" + ("" if note_onset_threshold is None else f", onset {note_onset_threshold:.4f}")
             + ("" if note_offset_threshold is None else f", offset {note_offset_threshold:.4f}")
-            + f", min note {note_min_ms:g} ms, bridged gap {note_gap_ms:g} ms (mean {args.tune_note_objective} note F1 {tuned_note_f1:.6f})")
+            + f", min note {note_min_ms:g} ms, bridged gap {note_gap_ms:g} ms"
+            + ("" if tune_smoothings is None else f", smoothing on {smooth_on:g} / off {smooth_off:g} logits")
+            + f" (mean {args.tune_note_objective} note F1 {tuned_note_f1:.6f})")
     if args.note_metrics:
         notes = E.note_metrics_dataset(model, ds, note_threshold, note_onset_threshold, dev,
                                        subset=args.subset, rank=rank, world=world, window_overlap=args.window_overlap,
@@ -289,6 +309,9 @@ def main():
                         print(f"EVAL_NOTE_OFFSET_THRESHOLD={note_offset_threshold:.4f}")
                     print(f"EVAL_NOTE_MIN_NOTE_MS={note_min_ms:g}")
                     print(f"EVAL_NOTE_BRIDGE_GAP_MS={note_gap_ms:g}")
+                    if tune_smoothings is not None:
+                        print(f"EVAL_NOTE_SMOOTH_ON={smooth_on:g}")
+                        print(f"EVAL_NOTE_SMOOTH_OFF={smooth_off:g}")
         else:
             print(f"\nMean framewise F1 over {len(per_sample)} samples at threshold {threshold:.4f}: {mean_f1:.6f}")
             results = {"mean_f1": mean_f1, "threshold": threshold, "per_sample_f1": per_sample, "split": args.split,
@@ -305,6 +328,8 @@ def main():
                     results["note_metrics"].update(threshold=note_threshold, tuned_objective=args.tune_note_objective)
                 if args.tune_note_decoder:
                     results["note_metrics"].update(min_note_ms=note_min_ms, bridge_gap_ms=note_gap_ms)
+                    if tune_smoothings is not None:
+                        results["note_metrics"].update(smooth_on=smooth_on, smooth_off=smooth_off)
             os.makedirs(args.out_dir, exist_ok=True)
             with open(os.path.join(args.out_dir, "results.json"), "w") as f:
                 json.dump(results, f)
