@@ -524,6 +524,16 @@ int    mt_frame_smooth(const float* frame_logits, float* out, float thr, float o
                        int B, int P, long long T, mt_stream_t stream);
 int    mt_frame_smooth_chunks(const float* frame_logits, float* out, float thr, float on_penalty, float off_penalty, int NB, int P, int T,
                               mt_stream_t stream);
+/* Long rows (DESIGN.md 6c "Long rows: segments per wave"): the same output, bit for bit, from one workgroup of `waves` wave64s per row,
+ * each walking a contiguous stretch of the row's 64-frame windows.  Arguments, limits and refusals are those of the twin without
+ * _split; on top of them waves outside [2, 16], or rows * waves at or past 2^26 (rows = B * P, or P for chunks): MT_EINVAL, no launch.
+ * mt_frame_smooth / mt_frame_smooth_chunks choose between the two kernels themselves, by the launch's rows and windows per row;
+ * MT_SMOOTH_SPLIT=0 in the environment keeps them to one wave per row, MT_SMOOTH_SPLIT=2..16 forces that many on rows of at least that
+ * many windows. */
+int    mt_frame_smooth_split(const float* frame_logits, float* out, float thr, float on_penalty, float off_penalty, const long long* lengths,
+                             int B, int P, long long T, int waves, mt_stream_t stream);
+int    mt_frame_smooth_chunks_split(const float* frame_logits, float* out, float thr, float on_penalty, float off_penalty, int NB, int P,
+                                    int T, int waves, mt_stream_t stream);
 /* mt_note_match_counts_clean / mt_note_match_list_clean for a grid of every decoder parameter in one pass (DESIGN.md 6c "Decoder
  * grid"): counts[b][i][j][k][c] (uint64 [B][Kf][Ko][Kk][Kc][4], zeroed on the stream) is bit for bit what the _clean entry point
  * returns for (thr_frame[i], thr_onset[j], thr_offset[k], min_frames = clean[c][0], bridge_frames = clean[c][1]) on the same inputs.

@@ -159,6 +159,8 @@ _SIGS = {
     "mt_notes_batch_clean": (i32, [vp, vp, C.c_float, C.c_float, vp, i32, i32, ll, vp, vp, vp, vp, ll, i32, i32, vp]),
     "mt_frame_smooth": (i32, [vp, vp, C.c_float, C.c_float, C.c_float, vp, i32, i32, ll, vp]),
     "mt_frame_smooth_chunks": (i32, [vp, vp, C.c_float, C.c_float, C.c_float, i32, i32, i32, vp]),
+    "mt_frame_smooth_split": (i32, [vp, vp, C.c_float, C.c_float, C.c_float, vp, i32, i32, ll, i32, vp]),
+    "mt_frame_smooth_chunks_split": (i32, [vp, vp, C.c_float, C.c_float, C.c_float, i32, i32, i32, i32, vp]),
     "mt_note_grid_counts": (i32, [vp, vp, vp, vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, vp, i32, i32, i32, vp]),
     "mt_note_grid_list": (i32, [vp, vp, vp, vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "mt_frame_smooth_paths": (i32, [vp, vp, vp, vp, i32, vp, i32, i32, ll, vp, vp, vp]),

@@ -1,5 +1,6 @@
 // mt_frame_smooth / mt_frame_smooth_chunks: the frame head of every pitch row smoothed by a two-state (off / on) HMM, the Viterbi path
 // written back as logits of +-64 (DESIGN.md 6c "Frame smoothing").  One wave64 per row, 64 frames per step, as the note decoders.
+// (mt_frame_smooth_split / mt_frame_smooth_chunks_split: several waves per row, each a stretch of it; see frame_smooth_split_kernel.)
 //
 // Evidence on a 1/64-logit grid: q_t = rint(clamp(x_t - logit(thr), +-64) * 64), its sign forced to agree with logit_active(x_t, thr)
 // (q >= 1 on an active frame, q <= 0 otherwise), penalties a = rint(64 on_penalty), b = rint(64 off_penalty) in [0, 4096].  The path
@@ -34,6 +35,7 @@
 // within +-8192, |c| <= 2^18 after a window, the identity's 2^30 only ever after the row's frames, |d| <= 8192.  Words: W = ceil(T / 64)
 // per row and candidate, every one of them written (zeros past the row's last window).
 #include <math.h>
+#include <stdlib.h>
 
 #include "mt_common.h"
 #include "note_decode.h"
@@ -79,8 +81,87 @@ __device__ __forceinline__ int quantise(float x, float thr, float c) {
     return logit_active(x, thr) ? max(q, 1) : min(q, 0);
 }
 
-// CHUNKS false: rows = B * P rows of a padded batch [B][P][T] with lengths.  CHUNKS true: rows = P, the NB chunks [NB][P][T] are one
-// row of NB * T frames per pitch (NBT), frame g in chunk g / T.  x and y may be the same buffer, so neither is __restrict__.
+// Where frame g of a row lies.  CHUNKS false: rows = B * P rows of a padded batch [B][P][T] with lengths.  CHUNKS true: rows = P, the
+// NB chunks [NB][P][T] are one row of NB * T frames per pitch (NBT), frame g in chunk g / T.
+template <bool CHUNKS, typename Index>
+struct RowAt {
+    long long row;
+    int P;
+    Index T;
+    __device__ __forceinline__ size_t operator()(Index g) const {
+        if constexpr (CHUNKS) {
+            const Index k = g / T;
+            return ((size_t)k * (size_t)P + (size_t)row) * (size_t)T + (size_t)(g - k * T);
+        } else {
+            return (size_t)row * (size_t)T + (size_t)g;
+        }
+    }
+};
+
+template <bool CHUNKS, typename Index>
+__device__ __forceinline__ Index row_length(const long long* __restrict__ lengths, long long row, int P, Index T, Index NBT) {
+    if constexpr (CHUNKS) return NBT;
+    else return lengths ? (Index)min((long long)T, max(0ll, lengths[row / P])) : T;
+}
+
+// One 64-frame window of the forward pass: this lane's frame as a function of d (the identity past L), scanned over the wave.
+__device__ __forceinline__ ClampAdd scan_window(bool in, float v, float thr, float c, int a, int b) {
+    ClampAdd f = {0, -SMOOTH_FAR, SMOOTH_FAR};
+    if (in) {
+        const int q = quantise(v, thr, c);
+        f = {q, q - a, q + b};
+    }
+    return scan_wave(f);
+}
+
+// The forward pass over the frames [lo, end) of a row of L frames (lo a multiple of 64, end <= L), d_prev = d of frame lo - 1: d of
+// every frame, and what it decides on its own.  seen(hi, dec) per window, in order: the ballots of the frames stored as +64 and of
+// those stored as +64 or -64.
+template <typename Index, typename At, typename Seen>
+__device__ __forceinline__ void smooth_forward(const float* x, float* y, const At& at, Index lo, Index end, Index L, int lane, float thr, float c,
+                                               int a, int b, int d_prev, Seen seen) {
+    walk_slabs<SMOOTH_SLAB, 1>(
+        end - lo, lane, [&](int, Index g) __attribute__((always_inline)) { return x[at(lo + g)]; },
+        [&](Index g0, bool in, const float(&v)[1]) __attribute__((always_inline)) {
+            const ClampAdd f = scan_window(in, v[0], thr, c, a, b);
+            const int d = clampi(d_prev + f.c, f.lo, f.hi);
+            d_prev = __builtin_amdgcn_readlane(d, 63);                          // (lanes past `end` hold the identity: d of frame end - 1)
+            const Index g = lo + g0 + lane;
+            const bool last = g == L - 1;                                       // the row's last frame is decisive: on iff d > 0
+            const bool on = in && (last ? d > 0 : d > b), off = in && !on && (last || d <= -a);
+            if (in) y[at(g)] = on ? 64.0f : off ? -64.0f : 0.0f;
+            seen(__ballot(on), __ballot(on || off));
+        });
+}
+
+// The backward pass over the same frames: the undecided ones take the state of the frame after them, slabs and windows in reverse.
+// next = s of the first frame at or above `end` (0 above the row, where frame L - 1 is decisive anyway).
+template <typename Index, typename At>
+__device__ __forceinline__ void smooth_backward(float* y, const At& at, Index lo, Index end, int lane, unsigned long long next) {
+    const Index n = end - lo, n_slabs = (n + 64 * SMOOTH_SLAB - 1) / (64 * SMOOTH_SLAB);
+    for (Index s = n_slabs - 1; s >= 0; --s) {
+        const Index s0 = s * (64 * SMOOTH_SLAB);
+        float v[SMOOTH_SLAB];
+#pragma unroll
+        for (int w = 0; w < SMOOTH_SLAB; ++w) {
+            const Index g = s0 + 64 * w + lane;
+            v[w] = g < n ? y[at(lo + g)] : 0.0f;
+        }
+#pragma unroll
+        for (int w = SMOOTH_SLAB - 1; w >= 0; --w) {
+            const Index g0 = s0 + 64 * w;
+            if (g0 >= n) continue;
+            const bool in = g0 + lane < n;
+            const unsigned long long hi = __ballot(in && v[w] > 0.0f), dec = hi | __ballot(in && v[w] < 0.0f);
+            const unsigned long long above = dec & ~((1ull << lane) - 1ull);    // decisive frames at or above this lane
+            const bool st = above ? (hi >> (__ffsll((long long)above) - 1) & 1ull) != 0ull : next != 0ull;
+            if (in && v[w] == 0.0f) y[at(lo + g0 + lane)] = st ? 64.0f : -64.0f;
+            if (dec) next = hi >> (__ffsll((long long)dec) - 1) & 1ull;
+        }
+    }
+}
+
+// One wave64 per row.  x and y may be the same buffer, so neither is __restrict__.
 template <bool CHUNKS, typename Index>
 __global__ __launch_bounds__(64 * SMOOTH_WAVES) void frame_smooth_kernel(const float* x, float* y, float thr, float c, int a, int b,
                                                                          const long long* __restrict__ lengths, long long rows, int P, Index T,
@@ -88,59 +169,68 @@ __global__ __launch_bounds__(64 * SMOOTH_WAVES) void frame_smooth_kernel(const f
     const long long row = (long long)blockIdx.x * SMOOTH_WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // wave-uniform
     const int lane = threadIdx.x & 63;
     if (row >= rows) return;
-    Index L;
-    if constexpr (CHUNKS) L = NBT;
-    else L = lengths ? (Index)min((long long)T, max(0ll, lengths[row / P])) : T;
-    const auto at = [&](Index g) __attribute__((always_inline)) -> size_t {
-        if constexpr (CHUNKS) {
-            const Index k = g / T;
-            return ((size_t)k * (size_t)P + (size_t)row) * (size_t)T + (size_t)(g - k * T);
-        } else {
-            return (size_t)row * (size_t)T + (size_t)g;
-        }
-    };
-    // forward: d of every frame, and what it decides on its own
-    int d_prev = 0;
+    const Index L = row_length<CHUNKS, Index>(lengths, row, P, T, NBT);
+    const RowAt<CHUNKS, Index> at = {row, P, T};
+    smooth_forward(x, y, at, (Index)0, L, L, lane, thr, c, a, b, 0, [](unsigned long long, unsigned long long) __attribute__((always_inline)) {});
+    smooth_backward(y, at, (Index)0, L, lane, 0ull);
+}
+
+// Long rows (DESIGN.md 6c "Long rows: segments per wave"): one workgroup of S = blockDim.x / 64 waves per row, S in [2, 16].  The row's
+// W = ceil(L / 64) windows are cut into S contiguous segments of seg = ceil(W / S) windows, wave s owning windows [s seg, min(W, (s + 1)
+// seg)); a wave whose segment is empty passes the identity on and holds no decisive frame.  Three walks over the own segment, two barriers:
+//   A  the segment as one function: the windows' scans composed from the identity, nothing stored.  Settled after every window -- on
+//      the d that occur, |d| <= SMOOTH_BAND, clamp(d + c, lo, hi) is the same function for every c at or past hi + SMOOTH_BAND (always
+//      hi) and at or below lo - SMOOTH_BAND (always lo), so c is clamped to that range: |c| <= 2^14 once the segment holds a frame,
+//      whatever its length, where the plain sum would reach 2^18 per window.  Triples to LDS, barrier; d_in = the triples of the
+//      segments below applied to 0 in order.
+//   B  smooth_forward from d_in, as the one-wave kernel's from 0; `has` = the segment holds a decisive frame, `low` = the Hi bit of its
+//      lowest one.  Bits to LDS, barrier.
+//   C  smooth_backward with next = `low` of the nearest segment above with `has`, else 0.
+// Lane l owns frame g0 + l in all three walks and a wave touches no frame outside its segment, so nothing passes between lanes
+// through memory and out may be frame_logits itself, as in the one-wave kernel.
+constexpr int SMOOTH_SPLIT_MAX = 16;       // waves per row at most: 1024 threads per workgroup
+constexpr int SMOOTH_BAND = 8192;          // |d| <= 8192 and a frame's lo, hi within +-8192
+
+__device__ __forceinline__ ClampAdd settle(const ClampAdd& f) { return {clampi(f.c, f.lo - SMOOTH_BAND, f.hi + SMOOTH_BAND), f.lo, f.hi}; }
+
+template <bool CHUNKS, typename Index>
+__global__ __launch_bounds__(64 * SMOOTH_SPLIT_MAX) void frame_smooth_split_kernel(const float* x, float* y, float thr, float c, int a, int b,
+                                                                                   const long long* __restrict__ lengths, int P, Index T,
+                                                                                   Index NBT) {
+    __shared__ ClampAdd totals[SMOOTH_SPLIT_MAX];
+    __shared__ int has_low[SMOOTH_SPLIT_MAX];                                   // bit 0 = has, bit 1 = low
+    const long long row = blockIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), S = (int)(blockDim.x >> 6);       // wave-uniform
+    const int lane = threadIdx.x & 63;
+    const Index L = row_length<CHUNKS, Index>(lengths, row, P, T, NBT);
+    const RowAt<CHUNKS, Index> at = {row, P, T};
+    const Index W = (L + 63) / 64, seg = (W + S - 1) / S;
+    const Index lo = min(L, min(W, (Index)wave * seg) * 64), end = min(L, min(W, ((Index)wave + 1) * seg) * 64);     // lo == end: empty
+    // A: the segment's function
+    ClampAdd tot = {0, -SMOOTH_FAR, SMOOTH_FAR};
     walk_slabs<SMOOTH_SLAB, 1>(
-        L, lane, [&](int, Index g) __attribute__((always_inline)) { return x[at(g)]; },
-        [&](Index g0, bool in, const float(&v)[1]) __attribute__((always_inline)) {
-            ClampAdd f = {0, -SMOOTH_FAR, SMOOTH_FAR};
-            if (in) {
-                const int q = quantise(v[0], thr, c);
-                f = {q, q - a, q + b};
-            }
-            f = scan_wave(f);
-            const int d = clampi(d_prev + f.c, f.lo, f.hi);
-            d_prev = __builtin_amdgcn_readlane(d, 63);                          // (lanes past L hold the identity: d of frame L - 1)
-            if (in) {
-                const Index g = g0 + lane;
-                const bool on = d > b, off = d <= -a;
-                y[at(g)] = g == L - 1 ? (d > 0 ? 64.0f : -64.0f) : on ? 64.0f : off ? -64.0f : 0.0f;
-            }
+        end - lo, lane, [&](int, Index g) __attribute__((always_inline)) { return x[at(lo + g)]; },
+        [&](Index, bool in, const float(&v)[1]) __attribute__((always_inline)) {
+            const ClampAdd f = scan_window(in, v[0], thr, c, a, b);
+            const ClampAdd win = {__builtin_amdgcn_readlane(f.c, 63), __builtin_amdgcn_readlane(f.lo, 63), __builtin_amdgcn_readlane(f.hi, 63)};
+            tot = settle(then(tot, win));
         });
-    // backward: the undecided frames take the state of the frame after them, slabs and windows in reverse
-    unsigned long long next = 0;                                                // s of the first frame of the window above (L - 1 is decisive)
-    const Index n_slabs = (L + 64 * SMOOTH_SLAB - 1) / (64 * SMOOTH_SLAB);
-    for (Index s = n_slabs - 1; s >= 0; --s) {
-        const Index s0 = s * (64 * SMOOTH_SLAB);
-        float v[SMOOTH_SLAB];
-#pragma unroll
-        for (int w = 0; w < SMOOTH_SLAB; ++w) {
-            const Index g = s0 + 64 * w + lane;
-            v[w] = g < L ? y[at(g)] : 0.0f;
-        }
-#pragma unroll
-        for (int w = SMOOTH_SLAB - 1; w >= 0; --w) {
-            const Index g0 = s0 + 64 * w;
-            if (g0 >= L) continue;
-            const bool in = g0 + lane < L;
-            const unsigned long long hi = __ballot(in && v[w] > 0.0f), dec = hi | __ballot(in && v[w] < 0.0f);
-            const unsigned long long above = dec & ~((1ull << lane) - 1ull);    // decisive frames at or above this lane
-            const bool st = above ? (hi >> (__ffsll((long long)above) - 1) & 1ull) != 0ull : next != 0ull;
-            if (in && v[w] == 0.0f) y[at(g0 + lane)] = st ? 64.0f : -64.0f;
-            if (dec) next = hi >> (__ffsll((long long)dec) - 1) & 1ull;
-        }
-    }
+    if (lane == 0) totals[wave] = tot;
+    __syncthreads();
+    int d_in = 0;
+    for (int i = 0; i < wave; ++i) d_in = clampi(d_in + totals[i].c, totals[i].lo, totals[i].hi);
+    // B: forward from d_in
+    int bits = 0;
+    smooth_forward(x, y, at, lo, end, L, lane, thr, c, a, b, d_in, [&](unsigned long long hi, unsigned long long dec) __attribute__((always_inline)) {
+        if (bits == 0 && dec) bits = 1 | (int)(hi >> (__ffsll((long long)dec) - 1) & 1ull) << 1;
+    });
+    if (lane == 0) has_low[wave] = bits;
+    __syncthreads();
+    // C: backward below the nearest decisive frame above
+    unsigned long long next = 0;
+    for (int i = S - 1; i > wave; --i)
+        if (has_low[i] & 1) next = (unsigned long long)(has_low[i] >> 1);
+    smooth_backward(y, at, lo, end, lane, next);
 }
 
 constexpr int SMOOTH_MAX_K = 16;           // candidates per mt_frame_smooth_paths call: one wave each, 1024 threads per workgroup
@@ -179,12 +269,7 @@ __global__ __launch_bounds__(64 * SMOOTH_MAX_K) void frame_smooth_paths_kernel(c
     walk_slabs<SMOOTH_SLAB, 1>(
         L, lane, [&](int, long long g) __attribute__((always_inline)) { return xr[g]; },
         [&](long long g0, bool in, const float(&v)[1]) __attribute__((always_inline)) {
-            ClampAdd f = {0, -SMOOTH_FAR, SMOOTH_FAR};
-            if (in) {
-                const int q = quantise(v[0], thr, c);
-                f = {q, q - a, q + b};
-            }
-            f = scan_wave(f);
+            const ClampAdd f = scan_window(in, v[0], thr, c, a, b);
             const int d = clampi(d_prev + f.c, f.lo, f.hi);
             d_prev = __builtin_amdgcn_readlane(d, 63);                          // (lanes past L hold the identity: d of frame L - 1)
             unsigned long long hi = __ballot(in && d > b), dec = hi | __ballot(in && d <= -a);
@@ -245,37 +330,89 @@ static int smooth_candidate(const char* who, float thr, float on_penalty, float 
     return MT_OK;
 }
 
-// The checks and the launch the two entry points share.  n = floats of either buffer.
+// Waves per row where the caller names none (mt_frame_smooth, mt_frame_smooth_chunks): MT_SMOOTH_SPLIT=0 never splits, 2..16 forces
+// that count on every row of at least that many windows, anything else is the rule measured in DESIGN.md 6c "Long rows: segments per
+// wave", a function of the launch's rows and windows per row alone.  The output is the same bits either way.
+static int smooth_auto_waves(long long rows, long long windows) {
+    // 16 waves where they were measured below one wave, fewer rows and longer rows included: at (88 rows, 206 windows) and at (704, 875).
+    // With rows to spare (11 264 x 15) every split was slower; what lies between was not measured and stays at one wave.
+    return (rows <= 88 && windows >= 206) || (rows <= 704 && windows >= 875) ? SMOOTH_SPLIT_MAX : 1;
+}
+
+static int smooth_waves(long long rows, long long windows) {
+    int waves = smooth_auto_waves(rows, windows);
+    if (const char* e = getenv("MT_SMOOTH_SPLIT")) {
+        char* rest = nullptr;
+        const long v = strtol(e, &rest, 10);
+        if (rest != e && *rest == 0 && (v == 0 || (v >= 2 && v <= SMOOTH_SPLIT_MAX))) waves = v == 0 || windows < v ? 1 : (int)v;
+    }
+    return rows * waves < (1ll << 26) ? waves : 1;                              // (64 threads per wave: the launch's threads stay below 2^32)
+}
+
+// The checks and the launch the entry points share.  n = floats of either buffer; waves = 0: smooth_waves' choice, else the
+// caller's (the _split entry points), 2..16.
 template <bool CHUNKS, typename Index>
 static int frame_smooth(const char* who, const float* x, float* y, float thr, float on_penalty, float off_penalty, const long long* lengths,
-                        long long rows, int P, Index T, Index NBT, size_t n, mt_stream_t stream) {
+                        long long rows, int P, Index T, Index NBT, size_t n, int waves, mt_stream_t stream) {
     float c;
     int a, b;
     if (const int rc = smooth_candidate(who, thr, on_penalty, off_penalty, c, a, b)) return rc;
     const uintptr_t xa = (uintptr_t)x, ya = (uintptr_t)y, bytes = n * sizeof(float);
     MT_REQUIRE(xa == ya || xa + bytes <= ya || ya + bytes <= xa, MT_EINVAL, "%s: out must be frame_logits itself or not overlap it", who);
-    const dim3 grid((unsigned)((rows + SMOOTH_WAVES - 1) / SMOOTH_WAVES)), block(64 * SMOOTH_WAVES);
-    hipLaunchKernelGGL((frame_smooth_kernel<CHUNKS, Index>), grid, block, 0, (hipStream_t)stream, x, y, thr, c, a, b, lengths, rows, P, T, NBT);
+    if (waves == 0) waves = smooth_waves(rows, ((long long)(CHUNKS ? NBT : T) + 63) / 64);
+    else MT_REQUIRE(rows * waves < (1ll << 26), MT_EINVAL, "%s: rows * waves must stay below 2^26", who);
+    if (waves > 1) {
+        hipLaunchKernelGGL((frame_smooth_split_kernel<CHUNKS, Index>), dim3((unsigned)rows), dim3(64 * waves), 0, (hipStream_t)stream, x, y, thr, c, a,
+                           b, lengths, P, T, NBT);
+    } else {
+        const dim3 grid((unsigned)((rows + SMOOTH_WAVES - 1) / SMOOTH_WAVES)), block(64 * SMOOTH_WAVES);
+        hipLaunchKernelGGL((frame_smooth_kernel<CHUNKS, Index>), grid, block, 0, (hipStream_t)stream, x, y, thr, c, a, b, lengths, rows, P, T, NBT);
+    }
     MT_CHECK_LAUNCH();
     return MT_OK;
 }
 
+static int smooth_batch(const char* who, const float* frame_logits, float* out, float thr, float on_penalty, float off_penalty,
+                        const long long* lengths, int B, int P, long long T, int waves, mt_stream_t stream) {
+    MT_REQUIRE(frame_logits && out, MT_EINVAL, "%s: null pointer", who);
+    MT_REQUIRE(B > 0 && P > 0 && T > 0 && (long long)B * P < 2147483647ll - SMOOTH_WAVES && T < 2147483647ll, MT_EINVAL,
+               "%s: bad dims (B, P, T > 0; B * P and T below 2^31)", who);
+    return frame_smooth<false, long long>(who, frame_logits, out, thr, on_penalty, off_penalty, lengths, (long long)B * P, P, T, 0ll,
+                                          (size_t)B * (size_t)P * (size_t)T, waves, stream);
+}
+
+static int smooth_chunks(const char* who, const float* frame_logits, float* out, float thr, float on_penalty, float off_penalty, int NB, int P,
+                         int T, int waves, mt_stream_t stream) {
+    MT_REQUIRE(frame_logits && out, MT_EINVAL, "%s: null pointer", who);
+    MT_REQUIRE(NB > 0 && P > 0 && T > 0 && (long long)NB * T < 2147483647ll - 64 * SMOOTH_SLAB, MT_EINVAL,
+               "%s: bad dims (NB, P, T > 0; NB * T below 2^31)", who);
+    return frame_smooth<true, int>(who, frame_logits, out, thr, on_penalty, off_penalty, nullptr, (long long)P, P, T, NB * T,
+                                   (size_t)NB * (size_t)P * (size_t)T, waves, stream);
+}
+
+#define MT_REQUIRE_SPLIT_WAVES(who) \
+    MT_REQUIRE(waves >= 2 && waves <= SMOOTH_SPLIT_MAX, MT_EINVAL, who ": waves must lie in [2, %d], got %d", SMOOTH_SPLIT_MAX, waves)
+
 extern "C" int mt_frame_smooth(const float* frame_logits, float* out, float thr, float on_penalty, float off_penalty, const long long* lengths,
                                int B, int P, long long T, mt_stream_t stream) {
-    MT_REQUIRE(frame_logits && out, MT_EINVAL, "mt_frame_smooth: null pointer");
-    MT_REQUIRE(B > 0 && P > 0 && T > 0 && (long long)B * P < 2147483647ll - SMOOTH_WAVES && T < 2147483647ll, MT_EINVAL,
-               "mt_frame_smooth: bad dims (B, P, T > 0; B * P and T below 2^31)");
-    return frame_smooth<false, long long>("mt_frame_smooth", frame_logits, out, thr, on_penalty, off_penalty, lengths, (long long)B * P, P, T, 0ll,
-                                          (size_t)B * (size_t)P * (size_t)T, stream);
+    return smooth_batch("mt_frame_smooth", frame_logits, out, thr, on_penalty, off_penalty, lengths, B, P, T, 0, stream);
 }
 
 extern "C" int mt_frame_smooth_chunks(const float* frame_logits, float* out, float thr, float on_penalty, float off_penalty, int NB, int P, int T,
                                       mt_stream_t stream) {
-    MT_REQUIRE(frame_logits && out, MT_EINVAL, "mt_frame_smooth_chunks: null pointer");
-    MT_REQUIRE(NB > 0 && P > 0 && T > 0 && (long long)NB * T < 2147483647ll - 64 * SMOOTH_SLAB, MT_EINVAL,
-               "mt_frame_smooth_chunks: bad dims (NB, P, T > 0; NB * T below 2^31)");
-    return frame_smooth<true, int>("mt_frame_smooth_chunks", frame_logits, out, thr, on_penalty, off_penalty, nullptr, (long long)P, P, T, NB * T,
-                                   (size_t)NB * (size_t)P * (size_t)T, stream);
+    return smooth_chunks("mt_frame_smooth_chunks", frame_logits, out, thr, on_penalty, off_penalty, NB, P, T, 0, stream);
+}
+
+extern "C" int mt_frame_smooth_split(const float* frame_logits, float* out, float thr, float on_penalty, float off_penalty,
+                                     const long long* lengths, int B, int P, long long T, int waves, mt_stream_t stream) {
+    MT_REQUIRE_SPLIT_WAVES("mt_frame_smooth_split");
+    return smooth_batch("mt_frame_smooth_split", frame_logits, out, thr, on_penalty, off_penalty, lengths, B, P, T, waves, stream);
+}
+
+extern "C" int mt_frame_smooth_chunks_split(const float* frame_logits, float* out, float thr, float on_penalty, float off_penalty, int NB, int P,
+                                            int T, int waves, mt_stream_t stream) {
+    MT_REQUIRE_SPLIT_WAVES("mt_frame_smooth_chunks_split");
+    return smooth_chunks("mt_frame_smooth_chunks_split", frame_logits, out, thr, on_penalty, off_penalty, NB, P, T, waves, stream);
 }
 
 extern "C" int mt_frame_smooth_paths(const float* frame_logits, const float* thr, const float* on_penalty, const float* off_penalty, int K,

@@ -157,13 +157,21 @@ def _lengths(lengths, B: int, dev) -> Optional[torch.Tensor]:
     return ln
 
 
-def _smoothed(x: torch.Tensor, thr: float, smooth: Tuple[float, float], ln: Optional[torch.Tensor], chunks: bool) -> torch.Tensor:
+SMOOTH_SPLIT_WAVES = (2, 16)                        # mt_frame_smooth_split / mt_frame_smooth_chunks_split: waves per row
+
+
+def _smoothed(x: torch.Tensor, thr: float, smooth: Tuple[float, float], ln: Optional[torch.Tensor], chunks: bool,
+              waves: Optional[int] = None) -> torch.Tensor:
     """The checked, contiguous (B, P, T) frame logits x smoothed into a new tensor; frames at or past a row's length are not written
-    (they hold x's values when there are lengths)."""
+    (they hold x's values when there are lengths).  waves None: the library picks its kernel; an integer: the _split entry points."""
     B, P, T = x.shape
     out = torch.empty_like(x) if ln is None else x.clone()
     with torch.cuda.device(x.device):
-        if chunks:
+        if waves is not None and chunks:
+            check(lib.mt_frame_smooth_chunks_split(ptr(x), ptr(out), thr, *smooth, B, P, T, waves, _lib.stream_ptr()), "mt_frame_smooth_chunks_split")
+        elif waves is not None:
+            check(lib.mt_frame_smooth_split(ptr(x), ptr(out), thr, *smooth, ptr(ln), B, P, T, waves, _lib.stream_ptr()), "mt_frame_smooth_split")
+        elif chunks:
             check(lib.mt_frame_smooth_chunks(ptr(x), ptr(out), thr, *smooth, B, P, T, _lib.stream_ptr()), "mt_frame_smooth_chunks")
         else:
             check(lib.mt_frame_smooth(ptr(x), ptr(out), thr, *smooth, ptr(ln), B, P, T, _lib.stream_ptr()), "mt_frame_smooth")
@@ -171,22 +179,28 @@ def _smoothed(x: torch.Tensor, thr: float, smooth: Tuple[float, float], ln: Opti
 
 
 def smooth_frame_logits(frame_logits: torch.Tensor, threshold: float = 0.5, on_penalty: float = 0.0, off_penalty: float = 0.0, lengths=None,
-                        chunks: bool = False) -> torch.Tensor:
+                        chunks: bool = False, waves: Optional[int] = None) -> torch.Tensor:
     """(B, P, T) or (P, T) frame logits ON THE DEVICE -> a float tensor of the same shape that holds, per pitch row, the Viterbi path
     of a two-state (off / on) HMM as logits: +64 where the path is on, -64 where it is off (DESIGN.md 6c "Frame smoothing").  The
     evidence of a frame is its logit minus logit(threshold); switching on costs on_penalty, switching off off_penalty (logits, 0 to
     64), so a blip survives only if its evidence pays for both and a dropout is bridged only if its counter-evidence is smaller than
     both.  Every consumer of frame logits reads the path from the result at any threshold.  lengths (B,): valid frames per row of the
     batch (None: all T); frames past them keep the input's values.  chunks=True: the B chunks are one recording of B * T frames per
-    pitch, as heads_to_notes_device concatenates them (no lengths then).  (0, 0) returns frame_logits itself and launches nothing."""
+    pitch, as heads_to_notes_device concatenates them (no lengths then).  (0, 0) returns frame_logits itself and launches nothing.
+    waves: None lets the library choose between one wave64 per row and several (DESIGN.md 6c "Long rows: segments per wave"); an
+    integer in [2, 16] asks for that many through mt_frame_smooth_split / mt_frame_smooth_chunks_split.  The same bits either way."""
     smooth = check_smoothing(on_penalty, off_penalty)
     thr = _check_threshold(threshold, "threshold")
+    if waves is not None and (isinstance(waves, bool) or not isinstance(waves, (int, np.integer))
+                              or not SMOOTH_SPLIT_WAVES[0] <= waves <= SMOOTH_SPLIT_WAVES[1]):
+        raise ValueError(f"waves must be None or an integer in [{SMOOTH_SPLIT_WAVES[0]}, {SMOOTH_SPLIT_WAVES[1]}], got {waves!r}")
     if chunks and lengths is not None:
         raise ValueError("lengths: chunks=True concatenates whole chunks, which have no lengths")
     if smooth == (0.0, 0.0):
         return frame_logits
     x = _rows(frame_logits, "frame_logits")
-    return _smoothed(x, thr, smooth, _lengths(lengths, x.shape[0], x.device), chunks).reshape(frame_logits.shape)
+    return _smoothed(x, thr, smooth, _lengths(lengths, x.shape[0], x.device), chunks,
+                     None if waves is None else int(waves)).reshape(frame_logits.shape)
 
 
 SMOOTH_MAX_K = 16                                   # mt_frame_smooth_paths: candidates per call

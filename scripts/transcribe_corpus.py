@@ -14,6 +14,8 @@ rolls: that exercises the whole path and gives throughput, the F1 is then meanin
 --overlap SECONDS runs whole recordings in overlapping 30 s windows on one frame grid (corpus.transcribe_shard_windows) instead
 of concatenating chunks: notes, .mid files and scores are then on the recording's own grid of 1 + n // 512 frames.
 --min-note-ms / --bridge-gap-ms clean the notes inside the decoder (short gaps bridged, then short notes dropped), as main.py does.
+--smooth-on / --smooth-off smooth the frame head before the decoder (a two-state HMM per pitch, penalties in logits), as main.py does:
+the notes, the .mid files and --note-metrics are the smoothed ones, the framewise F1 stays the raw threshold's.
 """
 import argparse
 import json
@@ -47,6 +49,11 @@ def main():
     ap.add_argument("--bridge-gap-ms", type=float, default=0.0,
                     help="note cleanup in the decoder: a dropout of the activity no longer than this many milliseconds does not end the "
                          "note (below 2048; default 0 = none)")
+    ap.add_argument("--smooth-on", type=float, default=0.0,
+                    help="frame smoothing before the decoder: evidence, in logits, that switching a pitch on must pay (0 to 64; with "
+                         "--smooth-off 0, the default = no smoothing); the penalties --tune_smooth_on / --tune_smooth_off of "
+                         "scripts/evaluate.py chose apply here as they are")
+    ap.add_argument("--smooth-off", type=float, default=0.0, help="frame smoothing: the same for switching a pitch off (0 to 64)")
     ap.add_argument("--note-metrics", action="store_true",
                     help="also score notes against the runs of the reference roll (onset / onset+offset F1, mir_eval's criteria on the "
                          "32 ms grid): adds mean_note_onset_f1 / mean_note_onset_offset_f1 to the JSON line")
@@ -61,8 +68,9 @@ def main():
     ap.add_argument("--dump-rolls", help="directory: write <name>.roll.bits.npy (np.packbits of the (88, T_total) roll) per recording")
     args = ap.parse_args()
     try:                                    # refused before a device is opened
-        from music_transcription_amd.notes import cleanup_frames
+        from music_transcription_amd.notes import check_smoothing, cleanup_frames
         clean = dict(zip(("min_note_frames", "bridge_frames"), cleanup_frames(args.min_note_ms, args.bridge_gap_ms)))
+        clean.update(zip(("smooth_on", "smooth_off"), check_smoothing(args.smooth_on, args.smooth_off)))
     except ValueError as e:
         ap.error(str(e))
 
