@@ -122,9 +122,9 @@ extern "C" int mt_mel_plan_init(void* plan, size_t plan_bytes, int sr, int hop, 
     std::vector<float> fb;
     build_filterbank(fb, sr, n_mels);
     const int nb = MT_N_FFT / 2 + 1;
-    int* fs = (int*)(h.data() + L.fstart);
-    int* grp = (int*)(h.data() + L.grp);                 // grp[i] = lmax, grp[32 + i] = row offset
-    float* well = (float*)(h.data() + L.well);
+    int* xb = (int*)(h.data() + L.xbase);
+    unsigned long long* endmask = (unsigned long long*)(h.data() + L.endmask);
+    float* well = (float*)(h.data() + L.well);           // [block][lane][tap]
     const int ngrp = (n_mels + 31) / 32;
     std::vector<int> lo_(ngrp * 32, 0), len_(ngrp * 32, 0);
     for (int m = 0; m < n_mels; ++m) {
@@ -137,16 +137,17 @@ extern "C" int mt_mel_plan_init(void* plan, size_t plan_bytes, int sr, int hop, 
     for (int i = 0; i < ngrp; ++i) {
         int lmax = 0;
         for (int l = 0; l < 32; ++l) lmax = std::max(lmax, len_[i * 32 + l]);
-        lmax = (lmax + 3) / 4 * 4;                       // the kernel's reduction loop is unrolled by 4
+        lmax = std::max(4, (lmax + 3) / 4 * 4);          // whole blocks of 4 taps, and every group ends in a block of its own
         MT_REQUIRE(off + lmax <= ELL_MAX_ROWS, MT_EUNSUPPORTED, "mt_mel_plan_init: filterbank too wide for the ELL table");
-        grp[i] = lmax; grp[32 + i] = off;
         for (int l = 0; l < 32; ++l) {
             const int m = i * 32 + l;
-            fs[m] = lo_[m];
+            xb[m] = lo_[m] - off;                        // the kernel adds the row: bin = lo + (row - off)
             for (int j = 0; j < lmax; ++j)
-                well[(size_t)(off + j) * 32 + l] = (m < n_mels && j < len_[m]) ? fb[(size_t)m * nb + lo_[m] + j] : 0.0f;
+                well[((size_t)((off + j) / 4) * 32 + l) * 4 + (off + j) % 4] =
+                    (m < n_mels && j < len_[m]) ? fb[(size_t)m * nb + lo_[m] + j] : 0.0f;
         }
         off += lmax;
+        endmask[(off / 4 - 1) >> 6] |= 1ull << ((off / 4 - 1) & 63);
     }
     hdr[4] = off;
     desc->sr = sr; desc->hop = hop; desc->n_mels = n_mels; desc->ell_rows = off;
@@ -169,9 +170,8 @@ extern "C" int mt_mel_db_f32(const void* plan, const mt_mel_desc* desc, const fl
     const char* p = (const char*)plan;
     hipStream_t st = (hipStream_t)stream;
     MT_CHECK_HIP(hipMemsetAsync(chunk_max_power, 0, (size_t)B * 4, st));
-    const int ngrp = (n_mels + 31) / 32;
-    const size_t lds = (size_t)NWAVE * 2 * XREG * 4 + 2 * 1024 * 8 + (size_t)n_mels * 33 * 4 + (size_t)ngrp * 32 * 4 + 32 * 4 +
-                       (size_t)desc->ell_rows * 32 * 4;
+    MT_REQUIRE(desc->ell_rows % 4 == 0, MT_EINVAL, "mt_mel_db_f32: bad descriptor");
+    const size_t lds = mel_lds_bytes(n_mels, desc->ell_rows);
     MT_REQUIRE(lds <= 160 * 1024, MT_EUNSUPPORTED, "mt_mel_db_f32: n_mels=%d needs %zu B of LDS", n_mels, lds);
     MT_SET_MAX_LDS((mel_kernel<false>), 160 * 1024);
     MT_REQUIRE((size_t)B * n_samples * 4 < (size_t)0x7fffffff, MT_EUNSUPPORTED, "mt_mel_db_f32: B*n_samples too large for one launch (split the batch)");
@@ -179,7 +179,7 @@ extern "C" int mt_mel_db_f32(const void* plan, const mt_mel_desc* desc, const fl
     dim3 grid(n_tiles < 256 ? n_tiles : 256);          // persistent: one workgroup per CU walks the tiles
     hipLaunchKernelGGL(mel_kernel<false>, grid, dim3(NWAVE * 64), lds, st, wave, n_samples, T, hop, n_mels, B, tiles_per_chunk,
                        (const float2*)(p + L.window), (const float2*)(p + L.tw1024), (const float2*)(p + L.w2048),
-                       (const int*)(p + L.fstart), (const int*)(p + L.grp), (const float*)(p + L.well), desc->ell_rows,
+                       (const int*)(p + L.xbase), (const unsigned long long*)(p + L.endmask), (const float*)(p + L.well), desc->ell_rows,
                        mel_db, (unsigned*)chunk_max_power, nullptr, nullptr, nullptr, nullptr, 0);
     MT_CHECK_LAUNCH();
     if (apply_clamp) {

@@ -12,12 +12,14 @@ constexpr float AMIN = 1e-10f;
 constexpr float TOP_DB = 80.0f;
 
 // Sparse mel filterbank in a padded ELL form keyed to the kernel's work split: lane l of a half-wave
-// reduces filters m = l + 32 i (i = 0 .. NI-1).  For group i every lane runs the same trip count
-// lmax[i] = max_l len(l + 32 i); w_ell[(off[i] + j) * 32 + l] is filter (l + 32 i)'s j-th weight (0 past its end),
-// applied to power bin fstart[l + 32 i] + j.
-constexpr int ELL_MAX_ROWS = 768;     // sum_i lmax[i]; 86 at n_mels = 320
+// reduces filters m = l + 32 g (g = 0 .. ngrp-1).  For group g every lane runs the same trip count
+// lmax[g] = max_l len(l + 32 g), rounded up to whole blocks of 4 taps; the groups' blocks follow each other, so the
+// reduction is ONE flat walk over nblk = sum_g lmax[g] / 4 blocks: well[(q * 32 + l) * 4 + t] is the weight of tap t of
+// block q for lane l (0 past its filter's end), applied to power bin xbase[l + 32 g] + 4 q + t, where
+// xbase[m] = fstart[m] - (first row of m's group); bit q of endmask says that block q is its group's last.
+constexpr int ELL_MAX_ROWS = 768;     // sum_g lmax[g]; 88 at n_mels = 320
 struct MelPlanLayout {
-    size_t window, tw1024, w2048, fstart, grp, well, total;
+    size_t window, tw1024, w2048, xbase, endmask, well, total;
 };
 static MelPlanLayout plan_layout(int n_mels) {
     MelPlanLayout L;
@@ -25,13 +27,17 @@ static MelPlanLayout plan_layout(int n_mels) {
     L.window = o; o += 2048 * 4;
     L.tw1024 = o; o += 32 * 32 * 8;
     L.w2048 = o;  o += 1024 * 8;
-    size_t nm = align_up((size_t)n_mels, 16);
-    nm = align_up((size_t)n_mels, 32);
-    L.fstart = o; o += nm * 4;
-    L.grp = o;    o += 2 * 32 * 4;                    // int lmax[32], off[32]
-    L.well = o;   o += (size_t)ELL_MAX_ROWS * 32 * 4;
+    const size_t nm = align_up((size_t)n_mels, 32);
+    L.xbase = o;   o += nm * 4;
+    L.endmask = o; o += 2 * 32 * 4;                   // unsigned long long[ELL_MAX_ROWS / 4 / 64 = 3], padded
+    L.well = o;    o += (size_t)ELL_MAX_ROWS * 32 * 4;
     L.total = o;
     return L;
+}
+// Dynamic LDS of one workgroup: the half-wave exchange regions, the two staged tables, the dB tile, xbase and the weights.
+static size_t mel_lds_bytes(int n_mels, int ell_rows) {
+    return (size_t)NWAVE * 2 * XREG * 4 + 2 * 1024 * 8 + (size_t)n_mels * 33 * 4 + align_up((size_t)n_mels, 32) * 4 +
+           (size_t)ell_rows * 32 * 4;
 }
 
 __host__ __device__ constexpr int brev5(int i) {
@@ -103,7 +109,7 @@ template <bool WIN>
 __global__ __launch_bounds__(NWAVE * 64) void mel_kernel(
     const float* __restrict__ wave, int n_samples, int T, int hop, int n_mels, int B, int tiles_per_chunk,
     const float2* __restrict__ window2, const float2* __restrict__ tw1024, const float2* __restrict__ w2048,
-    const int* __restrict__ fstart, const int* __restrict__ grp, const float* __restrict__ well, int ell_rows,
+    const int* __restrict__ xbase, const unsigned long long* __restrict__ endmask, const float* __restrict__ well, int ell_rows,
     float* __restrict__ out, unsigned* __restrict__ chunk_max,
     const long long* __restrict__ win_off, const int* __restrict__ win_len, const int* __restrict__ rec_end,
     const int* __restrict__ t_keep, int T_out) {
@@ -111,19 +117,19 @@ __global__ __launch_bounds__(NWAVE * 64) void mel_kernel(
     float* xbuf = (float*)smem;                                   // [NWAVE][2][XREG]
     float2* w2048_s = (float2*)(smem + NWAVE * 2 * XREG * 4);     // [1024]
     float2* win_s = w2048_s + 1024;                               // [1024] Hann window pairs (w[2n], w[2n+1])
-    float* tile = (float*)(win_s + 1024);                         // [n_mels][33]
-    const int ngrp = (n_mels + 31) >> 5;
-    int* fstart_s = (int*)(tile + n_mels * 33);                   // [ngrp * 32]
-    int* grp_s = fstart_s + ngrp * 32;                            // [32] trip count of each filter group
-    float* well_s = (float*)(grp_s + 32);                         // [ell_rows][32]
+    float* well_s = (float*)(win_s + 1024);                       // [nblk][32][4], read as 16-byte vectors
+    const int ngrp = (n_mels + 31) >> 5, nblk = ell_rows >> 2;
+    int* xbase_s = (int*)(well_s + ell_rows * 32);                // [ngrp * 32]
+    float* tile = (float*)(xbase_s + ngrp * 32);                  // [n_mels][33]
+    // end-of-group bits of the (at most ELL_MAX_ROWS / 4 = 192) blocks: three scalar registers for the whole launch
+    const unsigned long long em0 = endmask[0], em1 = endmask[1], em2 = endmask[2];
 
     const int tid = threadIdx.x;
     const int wv = tid >> 6, lane = tid & 63, half = lane >> 5, l = lane & 31;
     float* X = xbuf + (wv * 2 + half) * XREG;
 
     for (int i = tid; i < 1024; i += NWAVE * 64) { w2048_s[i] = w2048[i]; win_s[i] = window2[i]; }
-    for (int i = tid; i < ngrp * 32; i += NWAVE * 64) fstart_s[i] = fstart[i];
-    if (tid < 32) grp_s[tid] = grp[tid];
+    for (int i = tid; i < ngrp * 32; i += NWAVE * 64) xbase_s[i] = xbase[i];
     for (int i = tid; i < ell_rows * 32; i += NWAVE * 64) well_s[i] = well[i];
     for (int i = tid; i < NWAVE * 2 * XREG; i += NWAVE * 64) xbuf[i] = 0.0f;   // padded ELL rows read (x 0) past bin 1024
     __syncthreads();
@@ -142,7 +148,10 @@ __global__ __launch_bounds__(NWAVE * 64) void mel_kernel(
     do {                                                                                                \
         const int ti_ = (TI), bb_ = ti_ / tiles_per_chunk;                                              \
         const int f_ = (ti_ - bb_ * tiles_per_chunk) * FT + (IT) * (NWAVE * 2) + wv * 2 + half;         \
-        const int s0_ = f_ * hop - (MT_N_FFT / 2) + 2 * l;   /* first sample of this lane, may be < 0 or >= n_samples */ \
+        int s0_ = f_ * hop - (MT_N_FFT / 2) + 2 * l;         /* first sample of this lane, may be < 0 or >= n_samples */ \
+        /* opaque from here: the 32 offsets are derived where the loads are issued, a few instructions each, and not kept \
+           in (spilled) registers from the top of the tile, which put a scratch reload and a full wait between the loads */ \
+        asm volatile("" : "+v"(s0_));                                                                   \
         if constexpr (WIN) {                                                                            \
             /* a descriptor per window: base = the window's first sample (64-bit), range = its readable samples rounded \
                up to a whole pair (the store keeps a readable sample past each end; the odd one is zeroed when windowing) */ \
@@ -269,35 +278,71 @@ __global__ __launch_bounds__(NWAVE * 64) void mel_kernel(
             // ---- prefetch the next frame's samples (next iteration, or the first frame of this block's next tile):
             //      re/im/dr are dead from here, so the 64 registers of raw data cost no extra pressure, and the
             //      loads fly during the mel reduction, the dB conversion and (last iteration) the tile store
-            if (it + 1 < ITERS) MEL_ISSUE_LOADS(ti, it + 1);
-            else MEL_ISSUE_LOADS(ti + gridDim.x, 0);
+            {
+                const bool last = it + 1 == ITERS;
+                MEL_ISSUE_LOADS(last ? ti + (int)gridDim.x : ti, last ? 0 : it + 1);
+            }
             __builtin_amdgcn_sched_barrier(0);
-            // ---- sparse mel projection + dB: lane l reduces filters l + 32 i; uniform trip counts (ELL padded to x4).
-            //      The phase is a chain of dependent LDS round trips, not arithmetic: trip counts and row offsets come as
-            //      SCALAR loads from the plan (uniform loop control), and the taps of block j + 4 are requested before the
-            //      multiply-adds of block j.
-            for (int i = 0; i < ngrp; ++i) {
-                const int m = l + 32 * i;
-                const int n = grp[i], row = grp[32 + i];         // same for every lane; n a multiple of 4 (scalar loads)
-                const float* Xs = X + fstart_s[m];
-                const float* w = well_s + row * 32 + l;
+            // ---- sparse mel projection + dB: lane l reduces filters l + 32 g, one flat walk over the nblk blocks of 4 taps.
+            //      The phase is LDS latency, not arithmetic, so nothing in it waits for a read it has just issued: the taps of
+            //      block q + 2 (one 16-byte weight read, four power reads) are requested before the multiply-adds of block q,
+            //      in three rotating register sets, and the lane's power-bin base of a block is read two blocks before
+            //      that (once per block, so that no register in flight is ever copied); the loop control is scalar
+            //      (end-of-group bits in em0..2).
+            {
+                const float4* wq = (const float4*)well_s + l;
+                const int gl = ngrp - 1;
+                int gq = 0;                                        // group of the next block whose base is requested
+                int xbA, xbB, xbC;
+                float4 wA, wB, wC;
+                float xA[4], xB[4], xC[4];
                 float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
-                float w0 = w[0], w1 = w[32], w2 = w[64], w3 = w[96];
-                float x0 = Xs[0], x1 = Xs[1], x2 = Xs[2], x3 = Xs[3];
-                for (int j = 4; j < n; j += 4) {
-                    const float v0 = w[j * 32], v1 = w[(j + 1) * 32], v2 = w[(j + 2) * 32], v3 = w[(j + 3) * 32];
-                    const float y0 = Xs[j], y1 = Xs[j + 1], y2 = Xs[j + 2], y3 = Xs[j + 3];
-                    a0 = fmaf(w0, x0, a0); a1 = fmaf(w1, x1, a1); a2 = fmaf(w2, x2, a2); a3 = fmaf(w3, x3, a3);
-                    w0 = v0; w1 = v1; w2 = v2; w3 = v3;
-                    x0 = y0; x1 = y1; x2 = y2; x3 = y3;
+                int g = 0;                                         // group of the block being summed
+#define MEL_END(Q) ((((Q) < 64 ? em0 : (Q) < 128 ? em1 : em2) >> ((Q) & 63)) & 1ull)
+                /* blocks past the end are the last block again, requested and never summed */
+#define MEL_BASE(XB, P) do { XB = xbase_s[l + 32 * min(gq, gl)]; gq += (int)MEL_END(min((P), nblk - 1)); } while (0)
+#define MEL_REQ(W, XV, XB, XB2, P)                                                                      \
+                do {                                                                                    \
+                    MEL_BASE(XB2, (P) + 2);                                                             \
+                    const int p_ = min((P), nblk - 1);                                                  \
+                    const float* Xs_ = X + XB + 4 * p_;                                                 \
+                    W = wq[p_ * 32];                                                                    \
+                    XV[0] = Xs_[0]; XV[1] = Xs_[1]; XV[2] = Xs_[2]; XV[3] = Xs_[3];                     \
+                } while (0)
+#define MEL_SUM(W, XV, Q)                                                                               \
+                do {                                                                                    \
+                    a0 = fmaf(W.x, XV[0], a0); a1 = fmaf(W.y, XV[1], a1);                               \
+                    a2 = fmaf(W.z, XV[2], a2); a3 = fmaf(W.w, XV[3], a3);                               \
+                    if ((Q) < nblk && MEL_END(Q)) {                                                     \
+                        const float acc = (a0 + a1) + (a2 + a3);                                        \
+                        const int m = l + 32 * g;                                                       \
+                        if (m < n_mels && f < Tb) {                                                     \
+                            vmax = fmaxf(vmax, acc);                                                    \
+                            /* 10 log10(x) = (10 log10 2) log2(x); v_log_f32 is good to 1 ulp of log2 -> < 1e-5 dB */ \
+                            tile[m * 33 + fl] = 3.01029995663981195f * __log2f(fmaxf(acc, AMIN));       \
+                        }                                                                               \
+                        ++g;                                                                            \
+                        a0 = a1 = a2 = a3 = 0.0f;                                                       \
+                    }                                                                                   \
+                } while (0)
+                // the fences keep the prologue's reads in the loop's order, so that the counted waits at the loop's
+                // head (the compiler takes the worse of both ways in) are those of the steady state
+                MEL_BASE(xbA, 0);
+                MEL_BASE(xbB, 1);
+                __builtin_amdgcn_sched_barrier(0);
+                MEL_REQ(wA, xA, xbA, xbC, 0);
+                __builtin_amdgcn_sched_barrier(0);
+                MEL_REQ(wB, xB, xbB, xbA, 1);
+                __builtin_amdgcn_sched_barrier(0);
+                for (int q = 0; q < nblk; q += 3) {                // no early exit: a sum past the last block goes nowhere
+                    MEL_REQ(wC, xC, xbC, xbB, q + 2); MEL_SUM(wA, xA, q);
+                    MEL_REQ(wA, xA, xbA, xbC, q + 3); MEL_SUM(wB, xB, q + 1);
+                    MEL_REQ(wB, xB, xbB, xbA, q + 4); MEL_SUM(wC, xC, q + 2);
                 }
-                a0 = fmaf(w0, x0, a0); a1 = fmaf(w1, x1, a1); a2 = fmaf(w2, x2, a2); a3 = fmaf(w3, x3, a3);
-                const float acc = (a0 + a1) + (a2 + a3);
-                if (m < n_mels && f < Tb) {
-                    vmax = fmaxf(vmax, acc);
-                    // 10 log10(x) = (10 log10 2) log2(x); v_log_f32 is good to 1 ulp of log2 -> < 1e-5 dB
-                    tile[m * 33 + fl] = 3.01029995663981195f * __log2f(fmaxf(acc, AMIN));
-                }
+#undef MEL_BASE
+#undef MEL_REQ
+#undef MEL_SUM
+#undef MEL_END
             }
             lds_sync_wave();
             MDIAG(7);

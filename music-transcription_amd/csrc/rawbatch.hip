@@ -77,9 +77,8 @@ extern "C" int mt_mel_db_windows_f32(const void* plan, const mt_mel_desc* desc, 
     const char* p = (const char*)plan;
     hipStream_t st = (hipStream_t)stream;
     MT_CHECK_HIP(hipMemsetAsync(chunk_max_power, 0, (size_t)B * 4, st));
-    const int ngrp = (n_mels + 31) / 32;
-    const size_t lds = (size_t)NWAVE * 2 * XREG * 4 + 2 * 1024 * 8 + (size_t)n_mels * 33 * 4 + (size_t)ngrp * 32 * 4 + 32 * 4 +
-                       (size_t)desc->ell_rows * 32 * 4;
+    MT_REQUIRE(desc->ell_rows % 4 == 0, MT_EINVAL, "mt_mel_db_windows_f32: bad descriptor");
+    const size_t lds = mel_lds_bytes(n_mels, desc->ell_rows);
     MT_REQUIRE(lds <= 160 * 1024, MT_EUNSUPPORTED, "mt_mel_db_windows_f32: n_mels=%d needs %zu B of LDS", n_mels, lds);
     MT_SET_MAX_LDS((mel_kernel<true>), 160 * 1024);
     const int tiles_per_chunk = cdiv(T_full > T_out ? T_full : T_out, FT);
@@ -88,7 +87,7 @@ extern "C" int mt_mel_db_windows_f32(const void* plan, const mt_mel_desc* desc, 
     dim3 grid(n_tiles < 256 ? n_tiles : 256);
     hipLaunchKernelGGL(mel_kernel<true>, grid, dim3(NWAVE * 64), lds, st, store, max_win_len, T_full, hop, n_mels, B, tiles_per_chunk,
                        (const float2*)(p + L.window), (const float2*)(p + L.tw1024), (const float2*)(p + L.w2048),
-                       (const int*)(p + L.fstart), (const int*)(p + L.grp), (const float*)(p + L.well), desc->ell_rows,
+                       (const int*)(p + L.xbase), (const unsigned long long*)(p + L.endmask), (const float*)(p + L.well), desc->ell_rows,
                        mel_db, (unsigned*)chunk_max_power, win_off, win_len, rec_end, t_keep, T_out);
     MT_CHECK_LAUNCH();
     if (T_out > 0) {
