@@ -133,6 +133,26 @@ int    mt_roll_windows(const int* spans, const long long* pitch_off, const int* 
                        const long long* win_cols, const int* win_ncols, const int* t_keep, int B, int T_out,
                        float* roll, mt_stream_t stream);
 
+/* Training augmentation of the same windows (csrc/augment.hip): out[B][L_max] f32 (L_max a multiple of 4, >= every win_len[b]),
+ * row b = win_len[b] samples of window b read at speed r_b = rate_q32[b] / 2^32, then zeros.  Output i interpolates the window at
+ * pos = i * rate_q32[b] (64-bit): k = pos >> 32, frac = pos & 0xffffffff, ph = frac >> 24, mu = (frac & 0xffffff) * 2^-24,
+ * c_j = tab[ph][j] + mu * (tab[ph + 1][j] - tab[ph][j]), y_i = sum_{j < 32} c_j * x[k - 15 + j]; x is the store relative to
+ * win_off[b] and reads as 0 outside [-before[b], after[b]) (the window's recording; after[b] may be <= 0 or < win_len[b]).
+ * tab[257][32] f32 is the caller's phase table (16-byte aligned; rows 0 and 256 unit impulses at taps 15 and 16, so that
+ * rate_q32 = 2^32 copies the window bit for bit).  Every rate_q32[b] must lie in [rate_lo_q32, rate_hi_q32], itself within
+ * 2^32 * (1 +- 0.03); the kernel clamps a rate outside the bounds it was given, so that no read leaves the staged span.
+ * noise_rel (may be NULL: no noise) adds white noise after resampling: sigma_b = sqrt(mean y^2 over win_len[b]) *
+ * noise_rel[b], out_i = y_i + sigma_b * g(seed, b, i) with g a standard normal from a counter-based hash (Box-Muller);
+ * noise_rel[b] <= 0 or a silent window adds none.  The mean square is reduced in a fixed order: ws receives one f32 partial sum
+ * of squares per (window, tile of 2048 outputs), ws[b * ceil(L_max / 2048) + t], and they are added in a fixed f64 tree.
+ * ws / ws_bytes (mt_augment_ws_bytes) are needed only with noise_rel.  mt_mel_db_windows_f32 then takes `out` as its store
+ * with win_off[b] = b * L_max and rec_end = win_len.  All tables are device pointers.                                  */
+size_t mt_augment_ws_bytes(int B, int L_max);
+int    mt_augment_windows(const float* store, const long long* win_off, const int* win_len, const int* before,
+                          const int* after, const unsigned long long* rate_q32, unsigned long long rate_lo_q32,
+                          unsigned long long rate_hi_q32, const float* noise_rel, unsigned seed, const float* tab, int B,
+                          int L_max, float* out, void* ws, size_t ws_bytes, mt_stream_t stream);
+
 /* Overlapping windows on one frame grid (csrc/stitch.hip, windows.py): src[Bw][P][Tw] holds the rows of Bw windows, which may
  * come from several recordings.  For each window b, local frames t in [keep_lo[b], keep_hi[b]) of every row p are copied to
  * dst[dst_row[b]][p][dst_frame0[b] + t] of dst[R][P][T_dst]; nothing else in dst is written (the caller pre-fills padding).

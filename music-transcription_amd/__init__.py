@@ -41,7 +41,7 @@ from .train import make_optimizer, train_one_epoch                              
 from .data import CachedMaestroDataset, collate_fn, write_cache_chunk, write_cache_metadata   # noqa: F401
 from .notes import (heads_to_notes_device, note_grid_counts, note_match_counts, note_match_list, note_prf, note_sweep_counts,   # noqa: F401
                     notes_batch_device, smooth_frame_logits, smooth_frame_paths)
-from .rawdata import DeviceBatchLoader, HybridMaestroDataset, MaestroDataset                 # noqa: F401
+from .rawdata import Augment, DeviceBatchLoader, HybridMaestroDataset, MaestroDataset               # noqa: F401
 from .windows import WindowPlan, collect_logits_windows, plan_windows, transcribe_windows      # noqa: F401
 
 __version__ = "0.3.0"

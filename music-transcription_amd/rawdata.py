@@ -14,6 +14,8 @@ A batch is then two launches (csrc/rawbatch.hip): mt_mel_db_windows_f32 (mel of 
 and mt_roll_windows (labels), with the same bytes a cache record written by preprocess_and_cache holds, collated as
 data.collate_fn does.  A chunk is sliced from the recording resampled once, as the cache writer does; the reference
 resamples each slice on its own (librosa.load(offset, duration), soxr).
+With MaestroDataset(augment=Augment(...)) one more launch (csrc/augment.hip, mt_augment_windows) plays every window at a drawn
+speed and adds noise before the mel launch reads it, and the labels go through a column table built for the batch's speeds.
 """
 from __future__ import annotations
 
@@ -209,6 +211,77 @@ def roll_from_spans(spans: np.ndarray, pitch_off: np.ndarray, t_keep: int, cols:
     return out
 
 
+# ------------------------------------------------------------------ augmentation
+AUG_TAPS, AUG_PHASES, AUG_BETA = 32, 256, 10.0
+AUG_MAX_DEV = 0.03           # mt_augment_windows takes speeds within 1 +- 0.03 (50 cents = 1.0293)
+_ONE_Q32 = 1 << 32
+
+
+def augment_table(beta: float = AUG_BETA) -> np.ndarray:
+    """mt_augment_windows' interpolation table, float64 (AUG_PHASES + 1, AUG_TAPS): tab[ph][j] = sinc(t) * kaiser_beta(t / 16) at
+    t = j - 15 - ph / P (a full-band sinc, no cutoff narrowing), every row normalised to unit sum, rows 0 and P exact unit
+    impulses at taps 15 and 16 (speed 1 copies the window).  The device holds it as float32."""
+    half = AUG_TAPS // 2
+    ph = np.arange(AUG_PHASES + 1, dtype=np.float64)[:, None] / AUG_PHASES
+    t = np.arange(AUG_TAPS, dtype=np.float64)[None, :] - (half - 1) - ph
+    u = np.clip(1.0 - (t / half) ** 2, 0.0, None)
+    tab = np.sinc(t) * np.i0(beta * np.sqrt(u)) / np.i0(beta)
+    tab /= tab.sum(axis=1, keepdims=True)
+    tab[0] = 0.0
+    tab[0, half - 1] = 1.0
+    tab[AUG_PHASES] = 0.0
+    tab[AUG_PHASES, half] = 1.0
+    return tab
+
+
+def augmented_cols(start_time: float, end_time: float, fs: float, rate_q32: int) -> np.ndarray:
+    """column_grid for a window played at speed r = rate_q32 / 2^32: output time t0 + d shows source time t0 + r * d, so column
+    n samples source frame round((t0 + r * (times[n] - t0)) * fs), in float64.  r = 1 is column_grid itself."""
+    if int(rate_q32) == _ONE_Q32:
+        return column_grid(start_time, end_time, fs)
+    times = np.asarray(np.linspace(start_time, end_time, int((end_time - start_time) * fs)), dtype=np.float64)
+    r = float(int(rate_q32)) / float(_ONE_Q32)
+    return np.array(np.round((start_time + r * (times - start_time)) * fs), dtype=np.int64)
+
+
+class Augment:
+    """Per-window training augmentation of MaestroDataset's chunks, on the GPU (csrc/augment.hip):
+      * pitch_cents c: each window is played at speed 2^(cents / 1200), cents ~ U(-c, c) -- pitch and tempo move together and the
+        labels' columns move with the audio.  0 <= c <= 50, so no note leaves its semitone and the label rows stay what they are;
+      * snr_db (lo, hi) or None: white noise at a signal-to-noise ratio ~ U(lo, hi) dB against the window's own power.
+    Draws come from `generator` (a CPU torch.Generator; a fresh default-seeded one when None).  A level change is not offered:
+    the mel is normalised to the chunk maximum and clamped 80 dB under it, so gain is invisible to the model."""
+
+    def __init__(self, pitch_cents: float = 10.0, snr_db=None, generator: Optional[torch.Generator] = None):
+        pitch_cents = float(pitch_cents)
+        if not 0.0 <= pitch_cents <= 50.0:
+            raise ValueError(f"Augment: pitch_cents must be in [0, 50] (the labels' pitches never change), got {pitch_cents}")
+        if snr_db is not None:
+            try:
+                lo, hi = (float(v) for v in snr_db)
+            except (TypeError, ValueError):
+                raise ValueError(f"Augment: snr_db must be None or a (lo, hi) pair in dB, got {snr_db!r}") from None
+            if not 0.0 <= lo <= hi:
+                raise ValueError(f"Augment: snr_db needs 0 <= lo <= hi, got ({lo}, {hi})")
+            snr_db = (lo, hi)
+        self.pitch_cents, self.snr_db = pitch_cents, snr_db
+        self.generator = generator if generator is not None else torch.Generator()
+
+    def draw(self, n: int):
+        """The draws of one batch of n windows: (rate_q32 uint64 (n,), snr_db float64 (n,) -- NaN without noise --, seed < 2^31).
+        Order of the generator's use: n cents, n SNRs (only with snr_db), one seed."""
+        g = self.generator
+        cents = (torch.rand(n, dtype=torch.float64, generator=g).numpy() * 2.0 - 1.0) * self.pitch_cents
+        rate = np.rint(np.exp2(cents / 1200.0) * float(_ONE_Q32)).astype(np.uint64)
+        if self.snr_db is not None:
+            lo, hi = self.snr_db
+            snr = lo + (hi - lo) * torch.rand(n, dtype=torch.float64, generator=g).numpy()
+        else:
+            snr = np.full(n, np.nan)
+        seed = int(torch.randint(0, 1 << 31, (1,), generator=g).item())
+        return rate, snr, seed
+
+
 # ------------------------------------------------------------------ audio
 class RecordingStore:
     """Decoded recordings in one f32 device buffer (64-bit offsets), LRU of whole recordings when over budget."""
@@ -303,12 +376,20 @@ class MaestroDataset(Dataset):
     "roll" builds neither table and returns what it always did."""
 
     def __init__(self, root_dir, csv_path=None, year=None, split="train", sr=16000, n_mels=229, hop_length=512, subset_size=None,
-                 chunk_length=None, overlap=0.0, return_waveform=False, device=None, max_resident_bytes=None, onset_labels="roll"):
+                 chunk_length=None, overlap=0.0, return_waveform=False, device=None, max_resident_bytes=None, onset_labels="roll",
+                 augment=None):
         if return_waveform:
             raise NotImplementedError("return_waveform=True is the AST experiment's data path (out of scope)")
         if onset_labels not in ("roll", "midi"):
             raise ValueError(f"onset_labels must be 'roll' or 'midi', got {onset_labels!r}")
-        self.onset_labels = onset_labels
+        if augment is not None:
+            if not isinstance(augment, Augment):
+                raise TypeError(f"augment must be an Augment or None, got {type(augment).__name__}")
+            if chunk_length is None:
+                raise ValueError("MaestroDataset: augment needs chunk_length (whole-file items have no column table to move the "
+                                 "labels with the audio, and augmentation is a training feature)")
+        self.onset_labels, self.augment, self.last_augment = onset_labels, augment, None
+        self._aug_tab = None                                # mt_augment_windows' phase table, uploaded with the first augmented batch
         self.root_dir, self.sr, self.n_mels, self.hop_length = root_dir, int(sr), int(n_mels), int(hop_length)
         self.chunk_length, self.overlap, self.return_waveform = chunk_length, overlap, return_waveform
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -337,6 +418,8 @@ class MaestroDataset(Dataset):
             self.rec = np.array([x["file_idx"] for x in c], dtype=np.int64)
             self.start = np.array([x["start_sample"] for x in c], dtype=np.int64)
             self.win_len = np.array([x["end_sample"] - x["start_sample"] for x in c], dtype=np.int64)
+            self.chunk_t0 = np.array([x["start_time"] for x in c], dtype=np.float64)
+            self.chunk_t1 = np.array([x["end_time"] for x in c], dtype=np.float64)
             grids = [column_grid(x["start_time"], x["end_time"], fs) for x in c]
             self.ncols = np.array([len(g) for g in grids], dtype=np.int64)
             self.col_off = np.concatenate([[0], np.cumsum(self.ncols)[:-1]]).astype(np.int64) if c else np.zeros(0, np.int64)
@@ -429,6 +512,8 @@ class MaestroDataset(Dataset):
         B = len(idx)
         if B == 0:
             raise ValueError("get_batch: empty batch")
+        if self.augment is not None:
+            return self._get_batch_augmented(idx)
         recs = self.rec[idx]
         offs = self.store.offsets(recs.tolist())
         n_rec = np.array(self.store.n, dtype=np.int64)
@@ -457,6 +542,64 @@ class MaestroDataset(Dataset):
                 return mel, {"frame": roll, "onset": onset_roll}, torch.from_numpy(t_keep.copy())
         return mel, roll, torch.from_numpy(t_keep.copy())
 
+    def _get_batch_augmented(self, idx):
+        """get_batch with self.augment: mt_augment_windows writes the batch's windows, speed-changed and noised, into a dense
+        (B, L_max) buffer; mt_mel_db_windows_f32 reads that buffer as its store; the labels go through a column table built
+        for this batch's speeds (augmented_cols).  t_keep and T_out are those of the plain batch.  The draws stay in
+        self.last_augment = {"rate_q32" uint64 (B,), "snr_db" float64 (B,) (NaN: no noise), "seed" uint32 ()}."""
+        B, aug, dev = len(idx), self.augment, self.device
+        rate, snr, seed = aug.draw(B)
+        rate = np.ascontiguousarray(rate, dtype=np.uint64)
+        snr = np.ascontiguousarray(snr, dtype=np.float64)
+        if rate.shape != (B,) or snr.shape != (B,) or abs(int(rate.min()) - _ONE_Q32) > int(AUG_MAX_DEV * _ONE_Q32) \
+                or abs(int(rate.max()) - _ONE_Q32) > int(AUG_MAX_DEV * _ONE_Q32):
+            raise ValueError(f"Augment.draw: {B} speeds within 1 +- {AUG_MAX_DEV} expected")
+        self.last_augment = {"rate_q32": rate.copy(), "snr_db": snr.copy(), "seed": np.array(seed, dtype=np.uint32)}
+        noisy = bool(np.isfinite(snr).any())
+        recs = self.rec[idx]
+        offs = self.store.offsets(recs.tolist())
+        n_rec = np.array(self.store.n, dtype=np.int64)
+        t_keep, win_len = self.t_keep[idx], self.win_len[idx]
+        T_out = int(t_keep.max())
+        L_max = -(-int(win_len.max()) // 4) * 4
+        fs = self.sr / self.hop_length
+        grids = [augmented_cols(self.chunk_t0[i], self.chunk_t1[i], fs, int(r)) for i, r in zip(idx, rate)]
+        ncols = np.array([len(g) for g in grids], dtype=np.int64)
+        cols = np.concatenate(grids).astype(np.int32) if ncols.sum() else np.zeros(1, np.int32)
+        h64 = torch.empty((4, B), dtype=torch.int64, pin_memory=True)
+        h64.copy_(torch.from_numpy(np.stack([np.array([offs[int(r)] for r in recs], dtype=np.int64) + self.start[idx],
+                                             np.concatenate([[0], np.cumsum(ncols)[:-1]]).astype(np.int64),
+                                             np.arange(B, dtype=np.int64) * L_max, rate.view(np.int64)])))
+        noise_rel = np.where(np.isfinite(snr), 10.0 ** (-np.nan_to_num(snr) / 20.0), 0.0).astype(np.float32)
+        h32 = torch.empty((7, B), dtype=torch.int32, pin_memory=True)
+        h32.copy_(torch.from_numpy(np.stack([win_len, n_rec[recs] - self.start[idx], t_keep, recs, ncols, self.start[idx],
+                                             noise_rel.view(np.int32).astype(np.int64)])))
+        hcols = torch.from_numpy(cols).pin_memory()
+        if self._aug_tab is None:
+            self._aug_tab = torch.from_numpy(augment_table().astype(np.float32)).to(dev)
+        with torch.cuda.device(dev):
+            d64, d32, dcols = h64.to(dev, non_blocking=True), h32.to(dev, non_blocking=True), hcols.to(dev, non_blocking=True)
+            wave = torch.empty(B * L_max, dtype=torch.float32, device=dev)
+            ws_bytes = int(lib.mt_augment_ws_bytes(B, L_max)) if noisy else 0
+            ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=dev) if noisy else None
+            mel = torch.empty(B, 1, self.n_mels, T_out, dtype=torch.float32, device=dev)
+            cmax = torch.empty(B, dtype=torch.float32, device=dev)
+            roll = torch.empty(B, N_PITCH, T_out, dtype=torch.float32, device=dev)
+            st = _lib.stream_ptr()
+            check(lib.mt_augment_windows(ptr(self.store.buf), ptr(d64[0]), ptr(d32[0]), ptr(d32[5]), ptr(d32[1]), ptr(d64[3]), int(rate.min()),
+                                         int(rate.max()), ptr(d32[6]) if noisy else None, seed, ptr(self._aug_tab), B, L_max, ptr(wave), ptr(ws),
+                                         ws_bytes, st), "mt_augment_windows")
+            check(lib.mt_mel_db_windows_f32(ptr(self.fe.plan), self.fe.desc, ptr(wave), ptr(d64[2]), ptr(d32[0]), ptr(d32[0]), B,
+                                            int(win_len.max()), T_out, ptr(d32[2]), ptr(mel), ptr(cmax), st), "mt_mel_db_windows_f32")
+            check(lib.mt_roll_windows(ptr(self.spans), ptr(self.pitch_off), ptr(dcols), ptr(d32[3]), ptr(d64[1]), ptr(d32[4]), ptr(d32[2]),
+                                      B, T_out, ptr(roll), st), "mt_roll_windows")
+            if self.onset_labels == "midi":
+                onset_roll = torch.empty_like(roll)
+                check(lib.mt_roll_windows(ptr(self.onset_spans), ptr(self.onset_pitch_off), ptr(dcols), ptr(d32[3]), ptr(d64[1]),
+                                          ptr(d32[4]), ptr(d32[2]), B, T_out, ptr(onset_roll), st), "mt_roll_windows")
+                return mel, {"frame": roll, "onset": onset_roll}, torch.from_numpy(t_keep.copy())
+        return mel, roll, torch.from_numpy(t_keep.copy())
+
     def __getitem__(self, idx):
         if _in_worker():
             raise RuntimeError("MaestroDataset items are built on the GPU and cannot be read in a DataLoader worker process "
@@ -468,14 +611,17 @@ class MaestroDataset(Dataset):
 
 
 class HybridMaestroDataset(Dataset):
-    """data/cached_dataset.py:91-141: the cache when its metadata's chunk_length and overlap equal the request, else MaestroDataset."""
+    """data/cached_dataset.py:91-141: the cache when its metadata's chunk_length and overlap equal the request, else MaestroDataset.
+    A request with `augment` never uses the cache: its records hold features, and augmentation works on the waveform."""
 
-    def __init__(self, root_dir, cache_dir="cached_dataset", split="train", chunk_length=None, overlap=0.0, **kwargs):
+    def __init__(self, root_dir, cache_dir="cached_dataset", split="train", chunk_length=None, overlap=0.0, augment=None, **kwargs):
         from .data import CachedMaestroDataset
         self.use_cache = False
+        if augment is not None:
+            kwargs["augment"] = augment
         try:
             metadata_path = os.path.join(cache_dir, f"{split}_metadata.pkl")
-            if os.path.exists(metadata_path):
+            if augment is None and os.path.exists(metadata_path):
                 with open(metadata_path, "rb") as f:
                     metadata = pickle.load(f)
                 if metadata.get("chunk_length") == chunk_length and metadata.get("overlap") == overlap:

@@ -13,6 +13,9 @@ music_transcription_amd/rawdata.py), where --subset_size counts recordings as in
 (no --chunk_length and no usable cache) is refused before the first step.  `--train_all_heads --onset_labels midi` trains the
 onset head against the MIDI note-ons (a key struck again under the pedal or without a gap gets its onset) instead of the rising
 edges of the label roll; cache records hold no note list, so it always reads the recordings under --root_dir.
+`--augment_pitch_cents X` and `--augment_snr_db LO HI` (either or both) augment the training set on the GPU: each chunk is played at
+a speed within +-X cents and gets white noise at a signal-to-noise ratio drawn from [LO, HI] dB, the labels moving with the audio
+(rawdata.Augment).  They work on the waveform, so they too read the recordings under --root_dir; validation is never augmented.
 
 One process per GPU.  Every step is the HIP training step (train-mode forward, backward, fused clip + Adam); with more
 than one rank each rank draws its own shard of the shuffled chunk indices (DistributedSampler) and the flat gradient
@@ -67,6 +70,12 @@ def main():
                     help="onset targets of --train_all_heads: roll = rising edges of the label roll (default); midi = the MIDI note-ons, "
                          "re-struck keys included.  midi reads the recordings under --root_dir even where a cache matches (cache records "
                          "hold no note list)")
+    ap.add_argument("--augment_pitch_cents", type=float, default=None, metavar="X",
+                    help="training set only: play each chunk at a speed drawn from +-X cents (0..50; pitch and tempo move together, "
+                         "labels follow).  Reads the recordings under --root_dir even where a cache matches")
+    ap.add_argument("--augment_snr_db", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                    help="training set only: add white noise at a signal-to-noise ratio drawn from [LO, HI] dB per chunk.  Reads the "
+                         "recordings under --root_dir even where a cache matches")
     ap.add_argument("--run_dir", default="outputs/train_cnn")
     ap.add_argument("--num_workers", type=int, default=4)
     ap.add_argument("--seed", type=int, default=0)
@@ -79,6 +88,15 @@ def main():
     if midi_onsets and not args.train_all_heads:
         print("Error: --onset_labels midi sets the onset head's targets and needs --train_all_heads", file=sys.stderr)
         return 2
+
+    augmenting = args.augment_pitch_cents is not None or args.augment_snr_db is not None
+    if augmenting:
+        if not 0.0 <= (args.augment_pitch_cents or 0.0) <= 50.0:
+            print("Error: --augment_pitch_cents must be within 0..50 (the labels' pitches never change)", file=sys.stderr)
+            return 2
+        if args.augment_snr_db is not None and not 0.0 <= args.augment_snr_db[0] <= args.augment_snr_db[1]:
+            print("Error: --augment_snr_db needs 0 <= LO <= HI", file=sys.stderr)
+            return 2
 
     import pickle
     meta_path = os.path.join(args.cached_dir, "train_metadata.pkl")
@@ -93,13 +111,14 @@ def main():
     else:
         chunk_length, overlap, use_cache = args.chunk_length, args.chunk_overlap or 0.0, False
     cache_matches = use_cache
-    if midi_onsets:
+    if midi_onsets or augmenting:
         use_cache = False
     if not use_cache and chunk_length is None:
         print("Error: full-file training is not supported (the training recurrence takes chunk-length sequences): "
               "pass --chunk_length (e.g. 30.0) or a matching --cached_dir", file=sys.stderr)
         return 2
-    if midi_onsets:
+    if midi_onsets or augmenting:
+        needs = "--onset_labels midi reads the MIDI note lists" if midi_onsets else "--augment_* reads the waveforms"
         from music_transcription_amd.preprocess import read_maestro_csv
         try:
             n_rec = len(read_maestro_csv(args.root_dir, "train", args.year, args.subset_size, None))
@@ -108,7 +127,7 @@ def main():
         else:
             why_none = "its csv lists no train recordings"
         if n_rec == 0:
-            print(f"Error: --onset_labels midi reads the MIDI note lists of the recordings under --root_dir, and {args.root_dir} "
+            print(f"Error: {needs} of the recordings under --root_dir, and {args.root_dir} "
                   f"has none ({why_none})", file=sys.stderr)
             return 2
 
@@ -146,10 +165,18 @@ def main():
             why = "no cache" if meta is None else f"cache has chunk_length={meta.get('chunk_length')}, overlap={meta.get('overlap')}"
             if midi_onsets and cache_matches:
                 why = "the cache matches, but --onset_labels midi needs the MIDI note lists and cache records hold none"
+            elif augmenting and cache_matches:
+                why = "the cache matches, but --augment_* works on the waveforms and cache records hold features only"
             print(f"Data source: raw recordings {args.root_dir} on the GPU (chunk_length={chunk_length}, overlap={overlap}; {why})", flush=True)
         kw_raw = dict(year=args.year, n_mels=args.n_mels, subset_size=args.subset_size, chunk_length=chunk_length, device=dev,
                       onset_labels=args.onset_labels)
-        train_ds = mta.MaestroDataset(args.root_dir, split="train", overlap=overlap, **kw_raw)
+        augment = None
+        if augmenting:                                 # the training set only; each rank draws its own speeds and noise
+            augment = mta.Augment(pitch_cents=args.augment_pitch_cents or 0.0, snr_db=args.augment_snr_db,
+                                  generator=torch.Generator().manual_seed(args.seed + rank))
+            if rank == 0:
+                print(f"Augmentation (training set): pitch +-{augment.pitch_cents} cents, snr_db {augment.snr_db}", flush=True)
+        train_ds = mta.MaestroDataset(args.root_dir, split="train", overlap=overlap, augment=augment, **kw_raw)
         val_ds = mta.MaestroDataset(args.root_dir, split="validation", overlap=0.0, **kw_raw)
     sampler = DistributedSampler(train_ds, num_replicas=world, rank=rank, shuffle=True, seed=args.seed, drop_last=True) if world > 1 else None
     if use_cache:
