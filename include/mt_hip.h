@@ -425,6 +425,26 @@ int    mt_bce_masked_fwd_bwd(const float* logits, const float* targets, const lo
 /* onset/offset targets from a roll (transcription_model.py:176-185): rows x T, diff along T. */
 int    mt_onset_offset_targets(const float* roll, float* onset, float* offset, long long rows, int T,
                                mt_stream_t stream);
+/* Class-weighted / focal BCE for the frame, onset and offset heads in one pass (csrc/heads_loss.hip, DESIGN.md 6b "Weighted and focal
+ * loss").  Per valid cell of head h, logit x, target y in [0, 1], w = pos_weight[h], g = gamma[h]:
+ *   a = softplus(x), b = softplus(-x), l = w y exp(-g a) b + (1 - y) exp(-g b) a         (w = 1, g = 0: the BCE above)
+ *   loss_h = head_weight[h] sum_valid l / max(n_valid_frames*P, 1);  grad_h = head_weight[h] (dl/dx) / denom, exactly 0 in masked frames.
+ * loss (device, 4 floats) = {total, frame, onset, offset}, each part times its head weight, total = (frame + onset) + offset.
+ * Logits, roll, onset_roll and gradients are [B][P][T].  onset_logits and offset_logits both NULL: one head (loss[2] = loss[3] = 0, the
+ * onset / offset gradients are not written).  The offset target and, with onset_roll == NULL, the onset target are those of
+ * mt_onset_offset_targets bit for bit, formed from the roll inside the kernel (within a row, whatever lengths says); with onset_roll the
+ * onset head is trained against it.  NaN / Inf in a masked frame of any input reaches neither the loss nor a gradient; a non-finite roll
+ * value in the first masked frame counts as 0 in the last valid frame's offset target.  lengths, n_valid_frames: as
+ * mt_bce_masked_fwd_bwd.  head_weight, pos_weight, gamma: HOST arrays of 3 (frame, onset, offset), taken by value at the call; all three
+ * entries are checked also for one head.  Any gradient pointer may be NULL.  workspace: mt_heads_loss_workspace_bytes().
+ * MT_EINVAL, nothing written: a null frame_logits / roll / loss / workspace / host array, exactly one of onset_logits and offset_logits,
+ * onset_roll without onset_logits, a non-positive dim, pos_weight <= 0, head_weight < 0, gamma outside [0, 8], or a non-finite value.
+ * MT_EWORKSPACE: workspace too small.  Two launches on `stream`, no atomics, no synchronisation, allocation or copy; bitwise reproducible. */
+size_t mt_heads_loss_workspace_bytes(void);
+int    mt_heads_loss_fwd_bwd(const float* frame_logits, const float* onset_logits, const float* offset_logits, const float* roll,
+                             const float* onset_roll, const long long* lengths, long long n_valid_frames, const float* head_weight,
+                             const float* pos_weight, const float* gamma, float* loss, float* frame_grad, float* onset_grad,
+                             float* offset_grad, void* workspace, size_t workspace_bytes, int B, int P, int T, mt_stream_t stream);
 /* roll = (sigmoid(logits) > threshold) as float {0,1} (transcription_model.py:262-265, main.py:153-156). */
 int    mt_predict_threshold(const float* logits, float* roll, long long n, float threshold, mt_stream_t stream);
 /* counts[b] = {TP, FP, FN} (uint64) over the first lengths[b] frames (evaluate.py:361-373). */

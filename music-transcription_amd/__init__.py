@@ -35,7 +35,7 @@ from ._lib import MtError                            # noqa: F401
 from .frontend import MelFrontend, audio_to_mel, get_frontend, mel_filterbank, num_frames   # noqa: F401
 from .model import CNNRNNModel, CNNRNNModelLarge, TranscriptionModel                          # noqa: F401
 from . import ops                                                                             # noqa: F401
-from .ops import compute_loss, framewise_f1, mean_f1, predict_from_logits                     # noqa: F401
+from .ops import LossConfig, compute_loss, framewise_f1, heads_loss, mean_f1, predict_from_logits   # noqa: F401
 from .optim import FusedAdamClip, flatten_parameters, allreduce_mean_                        # noqa: F401
 from .train import make_optimizer, train_one_epoch                                            # noqa: F401  (train.evaluate = validation loss)
 from .data import CachedMaestroDataset, collate_fn, write_cache_chunk, write_cache_metadata   # noqa: F401

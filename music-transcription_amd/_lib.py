@@ -142,6 +142,8 @@ _SIGS = {
     "mt_bce_workspace_bytes": (sz, []),
     "mt_bce_masked_fwd_bwd": (i32, [vp, vp, vp, C.c_longlong, C.c_float, i32, vp, vp, vp, sz, i32, i32, i32, vp]),
     "mt_onset_offset_targets": (i32, [vp, vp, vp, C.c_longlong, i32, vp]),
+    "mt_heads_loss_workspace_bytes": (sz, []),
+    "mt_heads_loss_fwd_bwd": (i32, [vp, vp, vp, vp, vp, vp, C.c_longlong, vp, vp, vp, vp, vp, vp, vp, vp, sz, i32, i32, i32, vp]),
     "mt_predict_threshold": (i32, [vp, vp, C.c_longlong, C.c_float, vp]),
     "mt_f1_counts": (i32, [vp, vp, vp, vp, i32, i32, i32, vp]),
     "mt_f1_sweep_counts": (i32, [vp, vp, vp, vp, i32, vp, i32, i32, i32, vp]),

@@ -555,10 +555,11 @@ class TranscriptionModel(nn.Module):
             return self.model(x, return_all_heads=return_all_heads)
         return self.model(x)
 
-    def compute_loss(self, logits, targets, lengths=None):
-        """Masked BCE-with-logits (single tensor or frame/onset/offset dict; targets a roll or a frame/onset dict); see ops.compute_loss."""
+    def compute_loss(self, logits, targets, lengths=None, *, loss=None):
+        """Masked BCE-with-logits (single tensor or frame/onset/offset dict; targets a roll or a frame/onset dict); loss: an
+        ops.LossConfig for the weighted / focal loss, None for plain BCE; see ops.compute_loss."""
         from . import ops
-        return ops.compute_loss(logits, targets, lengths)
+        return ops.compute_loss(logits, targets, lengths, loss=loss)
 
     @torch.no_grad()
     def predict(self, x, threshold: float = 0.5, **kwargs):

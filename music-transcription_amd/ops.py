@@ -3,7 +3,10 @@ compute_loss (models/transcription_model.py:110-217), predict (:219-266) and the
 F1 (scripts/evaluate.py:361-378)."""
 from __future__ import annotations
 
-from typing import Optional
+import ctypes as C
+import math
+from dataclasses import dataclass
+from typing import Optional, Tuple
 
 import torch
 
@@ -62,10 +65,106 @@ def onset_offset_targets(targets):
     return on, off
 
 
-def compute_loss(logits, targets, lengths=None):
+def _three(v, name, lo, hi, lo_open):
+    """a scalar or 3 values (frame, onset, offset) -> 3 finite floats inside the range, else ValueError"""
+    vals = tuple(float(x) for x in v) if isinstance(v, (tuple, list)) else (float(v),) * 3
+    if len(vals) != 3:
+        raise ValueError(f"{name}: one value or three (frame, onset, offset), got {len(vals)}")
+    for x in vals:
+        if not math.isfinite(x) or x > hi or x < lo or (lo_open and x == lo):
+            raise ValueError(f"{name}: {x} is outside {'(' if lo_open else '['}{lo}, {hi}{']' if math.isfinite(hi) else ')'}")
+    return vals
+
+
+@dataclass(frozen=True)
+class LossConfig:
+    """Settings of the weighted / focal three-head loss (heads_loss): each field one value for all heads or (frame, onset, offset).
+    head_weights >= 0, pos_weight > 0 (torch's pos_weight: the factor on the positive term), 0 <= focal_gamma <= 8 (Lin et al. 2017;
+    0 = no focusing); all finite, else ValueError.  The defaults are today's loss, 0.5 frame + 0.25 onset + 0.25 offset plain BCE."""
+    head_weights: Tuple[float, float, float] = (0.5, 0.25, 0.25)
+    pos_weight: Tuple[float, float, float] = (1.0, 1.0, 1.0)
+    focal_gamma: Tuple[float, float, float] = (0.0, 0.0, 0.0)
+
+    def __post_init__(self):
+        object.__setattr__(self, "head_weights", _three(self.head_weights, "head_weights", 0.0, math.inf, False))
+        object.__setattr__(self, "pos_weight", _three(self.pos_weight, "pos_weight", 0.0, math.inf, True))
+        object.__setattr__(self, "focal_gamma", _three(self.focal_gamma, "focal_gamma", 0.0, 8.0, False))
+
+
+class _HeadsLoss(torch.autograd.Function):
+    """mt_heads_loss_fwd_bwd: the loss of one or three heads and every d/dlogits from ONE kernel pass over the roll."""
+
+    @staticmethod
+    def forward(ctx, frame, onset, offset, roll, onset_roll, lengths, cfg):
+        B, P, T = frame.shape
+        xs = [None if x is None else x.detach().contiguous().float() for x in (frame, onset, offset)]
+        y = roll.detach().contiguous().float()
+        yo = None if onset_roll is None else onset_roll.detach().contiguous().float()
+        dev = y.device
+        if lengths is not None:
+            len_host = lengths.detach().to("cpu", torch.int64)
+            n_valid = int(torch.clamp(len_host, 0, T).sum())
+            len_dev = len_host.to(dev)
+        else:
+            n_valid, len_dev = B * T, None
+        loss = torch.empty(4, dtype=torch.float32, device=dev)
+        grads = [torch.empty_like(x) if x is not None and need else None for x, need in zip(xs, ctx.needs_input_grad[:3])]
+        ws = torch.empty(lib.mt_heads_loss_workspace_bytes(), dtype=torch.uint8, device=dev)
+        f3 = C.c_float * 3
+        with torch.cuda.device(dev):
+            check(lib.mt_heads_loss_fwd_bwd(ptr(xs[0]), ptr(xs[1]), ptr(xs[2]), ptr(y), ptr(yo), ptr(len_dev), n_valid,
+                                            f3(*cfg.head_weights), f3(*cfg.pos_weight), f3(*cfg.focal_gamma), ptr(loss),
+                                            ptr(grads[0]), ptr(grads[1]), ptr(grads[2]), ptr(ws), ws.numel(), B, P, T, _lib.stream_ptr()),
+                  "mt_heads_loss_fwd_bwd")
+        ctx.grads = grads
+        _HeadsLoss.last_parts = loss
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        return tuple(None if gr is None else gr * g for gr in ctx.grads) + (None, None, None, None)
+
+
+def heads_loss(logits, targets, lengths=None, *, head_weights=(0.5, 0.25, 0.25), pos_weight=(1, 1, 1), focal_gamma=(0, 0, 0)):
+    """Class-weighted / focal masked BCE of the frame, onset and offset heads in one fused kernel (csrc/heads_loss.hip; formula and
+    gradient: DESIGN.md 6b "Weighted and focal loss").  `logits` is the three-head dict or a single tensor (B, 88, T); `targets` a roll
+    or the {"frame", "onset"} dict (onset head against the given onset roll), as compute_loss takes them.  pos_weight and focal_gamma:
+    one value for all heads or (frame, onset, offset); for a single tensor only element 0 is used and its head weight is 1.
+    Returns the total (differentiable with respect to the logits).  `heads_loss.last_parts` is then a detached device tensor of four
+    floats, {total, frame, onset, offset} of this call, each part already times its head weight: reading it costs no synchronisation
+    until the caller takes it to the host.  No host synchronisation beyond masked_bce's (lengths are read on the host, once)."""
+    cfg = LossConfig(head_weights, pos_weight, focal_gamma)
+    onset_roll = None
+    if isinstance(targets, dict):
+        if not isinstance(logits, dict):
+            raise ValueError("heads_loss: dict targets (frame / onset) go with the three-head dict of logits")
+        targets, onset_roll = targets["frame"], targets["onset"]
+    if isinstance(logits, dict):
+        frame, onset, offset = logits["frame"], logits["onset"], logits["offset"]
+    else:
+        frame, onset, offset = logits, None, None
+        cfg = LossConfig((1.0, 0.0, 0.0), cfg.pos_weight, cfg.focal_gamma)
+    heads = [t for t in (frame, onset, offset, targets, onset_roll) if t is not None]
+    _need_cuda(*heads)
+    if frame.dim() != 3 or any(t.shape != frame.shape for t in heads):
+        raise ValueError(f"heads_loss: logits and targets must all be (B, 88, T), got {[tuple(t.shape) for t in heads]}")
+    total = _HeadsLoss.apply(frame, onset, offset, targets, onset_roll, lengths, cfg)
+    heads_loss.last_parts = _HeadsLoss.last_parts
+    return total
+
+
+heads_loss.last_parts = None
+
+
+def compute_loss(logits, targets, lengths=None, *, loss: Optional[LossConfig] = None):
     """Single-head or dict (frame/onset/offset, weights .5/.25/.25) masked BCE.  With dict logits, `targets` may be the dict
     {"frame": roll, "onset": onset_roll} of MaestroDataset(onset_labels="midi"): the onset head is then trained against the given
-    onset roll (the MIDI note-ons) instead of the roll's rising edges; frame and offset terms as with a tensor."""
+    onset roll (the MIDI note-ons) instead of the roll's rising edges; frame and offset terms as with a tensor.
+    loss=None is that code path, launch for launch; a LossConfig computes heads_loss(...) with its settings in the fused kernel."""
+    if loss is not None:
+        if not isinstance(loss, LossConfig):
+            raise TypeError("compute_loss: loss is a LossConfig or None")
+        return heads_loss(logits, targets, lengths, head_weights=loss.head_weights, pos_weight=loss.pos_weight, focal_gamma=loss.focal_gamma)
     if isinstance(targets, dict):
         if not isinstance(logits, dict):
             raise ValueError("compute_loss: dict targets (frame / onset) go with the three-head dict of logits")

@@ -16,6 +16,7 @@ from typing import Iterable, List, Tuple
 import torch
 import torch.distributed as dist
 
+from . import ops
 from .optim import EarlyBucket, FusedAdamClip, flatten_parameters
 
 
@@ -57,12 +58,19 @@ def _forward(model, mel, all_heads: bool):
 
 
 def train_one_epoch(model, dataloader: Iterable, optimizer: FusedAdamClip, device, max_grad_norm: float = 1.0,
-                    log=None, all_heads: bool = False) -> Tuple[float, List[float]]:
+                    log=None, all_heads: bool = False, loss=None) -> Tuple[float, List[float]]:
+    """loss: an ops.LossConfig trains with the weighted / focal loss of ops.heads_loss instead of plain BCE (None, the default: the
+    call below is then exactly what it was).  With a config, `log` is also given the step's per-head losses as the keyword
+    parts={"frame", "onset", "offset"} (each already times its head weight; their sum is the step loss; without all_heads the
+    frame part alone is non-zero); its positional arguments (step, loss, gradient norm) are unchanged."""
     if not isinstance(optimizer, FusedAdamClip):
         raise TypeError("train_one_epoch drives the fused HIP optimizer: build it with make_optimizer(model, ...)")
     if all_heads:
         from .evaluate import require_heads
         require_heads(model, "train_one_epoch(all_heads=True)")
+    loss_cfg = loss
+    if loss_cfg is not None and not isinstance(loss_cfg, ops.LossConfig):
+        raise TypeError("train_one_epoch: loss is a LossConfig or None")
     model.train()
     optimizer.max_norm = float(max_grad_norm)
     total, step_losses, nan_count, n_batches = 0.0, [], 0, 0
@@ -81,8 +89,13 @@ def train_one_epoch(model, dataloader: Iterable, optimizer: FusedAdamClip, devic
         mel, roll, lengths = batch
         mel, roll = mel.to(device, non_blocking=True), _to_device(roll, device)
         logits = _forward(model, mel, all_heads)
-        loss = model.compute_loss(logits, roll, lengths)
-        step_loss = float(loss.item())
+        if loss_cfg is None:
+            loss = model.compute_loss(logits, roll, lengths)
+            step_loss, parts = float(loss.item()), None
+        else:
+            loss = model.compute_loss(logits, roll, lengths, loss=loss_cfg)
+            four = ops.heads_loss.last_parts.tolist()  # one copy for the total and the parts: the synchronisation .item() was
+            step_loss, parts = four[0], dict(zip(("frame", "onset", "offset"), four[1:]))
         bad = math.isnan(step_loss) or math.isinf(step_loss)
         if _world_size() > 1:
             # Data parallel: the skip must be COLLECTIVE.  optimizer.step() holds the gradient all-reduce, so a rank that
@@ -110,14 +123,18 @@ def train_one_epoch(model, dataloader: Iterable, optimizer: FusedAdamClip, devic
         total += step_loss
         step_losses.append(step_loss)
         if log is not None:
-            log(len(step_losses), step_loss, stats[0])
+            if parts is None:
+                log(len(step_losses), step_loss, stats[0])
+            else:
+                log(len(step_losses), step_loss, stats[0], parts=parts)
     avg = total / n_batches if step_losses else float("nan")
     return avg, step_losses
 
 
 @torch.no_grad()
 def evaluate(model, dataloader: Iterable, device, all_heads: bool = False) -> float:
-    """Mean validation loss (train_transcriber.py:161-191); all_heads as in train_one_epoch."""
+    """Mean validation loss (train_transcriber.py:161-191); all_heads as in train_one_epoch.  Always plain BCE, whatever LossConfig the
+    training used: the validation loss, and with it the choice of model_best, stays comparable between runs with different settings."""
     if all_heads:
         from .evaluate import require_heads
         require_heads(model, "evaluate(all_heads=True)")

@@ -16,6 +16,8 @@ edges of the label roll; cache records hold no note list, so it always reads the
 `--augment_pitch_cents X` and `--augment_snr_db LO HI` (either or both) augment the training set on the GPU: each chunk is played at
 a speed within +-X cents and gets white noise at a signal-to-noise ratio drawn from [LO, HI] dB, the labels moving with the audio
 (rawdata.Augment).  They work on the waveform, so they too read the recordings under --root_dir; validation is never augmented.
+`--pos_weight`, `--focal_gamma` and `--head_weights` (FRAME ONSET OFFSET each, or one value) train with the class-weighted / focal loss of
+ops.heads_loss in one fused kernel and add the per-head training losses to the epoch line; the validation loss stays plain BCE.
 
 One process per GPU.  Every step is the HIP training step (train-mode forward, backward, fused clip + Adam); with more
 than one rank each rank draws its own shard of the shuffled chunk indices (DistributedSampler) and the flat gradient
@@ -76,10 +78,35 @@ def main():
     ap.add_argument("--augment_snr_db", type=float, nargs=2, default=None, metavar=("LO", "HI"),
                     help="training set only: add white noise at a signal-to-noise ratio drawn from [LO, HI] dB per chunk.  Reads the "
                          "recordings under --root_dir even where a cache matches")
+    heads3 = ("FRAME", "ONSET", "OFFSET")
+    ap.add_argument("--pos_weight", type=float, nargs="+", default=None, metavar="W",
+                    help="training loss: weight of the positive class per head, FRAME ONSET OFFSET (torch's pos_weight; > 0, default 1 1 1).  "
+                         "One value for --model cnn_rnn or without --train_all_heads")
+    ap.add_argument("--focal_gamma", type=float, nargs="+", default=None, metavar="G",
+                    help="training loss: focal-loss exponent per head, FRAME ONSET OFFSET (0..8, default 0 0 0 = no focusing).  One value "
+                         "for --model cnn_rnn or without --train_all_heads")
+    ap.add_argument("--head_weights", type=float, nargs="+", default=None, metavar="H",
+                    help="training loss: weight of each head's term, FRAME ONSET OFFSET (>= 0, default 0.5 0.25 0.25; --train_all_heads only)")
     ap.add_argument("--run_dir", default="outputs/train_cnn")
     ap.add_argument("--num_workers", type=int, default=4)
     ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args()
+    # the weighted / focal training loss (music_transcription_amd.LossConfig); the validation loss stays plain BCE
+    loss_kw = {}
+    for flag, field, ok, rng in (("--pos_weight", "pos_weight", lambda v: v > 0, "> 0"), ("--focal_gamma", "focal_gamma", lambda v: 0 <= v <= 8, "within 0..8"),
+                                 ("--head_weights", "head_weights", lambda v: v >= 0, ">= 0")):
+        vals = getattr(args, field)
+        if vals is None:
+            continue
+        if len(vals) == 3 and not args.train_all_heads:
+            ap.error(f"{flag} {' '.join(heads3)} sets the three heads and needs --train_all_heads (one value without it)")
+        if field == "head_weights" and not args.train_all_heads:
+            ap.error("--head_weights weighs the three heads against each other and needs --train_all_heads")
+        if len(vals) not in (1, 3):
+            ap.error(f"{flag} takes one value or three ({' '.join(heads3)}), got {len(vals)}")
+        if not all(v == v and abs(v) != float("inf") and ok(v) for v in vals):
+            ap.error(f"{flag}: every value must be finite and {rng}")
+        loss_kw[field] = tuple(vals) if len(vals) == 3 else vals[0]
     if args.train_all_heads and (args.model not in ("cnn_rnn_large", "large") or not args.use_onset_offset_heads):
         print("Error: --train_all_heads needs --model cnn_rnn_large with its onset / offset heads (not --no_onset_offset_heads)",
               file=sys.stderr)
@@ -197,6 +224,10 @@ def main():
         if m and args.start_epoch == 1:
             start_epoch = int(m.group(1)) + 1
     opt = mta.make_optimizer(model, lr=args.lr, eps=1e-8, weight_decay=1e-5)
+    loss_cfg = mta.LossConfig(**loss_kw) if loss_kw else None
+    if loss_cfg is not None and rank == 0:
+        print(f"Training loss: head_weights {loss_cfg.head_weights}, pos_weight {loss_cfg.pos_weight}, focal_gamma {loss_cfg.focal_gamma} "
+              f"(validation loss: plain BCE)", flush=True)
     ckpt_dir = os.path.join(args.run_dir, "checkpoints")
     if rank == 0:
         os.makedirs(ckpt_dir, exist_ok=True)
@@ -211,13 +242,22 @@ def main():
         if sampler is not None:
             sampler.set_epoch(epoch)
         t0 = time.perf_counter()
-        train_loss, step_losses = T.train_one_epoch(model, train_loader, opt, dev, max_grad_norm=1.0, all_heads=args.train_all_heads)
+        head_sums = {}
+
+        def log_parts(step, step_loss, norm, parts=None):          # called with parts only under a LossConfig
+            for k, v in (parts or {}).items():
+                head_sums[k] = head_sums.get(k, 0.0) + v
+        train_loss, step_losses = T.train_one_epoch(model, train_loader, opt, dev, max_grad_norm=1.0, all_heads=args.train_all_heads,
+                                                    loss=loss_cfg, log=log_parts if loss_cfg is not None else None)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         val_loss = T.evaluate(model, val_loader, dev, all_heads=args.train_all_heads) if rank == 0 else float("nan")
         if rank == 0:
             rec = {"epoch": epoch, "train_loss": train_loss, "val_loss": val_loss, "steps": len(step_losses),
                    "chunks_per_s": round(len(step_losses) * args.batch_size * world / max(dt, 1e-9), 2)}
+            if loss_cfg is not None:                   # mean per-head training loss over the epoch's steps (each times its head weight)
+                heads = ("frame", "onset", "offset") if args.train_all_heads else ("frame",)
+                rec.update({f"train_{k}_loss": head_sums.get(k, 0.0) / max(len(step_losses), 1) for k in heads})
             history.append(rec)
             print(json.dumps(rec), flush=True)
             if epoch % args.save_every == 0 or epoch == args.epochs:
