@@ -634,6 +634,19 @@ int    mt_adam_clip_step_ex(float* params, const float* grads, float* exp_avg, f
                             float lr, float beta1, float beta2, float eps, float weight_decay, float max_norm,
                             int step, float grad_scale, const long long* keep_ranges, int n_keep,
                             float* stats, void* workspace, size_t workspace_bytes, mt_stream_t stream);
+/* _ema: mt_adam_clip_step_ex plus an exponential moving average of the parameters in the same pass (36 bytes per element instead
+ * of 28).  `ema` (device, n floats, not NULL) starts as a copy of params; ema_weight = 1 - decay of this step, in (0, 1]; anything
+ * else is MT_EINVAL and nothing is written.  Every element the step updates also gets ema' = fmaf(ema_weight, p' - ema, ema)
+ * (p' == ema gives ema' == ema exactly).  params, exp_avg, exp_avg_sq and stats are those of mt_adam_clip_step_ex bit for bit.
+ * Elements outside the keep ranges, and every element of a skipped step (stats[1] == 0), keep their `ema`.                        */
+int    mt_adam_clip_step_ema(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, long long n,
+                             float lr, float beta1, float beta2, float eps, float weight_decay, float max_norm,
+                             int step, float grad_scale, const long long* keep_ranges, int n_keep, float ema_weight,
+                             float* stats, void* workspace, size_t workspace_bytes, mt_stream_t stream);
+/* Exchanges two device buffers of n floats in place (the averaged weights go under the model and back without a temporary copy).
+ * a == b, n <= 0, overlapping buffers or a pointer that is not float-aligned: MT_EINVAL.  16 bytes per lane where a and b sit at
+ * the same offset inside a 16-byte line, one float per lane for the misaligned head and tail and where the offsets differ.       */
+int    mt_swap_f32(float* a, float* b, long long n, mt_stream_t stream);
 
 /* ------------------------------------------------------------------ training step
  * The kernels behind `loss.backward()` of train/train_transcriber.py:130 for CNNRNNModel in train mode

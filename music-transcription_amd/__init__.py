@@ -36,7 +36,7 @@ from .frontend import MelFrontend, audio_to_mel, get_frontend, mel_filterbank, n
 from .model import CNNRNNModel, CNNRNNModelLarge, TranscriptionModel                          # noqa: F401
 from . import ops                                                                             # noqa: F401
 from .ops import LossConfig, compute_loss, framewise_f1, heads_loss, mean_f1, predict_from_logits   # noqa: F401
-from .optim import FusedAdamClip, flatten_parameters, allreduce_mean_                        # noqa: F401
+from .optim import FusedAdamClip, LRSchedule, flatten_parameters, allreduce_mean_            # noqa: F401
 from .train import make_optimizer, train_one_epoch                                            # noqa: F401  (train.evaluate = validation loss)
 from .data import CachedMaestroDataset, collate_fn, write_cache_chunk, write_cache_metadata   # noqa: F401
 from .notes import (heads_to_notes_device, note_grid_counts, note_match_counts, note_match_list, note_prf, note_sweep_counts,   # noqa: F401

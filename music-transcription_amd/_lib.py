@@ -139,6 +139,8 @@ _SIGS = {
     "mt_adam_workspace_bytes": (sz, []),
     "mt_adam_clip_step": (i32, [vp, vp, vp, vp, ll] + [C.c_float] * 6 + [i32, vp, vp, sz, vp]),
     "mt_adam_clip_step_ex": (i32, [vp, vp, vp, vp, ll] + [C.c_float] * 6 + [i32, C.c_float, vp, i32, vp, vp, sz, vp]),
+    "mt_adam_clip_step_ema": (i32, [vp, vp, vp, vp, vp, ll] + [C.c_float] * 6 + [i32, C.c_float, vp, i32, C.c_float, vp, vp, sz, vp]),
+    "mt_swap_f32": (i32, [vp, vp, ll, vp]),
     "mt_bce_workspace_bytes": (sz, []),
     "mt_bce_masked_fwd_bwd": (i32, [vp, vp, vp, C.c_longlong, C.c_float, i32, vp, vp, vp, sz, i32, i32, i32, vp]),
     "mt_onset_offset_targets": (i32, [vp, vp, vp, C.c_longlong, i32, vp]),

@@ -42,7 +42,12 @@ struct AdamArgs {
     float lr, beta1, beta2, eps, weight_decay, max_norm, bc1, bc2_sqrt, grad_scale;
 };
 
+// EMA = false is the plain step.  EMA = true also moves an exponential moving average of the parameters, e' = e + w (p' - e), in the
+// same loop (one more stream: 36 bytes per element instead of 28); everything else is the same code, so the two cannot drift.  The
+// incremental form keeps e' == e exactly where p' == e.  Elements outside the keep ranges and a skipped step leave `ema` alone.
+template <bool EMA>
 __global__ void adam_clip_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                 float* __restrict__ ema, float ema_weight,
                                  Segs sg, const double* __restrict__ partial, int n_partial, AdamArgs a, float* __restrict__ stats) {
     __shared__ double total_s;
     if (threadIdx.x == 0) {
@@ -67,7 +72,32 @@ __global__ void adam_clip_kernel(float* __restrict__ p, const float* __restrict_
         const float vi = fmaf(a.beta2, v[i], (1.0f - a.beta2) * gi * gi);
         m[i] = mi;
         v[i] = vi;
-        p[i] = pi - step * mi / (sqrtf(vi) / a.bc2_sqrt + a.eps);
+        const float pn = pi - step * mi / (sqrtf(vi) / a.bc2_sqrt + a.eps);
+        p[i] = pn;
+        if (EMA) {
+            const float ei = ema[i];
+            ema[i] = fmaf(ema_weight, pn - ei, ei);
+        }
+    }
+}
+
+// Exchanges a[i] and b[i], i < n.  Elements [0, head) and [head + 4 nvec, n) go one float per lane, the 4 nvec in between as float4
+// (the host passes nvec > 0 only where a + head and b + head are both 16-byte aligned).
+__global__ void swap_f32_kernel(float* a, float* b, long long head, long long nvec, long long n) {
+    const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long long)gridDim.x * blockDim.x;
+    float4* a4 = reinterpret_cast<float4*>(a + head);
+    float4* b4 = reinterpret_cast<float4*>(b + head);
+    for (long long i = tid; i < nvec; i += stride) {
+        const float4 x = a4[i], y = b4[i];
+        a4[i] = y;
+        b4[i] = x;
+    }
+    const long long tail0 = head + 4 * nvec, n_scalar = head + (n - tail0);
+    for (long long i = tid; i < n_scalar; i += stride) {
+        const long long j = i < head ? i : tail0 + (i - head);
+        const float x = a[j], y = b[j];
+        a[j] = y;
+        b[j] = x;
     }
 }
 
@@ -82,10 +112,11 @@ extern "C" size_t mt_adam_workspace_bytes(void) { return OPT_BLOCKS * sizeof(dou
 // _ex: grad_scale multiplies every gradient on the fly (1 / world size after a SUM all-reduce; the buffer itself is not
 // modified); keep_ranges (HOST pointer, n_keep pairs [lo, hi), ascending, disjoint; NULL / 0 = the whole buffer) are the
 // only elements that are clipped, counted in the norm and updated -- everything else keeps params and moments untouched.
-extern "C" int mt_adam_clip_step_ex(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n,
-                                    float lr, float beta1, float beta2, float eps, float weight_decay, float max_norm, int step,
-                                    float grad_scale, const long long* keep_ranges, int n_keep,
-                                    float* stats, void* workspace, size_t workspace_bytes, mt_stream_t stream) {
+// (ema == NULL: the plain step; otherwise mt_adam_clip_step_ema, whose own checks have passed)
+static int adam_clip_step_impl(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n,
+                               float lr, float beta1, float beta2, float eps, float weight_decay, float max_norm, int step,
+                               float grad_scale, const long long* keep_ranges, int n_keep, float* ema, float ema_weight,
+                               float* stats, void* workspace, size_t workspace_bytes, mt_stream_t stream) {
     MT_REQUIRE(params && grads && exp_avg && exp_avg_sq && workspace && n > 0 && step >= 1, MT_EINVAL, "mt_adam_clip_step: bad arguments");
     MT_REQUIRE(workspace_bytes >= mt_adam_workspace_bytes(), MT_EWORKSPACE, "mt_adam_clip_step: workspace too small");
     MT_REQUIRE(grad_scale > 0.0f && n_keep >= 0 && n_keep <= OPT_MAX_SEG && (n_keep == 0 || keep_ranges), MT_EINVAL,
@@ -108,8 +139,50 @@ extern "C" int mt_adam_clip_step_ex(float* params, const float* grads, float* ex
     hipLaunchKernelGGL(sqnorm_partial_kernel, dim3(OPT_BLOCKS), dim3(256), 0, st, grads, sg, (double*)workspace);
     MT_CHECK_LAUNCH();
     AdamArgs a{lr, beta1, beta2, eps, weight_decay, max_norm, (float)(1.0 - pow((double)beta1, step)), (float)sqrt(1.0 - pow((double)beta2, step)), grad_scale};
-    hipLaunchKernelGGL(adam_clip_kernel, dim3(2048), dim3(256), 0, st, params, grads, exp_avg, exp_avg_sq, sg,
-                       (const double*)workspace, OPT_BLOCKS, a, stats);
+    if (ema)
+        hipLaunchKernelGGL(adam_clip_kernel<true>, dim3(2048), dim3(256), 0, st, params, grads, exp_avg, exp_avg_sq, ema, ema_weight, sg,
+                           (const double*)workspace, OPT_BLOCKS, a, stats);
+    else
+        hipLaunchKernelGGL(adam_clip_kernel<false>, dim3(2048), dim3(256), 0, st, params, grads, exp_avg, exp_avg_sq, (float*)nullptr, 0.0f, sg,
+                           (const double*)workspace, OPT_BLOCKS, a, stats);
+    MT_CHECK_LAUNCH();
+    return MT_OK;
+}
+extern "C" int mt_adam_clip_step_ex(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n,
+                                    float lr, float beta1, float beta2, float eps, float weight_decay, float max_norm, int step,
+                                    float grad_scale, const long long* keep_ranges, int n_keep,
+                                    float* stats, void* workspace, size_t workspace_bytes, mt_stream_t stream) {
+    return adam_clip_step_impl(params, grads, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, max_norm, step, grad_scale, keep_ranges,
+                               n_keep, nullptr, 0.0f, stats, workspace, workspace_bytes, stream);
+}
+// mt_adam_clip_step_ex plus an exponential moving average of the parameters: every updated element also gets
+// ema' = fmaf(ema_weight, p' - ema, ema), ema_weight = 1 - decay in (0, 1].  params, exp_avg, exp_avg_sq and stats are those of
+// mt_adam_clip_step_ex bit for bit; elements outside the keep ranges and a skipped step (stats[1] == 0) leave `ema` untouched.
+extern "C" int mt_adam_clip_step_ema(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema, long long n,
+                                     float lr, float beta1, float beta2, float eps, float weight_decay, float max_norm, int step,
+                                     float grad_scale, const long long* keep_ranges, int n_keep, float ema_weight,
+                                     float* stats, void* workspace, size_t workspace_bytes, mt_stream_t stream) {
+    MT_REQUIRE(ema && ema_weight > 0.0f && ema_weight <= 1.0f, MT_EINVAL,
+               "mt_adam_clip_step_ema: ema must not be NULL and ema_weight must lie in (0, 1] (got %g)", (double)ema_weight);
+    return adam_clip_step_impl(params, grads, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, max_norm, step, grad_scale, keep_ranges,
+                               n_keep, ema, ema_weight, stats, workspace, workspace_bytes, stream);
+}
+// Exchanges two equal-length, non-overlapping float buffers in place (the averaged weights go under the model and back without a
+// temporary copy).  16 bytes per lane where a and b share their offset inside a 16-byte line; the misaligned head and tail, or the
+// whole buffer where the two offsets differ, go one float per lane.
+extern "C" int mt_swap_f32(float* a, float* b, long long n, mt_stream_t stream) {
+    MT_REQUIRE(a && b && a != b && n > 0, MT_EINVAL, "mt_swap_f32: bad arguments");
+    MT_REQUIRE(((uintptr_t)a & 3) == 0 && ((uintptr_t)b & 3) == 0 && (a < b ? b - a : a - b) >= n, MT_EINVAL,
+               "mt_swap_f32: the buffers must be float-aligned and must not overlap");
+    long long head = n, nvec = 0;
+    if ((((uintptr_t)a ^ (uintptr_t)b) & 15) == 0) {
+        head = (long long)(((16 - ((uintptr_t)a & 15)) & 15) / 4);
+        if (head > n) head = n;
+        nvec = (n - head) / 4;
+    }
+    const long long work = nvec > n - 4 * nvec ? nvec : n - 4 * nvec;
+    const long long want = (work + 255) / 256;
+    hipLaunchKernelGGL(swap_f32_kernel, dim3((unsigned)(want < 2048 ? want : 2048)), dim3(256), 0, (hipStream_t)stream, a, b, head, nvec, n);
     MT_CHECK_LAUNCH();
     return MT_OK;
 }

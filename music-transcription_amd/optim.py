@@ -6,6 +6,8 @@ All parameters live in ONE flat fp32 buffer (parameters become views of it), so 
 launches and the data-parallel reduction is ONE RCCL all-reduce of the flat gradient."""
 from __future__ import annotations
 
+import contextlib
+import math
 from typing import Iterable, List
 
 import torch
@@ -131,14 +133,68 @@ def note_params_without_grad(net, no_grad) -> None:
     net._params_without_grad = set(no_grad) if prev is None else (set(prev) & set(no_grad))
 
 
+class LRSchedule:
+    """Learning rate of step t (1-based, the count the bias correction gets), host code in float64: linear warm-up
+    base_lr t / warmup_steps for t <= warmup_steps; then, with total_steps, a half cosine from base_lr down to min_lr at
+    total_steps, held at min_lr beyond it; without total_steps, base_lr."""
+
+    def __init__(self, base_lr: float, warmup_steps: int = 0, total_steps=None, min_lr: float = 0.0):
+        base_lr, min_lr = float(base_lr), float(min_lr)
+        if not (math.isfinite(base_lr) and base_lr > 0.0):
+            raise ValueError(f"LRSchedule: base_lr must be finite and positive, got {base_lr}")
+        if int(warmup_steps) != warmup_steps or warmup_steps < 0:
+            raise ValueError(f"LRSchedule: warmup_steps must be a non-negative integer, got {warmup_steps}")
+        if total_steps is not None and (int(total_steps) != total_steps or total_steps <= warmup_steps):
+            raise ValueError(f"LRSchedule: total_steps must be an integer above warmup_steps = {warmup_steps}, got {total_steps}")
+        if not (math.isfinite(min_lr) and 0.0 <= min_lr <= base_lr):
+            raise ValueError(f"LRSchedule: min_lr must lie in [0, base_lr], got {min_lr}")
+        self.base_lr, self.min_lr = base_lr, min_lr
+        self.warmup_steps = int(warmup_steps)
+        self.total_steps = None if total_steps is None else int(total_steps)
+
+    def at(self, t: int) -> float:
+        if self.warmup_steps and t <= self.warmup_steps:
+            return self.base_lr * max(t, 0) / self.warmup_steps
+        if self.total_steps is None:
+            return self.base_lr
+        if t >= self.total_steps:
+            return self.min_lr
+        x = (t - self.warmup_steps) / (self.total_steps - self.warmup_steps)
+        return self.min_lr + (self.base_lr - self.min_lr) * 0.5 * (1.0 + math.cos(math.pi * x))
+
+    def params(self) -> dict:
+        return dict(base_lr=self.base_lr, warmup_steps=self.warmup_steps, total_steps=self.total_steps, min_lr=self.min_lr)
+
+
+def ema_decay_at(ema_decay: float, t: int, warmup: bool = True) -> float:
+    """Decay of the weight average at step t (1-based): min(ema_decay, (1 + t) / (10 + t)) with the warm-up (the average follows the
+    first steps closely instead of holding on to the initial weights), ema_decay without."""
+    return min(float(ema_decay), (1.0 + t) / (10.0 + t)) if warmup else float(ema_decay)
+
+
 class FusedAdamClip:
     """clip_grad_norm_ + Adam (coupled L2) in libmt_hip.so over flat buffers.  step() returns a (2,) device tensor
-    {grad norm before clipping, 1.0 if the step was taken / 0.0 if skipped for a non-finite norm}: no host sync."""
+    {grad norm before clipping, 1.0 if the step was taken / 0.0 if skipped for a non-finite norm}: no host sync.
+
+    ema_decay (None = off: nothing allocated, the step is mt_adam_clip_step_ex as ever): `ema` starts as a copy of the flat
+    parameters and every step moves it towards the new weights inside the same kernel pass, ema += (1 - d_t) (p' - ema), d_t =
+    ema_decay_at(ema_decay, t, ema_warmup); averaged_weights() puts it under the model.  schedule (an LRSchedule, None = the
+    constant `lr`): the step's learning rate is schedule.at(t); `last_lr` is what the last step used."""
 
     def __init__(self, flat_params: torch.Tensor, flat_grads: torch.Tensor, lr=1e-4, betas=(0.9, 0.999), eps=1e-8,
-                 weight_decay=1e-5, max_norm=1.0):
+                 weight_decay=1e-5, max_norm=1.0, ema_decay=None, ema_warmup=True, schedule=None):
         if not flat_params.is_cuda:
             raise RuntimeError("FusedAdamClip runs on the GPU only")
+        if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:
+            raise ValueError(f"FusedAdamClip: ema_decay must lie in [0, 1), got {ema_decay}")
+        if schedule is not None and not isinstance(schedule, LRSchedule):
+            raise TypeError("FusedAdamClip: schedule is an LRSchedule or None")
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema_warmup = bool(ema_warmup)
+        self.ema = None if ema_decay is None else flat_params.detach().clone()
+        self.schedule = schedule
+        self.last_lr = None                 # the learning rate of the last step() (None before the first)
+        self._averaged = False              # inside averaged_weights(): the parameters are the average, `ema` holds the live ones
         self.p, self.g = flat_params, flat_grads
         self.m, self.v = torch.zeros_like(flat_params), torch.zeros_like(flat_params)
         self.lr, self.betas, self.eps, self.wd, self.max_norm = lr, betas, eps, weight_decay, max_norm
@@ -229,6 +285,8 @@ class FusedAdamClip:
         SUM and the 1 / world of the mean is applied inside the fused kernel (no extra pass over the buffer): after step()
         the flat gradient buffer holds the rank SUM, not the mean."""
         import ctypes as C
+        if self._averaged:
+            raise RuntimeError("FusedAdamClip.step() inside averaged_weights(): the parameters are the averaged ones there")
         self._reattach_grad_views()
         keep = self._keep_ranges()
         scale = 1.0
@@ -246,11 +304,73 @@ class FusedAdamClip:
             flat_ranges = [v for r in keep for v in r]
             kr, nk = (C.c_longlong * len(flat_ranges))(*flat_ranges), len(keep)
         self.t += 1
+        lr = self.lr if self.schedule is None else self.schedule.at(self.t)
+        self.last_lr = lr
         with torch.cuda.device(self.p.device):
-            check(lib.mt_adam_clip_step_ex(ptr(self.p), ptr(self.g), ptr(self.m), ptr(self.v), self.p.numel(), self.lr, self.betas[0],
-                                           self.betas[1], self.eps, self.wd, self.max_norm, self.t, scale, kr, nk, ptr(self.stats),
-                                           ptr(self.ws), self.ws.numel(), _lib.stream_ptr()), "mt_adam_clip_step_ex")
+            if self.ema is None:
+                check(lib.mt_adam_clip_step_ex(ptr(self.p), ptr(self.g), ptr(self.m), ptr(self.v), self.p.numel(), lr, self.betas[0],
+                                               self.betas[1], self.eps, self.wd, self.max_norm, self.t, scale, kr, nk, ptr(self.stats),
+                                               ptr(self.ws), self.ws.numel(), _lib.stream_ptr()), "mt_adam_clip_step_ex")
+            else:
+                w = 1.0 - ema_decay_at(self.ema_decay, self.t, self.ema_warmup)        # float64; the C float argument casts it once
+                check(lib.mt_adam_clip_step_ema(ptr(self.p), ptr(self.g), ptr(self.m), ptr(self.v), ptr(self.ema), self.p.numel(), lr,
+                                                self.betas[0], self.betas[1], self.eps, self.wd, self.max_norm, self.t, scale, kr, nk, w,
+                                                ptr(self.stats), ptr(self.ws), self.ws.numel(), _lib.stream_ptr()), "mt_adam_clip_step_ema")
         if self.net is not None:
             self.net._params_without_grad = None        # None = no backward pass since (the training step intersects)
         WEIGHTS_EPOCH[0] += 1
         return self.stats
+
+    def _swap_average(self):
+        with torch.cuda.device(self.p.device):
+            check(lib.mt_swap_f32(ptr(self.p), ptr(self.ema), self.p.numel(), _lib.stream_ptr()), "mt_swap_f32")
+        WEIGHTS_EPOCH[0] += 1                  # parameter memory changed behind torch's back: packed inference weights are rebuilt
+
+    @contextlib.contextmanager
+    def averaged_weights(self):
+        """Inside the block the model's parameters are the averaged weights (for validation and for saving); on exit, also when
+        the body raises, they are the live ones again, bit for bit.  Two in-place exchanges of the flat buffers, no temporary copy of
+        the model.  BatchNorm's running statistics are buffers, already averages, and are shared by both sets of weights."""
+        if self.ema is None:
+            raise RuntimeError("FusedAdamClip.averaged_weights(): no weight average is kept (ema_decay=None)")
+        if self._averaged:
+            raise RuntimeError("FusedAdamClip.averaged_weights() is already active")
+        self._swap_average()
+        self._averaged = True
+        try:
+            yield self
+        finally:
+            self._swap_average()
+            self._averaged = False
+
+    def state_dict(self) -> dict:
+        """Everything a resumed run needs besides the weights: step count, both moments and the weight average (CPU tensors), with
+        the hyper-parameters and the schedule's parameters as a record."""
+        if self._averaged:
+            raise RuntimeError("FusedAdamClip.state_dict() inside averaged_weights()")
+        return {"t": self.t, "last_lr": self.last_lr, "m": self.m.detach().cpu(), "v": self.v.detach().cpu(),
+                "ema": None if self.ema is None else self.ema.detach().cpu(),
+                "hyper": dict(lr=self.lr, betas=tuple(self.betas), eps=self.eps, weight_decay=self.wd, max_norm=self.max_norm,
+                              ema_decay=self.ema_decay, ema_warmup=self.ema_warmup),
+                "schedule": None if self.schedule is None else self.schedule.params()}
+
+    def load_state_dict(self, state: dict) -> None:
+        """Restores t, the moments and the weight average.  The hyper-parameters and the schedule stay those this optimizer was built
+        with (a resumed run may train for more epochs than the one that saved the state); the saved ones are a record."""
+        if self._averaged:
+            raise RuntimeError("FusedAdamClip.load_state_dict() inside averaged_weights()")
+        n = self.p.numel()
+        for k in ("m", "v"):
+            if state[k].numel() != n:
+                raise ValueError(f"FusedAdamClip.load_state_dict: {k} has {state[k].numel()} elements, the optimizer {n}")
+        if (state.get("ema") is None) != (self.ema is None):
+            raise ValueError("FusedAdamClip.load_state_dict: the state %s a weight average and the optimizer %s"
+                             % (("holds", "keeps none (ema_decay=None)") if self.ema is None else ("holds no", "keeps one")))
+        if self.ema is not None and state["ema"].numel() != n:
+            raise ValueError(f"FusedAdamClip.load_state_dict: ema has {state['ema'].numel()} elements, the optimizer {n}")
+        self.m.copy_(state["m"].reshape(-1))
+        self.v.copy_(state["v"].reshape(-1))
+        if self.ema is not None:
+            self.ema.copy_(state["ema"].reshape(-1))
+        self.t = int(state["t"])
+        self.last_lr = state.get("last_lr")

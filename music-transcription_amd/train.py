@@ -9,6 +9,7 @@ gradient is all-reduced (mean) over RCCL before the clip -- the data-parallel st
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 from typing import Iterable, List, Tuple
@@ -25,11 +26,13 @@ def _world_size() -> int:
 
 
 def make_optimizer(model, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-5,
-                   max_grad_norm: float = 1.0) -> FusedAdamClip:
+                   max_grad_norm: float = 1.0, ema_decay=None, ema_warmup: bool = True, schedule=None) -> FusedAdamClip:
     """optim.Adam(model.parameters(), lr, eps=1e-8, weight_decay=1e-5) of scripts/train_cnn.py:290, fused with
-    clip_grad_norm_ (train_transcriber.py:134).  Parameters become views of one flat buffer."""
+    clip_grad_norm_ (train_transcriber.py:134).  Parameters become views of one flat buffer.  ema_decay / ema_warmup / schedule
+    (all off by default): the weight average and the learning-rate schedule of optim.FusedAdamClip."""
     flat, grads = flatten_parameters(model.parameters())
-    opt = FusedAdamClip(flat, grads, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_norm=max_grad_norm)
+    opt = FusedAdamClip(flat, grads, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_norm=max_grad_norm,
+                        ema_decay=ema_decay, ema_warmup=ema_warmup, schedule=schedule)
     opt.net = getattr(model, "model", model)       # the training step records there which parameters got no gradient (optim._keep_ranges)
     if _world_size() == 1 and os.environ.get("MT_DIRECT_GRADS", "1") != "0":
         # single GPU: the step's backward pass writes gradients straight into the flat buffer (optim.FusedAdamClip.make_grad_target)
@@ -132,16 +135,21 @@ def train_one_epoch(model, dataloader: Iterable, optimizer: FusedAdamClip, devic
 
 
 @torch.no_grad()
-def evaluate(model, dataloader: Iterable, device, all_heads: bool = False) -> float:
+def evaluate(model, dataloader: Iterable, device, all_heads: bool = False, optimizer=None, averaged: bool = False) -> float:
     """Mean validation loss (train_transcriber.py:161-191); all_heads as in train_one_epoch.  Always plain BCE, whatever LossConfig the
-    training used: the validation loss, and with it the choice of model_best, stays comparable between runs with different settings."""
+    training used: the validation loss, and with it the choice of model_best, stays comparable between runs with different settings.
+    averaged=True runs the same loop on the optimizer's weight average (optimizer.averaged_weights()); the live weights are back
+    under the model when it returns."""
     if all_heads:
         from .evaluate import require_heads
         require_heads(model, "evaluate(all_heads=True)")
+    if averaged and not isinstance(optimizer, FusedAdamClip):
+        raise TypeError("evaluate(averaged=True) needs the optimizer that keeps the weight average: optimizer=make_optimizer(..., ema_decay=...)")
     model.eval()
     total, n = 0.0, 0
-    for mel, roll, lengths in dataloader:
-        logits = _forward(model, mel.to(device, non_blocking=True), all_heads)
-        total += float(model.compute_loss(logits, _to_device(roll, device), lengths).item())
-        n += 1
+    with optimizer.averaged_weights() if averaged else contextlib.nullcontext():
+        for mel, roll, lengths in dataloader:
+            logits = _forward(model, mel.to(device, non_blocking=True), all_heads)
+            total += float(model.compute_loss(logits, _to_device(roll, device), lengths).item())
+            n += 1
     return total / max(n, 1)

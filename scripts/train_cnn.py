@@ -18,6 +18,11 @@ a speed within +-X cents and gets white noise at a signal-to-noise ratio drawn f
 (rawdata.Augment).  They work on the waveform, so they too read the recordings under --root_dir; validation is never augmented.
 `--pos_weight`, `--focal_gamma` and `--head_weights` (FRAME ONSET OFFSET each, or one value) train with the class-weighted / focal loss of
 ops.heads_loss in one fused kernel and add the per-head training losses to the epoch line; the validation loss stays plain BCE.
+`--ema_decay D` keeps an exponential moving average of the weights as one more stream of the fused optimizer pass, validates it too
+(`val_loss_ema`) and writes `model_best_ema.pth`, `model_ema_epoch_N.pth` and `model_final_ema.pth` beside the live checkpoints, in the
+same format.  `--warmup_steps N`, `--lr_decay cosine` and `--min_lr X` schedule the learning rate over epochs x steps per epoch.  Beside
+every numbered and final checkpoint rank 0 writes `train_state.pth` (optimizer moments and step count, the average, best losses,
+history, RNG state); `--resume_state PATH` continues from it at the next epoch, where `--resume` restores the weights only.
 
 One process per GPU.  Every step is the HIP training step (train-mode forward, backward, fused clip + Adam); with more
 than one rank each rank draws its own shard of the shuffled chunk indices (DistributedSampler) and the flat gradient
@@ -87,6 +92,18 @@ def main():
                          "for --model cnn_rnn or without --train_all_heads")
     ap.add_argument("--head_weights", type=float, nargs="+", default=None, metavar="H",
                     help="training loss: weight of each head's term, FRAME ONSET OFFSET (>= 0, default 0.5 0.25 0.25; --train_all_heads only)")
+    ap.add_argument("--ema_decay", type=float, default=None, metavar="D",
+                    help="keep an exponential moving average of the weights (0 <= D < 1, e.g. 0.999) inside the fused optimizer pass; adds "
+                         "val_loss_ema to the epoch line and writes model_best_ema.pth, model_ema_epoch_N.pth and model_final_ema.pth")
+    ap.add_argument("--warmup_steps", type=int, default=0, metavar="N", help="linear learning-rate warm-up over the first N optimizer steps")
+    ap.add_argument("--lr_decay", choices=["none", "cosine"], default="none",
+                    help="cosine: after the warm-up the learning rate falls along a half cosine to --min_lr at the run's last step "
+                         "(epochs x steps per epoch)")
+    ap.add_argument("--min_lr", type=float, default=0.0, metavar="X", help="where --lr_decay cosine ends (default 0)")
+    ap.add_argument("--resume_state", default=None, metavar="PATH",
+                    help="continue a run from its train_state.pth: optimizer moments and step count, weight average, best validation "
+                         "losses, history and RNG state, with the weights of model_epoch_N.pth beside it (N = the state's epoch).  "
+                         "--resume alone restores weights only")
     ap.add_argument("--run_dir", default="outputs/train_cnn")
     ap.add_argument("--num_workers", type=int, default=4)
     ap.add_argument("--seed", type=int, default=0)
@@ -115,6 +132,21 @@ def main():
     if midi_onsets and not args.train_all_heads:
         print("Error: --onset_labels midi sets the onset head's targets and needs --train_all_heads", file=sys.stderr)
         return 2
+
+    if args.resume and args.resume_state:
+        print("Error: --resume (weights only) and --resume_state (the whole training state) cannot be combined", file=sys.stderr)
+        return 2
+    if args.ema_decay is not None and not 0.0 <= args.ema_decay < 1.0:
+        print("Error: --ema_decay must lie in [0, 1)", file=sys.stderr)
+        return 2
+    scheduled = args.warmup_steps > 0 or args.lr_decay == "cosine"
+    if args.warmup_steps < 0 or not 0.0 <= args.min_lr <= args.lr or (args.min_lr > 0.0 and args.lr_decay != "cosine"):
+        print("Error: --warmup_steps must be >= 0 and --min_lr within [0, --lr]; --min_lr needs --lr_decay cosine", file=sys.stderr)
+        return 2
+    if args.resume_state and not os.path.exists(args.resume_state):
+        print(f"Error: --resume_state {args.resume_state} not found", file=sys.stderr)
+        return 2
+    extended = args.ema_decay is not None or scheduled or args.resume_state is not None      # the epoch line gains lr and opt_step
 
     augmenting = args.augment_pitch_cents is not None or args.augment_snr_db is not None
     if augmenting:
@@ -223,7 +255,27 @@ def main():
         m = re.search(r"epoch_(\d+)", os.path.basename(args.resume))
         if m and args.start_epoch == 1:
             start_epoch = int(m.group(1)) + 1
-    opt = mta.make_optimizer(model, lr=args.lr, eps=1e-8, weight_decay=1e-5)
+    state = None
+    if args.resume_state:                              # every rank: the weights of the state's own epoch, then (below) the optimizer's
+        state = torch.load(args.resume_state, map_location="cpu")
+        weights = os.path.join(os.path.dirname(os.path.abspath(args.resume_state)), f"model_epoch_{state['epoch']}.pth")
+        if not os.path.exists(weights):
+            raise SystemExit(f"Error: --resume_state holds the state after epoch {state['epoch']} and needs that epoch's weights, {weights}")
+        model.load_state_dict(torch.load(weights, map_location=dev))
+        start_epoch = state["epoch"] + 1
+    schedule = None
+    if scheduled:                                      # the run's length in optimizer steps: epochs x this rank's steps per epoch
+        try:
+            schedule = mta.LRSchedule(args.lr, warmup_steps=args.warmup_steps, min_lr=args.min_lr,
+                                      total_steps=args.epochs * len(train_loader) if args.lr_decay == "cosine" else None)
+        except ValueError as e:
+            raise SystemExit(f"Error: {e} (epochs x steps per epoch = {args.epochs * len(train_loader)})")
+    if args.ema_decay is None and schedule is None:
+        opt = mta.make_optimizer(model, lr=args.lr, eps=1e-8, weight_decay=1e-5)
+    else:
+        opt = mta.make_optimizer(model, lr=args.lr, eps=1e-8, weight_decay=1e-5, ema_decay=args.ema_decay, schedule=schedule)
+        if rank == 0:
+            print(f"Optimizer: ema_decay {args.ema_decay}, schedule {schedule.params() if schedule else None}", flush=True)
     loss_cfg = mta.LossConfig(**loss_kw) if loss_kw else None
     if loss_cfg is not None and rank == 0:
         print(f"Training loss: head_weights {loss_cfg.head_weights}, pos_weight {loss_cfg.pos_weight}, focal_gamma {loss_cfg.focal_gamma} "
@@ -232,12 +284,30 @@ def main():
     if rank == 0:
         os.makedirs(ckpt_dir, exist_ok=True)
     history = []
-    best_val_loss = float("inf")
+    best_val_loss = best_val_loss_ema = float("inf")
+    if state is not None:
+        opt.load_state_dict(state["optimizer"])
+        history, best_val_loss, best_val_loss_ema = list(state["history"]), state["best_val_loss"], state["best_val_loss_ema"]
+        torch.set_rng_state(state["rng_state"])
+        if rank == 0:
+            print(f"Resumed from {args.resume_state}: epoch {state['epoch']} done, optimizer step {opt.t}, best val loss {best_val_loss:.4f}",
+                  flush=True)
 
     def save(name):                                    # plain state_dict with the reference's keys (rank 0 only)
         path = os.path.join(ckpt_dir, name)
         torch.save({k: v.detach().cpu() for k, v in model.state_dict().items()}, path)
         return path
+
+    def save_ema(name):                                # the same, with the averaged weights under the model while it is written
+        with opt.averaged_weights():
+            return save(name)
+    state_epoch = [None]
+
+    def save_state(epoch):                             # what --resume_state continues from; one file, overwritten (rank 0 only)
+        if state_epoch[0] != epoch:
+            torch.save({"epoch": epoch, "optimizer": opt.state_dict(), "best_val_loss": best_val_loss, "best_val_loss_ema": best_val_loss_ema,
+                        "history": history, "rng_state": torch.get_rng_state()}, os.path.join(ckpt_dir, "train_state.pth"))
+            state_epoch[0] = epoch
     for epoch in range(start_epoch, args.epochs + 1):
         if sampler is not None:
             sampler.set_epoch(epoch)
@@ -255,21 +325,38 @@ def main():
         if rank == 0:
             rec = {"epoch": epoch, "train_loss": train_loss, "val_loss": val_loss, "steps": len(step_losses),
                    "chunks_per_s": round(len(step_losses) * args.batch_size * world / max(dt, 1e-9), 2)}
+            if args.ema_decay is not None:             # the same validation loop on the averaged weights
+                rec["val_loss_ema"] = T.evaluate(model, val_loader, dev, all_heads=args.train_all_heads, optimizer=opt, averaged=True)
+            if extended:
+                rec.update({"lr": opt.last_lr, "opt_step": opt.t})
             if loss_cfg is not None:                   # mean per-head training loss over the epoch's steps (each times its head weight)
                 heads = ("frame", "onset", "offset") if args.train_all_heads else ("frame",)
                 rec.update({f"train_{k}_loss": head_sums.get(k, 0.0) / max(len(step_losses), 1) for k in heads})
             history.append(rec)
             print(json.dumps(rec), flush=True)
-            if epoch % args.save_every == 0 or epoch == args.epochs:
+            numbered = epoch % args.save_every == 0 or epoch == args.epochs
+            if numbered:
                 print(f"Checkpoint saved to {save(f'model_epoch_{epoch}.pth')}", flush=True)
+                if args.ema_decay is not None:
+                    save_ema(f"model_ema_epoch_{epoch}.pth")
             if val_loss < best_val_loss:               # best model = lowest validation loss (reference scripts/train_cnn.py:349-354)
                 best_val_loss = val_loss
                 save("model_best.pth")
                 print(f"New best model saved! Val loss: {val_loss:.4f}", flush=True)
+            if args.ema_decay is not None and rec["val_loss_ema"] < best_val_loss_ema:
+                best_val_loss_ema = rec["val_loss_ema"]
+                save_ema("model_best_ema.pth")
+                print(f"New best averaged model saved! Val loss: {best_val_loss_ema:.4f}", flush=True)
+            if numbered:
+                save_state(epoch)
         if world > 1:
             dist.barrier()
     if rank == 0:
         print(f"Final model saved to {save('model_final.pth')}", flush=True)       # reference scripts/train_cnn.py:180,:357
+        if args.ema_decay is not None:
+            save_ema("model_final_ema.pth")
+        if history:
+            save_state(history[-1]["epoch"])
         with open(os.path.join(args.run_dir, "history.json"), "w") as f:
             json.dump(history, f)
     if world > 1:
