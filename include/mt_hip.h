@@ -260,6 +260,21 @@ int    mt_lstm_bidir_fwd_xproj(const float* hx_prev, const float* w_ihx, const f
  * kernel with interleaved batch groups at every schedule and are gone, and mt_xcd_census with them.)                       */
 int    mt_lstm_bidir_fwd_ex(const float* gx, const float* w_hh, float* hx, void* sync_ws, size_t sync_bytes,
                             int B, int T, int H, int flags, mt_stream_t stream);
+/* Two workgroup sets when alone.  A plain inference launch with 2 .. 4 batch groups (H <= 512) carries twice the workgroups; when it
+ * starts, the device looks at its count of persistent inference launches that are running: nobody else -> the two sets run half the
+ * groups each ("wide"), otherwise the second set leaves at once ("narrow", the shape of a launch with one set).  Same bits either way.
+ * A caller that runs several layers on one stream keeps its place in that count across them, so that the work between its layers
+ * counts as running: MT_LSTM_KEEP on every layer but the last, MT_LSTM_HELD on every layer but the first (OR-ed into `flags`).
+ * mt_lstm_set_width_mode: 0 = decide on the device (default), 1 = always narrow, 2 = always wide (admission still applies); for tests.
+ * mt_lstm_width_offset: byte offset in the sync block of the decision word of the call's first launch, valid once the stream has
+ * drained: 0 = a launch with one set only, 1 = narrow, 2 = wide.                                                                  */
+#define MT_LSTM_HELD 0x100
+#define MT_LSTM_KEEP 0x200
+int    mt_lstm_set_width_mode(int mode);
+size_t mt_lstm_width_offset(void);
+/* 1 if launches that hold need[i] CUs each fit ncu CUs together with ONE launch's surplus (the largest of surplus[i]): at most one
+ * launch is wide at a time.  The arithmetic of the admission check, without a device.                                            */
+int    mt_persistent_fits(const double* need, const double* surplus, int n, int ncu);
 /* CUs held by persistent launches still pending on streams other than `stream` on the current device (see above). */
 int    mt_persistent_cus_in_flight(mt_stream_t stream);
 /* hx -> X[(t*B+b)*ldx + dir*H + j] bf16 (next GEMM's A) / y[b][t][dir*H + j] f32 (torch layout). */

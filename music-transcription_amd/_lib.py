@@ -120,6 +120,9 @@ _SIGS = {
     "mt_lstm_bidir_fwd_xproj": (i32, [vp, vp, vp, vp, vp, vp, sz, i32, i32, i32, vp]),
     "mt_lstm_bidir_fwd_ex": (i32, [vp, vp, vp, vp, sz, i32, i32, i32, i32, vp]),
     "mt_persistent_cus_in_flight": (i32, [vp]),
+    "mt_persistent_fits": (i32, [C.POINTER(C.c_double), C.POINTER(C.c_double), i32, i32]),
+    "mt_lstm_set_width_mode": (i32, [i32]),
+    "mt_lstm_width_offset": (sz, []),
     "mt_lstm_relayout_bf16": (i32, [vp, vp, i32, i32, i32, i32, vp]),
     "mt_lstm_unpack_f32": (i32, [vp, vp, i32, i32, i32, vp]),
     "mt_conv_cl_bf16": (i32, [vp, vp, vp, vp, vp] + [i32] * 11 + [vp]),

@@ -49,6 +49,7 @@
 // was removed in round 3 together with its placement census.)
 #include "lstm_handoff.h"
 #include <stdlib.h>
+#include <atomic>
 
 namespace mt {
 
@@ -71,6 +72,10 @@ struct LstmArgs {
     // poll pacing (units of 64 clocks): delay before a step's first payload poll, delay before every retry; tuning knobs
     // (MT_LSTM_POLL_FIRST / MT_LSTM_POLL_RETRY in the environment, read once)
     int sleep_first, sleep_retry;
+    // plain inference only (0 elsewhere).  hold: HOLD_BEGIN / HOLD_END, this launch's part in the device's count of running launches;
+    // width: 0 = a launch with one set of workgroups, else lstm_wide_kernel's mode + 1 (1 auto, 2 always narrow, 3 always wide);
+    // width_word: word of the sync block with this launch's claim (the decision is the word behind it)
+    int hold, width, width_word;
 };
 
 // v_exp_f32 + v_rcp_f32 (1 ulp each): absolute error ~1e-7, saturate cleanly for |x| large
@@ -145,6 +150,34 @@ __device__ __forceinline__ void vm_settle(u32x4& v) { asm volatile("" : "+v"(v))
 // them round-robin inside every step ("slots"): while group g's published h travels to its consumers (the ~1 us hand-off that
 // bounds a lone step), the workgroup computes the other groups' slots, and the gather of the next slot is already in flight
 // (measured at H = 512: 1.44 us per step for 32 chunks, 2.6 us for 96).
+// A workgroup's LDS (one object, so that the kernel with two workgroup sets below runs any of three instances of the recurrence in the same bytes)
+template <bool XP, bool G16>
+struct RecShared {
+    float red[4][64][20];       // [k-slice wave][lane][16 regs + pad]: 80-B lane stride, conflict-free b128
+    // (NG > 1: the four pad words of red[wv][lane] are thread (wv, lane)'s own -- they hold its cell state of every batch group between that
+    //  group's slots, read beside the partial sums and written back behind the cell update: NG registers less across the whole step)
+    f16_t hs[32][8];            // [batch][unit]
+    // Without the fused projection the workgroup has a FIFTH wave that does nothing but bring the gate pre-activations in: the 4-KB
+    // gx block of every (step, group) slot goes from HBM straight into this ring by LDS-DMA, GX_RING - 1 slots ahead of its use.
+    // HBM latency is then nobody's critical path -- in a compute wave's own memory queue those requests sat in front of the h gather
+    // (vector-memory loads return in order) and every step waited for HBM instead of for the hand-off.
+    float gring[XP ? 1 : 6][XP ? 4 : (G16 ? 512 : 1024)];      // (G16: 1024 f16 per slot)
+    int abort_s;
+};
+
+// Persistent inference launches (plain variant: no TRAIN, no XP) that are running on this device, as the device itself sees it -- what a
+// launch that could spread over two sets of workgroups (lstm_wide_kernel) asks when it starts.  A launch adds 1 when it starts (HOLD_BEGIN)
+// and takes it off when its workgroup (0, 0, 0) leaves (HOLD_END); a model forward keeps its 1 from its first layer's launch to its last
+// layer's (mt_lstm_bidir_fwd_ex, MT_LSTM_HELD / MT_LSTM_KEEP), so that its projection GEMMs between the layers count as "running" too.
+// A value left stale (a forward that failed between two layers) only means "somebody else is running": the narrow shape.
+__device__ unsigned mt_lstm_running;
+constexpr int HOLD_BEGIN = 1, HOLD_END = 2;
+constexpr unsigned WIDTH_NARROW = 1u, WIDTH_WIDE = 2u;      // a launch's decision word
+constexpr int SYNC_WIDTH_WORD = 32;                         // word of the sync block with the first launch's claim; its decision is the next one
+
+template <int NKSW, bool TRAIN, bool XP, int NG, bool G16>
+__device__ __forceinline__ void lstm_rec_body(const LstmArgs& a, const int zidx, RecShared<XP, G16>& sh);
+
 template <int NKSW, bool TRAIN = false, bool XP = false, int NG = 1, bool G16 = false>   // NKSW: 16-wide k-steps per wave: ceil(H/16/4); G16: gx is f16
 // Register budget: without the fused projection the kernel is held to 128 registers per lane (VGPRs + AGPRs; launch bound of
 // 4 waves per SIMD): a workgroup is five waves, so three workgroups share a CU (43 CUs per launch at H = 512) and the GEMMs of
@@ -154,21 +187,27 @@ template <int NKSW, bool TRAIN = false, bool XP = false, int NG = 1, bool G16 = 
 // launch) the f16-gx instances compile without scratch, but a launch under load runs 5.45 instead of 4.75 ms, the GEMMs gain nothing from
 // the 11 CUs, and the default schedule loses 3 %.  The bound stays at 4 waves per SIMD, where these instances take about 100 registers.
 __global__ __launch_bounds__(XP ? 256 : 320, XP ? 1 : (NKSW > 8 ? 2 : 4)) void lstm_rec_kernel(LstmArgs a) {
-    __shared__ __attribute__((aligned(16))) float red[4][64][20];       // [k-slice wave][lane][16 regs + pad]: 80-B lane stride, conflict-free b128
-    // (NG > 1: the four pad words of red[wv][lane] are thread (wv, lane)'s own -- they hold its cell state of every batch group between that
-    //  group's slots, read beside the partial sums and written back behind the cell update: NG registers less across the whole step)
-    __shared__ __attribute__((aligned(16))) f16_t hs[32][8];           // [batch][unit]
-    // Without the fused projection the workgroup has a FIFTH wave that does nothing but bring the gate pre-activations in: the 4-KB
-    // gx block of every (step, group) slot goes from HBM straight into this ring by LDS-DMA, GX_RING - 1 slots ahead of its use.
-    // HBM latency is then nobody's critical path -- in a compute wave's own memory queue those requests sat in front of the h gather
-    // (vector-memory loads return in order) and every step waited for HBM instead of for the hand-off.
+    __shared__ __attribute__((aligned(16))) RecShared<XP, G16> sh;
+    // (plain inference: workgroup (0, 0, 0) keeps the device's count of running launches; a.hold is 0 for the other variants)
+    const bool keeper = !TRAIN && !XP && (blockIdx.x | blockIdx.y | blockIdx.z) == 0 && threadIdx.x == 0;
+    if (keeper && (a.hold & HOLD_BEGIN)) __hip_atomic_fetch_add(&mt_lstm_running, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    lstm_rec_body<NKSW, TRAIN, XP, NG, G16>(a, blockIdx.z, sh);
+    if (keeper && (a.hold & HOLD_END)) __hip_atomic_fetch_sub(&mt_lstm_running, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// One workgroup's recurrence over the batch groups gbase .. gbase + ngh - 1, gbase = zidx * NG + a.g0 (every `return` in here is a wave leaving the
+// recurrence, on the abort path too: what the kernel does behind the call still runs)
+template <int NKSW, bool TRAIN, bool XP, int NG, bool G16>
+__device__ __forceinline__ void lstm_rec_body(const LstmArgs& a, const int zidx, RecShared<XP, G16>& sh) {
+    float (&red)[4][64][20] = sh.red;
+    f16_t (&hs)[32][8] = sh.hs;
     constexpr int GX_RING = XP ? 1 : 6;
     constexpr int GX_DMA = G16 ? 2 : 4;               // DMA instructions (1 KB each) per slot
-    __shared__ __attribute__((aligned(16))) float gring[GX_RING][XP ? 4 : (G16 ? 512 : 1024)];      // (G16: 1024 f16 per slot)
-    __shared__ int abort_s;
+    float (&gring)[GX_RING][XP ? 4 : (G16 ? 512 : 1024)] = sh.gring;
+    int& abort_s = sh.abort_s;
     const int tid = threadIdx.x, wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;   // (the wave index as a scalar: what depends on it alone stays out of the VGPRs)
     const int H = a.H, T = a.T, nkb = H >> 3, nks = H >> 4;
-    const int kb = blockIdx.x, d = blockIdx.y, gbase = blockIdx.z * NG + a.g0;
+    const int kb = blockIdx.x, d = blockIdx.y, gbase = zidx * NG + a.g0;
     const int ngh = min(NG, a.g0 + a.ngl - gbase);   // batch groups this workgroup carries
     const int b = lane & 31, hh = lane >> 5;
 
@@ -481,6 +520,74 @@ __global__ __launch_bounds__(XP ? 256 : 320, XP ? 1 : (NKSW > 8 ? 2 : 4)) void l
 #endif
 }
 
+// ---- Two workgroup sets when alone.  A lone launch with NG interleaved groups is bound by the work of its workgroups (3.7 us per step at
+// NG = 4 against 1.45 us for one group), on 43 of 256 CUs.  This kernel is the NG-group launch with TWICE the workgroups: set s = blockIdx.z
+// is a recurrence of its own over its own batch groups (no hand-off data is shared between the sets; hx, gx and the poison fill are per
+// group).  Which shape runs is decided ON THE DEVICE when the launch starts -- the host enqueues far ahead of the GPU and cannot know:
+//   * the first workgroup to arrive claims the launch (a word of the sync block, zeroed before every launch), looks at mt_lstm_running and
+//     publishes the decision in the next word with agent-scope release; the others read it in a bounded spin (abort word, time limit);
+//   * nobody else running: WIDE, set 0 runs the first ceil(NG / 2) groups and set 1 the rest, each with the instance for its group count
+//     (4 = 2 + 2, 3 = 2 + 1, 2 = 1 + 1; the arithmetic per group is the same, so is every output bit);
+//   * otherwise NARROW: set 1 leaves at once and set 0 runs all NG groups with today's instance -- under load what the recurrences leave
+//     to the GEMMs counts for more than their own speed.
+// Any launch that sees itself alone is the only holder of the count, and every launch that starts while it runs sees it: at most one launch
+// is wide at a time, which is what the admission budgets (residency.hip).  Registers and LDS are those of the largest instance inside.
+template <int NKSW, int NG, bool G16>
+__global__ __launch_bounds__(320, 4) void lstm_wide_kernel(LstmArgs a) {
+    static_assert(NKSW <= 8 && NG >= 2 && NG <= 4, "the interleaved plain inference instances");
+    __shared__ __attribute__((aligned(16))) RecShared<false, G16> sh;
+    __shared__ unsigned width_s;
+    unsigned* const claim = a.status + a.width_word;
+    if (threadIdx.x == 0) {
+        unsigned dec = 0;
+        if (__hip_atomic_exchange(claim, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) {
+            // the first to arrive.  `others`: launches (forwards) running beside this one
+            const unsigned others = (a.hold & HOLD_BEGIN) ? __hip_atomic_fetch_add(&mt_lstm_running, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+                                                          : __hip_atomic_load(&mt_lstm_running, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - 1u;
+            dec = a.width == 3 ? WIDTH_WIDE : (a.width == 2 ? WIDTH_NARROW : (others == 0u ? WIDTH_WIDE : WIDTH_NARROW));
+            __hip_atomic_store(claim + 1, dec, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+        } else {
+            unsigned t1 = 0;
+            for (unsigned it = 0;; ++it) {
+                dec = __hip_atomic_load(claim + 1, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
+                if (dec != 0u) break;
+                sleep64(2);
+                if ((it & 63u) == 63u && __hip_atomic_load(a.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) break;   // somebody gave up: leave with it
+                if ((it & 255u) == 255u) {
+                    const unsigned now = spin_clock();
+                    if (t1 == 0) t1 = now;
+                    else if (now - t1 > (unsigned)LSTM_SPIN_LIMIT_TICKS) {
+                        __hip_atomic_store(a.status, 0x40000000u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        break;
+                    }
+                }
+            }
+        }
+        width_s = dec;
+    }
+    __syncthreads();
+    const unsigned dec = (unsigned)__builtin_amdgcn_readfirstlane((int)width_s);
+    if (dec == 0u) return;                           // no decision within the time limit (the status word says so); the count may stay: "narrow"
+    const int set = blockIdx.z;
+    constexpr int N0 = (NG + 1) / 2, N1 = NG - N0;
+    if (dec == WIDTH_NARROW) {
+        if (set == 0) lstm_rec_body<NKSW, false, false, NG, G16>(a, 0, sh);
+    } else {
+        LstmArgs h = a;
+        if (set == 0) {
+            h.ngl = N0;
+            lstm_rec_body<NKSW, false, false, N0, G16>(h, 0, sh);
+        } else {
+            h.g0 = a.g0 + N0;
+            h.ngl = N1;
+            lstm_rec_body<NKSW, false, false, N1, G16>(h, 0, sh);
+        }
+    }
+    // (workgroup (0, 0) of set 0 has read the decision, so the claimant's + 1 is in the count)
+    if ((a.hold & HOLD_END) && (blockIdx.x | blockIdx.y | blockIdx.z) == 0 && threadIdx.x == 0)
+        __hip_atomic_fetch_sub(&mt_lstm_running, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // ---- B <= 16: one batch group with at most 16 live columns (round 4: the training step's shape, BASELINE configs[3] = 16 chunks per GPU; short
 // recordings at inference).  lstm_rec_kernel's 32x32x16 tiles are then half padding: half of the gathered h bytes, of the MFMA passes and of the
 // cell lanes work on columns nobody reads.  Same decomposition, hand-off, loader wave and hx / gx / gates / cx layouts, but on v_mfma_f32_16x16x32_f16:
@@ -715,16 +822,40 @@ __global__ void lstm_unpack_kernel(const f16_t* __restrict__ hx, float* __restri
 // plain inference with several batch groups: up to 4 groups interleaved inside one set of workgroups (see NG above)
 // (H > 512, NKSW > 8: a workgroup's W_hh slice takes 64 registers per lane and the interleaved variants would spill: one group per
 // workgroup -- those variants are not even built)
+// 2 .. 4 groups: the kernel with two workgroup sets, if the device has room for a wide launch beside what is pending (residency.hip); if not,
+// the launch is admitted as today's and runs today's kernel
+template <int NKSW, int NG, bool G16>
+static int launch_rec_sets(LstmArgs a, hipStream_t st) {
+    const int nwg = 2 * (a.H >> 3);
+    int wide_ok = 0;
+    const int rc = persistent_admit((const void*)lstm_wide_kernel<NKSW, NG, G16>, 320, 0, nwg, st, "mt_lstm_bidir_fwd", nwg, a.width == 3, &wide_ok);
+    if (rc != MT_OK) return rc;
+    if (wide_ok) return persistent_fire(lstm_wide_kernel<NKSW, NG, G16>, dim3(a.H >> 3, 2, 2), 320, a, st);
+    a.width = 0;
+    return persistent_fire(lstm_rec_kernel<NKSW, false, false, NG, G16>, dim3(a.H >> 3, 2, 1), 320, a, st);
+}
+
 template <int NKSW, bool G16>
 static int launch_rec_plain(const LstmArgs& a, int ngroups, hipStream_t st) {
     const dim3 one_set(a.H >> 3, 2, 1);
     if constexpr (NKSW <= 8) {
+        if (a.width != 0) {
+            if (ngroups == 2) return launch_rec_sets<NKSW, 2, G16>(a, st);
+            if (ngroups == 3) return launch_rec_sets<NKSW, 3, G16>(a, st);
+            if (ngroups == 4) return launch_rec_sets<NKSW, 4, G16>(a, st);
+        }
         if (ngroups == 2) return persistent_launch(lstm_rec_kernel<NKSW, false, false, 2, G16>, one_set, 320, a, st, "mt_lstm_bidir_fwd");
         if (ngroups == 3) return persistent_launch(lstm_rec_kernel<NKSW, false, false, 3, G16>, one_set, 320, a, st, "mt_lstm_bidir_fwd");
         if (ngroups > 3) return persistent_launch(lstm_rec_kernel<NKSW, false, false, 4, G16>, dim3(a.H >> 3, 2, cdiv(ngroups, 4)), 320, a, st, "mt_lstm_bidir_fwd");
     }
     return persistent_launch(lstm_rec_kernel<NKSW, false, false, 1, G16>, dim3(a.H >> 3, 2, ngroups), 320, a, st, "mt_lstm_bidir_fwd");
 }
+
+static bool lstm_c16() {
+    static const bool c16 = !(getenv("MT_LSTM_C16") && atoi(getenv("MT_LSTM_C16")) == 0);
+    return c16;
+}
+static std::atomic<int> g_width_mode{0};          // mt_lstm_set_width_mode
 
 // NKSW > 8 (H > 512) is a compile-time fact: no 16-column kernel, no fused projection, no interleaving -- only kernels that can be
 // launched are instantiated.  Block size: 256 for XP (no loader wave), 320 for everything else.
@@ -733,7 +864,7 @@ static int launch_rec(const LstmArgs& a, int ngroups, bool g16, hipStream_t st) 
     const dim3 per_group(a.H >> 3, 2, ngroups);
     if constexpr (NKSW <= 8) {
         // B <= 16 (one batch group, at most 16 live columns): the 16-column kernel (MT_LSTM_C16=0 keeps the 32-column one)
-        static const bool c16 = !(getenv("MT_LSTM_C16") && atoi(getenv("MT_LSTM_C16")) == 0);
+        const bool c16 = lstm_c16();
         constexpr int NK16 = (NKSW + 1) / 2;                       // 32-wide k-steps per wave
         if (c16 && !a.w_ihx && a.B <= 16 && ngroups == 1) {
             if (a.cx) return persistent_launch(lstm_rec16_kernel<NK16, true, false>, per_group, 320, a, st, "mt_lstm_bidir_fwd_train");
@@ -752,7 +883,8 @@ using namespace mt;
 
 extern "C" size_t mt_lstm_gx_bytes(int B, int T, int H) { return (size_t)cdiv(B, 32) * T * 2 * (H >> 3) * 4096; }
 extern "C" size_t mt_lstm_hx_bytes(int B, int T, int H) { return (size_t)cdiv(B, 32) * T * 2 * (H >> 3) * 512; }
-// (the hand-off has no flags: the sync workspace is the status word's own cache line, plus one spare line)
+// (the hand-off has no flags: the sync workspace is the status word's own cache line; from word SYNC_WIDTH_WORD on, behind it, a (claim, decision) pair
+//  of words per launch of the call for the launches with two workgroup sets)
 extern "C" size_t mt_lstm_sync_bytes(int B, int H) { (void)B; (void)H; return 512; }
 
 // One bidirectional LSTM layer's recurrence.  gx from mt_gemm_lstm_gx, w_hh = [fwd; reverse] (2 x 4H x H f32),
@@ -780,17 +912,28 @@ static int lstm_fwd_impl(const float* gx, const float* w_hh, float* hx, void* sy
     LstmArgs a{gx, w_hh, hx, (unsigned*)sync_ws, B, T, H, 0, 0,
                cx ? const_cast<float*>(gx) : nullptr, cx, w_ihx, bias, hx_prev,
                env_first >= 0 ? env_first : (cx ? PAYLOAD_POLL_SLEEP_TRAIN : ((!w_ihx && mt_persistent_cus_in_flight(stream) > 0) ? PAYLOAD_POLL_SLEEP_BUSY : PAYLOAD_POLL_SLEEP)),
-               env_retry >= 0 ? env_retry : 0};
+               env_retry >= 0 ? env_retry : 0, 0, 0, 0};
     // every workgroup of a launch must be resident (they wait on each other): at most 256 workgroups (one per CU) per launch --
     // for plain inference each set of 2 H/8 workgroups carries up to 4 batch groups interleaved (lstm_rec_kernel, NG), the
     // training / fused-projection variants one.  Further groups run as further launches.
     const int zmax = (256 / (2 * nkb)) > 0 ? (256 / (2 * nkb)) : 1;
     const int nksw = cdiv(nkb / 2, 4);
     const int per_launch = (cx || w_ihx || nksw > 8) ? zmax : 4 * zmax;
-    for (int g0 = 0; g0 < ng; g0 += per_launch) {
+    // plain inference launches keep the device's count of running launches (mt_lstm_running): the first launch of this call adds the caller's 1
+    // unless the caller holds it already (MT_LSTM_HELD), the last one takes it off unless the caller keeps it for a later call (MT_LSTM_KEEP)
+    const bool plain = !cx && !w_ihx && !(nksw <= 8 && B <= 16 && lstm_c16());
+    const int width_mode = g_width_mode.load(std::memory_order_relaxed);
+    int li = 0;
+    for (int g0 = 0; g0 < ng; g0 += per_launch, ++li) {
         a.g0 = g0;
         const int n = (ng - g0) < per_launch ? (ng - g0) : per_launch;
         a.ngl = n;
+        if (plain) {
+            a.hold = ((g0 == 0 && !(flags & MT_LSTM_HELD)) ? HOLD_BEGIN : 0) | ((g0 + per_launch >= ng && !(flags & MT_LSTM_KEEP)) ? HOLD_END : 0);
+            // (every launch of the call has its own claim / decision words in the sync block, as long as they last)
+            a.width_word = SYNC_WIDTH_WORD + 2 * li;
+            a.width = (nksw <= 8 && n >= 2 && n <= 4 && (size_t)(a.width_word + 2) * 4 <= mt_lstm_sync_bytes(B, H)) ? width_mode + 1 : 0;
+        }
         int rc;
         if (nksw <= 1) rc = launch_rec<1>(a, n, g16, st);
         else if (nksw <= 2) rc = launch_rec<2>(a, n, g16, st);
@@ -828,9 +971,19 @@ extern "C" int mt_lstm_bidir_fwd_train(float* gx_inout, const float* w_hh, float
 // flags: 0, or MT_GX_F16 (gx holds f16 gate pre-activations, as mt_gemm_lstm_gx_dt(.. | MT_GX_F16) stores them).
 extern "C" int mt_lstm_bidir_fwd_ex(const float* gx, const float* w_hh, float* hx, void* sync_ws, size_t sync_bytes,
                                     int B, int T, int H, int flags, mt_stream_t stream) {
-    MT_REQUIRE(flags == 0 || flags == MT_GX_F16, MT_EINVAL, "mt_lstm_bidir_fwd_ex: flags must be 0 or MT_GX_F16 (gx is f16)");
+    MT_REQUIRE((flags & ~(MT_GX_F16 | MT_LSTM_HELD | MT_LSTM_KEEP)) == 0, MT_EINVAL, "mt_lstm_bidir_fwd_ex: flags: MT_GX_F16 (gx is f16), MT_LSTM_HELD, MT_LSTM_KEEP");
     return lstm_fwd_impl(gx, w_hh, hx, sync_ws, sync_bytes, B, T, H, flags, stream);
 }
+
+// Test hook: 0 = the device decides when the launch starts (default), 1 = always narrow, 2 = always wide (still through admission).
+extern "C" int mt_lstm_set_width_mode(int mode) {
+    MT_REQUIRE(mode >= 0 && mode <= 2, MT_EINVAL, "mt_lstm_set_width_mode: mode %d (0 auto, 1 narrow, 2 wide)", mode);
+    g_width_mode.store(mode, std::memory_order_relaxed);
+    return MT_OK;
+}
+// Byte offset, inside a launch's sync block, of the word with its decision once the stream has drained: 0 = a launch with one set of
+// workgroups (one batch group, more than four, or no room for a wide launch), 1 = narrow, 2 = wide.
+extern "C" size_t mt_lstm_width_offset(void) { return (size_t)(SYNC_WIDTH_WORD + 1) * 4; }
 
 extern "C" int mt_lstm_relayout_dt(const float* hx, void* X, int ldx, float* Y, int ldy, int col_off, int B, int T, int H, int Hv,
                                    int dt, mt_stream_t stream) {

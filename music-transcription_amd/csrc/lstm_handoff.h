@@ -13,17 +13,18 @@ __device__ __forceinline__ void sleep64(int n) {
     for (int i = 0; i < n; ++i) __builtin_amdgcn_s_sleep(1);
 }
 
-int persistent_admit(const void* kernel, int block, size_t smem, int nwg, hipStream_t st, const char* who);   // residency.hip
+// nwg workgroups must be resident together.  surplus_wg > 0: the launch carries that many workgroups MORE when it runs wide (lstm.hip,
+// lstm_wide_kernel); *wide_ok tells whether the device has room for that -- if not, the launch is admitted with nwg alone and must be
+// launched without them.  forced: the surplus counts as part of the launch (several forced-wide launches may run at a time).
+int persistent_admit(const void* kernel, int block, size_t smem, int nwg, hipStream_t st, const char* who, int surplus_wg = 0, bool forced = false,
+                     int* wide_ok = nullptr);   // residency.hip
 int persistent_mark(hipStream_t st);
 int persistent_cancel(hipStream_t st);
 
-// every workgroup of a persistent launch must be resident: admission check first (fails fast), completion event behind it
-// (a launch that fails after its admission gives the reserved CUs back)
+// the launch of an admitted kernel: completion event behind it (a launch that fails after its admission gives the reserved CUs back)
 template <typename Args>
-static int persistent_launch(void (*kernel)(Args), dim3 grid, int nthreads, const Args& a, hipStream_t st, const char* who,
-                             const char* file = __builtin_FILE(), int line = __builtin_LINE()) {
-    int rc = persistent_admit((const void*)kernel, nthreads, 0, (int)(grid.x * grid.y * grid.z), st, who);
-    if (rc != MT_OK) return rc;
+static int persistent_fire(void (*kernel)(Args), dim3 grid, int nthreads, const Args& a, hipStream_t st,
+                           const char* file = __builtin_FILE(), int line = __builtin_LINE()) {
     hipLaunchKernelGGL(kernel, grid, dim3(nthreads), 0, st, a);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
@@ -32,6 +33,15 @@ static int persistent_launch(void (*kernel)(Args), dim3 grid, int nthreads, cons
         return MT_EHIP;
     }
     return persistent_mark(st);
+}
+
+// every workgroup of a persistent launch must be resident: admission check first (fails fast), then the launch
+template <typename Args>
+static int persistent_launch(void (*kernel)(Args), dim3 grid, int nthreads, const Args& a, hipStream_t st, const char* who,
+                             const char* file = __builtin_FILE(), int line = __builtin_LINE()) {
+    int rc = persistent_admit((const void*)kernel, nthreads, 0, (int)(grid.x * grid.y * grid.z), st, who);
+    if (rc != MT_OK) return rc;
+    return persistent_fire(kernel, grid, nthreads, a, st, file, line);
 }
 
 }  // namespace mt

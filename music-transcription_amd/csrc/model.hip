@@ -130,8 +130,13 @@ extern "C" int mt_cnnrnn_forward_ex(const mt_cnnrnn_weights* w, const float* mel
     const bool from_hx = dt == MT_DT_F16 && H == Hv && H % 64 == 0;
     // f16 operands + agent-scope recurrence: the gate pre-activations travel GEMM -> recurrence as f16 (MT_GX_F16, include/mt_hip.h)
     const int gx16 = (dt == MT_DT_F16) ? MT_GX_F16 : 0;
+    // the forward keeps its place in the device's count of running recurrences from its first layer to its last (MT_LSTM_KEEP / MT_LSTM_HELD,
+    // include/mt_hip.h), unless a layer runs the fused-projection kernel, which does not take part in that count
+    bool chain = true;
+    for (int l = 1; l < w->layers; ++l) chain = chain && !(w->w_ihx[l] && H <= 512);
     for (int l = 0; l < w->layers; ++l) {
         const bool last = l + 1 == w->layers;
+        const int hold = chain ? ((l > 0 ? MT_LSTM_HELD : 0) | (!last ? MT_LSTM_KEEP : 0)) : 0;
         // layers > 0 with packed W_ihx: input projection fused into the recurrence (reads the previous layer's hx directly)
         const bool fused = l > 0 && w->w_ihx[l] && H <= 512;
         if (fused) {
@@ -152,7 +157,7 @@ extern "C" int mt_cnnrnn_forward_ex(const mt_cnnrnn_weights* w, const float* mel
             }
             if ((rc = rec(events, n_events, ei, st)) != MT_OK) return rc;
             if ((rc = mt_lstm_bidir_fwd_ex((const float*)(ws + p.gx), w->w_hh[l], (float*)hcur, ws + p.sync + p.sync_stride * l,
-                                           p.sync_stride, B, T, H, gx16, stream)) != MT_OK) return rc;
+                                           p.sync_stride, B, T, H, gx16 | hold, stream)) != MT_OK) return rc;
         }
         if ((rc = rec(events, n_events, ei, st)) != MT_OK) return rc;
         // the next consumer of feature ROWS: a GEMM-projected layer, or the final fc (none when they read hx directly)
