@@ -153,6 +153,19 @@ int    mt_augment_windows(const float* store, const long long* win_off, const in
                           unsigned long long rate_hi_q32, const float* noise_rel, unsigned seed, const float* tab, int B,
                           int L_max, float* out, void* ws, size_t ws_bytes, mt_stream_t stream);
 
+/* Onset-regression targets of the same windows (csrc/onset_regress.hip, DESIGN.md 6c "Sub-frame onsets"): onset[B][88][T_out] f32 in
+ * [0, 1], a triangle of half-width onset_width frames around every MIDI note-on.  on_tick = the note-ons of all recordings in ticks
+ * of 100 us (int32), those of pitch 21 + p in recording r at tick_off[r*89 + p] .. tick_off[r*89 + p + 1] - 1, rising.  All integers, in
+ * units of 12.5 us (a 16 kHz sample is 5, a tick 8, a frame of 512 samples 2560): frame t of window b is centred at source time
+ *   tau = 5 start[b] + ((2560 t rate_q32[b] + 2^31) >> 32)      (start[b] = the window's first sample inside its recording; rate_q32
+ * NULL = 2^32 for every window, else mt_augment_windows' speeds), W = 2560 onset_width, d = min over the pitch's note-ons of
+ * |tau - 8 on_tick|, and onset = d < W ? (float)(W - d) / (float)W : 0 with one correctly rounded f32 division.  Columns >= t_keep[b] are
+ * 0; a pitch without notes gives a zero row.  onset_width outside [2, 8] or T_out > 2^19: MT_EINVAL.  The units assume sr 16000 and hop
+ * 512 (the caller's guard).  All tables are device pointers; one launch on `stream`, every cell of onset is written. */
+int    mt_onset_regress_windows(const int* on_tick, const long long* tick_off, const int* win_rec, const int* start,
+                                const unsigned long long* rate_q32, const int* t_keep, int B, int T_out, int onset_width,
+                                float* onset, mt_stream_t stream);
+
 /* Overlapping windows on one frame grid (csrc/stitch.hip, windows.py): src[Bw][P][Tw] holds the rows of Bw windows, which may
  * come from several recordings.  For each window b, local frames t in [keep_lo[b], keep_hi[b]) of every row p are copied to
  * dst[dst_row[b]][p][dst_frame0[b] + t] of dst[R][P][T_dst]; nothing else in dst is written (the caller pre-fills padding).
@@ -563,6 +576,20 @@ int    mt_heads_to_notes_clean(const float* frame_logits, const float* onset_log
 int    mt_notes_batch_clean(const float* frame_logits, const float* onset_logits, float thr_frame, float thr_onset, const long long* lengths,
                             int B, int P, long long T, int* counts, long long* row_off, int* starts, int* ends, long long capacity,
                             int min_frames, int bridge_frames, mt_stream_t stream);
+/* Sub-frame onsets of decoded notes (csrc/onset_regress.hip, DESIGN.md 6c "Sub-frame onsets"): on_tick[i] (int32, ticks of 100 us) for
+ * the n notes [starts[i], ends[i]) of any onset-gated decoder above, cleaned or not.  row_off (int64, rows + 1 entries, rising from 0
+ * to n) gives the notes of row r as row_off[r] .. row_off[r + 1] - 1; the kernel finds a note's row by binary search.  chunks == 0:
+ * onset_logits[NB][P][T] is a padded batch, rows = NB * P, row b*P + p has L = clamp(lengths[b], 0, T) valid frames (lengths int64,
+ * device, NULL = all T).  chunks != 0: the NB chunks are one recording of L = NB * T frames per pitch, rows = P, frame g at chunk g / T,
+ * t = g % T, and lengths must be NULL.  Per note, with q[g] = 1 / (1 + exp(-x[g])) in f32 inside [0, L) and 0 outside (nothing outside
+ * is loaded: the padding may hold NaN): the peak k starts at s and steps to k + 1 while k + 1 <= min(s + reach, e - 1, L - 1) and
+ * q[k + 1] > q[k]; with A = q[k - 1], B = q[k], C = q[k + 1], m = min(A, C): shift = 0 if B - m < 2^-10, else (C - A) / (2 (B - A)) if
+ * C > A, else (C - A) / (2 (B - C)), clamped to [-0.5, 0.5]; on_tick = clamp(320 k + (int)rintf(320 shift), 0, 320 e - 1).  As k >= s and
+ * the notes of a row do not overlap, the ticks of a row stay sorted.  reach in [0, 8]; n notes are refined (n = 0 launches nothing and
+ * needs no pointers); 320 L must stay below 2^31.  One launch on `stream`, one thread per note. */
+int    mt_refine_onsets(const int* starts, const int* ends, const long long* row_off, long long rows, long long n,
+                        const float* onset_logits, int NB, int P, long long T, const long long* lengths, int chunks, int reach,
+                        int* on_tick, mt_stream_t stream);
 /* Frame smoothing (csrc/smooth.hip, DESIGN.md 6c "Frame smoothing"): per pitch row, the Viterbi path of a two-state (off / on) HMM over
  * the frame head, written as logits.  Evidence q_t = rint(clamp(x_t - logit(thr), -64, 64) * 64), forced to q_t >= 1 where the frame is
  * active as mt_predict_threshold has it and to q_t <= 0 where it is not; a = rint(64 * on_penalty), b = rint(64 * off_penalty); the

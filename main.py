@@ -2,7 +2,7 @@
 """Inference CLI with the reference's interface (main.py:290-362):
 
     python main.py audio_file model_file [-o OUT.mid] [-d {cpu,cuda}] [-t THRESHOLD] [--decoder {frame,onset,onset_offset}] [--overlap SECONDS]
-                   [--min-note-ms MS] [--bridge-gap-ms MS] [--smooth-on LOGITS] [--smooth-off LOGITS]
+                   [--min-note-ms MS] [--bridge-gap-ms MS] [--smooth-on LOGITS] [--smooth-off LOGITS] [--refine-onsets] [--refine-reach N]
 
 Exit code 1 with a message when a file is missing or transcription fails.  The checkpoint must be a
 CNNRNNModelLarge(320, 512, 3) state_dict as in the reference (main.py:16-20); --model-type/--n-mels/
@@ -49,6 +49,12 @@ def main():
                     help="frame smoothing: the cost in logits of switching a pitch off (0 to 64; default 0).  A dropout is bridged only "
                          "if its counter-evidence is smaller than --smooth-on + --smooth-off.  Both 0 = no smoothing.  Chunks and "
                          "--overlap alike; the onset and offset heads are not smoothed; note cleanup then sees the smoothed activity")
+    ap.add_argument("--refine-onsets", action="store_true",
+                    help="--decoder onset / onset_offset: give every note a sub-frame start time from the onset head's values around "
+                         "its peak (a head trained with train_cnn.py --onset_target regress).  Chunks and --overlap alike, but on "
+                         "concatenated chunks the frame grid itself drifts 16 ms per chunk: --overlap is where sub-frame times mean something")
+    ap.add_argument("--refine-reach", type=int, default=2,
+                    help="--refine-onsets: frames the peak search may walk from a note's first frame (0..8; default 2)")
     ap.add_argument("--model-type", default="cnn_rnn_large")
     ap.add_argument("--n-mels", type=int, default=320)
     ap.add_argument("--hidden-size", type=int, default=512)
@@ -58,6 +64,9 @@ def main():
         from music_transcription_amd.notes import check_smoothing, cleanup_frames
         min_note_frames, bridge_frames = cleanup_frames(args.min_note_ms, args.bridge_gap_ms)
         smooth_on, smooth_off = check_smoothing(args.smooth_on, args.smooth_off)
+        if args.refine_onsets:
+            from music_transcription_amd.transcribe import check_refine_decoder
+            check_refine_decoder(True, args.decoder, args.refine_reach)
     except ValueError as e:
         ap.error(str(e))
     if not os.path.exists(args.audio_file):
@@ -72,7 +81,7 @@ def main():
         out = transcribe_audio(args.audio_file, args.model_file, args.output, args.device, args.threshold,
                                decoder=args.decoder, onset_threshold=args.onset_threshold, overlap=args.overlap,
                                offset_threshold=args.offset_threshold, min_note_frames=min_note_frames, bridge_frames=bridge_frames,
-                               smooth_on=smooth_on, smooth_off=smooth_off,
+                               smooth_on=smooth_on, smooth_off=smooth_off, refine_onsets=args.refine_onsets, refine_reach=args.refine_reach,
                                model_type=args.model_type, n_mels=args.n_mels, hidden_size=args.hidden_size,
                                num_layers=args.num_layers)
         print("=" * 60 + f"\nTranscription completed successfully!\nOutput: {out}\n" + "=" * 60)

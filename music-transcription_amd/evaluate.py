@@ -134,7 +134,7 @@ def note_metrics_dataset(model, dataset, threshold: float = 0.5, onset_threshold
                          subset: Optional[int] = None, max_batch: int = 128, rank: int = 0, world: int = 1,
                          window_overlap: Optional[float] = None, note_reference: str = "roll",
                          offset_threshold: Optional[float] = None, min_note_frames: int = 1, bridge_frames: int = 0,
-                         smooth_on: float = 0.0, smooth_off: float = 0.0) -> dict:
+                         smooth_on: float = 0.0, smooth_off: float = 0.0, refine_onsets: bool = False, refine_reach: int = 2) -> dict:
     """Note-level metrics of every sample, identical on every rank: {"mean": {key: value}, "per_sample": {key: [values]}} over
     NOTE_METRIC_KEYS (onset / onset_offset x precision / recall / f1).  onset_threshold=None: notes are the runs of
     sigmoid(frame) > threshold (the frame decoder); otherwise the onset-gated decoder with the onset head at onset_threshold.
@@ -143,23 +143,35 @@ def note_metrics_dataset(model, dataset, threshold: float = 0.5, onset_threshold
     (dataset.ref_notes: a whole-file MaestroDataset built with onset_labels="midi").  Unweighted means over samples, as
     evaluate_dataset (window_overlap too).  min_note_frames / bridge_frames: the estimates are cleaned in the decoder (DESIGN.md 6c "Note cleanup"),
     whichever of the three it is; the result then names the two ("min_note_frames", "bridge_frames").  smooth_on / smooth_off: the frame
-    head is smoothed before the decoder (DESIGN.md 6c "Frame smoothing"); the result then names those two as well."""
-    from .notes import check_cleanup, check_smoothing, note_match_counts, note_match_list, note_prf
+    head is smoothed before the decoder (DESIGN.md 6c "Frame smoothing"); the result then names those two as well.
+    refine_onsets (onset-gated or offset-gated decoder, note_reference="midi"): the notes are decoded as lists, their onsets refined to
+    sub-frame ticks (mt_refine_onsets with reach refine_reach; DESIGN.md 6c "Sub-frame onsets"), copied to the host and scored there
+    with notes.note_match_ticks -- the device matcher takes estimates on the frame grid only; the result then names "refine_reach"."""
+    from .notes import check_cleanup, check_smoothing, note_match_counts, note_match_list, note_match_ticks, note_prf, notes_ticks_device
     clean = check_cleanup(min_note_frames, bridge_frames)
     smooth = check_smoothing(smooth_on, smooth_off)
     _check_note_reference(dataset, note_reference)
     onset, offset = onset_threshold is not None, offset_threshold is not None
     if offset and not onset:
         raise ValueError("offset_threshold: the offset-gated decoder needs onset_threshold as well")
+    if refine_onsets and (not onset or note_reference != "midi"):
+        raise ValueError("refine_onsets: sub-frame onsets are read off the onset head and scored against the MIDI note list in ticks: "
+                         "it needs onset_threshold (the onset-gated or offset-gated decoder) and note_reference='midi'")
     n = len(dataset) if subset is None else min(subset, len(dataset))
     mine = list(shard_range(n, rank, world))
     lr = _collect(model, dataset, mine, device, window_overlap, all_heads=onset, with_offset=offset)
     vals = {k: [] for k in NOTE_METRIC_KEYS}
     match = note_match_list if note_reference == "midi" else note_match_counts
     for frame, on, ref, lengths, off in _note_groups(lr, dataset, onset, note_reference, max_batch, offset):
-        counts = match(frame, ref, threshold, on, onset_threshold if onset else 0.5, lengths, offset_logits=off,
-                       offset_threshold=offset_threshold if offset else 0.5, min_note_frames=clean[0], bridge_frames=clean[1],
-                       smooth_on=smooth[0], smooth_off=smooth[1])
+        if refine_onsets:
+            est = notes_ticks_device(frame, on, threshold, onset_threshold, lengths, offset_logits=off,
+                                     offset_threshold=offset_threshold if offset else 0.5, min_note_frames=clean[0], bridge_frames=clean[1],
+                                     smooth_on=smooth[0], smooth_off=smooth[1], refine_reach=refine_reach)
+            counts = note_match_ticks(est, ref)
+        else:
+            counts = match(frame, ref, threshold, on, onset_threshold if onset else 0.5, lengths, offset_logits=off,
+                           offset_threshold=offset_threshold if offset else 0.5, min_note_frames=clean[0], bridge_frames=clean[1],
+                           smooth_on=smooth[0], smooth_off=smooth[1])
         for m in note_prf(counts):
             for c in ("onset", "onset_offset"):
                 for k, v in zip(("precision", "recall", "f1"), m[c]):
@@ -170,6 +182,8 @@ def note_metrics_dataset(model, dataset, threshold: float = 0.5, onset_threshold
         out["min_note_frames"], out["bridge_frames"] = clean
     if smooth != (0.0, 0.0):
         out["smooth_on"], out["smooth_off"] = smooth
+    if refine_onsets:
+        out["refine_reach"] = int(refine_reach)
     return out
 
 

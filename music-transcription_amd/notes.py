@@ -27,6 +27,9 @@
     (mt_frame_smooth_paths), and `smoothings=` on `note_grid_counts` = a list of penalty pairs as one more axis of the grid, which
     then reads such words as its frame axis (mt_note_grid_counts_paths / mt_note_grid_list_paths; DESIGN.md 6c "Smoothing in the
     decoder grid").
+  * `refine_onsets_device` = sub-frame onsets in ticks of 100 us for the notes of any onset-gated decoder, from the three onset-head values
+    around the peak near each note's start (mt_refine_onsets; DESIGN.md 6c "Sub-frame onsets"); `refine_onsets=` on the two note-list
+    calls stamps the notes with them.  `note_match_ticks` scores such off-grid estimates against a note list on the host.
 """
 from __future__ import annotations
 
@@ -498,62 +501,103 @@ def note_prf(counts) -> List[Dict[str, Tuple[float, float, float]]]:
 def heads_to_notes_device(frame_logits: torch.Tensor, onset_logits: Optional[torch.Tensor], threshold: float = 0.5,
                           onset_threshold: float = 0.5, fs: float = FS, min_midi: int = 21, offset_logits: Optional[torch.Tensor] = None,
                           offset_threshold: float = 0.5, min_note_frames: int = 1, bridge_frames: int = 0, smooth_on: float = 0.0,
-                          smooth_off: float = 0.0) -> List[Tuple[int, float, float]]:
+                          smooth_off: float = 0.0, refine_onsets: bool = False, refine_reach: int = 2) -> List[Tuple[int, float, float]]:
     """(n_chunks, 88, T) frame and onset logits ON THE DEVICE -> notes of the onset-gated decoder over the chunks concatenated in
     time, in the reference's note order (pitch-major, then time); only counts and two ints per note reach the host.  With
     offset_logits: the notes of the offset-gated decoder (mt_heads_to_notes_off), which end where the offset head fires.  With
     (min_note_frames, bridge_frames) other than (1, 0): the cleaned notes (mt_heads_to_notes_clean), and then onset_logits may be
     None: the frame decoder's notes, cleaned.  With (smooth_on, smooth_off) other than (0, 0) the frame head is smoothed first, over
-    the chunks concatenated in time (smooth_frame_logits, chunks=True)."""
+    the chunks concatenated in time (smooth_frame_logits, chunks=True).  refine_onsets=True: one more launch (mt_refine_onsets, reach
+    refine_reach) gives every note a sub-frame onset; its start is then on_tick / 1e4 seconds, its end unchanged (e / fs), and the
+    ticks ride in the note copy.  The frame decoder has no onset head to refine from: it raises."""
     clean = check_cleanup(min_note_frames, bridge_frames)
     smooth = check_smoothing(smooth_on, smooth_off)
+    reach = _check_refine(refine_onsets, refine_reach, onset_logits)
     x, on, off, thr, othr, kthr, _ = _heads(frame_logits, onset_logits, offset_logits, threshold, onset_threshold, offset_threshold,
                                             onset_required=clean == (1, 0), mismatch="frame {frame} and onset {onset} logits differ in shape")
-    NB, P, T = x.shape
-    dev = x.device
     if smooth != (0.0, 0.0):
         x = _smoothed(x, thr, smooth, None, True)
+    c, s, e, tick = _heads_to_notes_raw(x, on, off, (thr, othr, kthr), clean, reach)
+    pitches = np.repeat(np.arange(x.shape[1]) + min_midi, c)
+    if reach is not None:
+        return [(int(pp), float(a) / TICKS_PER_SECOND, float(b) / fs) for pp, a, b in zip(pitches, tick, e)]
+    return [(int(pp), float(a) / fs, float(b) / fs) for pp, a, b in zip(pitches, s, e)]
+
+
+def _heads_to_notes_raw(x, on, off, thrs, clean, reach: Optional[int]):
+    """The mt_heads_to_notes family on checked (NB, P, T) heads -> host arrays (counts (P,), starts, ends, ticks); ticks None without
+    `reach`, else mt_refine_onsets' onsets of the same notes, which ride in the note copy."""
+    NB, P, T = x.shape
+    dev = x.device
     counts = torch.empty(P, dtype=torch.int32, device=dev)
     cap = max(1024, NB * 64)
     while True:
-        starts, ends = torch.empty(cap, dtype=torch.int32, device=dev), torch.empty(cap, dtype=torch.int32, device=dev)
+        if reach is None:
+            starts, ends = torch.empty(cap, dtype=torch.int32, device=dev), torch.empty(cap, dtype=torch.int32, device=dev)
+        else:
+            se = torch.empty(3, cap, dtype=torch.int32, device=dev)                            # starts | ends | ticks: one copy
+            starts, ends = se[0], se[1]
         with torch.cuda.device(dev):
-            _decode("mt_heads_to_notes", clean, x, on, off, (thr, othr, kthr),
-                    (NB, P, T, ptr(counts), ptr(starts), ptr(ends), cap, _lib.stream_ptr()))
+            _decode("mt_heads_to_notes", clean, x, on, off, thrs, (NB, P, T, ptr(counts), ptr(starts), ptr(ends), cap, _lib.stream_ptr()))
         c = counts.cpu().numpy()
         total = int(c.sum())
         if total <= cap:
             break
         cap = total
-    s, e = starts[:total].cpu().numpy(), ends[:total].cpu().numpy()
-    pitches = np.repeat(np.arange(P) + min_midi, c)
-    return [(int(pp), float(a) / fs, float(b) / fs) for pp, a, b in zip(pitches, s, e)]
+    if reach is None:
+        return c, starts[:total].cpu().numpy(), ends[:total].cpu().numpy(), None
+    row_off = torch.zeros(P + 1, dtype=torch.int64, device=dev)
+    row_off[1:] = torch.cumsum(counts, 0)
+    _refine(starts, ends, row_off, total, on, None, True, reach, se[2])
+    s, e, tick = se[:, :total].cpu().numpy()
+    return c, s, e, tick
 
 
 def notes_batch_device(frame_logits: torch.Tensor, onset_logits: Optional[torch.Tensor] = None, threshold: float = 0.5,
                        onset_threshold: float = 0.5, lengths=None, fs: float = FS, min_midi: int = 21, min_note_frames: int = 1,
-                       bridge_frames: int = 0, smooth_on: float = 0.0, smooth_off: float = 0.0) -> List[List[Tuple[int, float, float]]]:
+                       bridge_frames: int = 0, smooth_on: float = 0.0, smooth_off: float = 0.0, refine_onsets: bool = False,
+                       refine_reach: int = 2) -> List[List[Tuple[int, float, float]]]:
     """(B, P, T) frame logits of B whole recordings ON THE DEVICE, padded to T, with lengths (B,) valid frames each (None: all T) ->
     one note list per recording: what transcribe.notes_from_logits_device (onset_logits None) or heads_to_notes_device returns on
     that recording's rows trimmed to its length.  The padding is never read.  One launch of mt_notes_batch, one device-to-host copy
     of the counts and offsets and one of the notes; a second launch only when the first capacity guess was short.  With
     (min_note_frames, bridge_frames) other than (1, 0) the notes are cleaned in the decoder (mt_notes_batch_clean).  With
-    (smooth_on, smooth_off) other than (0, 0) the frame head is smoothed first (smooth_frame_logits, over the same lengths)."""
+    (smooth_on, smooth_off) other than (0, 0) the frame head is smoothed first (smooth_frame_logits, over the same lengths).
+    refine_onsets=True (onset-gated decoder only): as in heads_to_notes_device, a note's start is its refined on_tick / 1e4 seconds."""
     clean = check_cleanup(min_note_frames, bridge_frames)
     smooth = check_smoothing(smooth_on, smooth_off)
+    reach = _check_refine(refine_onsets, refine_reach, onset_logits)
     x, on, _, thr, othr, _, _ = _heads(frame_logits, onset_logits, None, threshold, onset_threshold, 0.5,
                                        mismatch="frame {frame} and onset {onset} logits differ in shape")
     B, P, T = x.shape
-    dev = x.device
-    ln = _lengths(lengths, B, dev)
+    ln = _lengths(lengths, B, x.device)
     if smooth != (0.0, 0.0):
         x = _smoothed(x, thr, smooth, ln, False)
+    off, c, s, e, tick = _notes_batch_raw(x, on, ln, thr, othr, clean, reach)
+    if reach is not None:
+        s, fs_on = tick, float(TICKS_PER_SECOND)            # starts in ticks
+    else:
+        fs_on = fs
+    pitches = np.tile(np.arange(P) + min_midi, B)
+    out = []
+    for b in range(B):
+        lo, hi = int(off[b * P]), int(off[(b + 1) * P])
+        pp = np.repeat(pitches[b * P:(b + 1) * P], c[b * P:(b + 1) * P])
+        out.append([(int(q), float(a) / fs_on, float(z) / fs) for q, a, z in zip(pp, s[lo:hi], e[lo:hi])])
+    return out
+
+
+def _notes_batch_raw(x, on, ln, thr, othr, clean, reach: Optional[int]):
+    """mt_notes_batch / mt_notes_batch_clean on checked (B, P, T) heads -> host arrays (row_off (B * P + 1,), counts (B * P,), starts,
+    ends, ticks); ticks None without `reach`, else mt_refine_onsets' onsets of the same notes, which ride in the note copy."""
+    B, P, T = x.shape
+    dev = x.device
     rows = B * P
     meta = torch.empty(rows + 1 + (rows + 1) // 2, dtype=torch.int64, device=dev)      # row_off (rows + 1) | counts (rows int32): one copy
     row_off, counts = meta[:rows + 1], meta[rows + 1:].view(torch.int32)[:rows]
     cap = max(1024, (B * T) // 16)
     while True:
-        se = torch.empty(2, cap, dtype=torch.int32, device=dev)
+        se = torch.empty(2 if reach is None else 3, cap, dtype=torch.int32, device=dev)
         with torch.cuda.device(dev):
             _decode("mt_notes_batch", clean, x, on, None, (thr, othr, 0.5),
                     (ptr(ln), B, P, T, ptr(counts), ptr(row_off), ptr(se[0]), ptr(se[1]), cap, _lib.stream_ptr()), offset_head=False)
@@ -563,11 +607,170 @@ def notes_batch_device(frame_logits: torch.Tensor, onset_logits: Optional[torch.
         if total <= cap:
             break
         cap = total
-    s, e = se[:, :total].cpu().numpy()
-    pitches = np.tile(np.arange(P) + min_midi, B)
-    out = []
-    for b in range(B):
-        lo, hi = int(off[b * P]), int(off[(b + 1) * P])
-        pp = np.repeat(pitches[b * P:(b + 1) * P], c[b * P:(b + 1) * P])
-        out.append([(int(q), float(a) / fs, float(z) / fs) for q, a, z in zip(pp, s[lo:hi], e[lo:hi])])
+    if reach is None:
+        s, e = se[:, :total].cpu().numpy()
+        return off, c, s, e, None
+    _refine(se[0], se[1], row_off, total, on, ln, False, reach, se[2])
+    s, e, tick = se[:, :total].cpu().numpy()
+    return off, c, s, e, tick
+
+
+def notes_ticks_device(frame_logits: torch.Tensor, onset_logits: torch.Tensor, threshold: float = 0.5, onset_threshold: float = 0.5,
+                       lengths=None, offset_logits: Optional[torch.Tensor] = None, offset_threshold: float = 0.5, min_note_frames: int = 1,
+                       bridge_frames: int = 0, smooth_on: float = 0.0, smooth_off: float = 0.0, refine_reach: int = 2) -> Dict[str, np.ndarray]:
+    """The notes of a padded batch (B, P, T) with refined onsets, as a note list on the host for note_match_ticks: {"on", "off"} int32
+    ticks of 100 us (on = mt_refine_onsets' sub-frame onset, off = 320 e) and "ptr" int64 (B * P + 1,), in the layout of
+    MaestroDataset.ref_notes.  The onset-gated decoder goes through mt_notes_batch* and one refinement launch for the whole batch; with
+    offset_logits (the batched extractor reads two heads) every recording is decoded on its own valid frames with
+    mt_heads_to_notes_off / _clean and refined there."""
+    clean = check_cleanup(min_note_frames, bridge_frames)
+    smooth = check_smoothing(smooth_on, smooth_off)
+    reach = _check_refine(True, refine_reach, onset_logits)
+    x, on, off, thr, othr, kthr, _ = _heads(frame_logits, onset_logits, offset_logits, threshold, onset_threshold, offset_threshold,
+                                            mismatch="frame {frame} and onset {onset} logits differ in shape")
+    B, P, T = x.shape
+    ln = _lengths(lengths, B, x.device)
+    if smooth != (0.0, 0.0):
+        x = _smoothed(x, thr, smooth, ln, False)
+    if off is None:
+        ptrs, _, _, e, tick = _notes_batch_raw(x, on, ln, thr, othr, clean, reach)
+        return {"on": tick.astype(np.int32), "off": (e * TICKS_PER_FRAME).astype(np.int32), "ptr": ptrs.astype(np.int64)}
+    lens = [T] * B if ln is None else [min(max(int(v), 0), T) for v in ln.cpu().numpy()]
+    ons, offs, ptrs = [], [], [np.zeros(1, np.int64)]
+    for b, L in enumerate(lens):
+        if L == 0:
+            c, e, tick = np.zeros(P, np.int32), np.zeros(0, np.int32), np.zeros(0, np.int32)
+        else:
+            cut = lambda h: h[b:b + 1, :, :L].contiguous()
+            c, _, e, tick = _heads_to_notes_raw(cut(x), cut(on), cut(off), (thr, othr, kthr), clean, reach)
+        ons.append(tick)
+        offs.append(e * TICKS_PER_FRAME)
+        ptrs.append(ptrs[-1][-1] + np.cumsum(c, dtype=np.int64))
+    return {"on": np.concatenate(ons).astype(np.int32), "off": np.concatenate(offs).astype(np.int32), "ptr": np.concatenate(ptrs)}
+
+
+TICKS_PER_SECOND = 10000           # ticks of 100 us
+MAX_REFINE_REACH = 8               # mt_refine_onsets: frames the peak search may walk from a note's start
+
+
+def _check_refine(refine_onsets, refine_reach, onset_logits) -> Optional[int]:
+    """The checked reach of a decoder call with refine_onsets, None without.  Raises before any GPU work."""
+    if not refine_onsets:
+        return None
+    if onset_logits is None:
+        raise ValueError("refine_onsets: sub-frame onsets are read off the onset head, and the frame decoder has none (pass onset_logits)")
+    if isinstance(refine_reach, bool) or not isinstance(refine_reach, (int, np.integer)) or not 0 <= refine_reach <= MAX_REFINE_REACH:
+        raise ValueError(f"refine_reach must be an integer number of frames in [0, {MAX_REFINE_REACH}], got {refine_reach!r}")
+    return int(refine_reach)
+
+
+def _refine(starts, ends, row_off, n: int, on: torch.Tensor, ln: Optional[torch.Tensor], chunks: bool, reach: int, out: torch.Tensor) -> None:
+    """mt_refine_onsets on checked arguments: on contiguous (NB, P, T) f32, starts / ends / out int32 with at least n entries."""
+    NB, P, T = on.shape
+    with torch.cuda.device(on.device):
+        check(lib.mt_refine_onsets(ptr(starts), ptr(ends), ptr(row_off), P if chunks else NB * P, n, ptr(on), NB, P, T, ptr(ln), int(chunks),
+                                   reach, ptr(out), _lib.stream_ptr()), "mt_refine_onsets")
+
+
+def refine_onsets_device(starts: torch.Tensor, ends: torch.Tensor, row_off: torch.Tensor, onset_logits: torch.Tensor, lengths=None,
+                         chunks: bool = False, reach: int = 2) -> torch.Tensor:
+    """Sub-frame onsets of decoded notes ON THE DEVICE -> int32 device tensor on_tick (n,), ticks of 100 us (mt_refine_onsets; DESIGN.md
+    6c "Sub-frame onsets").  starts / ends: int32 (n,) frames [s, e) of the notes of any onset-gated decoder; row_off: int64
+    (rows + 1,) rising from 0 to n, the notes of row r at row_off[r]:row_off[r + 1].  onset_logits (B, P, T): chunks=False a padded
+    batch (rows = B * P, lengths (B,) valid frames, None = all T; the padding is never read), chunks=True the B chunks concatenated in
+    time (rows = P, no lengths).  Per note the peak of sigmoid(onset) is searched from s over at most `reach` frames (0..8) inside the
+    note, and the onset is 320 k + rint(320 shift) with the shift of the triangle through the peak and its neighbours, clamped to
+    [0, 320 e - 1].  One read-back (row_off's last entry) checks the tables; the result stays on the device."""
+    if onset_logits is None:
+        raise ValueError("refine_onsets_device: needs the onset head's logits")
+    reach = _check_refine(True, reach, onset_logits)
+    on = _rows(onset_logits, "onset_logits")
+    NB, P, T = on.shape
+    dev = on.device
+    if chunks and lengths is not None:
+        raise ValueError("lengths: chunks=True concatenates whole chunks, which have no lengths")
+    rows = P if chunks else NB * P
+    for t, dt, name in ((starts, torch.int32, "starts"), (ends, torch.int32, "ends"), (row_off, torch.int64, "row_off")):
+        if not torch.is_tensor(t) or t.device != dev or t.dtype != dt or t.dim() != 1:
+            raise ValueError(f"{name}: expected a 1-d {dt} tensor on {dev}")
+    n = int(starts.numel())
+    if ends.numel() != n or row_off.numel() != rows + 1:
+        raise ValueError(f"refine_onsets_device: {n} starts, {ends.numel()} ends, row_off of {row_off.numel()} entries for {rows} rows")
+    if bool((row_off[0] != 0) | (row_off[-1] != n) | (row_off[1:] < row_off[:-1]).any()):
+        raise ValueError("row_off must rise from 0 to the number of notes")
+    out = torch.empty(n, dtype=torch.int32, device=dev)
+    _refine(starts.contiguous(), ends.contiguous(), row_off.contiguous(), n, on, _lengths(lengths, NB, dev), chunks, reach, out)
     return out
+
+
+def _max_matching(adj: List[List[int]], n_right: int) -> int:
+    """Size of a maximum matching of a bipartite graph, adj[i] = the right vertices of left vertex i (augmenting paths)."""
+    match, size = [-1] * n_right, 0
+    for root in range(len(adj)):
+        if not adj[root]:
+            continue
+        seen = [False] * n_right
+        stack, path, found = [[root, 0]], [], False         # depth-first without recursion: stack[d] = [left vertex, next edge], path[d] = its right vertex
+        while stack and not found:
+            i, it = stack[-1]
+            if it == len(adj[i]):
+                stack.pop()
+                if path:
+                    path.pop()
+                continue
+            stack[-1][1] = it + 1
+            j = adj[i][it]
+            if seen[j]:
+                continue
+            seen[j] = True
+            path.append(j)
+            if match[j] < 0:
+                found = True
+            else:
+                stack.append([match[j], 0])
+        if found:
+            for (i, _), j in zip(stack, path):
+                match[j] = i
+            size += 1
+    return size
+
+
+def note_match_ticks(est_notes, ref_notes) -> np.ndarray:
+    """Score estimated notes whose onsets lie off the frame grid (refine_onsets_device) against a note list, on the host.  Both
+    arguments are {"on", "off", "ptr"} in the layout of MaestroDataset.ref_notes (ticks of 100 us, ptr with rows + 1 entries rising from
+    0, the same number of rows on both sides, a multiple of 88; tensors or arrays) -> (B, 4) uint64 {n_ref, n_est, tp_onset,
+    tp_onset_offset}, B = rows / 88.  mt_note_match_list's criteria: onsets match when |d on| <= 500 ticks, and for tp_onset_offset
+    also 5 |d off| <= max(2500, reference length); each tp is a maximum matching, found per pitch row with augmenting paths.
+    mt_note_match_list's streaming matcher relies on at most two frame-grid estimates inside a +-500 tick window, which refined
+    onsets do not guarantee; a device matcher for tick estimates does not exist."""
+    def host(d, name):
+        out = []
+        for k in ("on", "off", "ptr"):
+            v = d[k]
+            v = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+            out.append(np.asarray(v, dtype=np.int64).reshape(-1))
+        on, off, pt = out
+        if pt.size < 1 or pt[0] != 0 or pt[-1] != on.size or on.size != off.size or (np.diff(pt) < 0).any():
+            raise ValueError(f"{name}: ptr must rise from 0 to the number of notes, on / off of equal length")
+        return on, off, pt
+    e_on, e_off, e_ptr = host(est_notes, "est_notes")
+    r_on, r_off, r_ptr = host(ref_notes, "ref_notes")
+    rows = e_ptr.size - 1
+    if r_ptr.size - 1 != rows or rows % _lib.N_PITCH:
+        raise ValueError(f"note_match_ticks: {rows} estimated and {r_ptr.size - 1} reference rows (expected equal multiples of {_lib.N_PITCH})")
+    counts = np.zeros((rows // _lib.N_PITCH, 4), dtype=np.uint64)
+    for r in range(rows):
+        eo, ef = e_on[e_ptr[r]:e_ptr[r + 1]], e_off[e_ptr[r]:e_ptr[r + 1]]
+        ro, rf = r_on[r_ptr[r]:r_ptr[r + 1]], r_off[r_ptr[r]:r_ptr[r + 1]]
+        c = counts[r // _lib.N_PITCH]
+        c[0] += np.uint64(ro.size)
+        c[1] += np.uint64(eo.size)
+        if not ro.size or not eo.size:
+            continue
+        near = np.abs(ro[:, None] - eo[None, :]) <= 500
+        if not near.any():
+            continue
+        both = near & (5 * np.abs(rf[:, None] - ef[None, :]) <= np.maximum(2500, rf - ro)[:, None])
+        c[2] += np.uint64(_max_matching([np.flatnonzero(row).tolist() for row in near], eo.size))
+        c[3] += np.uint64(_max_matching([np.flatnonzero(row).tolist() for row in both], eo.size))
+    return counts

@@ -133,6 +133,7 @@ def _merge_spans(u, v, p):
 
 TICKS_PER_SECOND = 10000     # note times in ticks of 100 us: one model frame (512 / 16000 s) is exactly 320 ticks
 TICKS_PER_FRAME = 320
+ONSET_WIDTH_RANGE = (2, 8)   # mt_onset_regress_windows: half-width of the onset triangle in frames
 
 
 class NoteTable(NamedTuple):
@@ -373,15 +374,36 @@ class MaestroDataset(Dataset):
     onset_labels="midi" keeps every recording's note list (label_notes) on the device as well: get_batch then returns the
     labels as {"frame": roll, "onset": onset_roll}, the onset roll marking the MIDI note-ons (re-struck keys included) on
     the roll's column grid, and ref_notes(indices) gives the note lists notes.note_match_list scores against.  The default
-    "roll" builds neither table and returns what it always did."""
+    "roll" builds neither table and returns what it always did.
+
+    onset_target="regress" (with onset_labels="midi") replaces the onset roll by a regression target (mt_onset_regress_windows,
+    DESIGN.md 6c "Sub-frame onsets"): a triangle of half-width onset_width frames (2..8) around every note-on, measured from the
+    centre of the mel's own frame t (sample 512 t of the window), so that the head's values around a peak tell where inside the
+    frame the key went down.  No column table is involved: for chunk items the point target inherits the reference's stretched
+    column grid, the regression target does not.  Under augmentation the frame centres are mapped to source time with the
+    window's speed; the triangle's width is kept in source time, hence up to 3 % narrower or wider in mel frames.  The default
+    "point" is the onset roll above, launch for launch."""
 
     def __init__(self, root_dir, csv_path=None, year=None, split="train", sr=16000, n_mels=229, hop_length=512, subset_size=None,
                  chunk_length=None, overlap=0.0, return_waveform=False, device=None, max_resident_bytes=None, onset_labels="roll",
-                 augment=None):
+                 augment=None, onset_target="point", onset_width=2):
         if return_waveform:
             raise NotImplementedError("return_waveform=True is the AST experiment's data path (out of scope)")
         if onset_labels not in ("roll", "midi"):
             raise ValueError(f"onset_labels must be 'roll' or 'midi', got {onset_labels!r}")
+        if onset_target not in ("point", "regress"):
+            raise ValueError(f"onset_target must be 'point' or 'regress', got {onset_target!r}")
+        if onset_target == "regress":
+            if onset_labels != "midi":
+                raise ValueError("onset_target='regress' is built from the MIDI note-ons: it needs onset_labels='midi'")
+            if isinstance(onset_width, bool) or not isinstance(onset_width, (int, np.integer)) \
+                    or not ONSET_WIDTH_RANGE[0] <= onset_width <= ONSET_WIDTH_RANGE[1]:
+                raise ValueError(f"onset_width must be an integer number of frames in [{ONSET_WIDTH_RANGE[0]}, {ONSET_WIDTH_RANGE[1]}] (at 1 the "
+                                 f"triangle's side values clamp at 0 and the sub-frame time cannot be recovered), got {onset_width!r}")
+            if int(hop_length) * TICKS_PER_SECOND != TICKS_PER_FRAME * int(sr):
+                raise ValueError(f"onset_target='regress': the target is computed in exact units of 12.5 us on the grid of {TICKS_PER_FRAME} "
+                                 f"ticks per frame (sr 16000, hop 512); got sr {sr}, hop {hop_length}")
+        self.onset_target, self.onset_width = onset_target, int(onset_width)
         if augment is not None:
             if not isinstance(augment, Augment):
                 raise TypeError(f"augment must be an Augment or None, got {type(augment).__name__}")
@@ -457,6 +479,12 @@ class MaestroDataset(Dataset):
         sp_all = np.concatenate(on_sp) if base else np.zeros((1, 2), np.int32)
         self.onset_spans = torch.from_numpy(np.ascontiguousarray(sp_all, dtype=np.int32)).to(dev)
         self.onset_pitch_off = torch.from_numpy(np.concatenate(on_po) if on_po else np.zeros(N_PITCH + 1, np.int64)).to(dev)
+        if self.onset_target == "regress":                  # every note-on in ticks, in the layout of onset_pitch_off
+            ticks = np.concatenate([nt.on_tick for nt in tables]) if tables else np.zeros(0, np.int32)
+            bases = np.concatenate([[0], np.cumsum([len(nt.on_tick) for nt in tables])]).astype(np.int64)
+            t_off = np.concatenate([nt.pitch_off + b for nt, b in zip(tables, bases)]) if tables else np.zeros(N_PITCH + 1, np.int64)
+            self.onset_ticks = torch.from_numpy(np.ascontiguousarray(ticks if ticks.size else np.zeros(1), dtype=np.int32)).to(dev)
+            self.onset_tick_off = torch.from_numpy(np.ascontiguousarray(t_off, dtype=np.int64)).to(dev)
         if self.chunk_length is not None:
             return
         if self.hop_length * TICKS_PER_SECOND != TICKS_PER_FRAME * self.sr:
@@ -522,8 +550,9 @@ class MaestroDataset(Dataset):
         h64 = torch.empty((2, B), dtype=torch.int64, pin_memory=True)
         h64[0] = torch.from_numpy(np.array([offs[int(r)] for r in recs], dtype=np.int64) + self.start[idx])
         h64[1] = torch.from_numpy(self.col_off[idx])
-        h32 = torch.empty((5, B), dtype=torch.int32, pin_memory=True)
-        h32.copy_(torch.from_numpy(np.stack([self.win_len[idx], n_rec[recs] - self.start[idx], t_keep, recs, self.ncols[idx]])))
+        h32 = torch.empty((6, B), dtype=torch.int32, pin_memory=True)
+        h32.copy_(torch.from_numpy(np.stack([self.win_len[idx], n_rec[recs] - self.start[idx], t_keep, recs, self.ncols[idx],
+                                             self.start[idx]])))
         dev = self.device
         with torch.cuda.device(dev):
             d64, d32 = h64.to(dev, non_blocking=True), h32.to(dev, non_blocking=True)
@@ -535,6 +564,9 @@ class MaestroDataset(Dataset):
                                             int(self.win_len[idx].max()), T_out, ptr(d32[2]), ptr(mel), ptr(cmax), st), "mt_mel_db_windows_f32")
             check(lib.mt_roll_windows(ptr(self.spans), ptr(self.pitch_off), ptr(self.cols), ptr(d32[3]), ptr(d64[1]), ptr(d32[4]), ptr(d32[2]),
                                       B, T_out, ptr(roll), st), "mt_roll_windows")
+            if self.onset_target == "regress":              # triangles around the note-ons, measured from the mel's frame centres
+                return mel, {"frame": roll, "onset": self._onset_regress(d32[3], d32[5], None, d32[2], B, T_out, st)}, \
+                    torch.from_numpy(t_keep.copy())
             if self.onset_labels == "midi":                 # the note-ons on the same columns: point spans through the same kernel
                 onset_roll = torch.empty_like(roll)
                 check(lib.mt_roll_windows(ptr(self.onset_spans), ptr(self.onset_pitch_off), ptr(self.cols), ptr(d32[3]), ptr(d64[1]),
@@ -593,12 +625,22 @@ class MaestroDataset(Dataset):
                                             int(win_len.max()), T_out, ptr(d32[2]), ptr(mel), ptr(cmax), st), "mt_mel_db_windows_f32")
             check(lib.mt_roll_windows(ptr(self.spans), ptr(self.pitch_off), ptr(dcols), ptr(d32[3]), ptr(d64[1]), ptr(d32[4]), ptr(d32[2]),
                                       B, T_out, ptr(roll), st), "mt_roll_windows")
+            if self.onset_target == "regress":              # frame centres in source time: the batch's own speeds
+                return mel, {"frame": roll, "onset": self._onset_regress(d32[3], d32[5], d64[3], d32[2], B, T_out, st)}, \
+                    torch.from_numpy(t_keep.copy())
             if self.onset_labels == "midi":
                 onset_roll = torch.empty_like(roll)
                 check(lib.mt_roll_windows(ptr(self.onset_spans), ptr(self.onset_pitch_off), ptr(dcols), ptr(d32[3]), ptr(d64[1]),
                                           ptr(d32[4]), ptr(d32[2]), B, T_out, ptr(onset_roll), st), "mt_roll_windows")
                 return mel, {"frame": roll, "onset": onset_roll}, torch.from_numpy(t_keep.copy())
         return mel, roll, torch.from_numpy(t_keep.copy())
+
+    def _onset_regress(self, win_rec, start, rate_q32, t_keep, B, T_out, st) -> torch.Tensor:
+        """mt_onset_regress_windows on the batch's device tables (start: each window's first sample inside its recording)."""
+        y = torch.empty(B, N_PITCH, T_out, dtype=torch.float32, device=self.device)
+        check(lib.mt_onset_regress_windows(ptr(self.onset_ticks), ptr(self.onset_tick_off), ptr(win_rec), ptr(start), ptr(rate_q32), ptr(t_keep),
+                                           B, T_out, self.onset_width, ptr(y), st), "mt_onset_regress_windows")
+        return y
 
     def __getitem__(self, idx):
         if _in_worker():
@@ -612,16 +654,20 @@ class MaestroDataset(Dataset):
 
 class HybridMaestroDataset(Dataset):
     """data/cached_dataset.py:91-141: the cache when its metadata's chunk_length and overlap equal the request, else MaestroDataset.
-    A request with `augment` never uses the cache: its records hold features, and augmentation works on the waveform."""
+    A request with `augment` never uses the cache: its records hold features, and augmentation works on the waveform.  Nor does
+    one with onset_target="regress": the cache holds rolls, and the regression target is built from the MIDI note-ons."""
 
-    def __init__(self, root_dir, cache_dir="cached_dataset", split="train", chunk_length=None, overlap=0.0, augment=None, **kwargs):
+    def __init__(self, root_dir, cache_dir="cached_dataset", split="train", chunk_length=None, overlap=0.0, augment=None,
+                 onset_target="point", onset_width=2, **kwargs):
         from .data import CachedMaestroDataset
         self.use_cache = False
         if augment is not None:
             kwargs["augment"] = augment
+        if onset_target != "point":
+            kwargs["onset_target"], kwargs["onset_width"] = onset_target, onset_width
         try:
             metadata_path = os.path.join(cache_dir, f"{split}_metadata.pkl")
-            if augment is None and os.path.exists(metadata_path):
+            if augment is None and onset_target == "point" and os.path.exists(metadata_path):
                 with open(metadata_path, "rb") as f:
                     metadata = pickle.load(f)
                 if metadata.get("chunk_length") == chunk_length and metadata.get("overlap") == overlap:

@@ -296,18 +296,32 @@ def check_decoder(decoder: str, model_type: str = None, model=None) -> None:
                          f"(model type {model_type!r} has none)")
 
 
+def check_refine_decoder(refine_onsets: bool, decoder: str, refine_reach: int = 2) -> None:
+    """Sub-frame onsets are read off the onset head: refuse refine_onsets with the frame decoder (and a reach outside 0..8), before any GPU work."""
+    if not refine_onsets:
+        return
+    if decoder not in HEAD_DECODERS:
+        raise ValueError(f"refine_onsets needs decoder 'onset' or 'onset_offset' (the frame decoder has no onset head to refine from), got {decoder!r}")
+    from .notes import _check_refine
+    _check_refine(True, refine_reach, True)
+
+
 @torch.no_grad()
 def transcribe_chunks_to_notes(model: "TranscriptionModel", chunks, threshold: float = THRESHOLD, batch: int = 128, n_mels: int = N_MELS,
                                device: str = "cuda", decoder: str = "frame", onset_threshold: float = THRESHOLD,
                                offset_threshold: float = THRESHOLD, min_note_frames: int = 1,
-                               bridge_frames: int = 0, smooth_on: float = 0.0, smooth_off: float = 0.0) -> List[Tuple[int, float, float]]:
+                               bridge_frames: int = 0, smooth_on: float = 0.0, smooth_off: float = 0.0, refine_onsets: bool = False,
+                               refine_reach: int = 2) -> List[Tuple[int, float, float]]:
     """(n, 480000) waveform chunks -> notes; mel, forward, threshold, concatenation and run-length all on the GPU.  decoder="onset":
     notes start at rising edges of the onset head and last while frame or onset is active (notes.heads_to_notes_device);
     decoder="onset_offset": those notes, ended where the offset head fires.  min_note_frames / bridge_frames: note
     cleanup in the decoder, any of the three (DESIGN.md 6c "Note cleanup").  smooth_on / smooth_off: the frame head is smoothed before
-    any of the three decodes it (DESIGN.md 6c "Frame smoothing")."""
+    any of the three decodes it (DESIGN.md 6c "Frame smoothing").  refine_onsets (onset / onset_offset decoders): note starts are
+    sub-frame onsets read off the onset head (DESIGN.md 6c "Sub-frame onsets"); on concatenated chunks the frame grid itself drifts
+    16 ms per chunk, so sub-frame times mean most with overlapping windows."""
     from .notes import check_cleanup, check_smoothing
     check_decoder(decoder, model=model)
+    check_refine_decoder(refine_onsets, decoder)
     clean = check_cleanup(min_note_frames, bridge_frames)
     smooth = check_smoothing(smooth_on, smooth_off)
     with_heads, with_offset = decoder in HEAD_DECODERS, decoder == "onset_offset"
@@ -331,7 +345,8 @@ def transcribe_chunks_to_notes(model: "TranscriptionModel", chunks, threshold: f
         from .notes import heads_to_notes_device
         notes = heads_to_notes_device(torch.cat(outs), torch.cat(onsets), threshold, onset_threshold, SR / HOP_LENGTH,
                                       offset_logits=torch.cat(offsets) if with_offset else None, offset_threshold=offset_threshold,
-                                      min_note_frames=clean[0], bridge_frames=clean[1], smooth_on=smooth[0], smooth_off=smooth[1])
+                                      min_note_frames=clean[0], bridge_frames=clean[1], smooth_on=smooth[0], smooth_off=smooth[1],
+                                      refine_onsets=refine_onsets, refine_reach=refine_reach)
     else:
         notes = notes_from_logits_device(torch.cat(outs), threshold, SR / HOP_LENGTH, min_note_frames=clean[0], bridge_frames=clean[1],
                                          smooth_on=smooth[0], smooth_off=smooth[1])
@@ -405,14 +420,17 @@ def transcribe_chunks(model: TranscriptionModel, chunks, threshold: float = THRE
 def transcribe_windows_to_notes(model: "TranscriptionModel", y: torch.Tensor, overlap: float, threshold: float = THRESHOLD, batch: int = 128,
                                 n_mels: int = N_MELS, decoder: str = "frame", onset_threshold: float = THRESHOLD,
                                 offset_threshold: float = THRESHOLD, min_note_frames: int = 1,
-                                bridge_frames: int = 0, smooth_on: float = 0.0, smooth_off: float = 0.0) -> List[Tuple[int, float, float]]:
+                                bridge_frames: int = 0, smooth_on: float = 0.0, smooth_off: float = 0.0, refine_onsets: bool = False,
+                                refine_reach: int = 2) -> List[Tuple[int, float, float]]:
     """1-D device recording -> notes decoded from ONE (1, 88, 1 + n // 512) logit roll on the recording's frame grid, stitched from
     overlapping 30 s windows (windows.transcribe_windows): no per-chunk drift, no cold chunk edges inside the recording.
     min_note_frames / bridge_frames: note cleanup in the decoder (DESIGN.md 6c "Note cleanup"); smooth_on / smooth_off: the frame head
-    is smoothed first (DESIGN.md 6c "Frame smoothing")."""
+    is smoothed first (DESIGN.md 6c "Frame smoothing"); refine_onsets (onset / onset_offset decoders): note starts are sub-frame
+    onsets read off the onset head (DESIGN.md 6c "Sub-frame onsets")."""
     from .notes import check_cleanup, check_smoothing
     from .windows import transcribe_windows
     check_decoder(decoder, model=model)
+    check_refine_decoder(refine_onsets, decoder)
     clean = check_cleanup(min_note_frames, bridge_frames)
     smooth = check_smoothing(smooth_on, smooth_off)
     with_offset = decoder == "onset_offset"
@@ -421,19 +439,23 @@ def transcribe_windows_to_notes(model: "TranscriptionModel", y: torch.Tensor, ov
         from .notes import heads_to_notes_device
         return heads_to_notes_device(heads[0][None], heads[1][None], threshold, onset_threshold, SR / HOP_LENGTH,
                                      offset_logits=heads[2][None] if with_offset else None, offset_threshold=offset_threshold,
-                                     min_note_frames=clean[0], bridge_frames=clean[1], smooth_on=smooth[0], smooth_off=smooth[1])
+                                     min_note_frames=clean[0], bridge_frames=clean[1], smooth_on=smooth[0], smooth_off=smooth[1],
+                                     refine_onsets=refine_onsets, refine_reach=refine_reach)
     return notes_from_logits_device(heads[None], threshold, SR / HOP_LENGTH, min_note_frames=clean[0], bridge_frames=clean[1],
                                     smooth_on=smooth[0], smooth_off=smooth[1])
 
 
 def transcribe_audio(audio_path: str, model_path: str, output_path=None, device=None, threshold: float = THRESHOLD, decoder: str = "frame",
                      onset_threshold: float = THRESHOLD, overlap: float = 0.0, offset_threshold: float = THRESHOLD, min_note_frames: int = 1,
-                     bridge_frames: int = 0, smooth_on: float = 0.0, smooth_off: float = 0.0, **model_kw):
+                     bridge_frames: int = 0, smooth_on: float = 0.0, smooth_off: float = 0.0, refine_onsets: bool = False,
+                     refine_reach: int = 2, **model_kw):
     """overlap = 0: the reference's chunk concatenation (main.py:60-100, :164-186); overlap > 0 (seconds): overlapping windows
     stitched on the recording's own frame grid (transcribe_windows_to_notes).  smooth_on / smooth_off: frame smoothing before the
-    decoder, in either mode (DESIGN.md 6c "Frame smoothing")."""
+    decoder, in either mode (DESIGN.md 6c "Frame smoothing").  refine_onsets: sub-frame note starts from the onset head, in either
+    mode, with the onset and onset_offset decoders (DESIGN.md 6c "Sub-frame onsets")."""
     from .notes import check_cleanup, check_smoothing
     check_decoder(decoder, model_type=model_kw.get("model_type", MODEL_TYPE))
+    check_refine_decoder(refine_onsets, decoder, refine_reach)
     clean = check_cleanup(min_note_frames, bridge_frames)    # refused before any GPU work, like the decoder
     smooth = check_smoothing(smooth_on, smooth_off)
     if overlap:
@@ -451,13 +473,15 @@ def transcribe_audio(audio_path: str, model_path: str, output_path=None, device=
               f"overlapping by {overlap}s")
         notes = transcribe_windows_to_notes(model, y, overlap, threshold, n_mels=model_kw.get("n_mels", N_MELS), decoder=decoder,
                                             onset_threshold=onset_threshold, offset_threshold=offset_threshold, min_note_frames=clean[0],
-                                            bridge_frames=clean[1], smooth_on=smooth[0], smooth_off=smooth[1])
+                                            bridge_frames=clean[1], smooth_on=smooth[0], smooth_off=smooth[1], refine_onsets=refine_onsets,
+                                            refine_reach=refine_reach)
     else:
         chunks, duration = split_into_chunks_device(y)
         print(f"Audio duration: {duration:.2f} seconds; {len(chunks)} chunks of {CHUNK_LENGTH}s")
         notes = transcribe_chunks_to_notes(model, chunks, threshold, n_mels=model_kw.get("n_mels", N_MELS), device=device, decoder=decoder,
                                            onset_threshold=onset_threshold, offset_threshold=offset_threshold, min_note_frames=clean[0],
-                                           bridge_frames=clean[1], smooth_on=smooth[0], smooth_off=smooth[1])
+                                           bridge_frames=clean[1], smooth_on=smooth[0], smooth_off=smooth[1], refine_onsets=refine_onsets,
+                                           refine_reach=refine_reach)
     if output_path is None:
         p = Path(audio_path)
         output_path = p.parent / f"{p.stem}_transcription.mid"

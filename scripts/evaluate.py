@@ -27,6 +27,9 @@ decoder together, with any --decoder: its thresholds (frame; onset; offset) and 
 `--tune_note_decoder --tune_smooth_on 0 1 2 --tune_smooth_off 0 1 2` tunes the two penalties with everything else: every pair of the
 two lists is one more candidate of each round's grid (one packed-path launch per group and tile of 16 frame candidates), and the
 note metrics are reported at the chosen pair.
+`--note_metrics --note_reference midi --decoder onset|onset_offset --refine_onsets [--refine_reach N]` gives every decoded note a
+sub-frame onset (notes.refine_onsets_device), copies the note lists to the host and scores them there in ticks of 100 us
+(notes.note_match_ticks); the same EVAL_NOTE_* lines.  Cleanup and smoothing flags stay allowed; the tuners are refused.
 MIDI / plot outputs, background mode and the results browser are out of scope.
 """
 import argparse
@@ -87,6 +90,13 @@ def main():
     ap.add_argument("--smooth_off", type=float, default=0.0,
                     help="with --note_metrics: frame smoothing, the cost in logits of switching a pitch off (0 to 64; default 0 = with "
                          "--smooth_on 0, no smoothing)")
+    ap.add_argument("--refine_onsets", action="store_true",
+                    help="with --note_metrics --note_reference midi --decoder onset / onset_offset: give every decoded note a sub-frame onset "
+                         "from the onset head's values around its peak (a head trained with train_cnn.py --onset_target regress) and score "
+                         "the note lists on the host in 100 us ticks; prints the same EVAL_NOTE_* lines.  Not with the three tuners")
+    ap.add_argument("--refine_reach", type=int, default=2,
+                    help="--refine_onsets: frames the peak search may walk from a note's first frame (0..8; default 2 = the default "
+                         "--onset_width of training)")
     ap.add_argument("--window_overlap", type=float, default=None,
                     help="full files only: run every recording in overlapping 30 s windows (this many seconds of overlap, 0.256 to 15) "
                          "stitched on its own frame grid, instead of one recurrence over the whole file; lifts the T * hidden_size < 2^24 "
@@ -169,6 +179,18 @@ def main():
             smooth_on, smooth_off = check_smoothing(args.smooth_on, args.smooth_off)
         except ValueError as e:
             ap.error(str(e))
+    if args.refine_onsets:
+        if not args.note_metrics or args.note_reference != "midi":
+            ap.error("--refine_onsets refines the notes of --note_metrics and scores them against the MIDI note list in ticks: it needs "
+                     "--note_metrics --note_reference midi")
+        if args.decoder not in ("onset", "onset_offset"):
+            ap.error("--refine_onsets reads the onset head and needs --decoder onset or onset_offset")
+        for flag in ("tune_threshold", "tune_note_thresholds", "tune_note_decoder"):
+            if getattr(args, flag):
+                ap.error(f"--refine_onsets cannot be combined with --{flag}: the tuners count on the device, on the frame grid; tune "
+                         "without it, then evaluate with it at the values reported")
+        if not 0 <= args.refine_reach <= 8:
+            ap.error("--refine_reach must lie in 0..8 frames")
     say = (lambda *a, **k: None) if args.headless else print
 
     if args.note_reference == "midi" and args.data_source != "full":
@@ -293,7 +315,8 @@ def main():
                                        subset=args.subset, rank=rank, world=world, window_overlap=args.window_overlap,
                                        note_reference=args.note_reference, offset_threshold=note_offset_threshold,
                                        min_note_frames=min_note_frames, bridge_frames=bridge_frames, smooth_on=smooth_on,
-                                       smooth_off=smooth_off)
+                                       smooth_off=smooth_off, **(dict(refine_onsets=True, refine_reach=args.refine_reach)
+                                                                 if args.refine_onsets else {}))
     if rank == 0:
         if args.headless:
             print(f"EVAL_MEAN_F1={mean_f1:.6f}")

@@ -13,6 +13,9 @@ music_transcription_amd/rawdata.py), where --subset_size counts recordings as in
 (no --chunk_length and no usable cache) is refused before the first step.  `--train_all_heads --onset_labels midi` trains the
 onset head against the MIDI note-ons (a key struck again under the pedal or without a gap gets its onset) instead of the rising
 edges of the label roll; cache records hold no note list, so it always reads the recordings under --root_dir.
+`--onset_target regress [--onset_width J]` (with the two flags above) trains the onset head against a triangle of J frames around each
+note-on's true time instead of one hot cell, so that `--refine-onsets` can recover sub-frame onsets at decode time (DESIGN.md 6c
+"Sub-frame onsets"); the training set only, the validation loss keeps the point target.
 `--augment_pitch_cents X` and `--augment_snr_db LO HI` (either or both) augment the training set on the GPU: each chunk is played at
 a speed within +-X cents and gets white noise at a signal-to-noise ratio drawn from [LO, HI] dB, the labels moving with the audio
 (rawdata.Augment).  They work on the waveform, so they too read the recordings under --root_dir; validation is never augmented.
@@ -77,6 +80,11 @@ def main():
                     help="onset targets of --train_all_heads: roll = rising edges of the label roll (default); midi = the MIDI note-ons, "
                          "re-struck keys included.  midi reads the recordings under --root_dir even where a cache matches (cache records "
                          "hold no note list)")
+    ap.add_argument("--onset_target", choices=["point", "regress"], default="point",
+                    help="training set only, with --train_all_heads --onset_labels midi: point = one hot cell per note-on (default); regress = "
+                         "a triangle of --onset_width frames around the true onset time, from which --refine-onsets / --refine_onsets "
+                         "recover sub-frame onsets at decode time.  The validation loss keeps the point target")
+    ap.add_argument("--onset_width", type=int, default=2, metavar="J", help="half-width of the --onset_target regress triangle in frames (2..8)")
     ap.add_argument("--augment_pitch_cents", type=float, default=None, metavar="X",
                     help="training set only: play each chunk at a speed drawn from +-X cents (0..50; pitch and tempo move together, "
                          "labels follow).  Reads the recordings under --root_dir even where a cache matches")
@@ -132,6 +140,14 @@ def main():
     if midi_onsets and not args.train_all_heads:
         print("Error: --onset_labels midi sets the onset head's targets and needs --train_all_heads", file=sys.stderr)
         return 2
+    if args.onset_target == "regress":
+        if not (midi_onsets and args.train_all_heads):
+            print("Error: --onset_target regress builds the onset head's targets from the MIDI note-on times and needs "
+                  "--train_all_heads --onset_labels midi", file=sys.stderr)
+            return 2
+        if not 2 <= args.onset_width <= 8:
+            print("Error: --onset_width must lie in 2..8 frames", file=sys.stderr)
+            return 2
 
     if args.resume and args.resume_state:
         print("Error: --resume (weights only) and --resume_state (the whole training state) cannot be combined", file=sys.stderr)
@@ -235,7 +251,12 @@ def main():
                                   generator=torch.Generator().manual_seed(args.seed + rank))
             if rank == 0:
                 print(f"Augmentation (training set): pitch +-{augment.pitch_cents} cents, snr_db {augment.snr_db}", flush=True)
-        train_ds = mta.MaestroDataset(args.root_dir, split="train", overlap=overlap, augment=augment, **kw_raw)
+        kw_train = {}
+        if args.onset_target == "regress":             # the training set only: the validation loss keeps the point target
+            kw_train = dict(onset_target="regress", onset_width=args.onset_width)
+            if rank == 0:
+                print(f"Onset target (training set): regression triangles of {args.onset_width} frames", flush=True)
+        train_ds = mta.MaestroDataset(args.root_dir, split="train", overlap=overlap, augment=augment, **kw_raw, **kw_train)
         val_ds = mta.MaestroDataset(args.root_dir, split="validation", overlap=0.0, **kw_raw)
     sampler = DistributedSampler(train_ds, num_replicas=world, rank=rank, shuffle=True, seed=args.seed, drop_last=True) if world > 1 else None
     if use_cache:
