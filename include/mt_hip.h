@@ -576,6 +576,33 @@ int    mt_heads_to_notes_clean(const float* frame_logits, const float* onset_log
 int    mt_notes_batch_clean(const float* frame_logits, const float* onset_logits, float thr_frame, float thr_onset, const long long* lengths,
                             int B, int P, long long T, int* counts, long long* row_off, int* starts, int* ends, long long capacity,
                             int min_frames, int bridge_frames, mt_stream_t stream);
+/* Peak-picked onsets in the decoders (csrc/note_decode.h peak_mask, DESIGN.md 6c "Peak-picked onsets"), for an onset head trained
+ * against the triangular target of mt_onset_regress_targets.  Each call is its _clean namesake -- the same arguments, contract and
+ * cleanup, (min_frames, bridge_frames) = (1, 0) for none -- with another rule for where a note opens.  Per pitch row with valid frames
+ * [0, L) and onset logits x (with chunks, mt_heads_to_notes_peak: the chunks concatenated in time, neighbours across chunk
+ * boundaries), frame t is an onset iff 1 / (1 + exp(-x[t])) > thr_onset (the expression of the other decoders), x[t] > x[u] for every u
+ * of [0, L) in [t - peak_reach, t - 1], and x[t] >= x[u] for every u of [0, L) in [t + 1, t + peak_reach]: a local maximum of the
+ * logits, not of their sigmoids, which saturate into ties.  A plateau gives its first frame, and the onsets of a row are more than
+ * peak_reach frames apart.  Frames outside [0, L) take no part and are never loaded.  The rest is the decoder of the namesake: the
+ * activity is a = f | (sigmoid(x) > thr_onset), a note opens at every onset frame and stays open while a holds, until a drops or the
+ * next onset frame; the offset-gated decoder uses the onset frames where it used the onset mask's rising edges; bridging fills a and
+ * leaves the onset frames alone; short notes are dropped last.  onset_logits == NULL (the frame decoder has no onset head) or
+ * peak_reach outside 1..8: MT_EINVAL, nothing is launched or written.  offset_logits may be NULL (the onset-gated decoder).  What the
+ * rule does to note F1 on MAESTRO has not been measured. */
+int    mt_note_match_counts_peak(const float* frame_logits, const float* onset_logits, const float* offset_logits, float thr_frame,
+                                 float thr_onset, float thr_offset, const float* ref_roll, const long long* lengths,
+                                 unsigned long long* counts, int B, int P, int T, int min_frames, int bridge_frames, int peak_reach,
+                                 mt_stream_t stream);
+int    mt_note_match_list_peak(const float* frame_logits, const float* onset_logits, const float* offset_logits, float thr_frame,
+                               float thr_onset, float thr_offset, const int* ref_on, const int* ref_off, const long long* ref_ptr,
+                               const long long* lengths, unsigned long long* counts, int B, int P, int T, int min_frames, int bridge_frames,
+                               int peak_reach, mt_stream_t stream);
+int    mt_heads_to_notes_peak(const float* frame_logits, const float* onset_logits, const float* offset_logits, float thr_frame,
+                              float thr_onset, float thr_offset, int NB, int P, int T, int* counts, int* starts, int* ends, int capacity,
+                              int min_frames, int bridge_frames, int peak_reach, mt_stream_t stream);
+int    mt_notes_batch_peak(const float* frame_logits, const float* onset_logits, float thr_frame, float thr_onset, const long long* lengths,
+                           int B, int P, long long T, int* counts, long long* row_off, int* starts, int* ends, long long capacity,
+                           int min_frames, int bridge_frames, int peak_reach, mt_stream_t stream);
 /* Sub-frame onsets of decoded notes (csrc/onset_regress.hip, DESIGN.md 6c "Sub-frame onsets"): on_tick[i] (int32, ticks of 100 us) for
  * the n notes [starts[i], ends[i]) of any onset-gated decoder above, cleaned or not.  row_off (int64, rows + 1 entries, rising from 0
  * to n) gives the notes of row r as row_off[r] .. row_off[r + 1] - 1; the kernel finds a note's row by binary search.  chunks == 0:

@@ -55,6 +55,13 @@ def main():
                          "concatenated chunks the frame grid itself drifts 16 ms per chunk: --overlap is where sub-frame times mean something")
     ap.add_argument("--refine-reach", type=int, default=2,
                     help="--refine-onsets: frames the peak search may walk from a note's first frame (0..8; default 2)")
+    ap.add_argument("--onset-detect", choices=["edge", "peak"], default="edge",
+                    help="--decoder onset / onset_offset: where a note opens.  edge (default): at every rising edge of the thresholded "
+                         "onset head; peak: at every local maximum of the onset logits within --peak-reach frames that passes "
+                         "--onset-threshold (a head trained with train_cnn.py --onset_target regress: the edge rule merges a key "
+                         "re-struck within --onset_width frames into one note and stamps notes early)")
+    ap.add_argument("--peak-reach", type=int, default=1,
+                    help="--onset-detect peak: a peak must be the largest logit of this many frames on either side (1..8; default 1)")
     ap.add_argument("--model-type", default="cnn_rnn_large")
     ap.add_argument("--n-mels", type=int, default=320)
     ap.add_argument("--hidden-size", type=int, default=512)
@@ -67,6 +74,9 @@ def main():
         if args.refine_onsets:
             from music_transcription_amd.transcribe import check_refine_decoder
             check_refine_decoder(True, args.decoder, args.refine_reach)
+        if args.onset_detect != "edge" or args.peak_reach != 1:
+            from music_transcription_amd.transcribe import check_detect_decoder
+            check_detect_decoder("peak", args.decoder, args.peak_reach)
     except ValueError as e:
         ap.error(str(e))
     if not os.path.exists(args.audio_file):
@@ -82,6 +92,7 @@ def main():
                                decoder=args.decoder, onset_threshold=args.onset_threshold, overlap=args.overlap,
                                offset_threshold=args.offset_threshold, min_note_frames=min_note_frames, bridge_frames=bridge_frames,
                                smooth_on=smooth_on, smooth_off=smooth_off, refine_onsets=args.refine_onsets, refine_reach=args.refine_reach,
+                               onset_detect=args.onset_detect, peak_reach=args.peak_reach,
                                model_type=args.model_type, n_mels=args.n_mels, hidden_size=args.hidden_size,
                                num_layers=args.num_layers)
         print("=" * 60 + f"\nTranscription completed successfully!\nOutput: {out}\n" + "=" * 60)

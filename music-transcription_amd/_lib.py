@@ -168,6 +168,10 @@ _SIGS = {
     "mt_note_match_list_clean": (i32, [vp, vp, vp, C.c_float, C.c_float, C.c_float, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "mt_heads_to_notes_clean": (i32, [vp, vp, vp, C.c_float, C.c_float, C.c_float, i32, i32, i32, vp, vp, vp, i32, i32, i32, vp]),
     "mt_notes_batch_clean": (i32, [vp, vp, C.c_float, C.c_float, vp, i32, i32, ll, vp, vp, vp, vp, ll, i32, i32, vp]),
+    "mt_note_match_counts_peak": (i32, [vp, vp, vp, C.c_float, C.c_float, C.c_float, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "mt_note_match_list_peak": (i32, [vp, vp, vp, C.c_float, C.c_float, C.c_float, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "mt_heads_to_notes_peak": (i32, [vp, vp, vp, C.c_float, C.c_float, C.c_float, i32, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "mt_notes_batch_peak": (i32, [vp, vp, C.c_float, C.c_float, vp, i32, i32, ll, vp, vp, vp, vp, ll, i32, i32, i32, vp]),
     "mt_frame_smooth": (i32, [vp, vp, C.c_float, C.c_float, C.c_float, vp, i32, i32, ll, vp]),
     "mt_frame_smooth_chunks": (i32, [vp, vp, C.c_float, C.c_float, C.c_float, i32, i32, i32, vp]),
     "mt_frame_smooth_split": (i32, [vp, vp, C.c_float, C.c_float, C.c_float, vp, i32, i32, ll, i32, vp]),

@@ -41,7 +41,8 @@ def transcribe_shard(model, rec_ids: Sequence[int], chunks_of: Callable[[int], t
                      reference_roll_of: Optional[Callable[[int, int], Optional[torch.Tensor]]] = None,
                      midi_path_of: Optional[Callable[[int], Optional[str]]] = None, warm: bool = True, decoder: str = "frame",
                      onset_threshold: float = 0.5, note_metrics: bool = False, min_note_frames: int = 1,
-                     bridge_frames: int = 0, smooth_on: float = 0.0, smooth_off: float = 0.0) -> Dict[str, object]:
+                     bridge_frames: int = 0, smooth_on: float = 0.0, smooth_off: float = 0.0, onset_detect: str = "edge",
+                     peak_reach: int = 1) -> Dict[str, object]:
     """rec_ids: the recordings of this rank; chunks_of(i) -> (n_i, 480000) float32 CUDA tensor (decode + resample + split for
     real audio: part of the measured time; a view of resident synthetic audio otherwise).  Returns {"wall_s", "chunks",
     "notes": {i: [(pitch, start, end)]}, "f1": {i: float}, "n_notes", "finite"}; wall_s covers slab assembly, every forward,
@@ -50,12 +51,17 @@ def transcribe_shard(model, rec_ids: Sequence[int], chunks_of: Callable[[int], t
     {i: (onset F1, onset+offset F1)} against the runs of the reference roll, estimated notes from the same decoder.
     min_note_frames / bridge_frames: note cleanup in the decoder (DESIGN.md 6c "Note cleanup"), for the notes and for note_f1 alike.
     smooth_on / smooth_off: frame smoothing before the decoder (DESIGN.md 6c "Frame smoothing"), over the recording's chunks
-    concatenated in time, for the notes and for note_f1 alike; the framewise "f1" stays the raw threshold's.  (0, 0): none."""
+    concatenated in time, for the notes and for note_f1 alike; the framewise "f1" stays the raw threshold's.  (0, 0): none.
+    onset_detect="peak" (decoder="onset"): notes open at the peaks of the onset logits over peak_reach frames (DESIGN.md 6c "Peak-picked
+    onsets"), for the notes and for note_f1 alike."""
     _check_corpus_decoder(decoder)
     tr.check_decoder(decoder, model=model)
+    tr.check_detect_decoder(onset_detect, decoder, peak_reach)
     clean = dict(zip(("min_note_frames", "bridge_frames"), check_cleanup(min_note_frames, bridge_frames)))
     clean.update(zip(("smooth_on", "smooth_off"), check_smoothing(smooth_on, smooth_off)))
     heads = decoder == "onset"
+    if heads:                                    # (the frame decoder's calls have no onset head and take neither)
+        clean.update(onset_detect=onset_detect, peak_reach=int(peak_reach))
     dev = torch.device(device)
     net = model.model
     fe = get_frontend(SR, n_mels, HOP, str(dev))
@@ -256,7 +262,7 @@ def transcribe_shard_windows(model, rec_ids: Sequence[int], audio_of: Callable[[
                              reference_roll_of: Optional[Callable[[int, int], Optional[torch.Tensor]]] = None,
                              midi_path_of: Optional[Callable[[int], Optional[str]]] = None, note_metrics: bool = False,
                              warm: bool = True, min_note_frames: int = 1, bridge_frames: int = 0, smooth_on: float = 0.0,
-                             smooth_off: float = 0.0) -> Dict[str, object]:
+                             smooth_off: float = 0.0, onset_detect: str = "edge", peak_reach: int = 1) -> Dict[str, object]:
     """transcribe_shard on the window grid.  audio_of(i) -> recording i as 1-D float32 at 16 kHz on the device, any length (0 samples
     included).  Recordings are taken in rec_ids order into groups (plan_groups; group_windows defaults to batch * streams).  A group
     runs exactly the slabs of windows.transcribe_windows(model, [its recordings], overlap_s, batch, all_heads) into zero-filled
@@ -267,13 +273,16 @@ def transcribe_shard_windows(model, rec_ids: Sequence[int], audio_of: Callable[[
     roll on the recording's frame grid or None; scored over min(frames, reference frames).  Returns transcribe_shard's keys with
     "windows" for "chunks", and "groups" (lists of recording ids) and "frames" {i: 1 + n_i // 512}.  min_note_frames /
     bridge_frames as in transcribe_shard; smooth_on / smooth_off too, here over each recording's own frames (the lengths the decoder
-    and the matcher are given)."""
+    and the matcher are given); onset_detect / peak_reach as in transcribe_shard too (mt_notes_batch_peak for the notes)."""
     _check_corpus_decoder(decoder)
     tr.check_decoder(decoder, model=model)
+    tr.check_detect_decoder(onset_detect, decoder, peak_reach)
     clean = dict(zip(("min_note_frames", "bridge_frames"), check_cleanup(min_note_frames, bridge_frames)))
     clean.update(zip(("smooth_on", "smooth_off"), check_smoothing(smooth_on, smooth_off)))
     W.overlap_frames(overlap_s)
     heads = decoder == "onset"
+    if heads:                                    # (the frame decoder's calls have no onset head and take neither)
+        clean.update(onset_detect=onset_detect, peak_reach=int(peak_reach))
     dev = torch.device(device)
     net, n_mels, fe = W._window_setup(model, n_mels, heads, dev)
     from .model import CNNRNNModelLarge

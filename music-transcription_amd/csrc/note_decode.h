@@ -13,6 +13,9 @@
 // Onset-gated decoder (the Onsets-and-Frames rule): a = frame-active OR onset-active; a note opens at every rising edge of
 // the onset mask, stays open while a holds, and closes at the first frame where a drops or the next onset edge starts a new
 // note (a re-struck key).  With onset := frame this is the plain run-length decoder of mt_roll_to_notes.
+// PEAK (the mt_*_peak entry points; DESIGN.md 6c "Peak-picked onsets"): the frames where a note opens are not the onset mask's rising
+// edges but the local maxima of the onset logits above the threshold (peak_mask); everything else is the same decoder.  The test
+// runs inside the cleanup pipeline, which holds every window back by one and so has both neighbour windows in registers.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -31,9 +34,12 @@ struct WindowEvents {
     unsigned long long starts, closes;
 };
 
-__device__ __forceinline__ WindowEvents decode_window(bool o, bool a, int lane, unsigned long long& o_prev, unsigned long long& open_prev) {
-    const unsigned long long om = __ballot(o), am = __ballot(a);
-    const unsigned long long st = om & ~((om << 1) | o_prev);
+// PEAK: the starts are given (pk, a subset of the onset mask: the window's peaks); o and o_prev are not read.
+template <bool PEAK = false>
+__device__ __forceinline__ WindowEvents decode_window(bool o, bool a, int lane, unsigned long long& o_prev, unsigned long long& open_prev,
+                                                      unsigned long long pk = 0ull) {
+    const unsigned long long om = PEAK ? 0ull : __ballot(o), am = __ballot(a);
+    const unsigned long long st = PEAK ? pk : om & ~((om << 1) | o_prev);
     // open at lane l  <=>  a holds on every frame from the last start of this a-run up to l (or from before the window)
     const unsigned long long upto = (2ull << lane) - 1ull;                 // bits 0..lane (all ones at lane 63)
     const unsigned long long gaps = ~am & upto;
@@ -44,7 +50,7 @@ __device__ __forceinline__ WindowEvents decode_window(bool o, bool a, int lane, 
     WindowEvents ev;
     ev.starts = st;
     ev.closes = ((opm << 1) | open_prev) & (~am | st);
-    o_prev = om >> 63;
+    if constexpr (!PEAK) o_prev = om >> 63;
     open_prev = opm >> 63;
     return ev;
 }
@@ -53,18 +59,19 @@ __device__ __forceinline__ WindowEvents decode_window(bool o, bool a, int lane, 
 // activity, e = its rising edge.  An edge at frame t makes t the note's last frame: open[t] = st[t] | (open[t-1] & a[t] & !e[t-1]).
 // Only edges cut (an offset still smeared over the next note's start does not), and only onset edges open a note (the rest of
 // a frame run after a cut opens nothing).  With kill = e shifted by one frame and a' = (a & ~kill) | st this is decode_window
-// on a'.  Two more carries: k_prev / e_prev = k / e of frame g0 - 1.
+// on a'.  Two more carries: k_prev / e_prev = k / e of frame g0 - 1.  PEAK: st = pk, as in decode_window.
+template <bool PEAK = false>
 __device__ __forceinline__ WindowEvents decode_window_off(bool o, bool a, bool k, int lane, unsigned long long& o_prev,
                                                           unsigned long long& open_prev, unsigned long long& k_prev,
-                                                          unsigned long long& e_prev) {
-    const unsigned long long om = __ballot(o), km = __ballot(k);
-    const unsigned long long st = om & ~((om << 1) | o_prev);
+                                                          unsigned long long& e_prev, unsigned long long pk = 0ull) {
+    const unsigned long long om = PEAK ? 0ull : __ballot(o), km = __ballot(k);
+    const unsigned long long st = PEAK ? pk : om & ~((om << 1) | o_prev);
     const unsigned long long em = km & ~((km << 1) | k_prev);
     const unsigned long long kill = (em << 1) | e_prev;
     const bool a2 = (a && !(kill >> lane & 1ull)) || (st >> lane & 1ull);
     k_prev = km >> 63;
     e_prev = em >> 63;
-    return decode_window(o, a2, lane, o_prev, open_prev);
+    return decode_window<PEAK>(o, a2, lane, o_prev, open_prev, pk);
 }
 
 // The decoder's state between windows: o / open (and, offset-gated, k / e) of the frame before the window.
@@ -99,19 +106,48 @@ struct CarryClean : std::conditional_t<OFF, CarryOffset, CarryOnset> {
     WindowEvents held = {0ull, 0ull};
     unsigned long long dropped_open = 0;
 };
-template <bool OFF, bool CLEAN = false>
-using DecodeCarry = std::conditional_t<CLEAN, CarryClean<OFF>, std::conditional_t<OFF, CarryOffset, CarryOnset>>;
+// Peak picking on top of the cleanup pipeline.  Per lane (the only carries that are not wave-uniform): the onset logit of this lane's
+// frame in the window the pipeline holds (xo) and in the one before it (xp); -inf stands for a frame outside the row, before frame 0
+// included, so a comparison with it holds for every logit that can pass the threshold.
+constexpr int PEAK_MAX_REACH = 8;
+template <bool OFF>
+struct CarryPeak : CarryClean<OFF> {
+    float xo = -__builtin_inff(), xp = -__builtin_inff();
+};
+template <bool OFF, bool CLEAN = false, bool PEAK = false>
+using DecodeCarry =
+    std::conditional_t<PEAK, CarryPeak<OFF>, std::conditional_t<CLEAN, CarryClean<OFF>, std::conditional_t<OFF, CarryOffset, CarryOnset>>>;
 
 struct NoteThr { float frame, onset, offset; };   // thresholds of the three heads (offset: read by the offset-gated decoder only)
+
+// The peaks of the held window: bit l = frame t = g0 + l is onset-active (om) and its logit x[t] is > x[u] for every frame u of the row
+// in [t - reach, t - 1] and >= x[u] for every u in [t + 1, t + reach] -- a plateau gives its first frame, and two peaks are more than
+// `reach` frames apart.  xc / xb / xn = this lane's logit in the window, the one before and the one after it (-inf outside the row).
+// Neighbour d below lane l is lane l - d of this window or, for l < d, lane 64 + l - d of the one before: one select and one
+// cross-lane move per neighbour, since the lanes that read the other window (>= 64 - d) are never read for this one; the same above.
+__device__ __forceinline__ unsigned long long peak_mask(unsigned long long om, float xc, float xb, float xn, int reach, int lane) {
+    bool pk = om >> lane & 1ull;
+#pragma unroll 1
+    for (int d = 1; d <= reach; ++d) {
+        const float lo = __shfl(lane >= 64 - d ? xb : xc, (lane - d) & 63, 64);
+        const float hi = __shfl(lane < d ? xn : xc, (lane + d) & 63, 64);
+        pk = pk && xc > lo && xc >= hi;
+    }
+    return __ballot(pk);
+}
 
 // One call of the cleanup pipeline: the masks am / om / km of window w arrive (a = f | o, onset, offset activity; inactive outside
 // the row), window w - 1 is bridged and decoded, and the cleaned events of window w - 2 are returned.  Neither stage changes what
 // the matchers of notes.hip rest on: bridging adds no onset edge (the onset mask is untouched; the frame decoder's edges of f' are
 // a subset of those of f) and dropping removes notes whole, so onsets of one pitch stay >= 2 frames apart and a note has ended
 // when the next one starts.
-template <bool OFF>
+// PEAK: xo_n = this lane's onset logit of window w (-inf outside the row) arrives as well, and window w - 1 opens its notes at its
+// peaks (peak_mask over `reach` frames, its neighbours the windows w - 2 and w) instead of at the onset mask's rising edges.  A peak
+// is onset-active, peaks are >= 2 frames apart and bridging does not touch them, so the matchers' premises hold as before.
+template <bool OFF, bool PEAK = false>
 __device__ __forceinline__ WindowEvents clean_step(unsigned long long am_n, unsigned long long om_n, unsigned long long km_n, bool has_onset,
-                                                   const NoteClean& cl, int lane, CarryClean<OFF>& c) {
+                                                   const NoteClean& cl, int lane, DecodeCarry<OFF, true, PEAK>& c, float xo_n = 0.0f,
+                                                   int reach = 1) {
     const unsigned long long below = (1ull << lane) - 1ull, above = ~((2ull << lane) - 1ull);      // bits under / over this lane
     // bridge: this lane's inactive run is next - prev - 1 frames long, prev / next = the active frames around it
     const unsigned long long am = c.am, ab = am & below, aa = am & above;
@@ -122,8 +158,14 @@ __device__ __forceinline__ WindowEvents clean_step(unsigned long long am_n, unsi
     // decode the bridged window; without an onset head o := f'
     const bool a = af >> lane & 1ull, o = has_onset ? (c.om >> lane & 1ull) : a;
     WindowEvents ev;
-    if constexpr (OFF) ev = decode_window_off(o, a, c.km >> lane & 1ull, lane, c.o_prev, c.open_prev, c.k_prev, c.e_prev);
-    else ev = decode_window(o, a, lane, c.o_prev, c.open_prev);
+    unsigned long long pk = 0ull;
+    if constexpr (PEAK) {
+        pk = peak_mask(c.om, c.xo, c.xp, xo_n, reach, lane);
+        c.xp = c.xo;
+        c.xo = xo_n;
+    }
+    if constexpr (OFF) ev = decode_window_off<PEAK>(o, a, c.km >> lane & 1ull, lane, c.o_prev, c.open_prev, c.k_prev, c.e_prev, pk);
+    else ev = decode_window<PEAK>(o, a, lane, c.o_prev, c.open_prev, pk);
     c.am = am_n;
     c.om = om_n;
     c.km = km_n;
@@ -147,16 +189,21 @@ __device__ __forceinline__ WindowEvents clean_step(unsigned long long am_n, unsi
 // One window of a decoder.  x = the window's logits of this lane's frame, x[0] frame, x[1] onset, x[2] offset (OFF only); `in` = the
 // frame is inside the row.  Without an onset head (the frame decoder) onset := frame.  CLEAN: the same window through the cleanup
 // pipeline, so the events are those of the window decode_delay<CLEAN> frames back and flush_clean feeds the windows that bring the
-// last ones out; otherwise cl is not read.
-template <bool OFF, bool CLEAN, int NCH>
+// last ones out; otherwise cl is not read.  PEAK (with CLEAN and an onset head only): notes open at the peaks of the onset logits
+// within `reach` frames; otherwise reach is not read.
+template <bool OFF, bool CLEAN, bool PEAK = false, int NCH>
 __device__ __forceinline__ WindowEvents decode_step(bool in, const float (&x)[NCH], bool has_onset, const NoteThr& thr, const NoteClean& cl,
-                                                    int lane, DecodeCarry<OFF, CLEAN>& c) {
+                                                    int lane, DecodeCarry<OFF, CLEAN, PEAK>& c, int reach = 1) {
     static_assert(NCH >= (OFF ? 3 : 2), "frame, onset (and offset) logits");
+    static_assert(CLEAN || !PEAK, "peak picking lives in the cleanup pipeline, whose held window has both neighbours");
     const bool f = in && logit_active(x[0], thr.frame);
     const bool o = has_onset ? (in && logit_active(x[1], thr.onset)) : f;
     bool k = false;
     if constexpr (OFF) k = in && logit_active(x[2], thr.offset);
-    if constexpr (CLEAN) return clean_step<OFF>(__ballot(f || o), __ballot(o), OFF ? __ballot(k) : 0ull, has_onset, cl, lane, c);
+    if constexpr (PEAK)
+        return clean_step<OFF, true>(__ballot(f || o), __ballot(o), OFF ? __ballot(k) : 0ull, true, cl, lane, c, in ? x[1] : -__builtin_inff(),
+                                     reach);
+    else if constexpr (CLEAN) return clean_step<OFF>(__ballot(f || o), __ballot(o), OFF ? __ballot(k) : 0ull, has_onset, cl, lane, c);
     else if constexpr (OFF) return decode_window_off(o, f || o, k, lane, c.o_prev, c.open_prev, c.k_prev, c.e_prev);
     else return decode_window(o, f || o, lane, c.o_prev, c.open_prev);
 }

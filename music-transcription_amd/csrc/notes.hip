@@ -172,13 +172,15 @@ __device__ __forceinline__ void counts_add(unsigned long long* c, int n_ref, int
 
 // counts[b] += {n_ref, n_est, tp_onset, tp_onset_offset} of pitch row (b, p).  Frames at or past lengths[b] are inactive on both sides.
 // OFF: the offset-gated decoder with the offset head `offset` at thr_k; otherwise neither is read.  CLEAN: note cleanup by cl (DESIGN.md
-// 6c "Note cleanup"); otherwise cl is not read.  This holds for every decoding kernel of this file.
-template <bool OFF, bool CLEAN>
+// 6c "Note cleanup"); otherwise cl is not read.  PEAK (with CLEAN and an onset head; the mt_*_peak entry points): notes open at the
+// peaks of the onset logits within `reach` frames (DESIGN.md 6c "Peak-picked onsets"); otherwise reach is not read.  This holds for
+// every decoding kernel of this file.
+template <bool OFF, bool CLEAN, bool PEAK = false>
 __global__ __launch_bounds__(64 * NOTE_WAVES) void note_match_kernel(const float* __restrict__ frame, const float* __restrict__ onset,
                                                                      const float* __restrict__ offset, float thr_f, float thr_o, float thr_k,
                                                                      NoteClean cl, const float* __restrict__ ref,
                                                                      const long long* __restrict__ lengths,
-                                                                     unsigned long long* __restrict__ counts, int B, int P, int T) {
+                                                                     unsigned long long* __restrict__ counts, int B, int P, int T, int reach) {
     const int row = blockIdx.x * NOTE_WAVES + wave_in_block<CLEAN>();
     const int lane = threadIdx.x & 63;
     if (row >= B * P) return;
@@ -190,11 +192,11 @@ __global__ __launch_bounds__(64 * NOTE_WAVES) void note_match_kernel(const float
     MatchState s;
     match_init(s);
     const NoteThr thr{thr_f, thr_o, thr_k};
-    DecodeCarry<OFF, CLEAN> c;
+    DecodeCarry<OFF, CLEAN, PEAK> c;
     unsigned long long r_prev = 0, rs[HOLD + 1] = {}, re[HOLD + 1] = {};      // run edges of the reference, [0] = HOLD windows back
     // one window, for either walk: x = frame, onset, (offset,) roll of this lane's frame
     const auto window = [&](int g0, bool in, const float(&x)[NCH]) __attribute__((always_inline)) {
-        const WindowEvents est = decode_step<OFF, CLEAN>(in, x, onset != nullptr, thr, cl, lane, c);
+        const WindowEvents est = decode_step<OFF, CLEAN, PEAK>(in, x, onset != nullptr, thr, cl, lane, c, reach);
         const unsigned long long rm = __ballot(in && x[ROLL] > 0.0f);
         rs[HOLD] = rm & ~((rm << 1) | r_prev);
         re[HOLD] = ~rm & ((rm << 1) | r_prev);
@@ -376,14 +378,15 @@ __device__ __forceinline__ void list_finish(ListState& s, RefCursor& r, bool est
 
 // counts[b] += {n_ref, n_est, tp_onset, tp_onset_offset} of pitch row (b, p) against the notes ref_on/ref_off[ref_ptr[row] .. ref_ptr[row+1]).
 // Frames at or past L = lengths[b] are inactive; reference notes with on >= 320 L are not read and offsets are clipped to 320 L.
-// OFF, CLEAN as in note_match_kernel; the cursor follows the delayed events by itself.
-template <bool OFF, bool CLEAN>
+// OFF, CLEAN, PEAK as in note_match_kernel; the cursor follows the delayed events by itself.
+template <bool OFF, bool CLEAN, bool PEAK = false>
 __global__ __launch_bounds__(64 * NOTE_WAVES) void note_match_list_kernel(const float* __restrict__ frame, const float* __restrict__ onset,
                                                                           const float* __restrict__ offset, float thr_f, float thr_o, float thr_k,
                                                                           NoteClean cl, const int* __restrict__ ref_on,
                                                                           const int* __restrict__ ref_off, const long long* __restrict__ ref_ptr,
                                                                           const long long* __restrict__ lengths,
-                                                                          unsigned long long* __restrict__ counts, int B, int P, int T) {
+                                                                          unsigned long long* __restrict__ counts, int B, int P, int T,
+                                                                          int reach) {
     const int row = blockIdx.x * NOTE_WAVES + wave_in_block<true>();
     const int lane = threadIdx.x & 63;
     if (row >= B * P) return;
@@ -397,9 +400,10 @@ __global__ __launch_bounds__(64 * NOTE_WAVES) void note_match_list_kernel(const 
     ListState s;
     list_init(s);
     const NoteThr thr{thr_f, thr_o, thr_k};
-    DecodeCarry<OFF, CLEAN> c;
+    DecodeCarry<OFF, CLEAN, PEAK> c;
     const auto window = [&](int g0, bool in, const float(&x)[NCH]) __attribute__((always_inline)) {
-        list_window(s, r, decode_step<OFF, CLEAN>(in, x, onset != nullptr, thr, cl, lane, c), g0 - decode_delay<CLEAN>, lane, end_tick);
+        list_window(s, r, decode_step<OFF, CLEAN, PEAK>(in, x, onset != nullptr, thr, cl, lane, c, reach), g0 - decode_delay<CLEAN>, lane,
+                    end_tick);
     };
     walk_slabs<NOTE_SLAB, NCH>(
         L, lane,
@@ -418,13 +422,14 @@ __global__ __launch_bounds__(64 * NOTE_WAVES) void note_match_list_kernel(const 
 // The NB chunks of frame / onset [NB][P][T] are one recording of NB*T frames per pitch (as mt_roll_to_notes).  fill == 0: counts[p] =
 // notes of pitch p.  fill == 1: note k of pitch p goes to [sum of the lower pitches' counts + k], nothing when that exceeds capacity.
 // OFF: the offset-gated decoder; its carries cross chunk boundaries with the onset carry (the walk is over the concatenated frames).
-// CLEAN as in note_match_kernel.  The cleaning instances alone take onset == nullptr (the frame decoder: mt_roll_to_notes' notes,
+// CLEAN, PEAK as in note_match_kernel; a peak's neighbours cross chunk boundaries with the walk.  The cleaning instances alone take onset == nullptr (the frame decoder: mt_roll_to_notes' notes,
 // cleaned) and skip a pitch without notes in the fill pass; the host refuses a null onset head for the others.
-template <bool OFF, bool CLEAN>
+template <bool OFF, bool CLEAN, bool PEAK = false>
 __global__ __launch_bounds__(64 * NOTE_WAVES) void heads_notes_kernel(const float* __restrict__ frame, const float* __restrict__ onset,
                                                                       const float* __restrict__ offset, float thr_f, float thr_o, float thr_k,
                                                                       NoteClean cl, int NB, int P, int T, int fill, int* __restrict__ counts,
-                                                                      int* __restrict__ starts, int* __restrict__ ends, int capacity) {
+                                                                      int* __restrict__ starts, int* __restrict__ ends, int capacity,
+                                                                      int reach) {
     const int p = blockIdx.x * NOTE_WAVES + wave_in_block<CLEAN>();
     const int lane = threadIdx.x & 63;
     if (p >= P) return;
@@ -439,10 +444,10 @@ __global__ __launch_bounds__(64 * NOTE_WAVES) void heads_notes_kernel(const floa
     const bool has_onset = !CLEAN || onset != nullptr;
     int n_on = 0, n_off = 0;
     const NoteThr thr{thr_f, thr_o, thr_k};
-    DecodeCarry<OFF, CLEAN> c;
+    DecodeCarry<OFF, CLEAN, PEAK> c;
     const auto window = [&](int g0, bool in, const float(&x)[NCH]) __attribute__((always_inline)) {
-        emit_window(decode_step<OFF, CLEAN>(in, x, has_onset, thr, cl, lane, c), g0 - decode_delay<CLEAN>, lane, fill != 0, starts + out,
-                    ends + out, n_on, n_off);
+        emit_window(decode_step<OFF, CLEAN, PEAK>(in, x, has_onset, thr, cl, lane, c, reach), g0 - decode_delay<CLEAN>, lane, fill != 0,
+                    starts + out, ends + out, n_on, n_off);
     };
     walk_slabs<NOTE_SLAB, NCH>(
         n, lane,
@@ -873,12 +878,24 @@ static bool thrs_ok(const NoteThr& thr, bool onset, bool off) {
 }
 
 // The instance of a decoding kernel template <OFF, CLEAN> that serves an entry point.
-#define NOTE_INSTANCE(kernel, off, clean) \
-    ((clean) ? ((off) ? kernel<true, true> : kernel<false, true>) : ((off) ? kernel<true, false> : kernel<false, false>))
+#define NOTE_INSTANCE(kernel, off, clean, peak)                                       \
+    ((peak)    ? ((off) ? kernel<true, true, true> : kernel<false, true, true>)       \
+     : (clean) ? ((off) ? kernel<true, true> : kernel<false, true>)                   \
+               : ((off) ? kernel<true, false> : kernel<false, false>))
+
+// The host's check of a _peak entry point: peak picking reads the onset head, over 1 .. PEAK_MAX_REACH frames.  reach 0 = an entry
+// point without it (the rising edges of the onset mask).
+#define MT_REQUIRE_PEAK(reach, peak, onset, who)                                                                                        \
+    MT_REQUIRE(!(peak) || ((onset) && (reach) >= 1 && (reach) <= mt::PEAK_MAX_REACH), MT_EINVAL,                                          \
+               "%s: needs onset_logits (the frame decoder has no onset head to pick peaks from) and 1 <= peak_reach <= %d", who,       \
+               mt::PEAK_MAX_REACH)
 
 // cl: the cleaning instances (the _clean entry points, whatever the two values); null: the instances without the stage.
+// peak: the peak-picking instances (the _peak entry points, which clean as well), over `reach` frames.
 static int note_match(const char* who, bool off, const float* frame, const float* onset, const float* offset, NoteThr thr, const float* ref,
-                      const long long* lengths, unsigned long long* counts, int B, int P, int T, mt_stream_t stream, const NoteClean* cl = nullptr) {
+                      const long long* lengths, unsigned long long* counts, int B, int P, int T, mt_stream_t stream, const NoteClean* cl = nullptr,
+                      bool peak = false, int reach = 0) {
+    MT_REQUIRE_PEAK(reach, peak, onset, who);
     MT_REQUIRE(frame && ref && counts && (!off || (onset && offset)), MT_EINVAL, "%s: null pointer", who);
     MT_REQUIRE_CLEAN(cl, who);
     MT_REQUIRE(B > 0 && P > 0 && T > 0 && (long long)B * P < 2147483647ll && T < (1 << 30), MT_EINVAL, "%s: bad dims", who);
@@ -886,16 +903,17 @@ static int note_match(const char* who, bool off, const float* frame, const float
     hipStream_t st = (hipStream_t)stream;
     MT_CHECK_HIP(hipMemsetAsync(counts, 0, (size_t)B * 4 * sizeof(unsigned long long), st));
     const dim3 grid((B * P + NOTE_WAVES - 1) / NOTE_WAVES), block(64 * NOTE_WAVES);
-    const auto kernel = NOTE_INSTANCE(note_match_kernel, off, cl != nullptr);
+    const auto kernel = NOTE_INSTANCE(note_match_kernel, off, cl != nullptr, peak);
     hipLaunchKernelGGL(kernel, grid, block, 0, st, frame, onset, offset, thr.frame, thr.onset, thr.offset,
-                       cl ? *cl : NoteClean{}, ref, lengths, counts, B, P, T);
+                       cl ? *cl : NoteClean{}, ref, lengths, counts, B, P, T, reach);
     MT_CHECK_LAUNCH();
     return MT_OK;
 }
 
 static int note_match_list(const char* who, bool off, const float* frame, const float* onset, const float* offset, NoteThr thr, const int* ref_on,
                            const int* ref_off, const long long* ref_ptr, const long long* lengths, unsigned long long* counts, int B, int P, int T,
-                           mt_stream_t stream, const NoteClean* cl = nullptr) {
+                           mt_stream_t stream, const NoteClean* cl = nullptr, bool peak = false, int reach = 0) {
+    MT_REQUIRE_PEAK(reach, peak, onset, who);
     MT_REQUIRE(frame && ref_on && ref_off && ref_ptr && counts && (!off || (onset && offset)), MT_EINVAL, "%s: null pointer", who);
     MT_REQUIRE_CLEAN(cl, who);
     MT_REQUIRE(B > 0 && P > 0 && T > 0 && (long long)B * P < 2147483647ll && (long long)T * TICKS_PER_FRAME < 2147483647ll - 64 * NOTE_SLAB,
@@ -904,25 +922,27 @@ static int note_match_list(const char* who, bool off, const float* frame, const 
     hipStream_t st = (hipStream_t)stream;
     MT_CHECK_HIP(hipMemsetAsync(counts, 0, (size_t)B * 4 * sizeof(unsigned long long), st));
     const dim3 grid((B * P + NOTE_WAVES - 1) / NOTE_WAVES), block(64 * NOTE_WAVES);
-    const auto kernel = NOTE_INSTANCE(note_match_list_kernel, off, cl != nullptr);
+    const auto kernel = NOTE_INSTANCE(note_match_list_kernel, off, cl != nullptr, peak);
     hipLaunchKernelGGL(kernel, grid, block, 0, st, frame, onset, offset, thr.frame, thr.onset, thr.offset,
-                       cl ? *cl : NoteClean{}, ref_on, ref_off, ref_ptr, lengths, counts, B, P, T);
+                       cl ? *cl : NoteClean{}, ref_on, ref_off, ref_ptr, lengths, counts, B, P, T, reach);
     MT_CHECK_LAUNCH();
     return MT_OK;
 }
 
 static int heads_notes(const char* who, bool off, const float* frame, const float* onset, const float* offset, NoteThr thr, int NB, int P, int T,
-                       int* counts, int* starts, int* ends, int capacity, mt_stream_t stream, const NoteClean* cl = nullptr) {
+                       int* counts, int* starts, int* ends, int capacity, mt_stream_t stream, const NoteClean* cl = nullptr, bool peak = false,
+                       int reach = 0) {
+    MT_REQUIRE_PEAK(reach, peak, onset, who);
     // (the cleaning instances alone decode without an onset head: the frame decoder)
     MT_REQUIRE(frame && (onset || (cl && !off)) && (!off || offset) && counts && starts && ends && capacity > 0, MT_EINVAL, "%s: bad arguments", who);
     MT_REQUIRE(NB > 0 && P > 0 && T > 0 && (long long)NB * T < 2147483647ll - 64 * NOTE_SLAB, MT_EINVAL, "%s: bad dims", who);
     MT_REQUIRE(thrs_ok(thr, onset != nullptr, off), MT_EINVAL, "%s: thresholds must lie in (0, 1)", who);
     MT_REQUIRE_CLEAN(cl, who);
     const dim3 grid((P + NOTE_WAVES - 1) / NOTE_WAVES), block(64 * NOTE_WAVES);
-    const auto kernel = NOTE_INSTANCE(heads_notes_kernel, off, cl != nullptr);
+    const auto kernel = NOTE_INSTANCE(heads_notes_kernel, off, cl != nullptr, peak);
     for (int fill = 0; fill < 2; ++fill) {                     // count, then write
         hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)stream, frame, onset, offset, thr.frame,
-                           thr.onset, thr.offset, cl ? *cl : NoteClean{}, NB, P, T, fill, counts, starts, ends, capacity);
+                           thr.onset, thr.offset, cl ? *cl : NoteClean{}, NB, P, T, fill, counts, starts, ends, capacity, reach);
         MT_CHECK_LAUNCH();
     }
     return MT_OK;
@@ -1148,4 +1168,34 @@ extern "C" int mt_heads_to_notes_clean(const float* frame_logits, const float* o
     const NoteClean cl{min_frames, bridge_frames};
     return heads_notes("mt_heads_to_notes_clean", offset_logits != nullptr, frame_logits, onset_logits, offset_logits,
                        {thr_frame, thr_onset, offset_logits ? thr_offset : 0.5f}, NB, P, T, counts, starts, ends, capacity, stream, &cl);
+}
+
+// The three with peak-picked onsets (DESIGN.md 6c "Peak-picked onsets"): their _clean namesakes, (1, 0) = no cleanup, except that a
+// note opens at every local maximum of the onset logits over peak_reach frames that passes thr_onset.  onset_logits is required.
+extern "C" int mt_note_match_counts_peak(const float* frame_logits, const float* onset_logits, const float* offset_logits, float thr_frame,
+                                         float thr_onset, float thr_offset, const float* ref_roll, const long long* lengths,
+                                         unsigned long long* counts, int B, int P, int T, int min_frames, int bridge_frames, int peak_reach,
+                                         mt_stream_t stream) {
+    const NoteClean cl{min_frames, bridge_frames};
+    return note_match("mt_note_match_counts_peak", offset_logits != nullptr, frame_logits, onset_logits, offset_logits,
+                      {thr_frame, thr_onset, offset_logits ? thr_offset : 0.5f}, ref_roll, lengths, counts, B, P, T, stream, &cl, true, peak_reach);
+}
+
+extern "C" int mt_note_match_list_peak(const float* frame_logits, const float* onset_logits, const float* offset_logits, float thr_frame,
+                                       float thr_onset, float thr_offset, const int* ref_on, const int* ref_off, const long long* ref_ptr,
+                                       const long long* lengths, unsigned long long* counts, int B, int P, int T, int min_frames,
+                                       int bridge_frames, int peak_reach, mt_stream_t stream) {
+    const NoteClean cl{min_frames, bridge_frames};
+    return note_match_list("mt_note_match_list_peak", offset_logits != nullptr, frame_logits, onset_logits, offset_logits,
+                           {thr_frame, thr_onset, offset_logits ? thr_offset : 0.5f}, ref_on, ref_off, ref_ptr, lengths, counts, B, P, T, stream, &cl,
+                           true, peak_reach);
+}
+
+extern "C" int mt_heads_to_notes_peak(const float* frame_logits, const float* onset_logits, const float* offset_logits, float thr_frame,
+                                      float thr_onset, float thr_offset, int NB, int P, int T, int* counts, int* starts, int* ends, int capacity,
+                                      int min_frames, int bridge_frames, int peak_reach, mt_stream_t stream) {
+    const NoteClean cl{min_frames, bridge_frames};
+    return heads_notes("mt_heads_to_notes_peak", offset_logits != nullptr, frame_logits, onset_logits, offset_logits,
+                       {thr_frame, thr_onset, offset_logits ? thr_offset : 0.5f}, NB, P, T, counts, starts, ends, capacity, stream, &cl, true,
+                       peak_reach);
 }

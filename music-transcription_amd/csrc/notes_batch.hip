@@ -17,13 +17,15 @@ constexpr int PREFIX_THREADS = 256;
 // FILL = false: counts[row] = notes of the row.  FILL = true: note k of the row goes to [row_off[row] + k]; a row without notes, or one
 // whose notes would end past `capacity`, is left alone (the host sees row_off[rows] > capacity and retries with larger buffers).
 // CLEAN: note cleanup by cl -- a window's events arrive decode_delay frames late and the flush closes a note open at L; otherwise
-// cl is not read.
-template <bool FILL, bool CLEAN>
+// cl is not read.  PEAK (with CLEAN and an onset head; mt_notes_batch_peak): notes open at the peaks of the onset logits within
+// `reach` frames (DESIGN.md 6c "Peak-picked onsets"); otherwise reach is not read.
+template <bool FILL, bool CLEAN, bool PEAK = false>
 __global__ __launch_bounds__(64 * BATCH_WAVES) void notes_batch_kernel(const float* __restrict__ frame, const float* __restrict__ onset,
                                                                        float thr_f, float thr_o, NoteClean cl,
                                                                        const long long* __restrict__ lengths, long long rows, int P, long long T,
                                                                        int* __restrict__ counts, const long long* __restrict__ row_off,
-                                                                       int* __restrict__ starts, int* __restrict__ ends, long long capacity) {
+                                                                       int* __restrict__ starts, int* __restrict__ ends, long long capacity,
+                                                                       int reach) {
     const long long row = (long long)blockIdx.x * BATCH_WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // wave-uniform
     const int lane = threadIdx.x & 63;
     if (row >= rows) return;
@@ -39,10 +41,10 @@ __global__ __launch_bounds__(64 * BATCH_WAVES) void notes_batch_kernel(const flo
     const float* __restrict__ xo_row = onset ? onset + (size_t)row * (size_t)T : nullptr;
     const NoteThr thr{thr_f, thr_o, 0.5f};
     int n_on = 0, n_off = 0;
-    DecodeCarry<false, CLEAN> c;
+    DecodeCarry<false, CLEAN, PEAK> c;
     const auto window = [&](long long g0, bool in, const float(&x)[2]) __attribute__((always_inline)) {
-        emit_window(decode_step<false, CLEAN>(in, x, xo_row != nullptr, thr, cl, lane, c), g0 - decode_delay<CLEAN>, lane, FILL, starts + out,
-                    ends + out, n_on, n_off);
+        emit_window(decode_step<false, CLEAN, PEAK>(in, x, xo_row != nullptr, thr, cl, lane, c, reach), g0 - decode_delay<CLEAN>, lane, FILL,
+                    starts + out, ends + out, n_on, n_off);
     };
     walk_slabs<BATCH_SLAB, 2>(
         L, lane, [&](int ch, long long g) __attribute__((always_inline)) { return ch == 0 ? xf_row[g] : xo_row ? xo_row[g] : 0.0f; }, window);
@@ -78,9 +80,12 @@ __global__ __launch_bounds__(PREFIX_THREADS) void notes_batch_prefix_kernel(cons
 using namespace mt;
 
 // cl: the cleaning instances (mt_notes_batch_clean, whatever the two values); null: the instances without the stage.
+// peak: the peak-picking instances (mt_notes_batch_peak, which cleans as well), over `reach` frames.
 static int notes_batch(const char* who, const float* frame_logits, const float* onset_logits, float thr_frame, float thr_onset,
                        const long long* lengths, int B, int P, long long T, int* counts, long long* row_off, int* starts, int* ends,
-                       long long capacity, mt_stream_t stream, const NoteClean* cl) {
+                       long long capacity, mt_stream_t stream, const NoteClean* cl, bool peak = false, int reach = 0) {
+    MT_REQUIRE(!peak || (onset_logits && reach >= 1 && reach <= PEAK_MAX_REACH), MT_EINVAL,
+               "%s: needs onset_logits (the frame decoder has no onset head to pick peaks from) and 1 <= peak_reach <= %d", who, PEAK_MAX_REACH);
     MT_REQUIRE(frame_logits && counts && row_off && capacity >= 0 && ((starts && ends) || capacity == 0), MT_EINVAL,
                "%s: null pointer or negative capacity", who);
     MT_REQUIRE(B > 0 && P > 0 && T > 0 && (long long)B * P < 2147483647ll - BATCH_WAVES && T < 2147483647ll, MT_EINVAL,
@@ -91,17 +96,17 @@ static int notes_batch(const char* who, const float* frame_logits, const float* 
     hipStream_t st = (hipStream_t)stream;
     const long long rows = (long long)B * P;
     const dim3 grid((unsigned)((rows + BATCH_WAVES - 1) / BATCH_WAVES)), block(64 * BATCH_WAVES);
-    const auto count = cl ? notes_batch_kernel<false, true> : notes_batch_kernel<false, false>;
-    const auto fill = cl ? notes_batch_kernel<true, true> : notes_batch_kernel<true, false>;
+    const auto count = peak ? notes_batch_kernel<false, true, true> : cl ? notes_batch_kernel<false, true> : notes_batch_kernel<false, false>;
+    const auto fill = peak ? notes_batch_kernel<true, true, true> : cl ? notes_batch_kernel<true, true> : notes_batch_kernel<true, false>;
     const NoteClean clean = cl ? *cl : NoteClean{};
     hipLaunchKernelGGL(count, grid, block, 0, st, frame_logits, onset_logits, thr_frame, thr_onset, clean, lengths, rows, P, T, counts,
-                       (const long long*)nullptr, (int*)nullptr, (int*)nullptr, 0ll);
+                       (const long long*)nullptr, (int*)nullptr, (int*)nullptr, 0ll, reach);
     MT_CHECK_LAUNCH();
     hipLaunchKernelGGL(notes_batch_prefix_kernel, dim3(1), dim3(PREFIX_THREADS), 0, st, (const int*)counts, rows, row_off);
     MT_CHECK_LAUNCH();
     if (capacity > 0) {
         hipLaunchKernelGGL(fill, grid, block, 0, st, frame_logits, onset_logits, thr_frame, thr_onset, clean, lengths, rows, P, T, counts,
-                           (const long long*)row_off, starts, ends, capacity);
+                           (const long long*)row_off, starts, ends, capacity, reach);
         MT_CHECK_LAUNCH();
     }
     return MT_OK;
@@ -120,4 +125,12 @@ extern "C" int mt_notes_batch_clean(const float* frame_logits, const float* onse
     const NoteClean cl{min_frames, bridge_frames};
     return notes_batch("mt_notes_batch_clean", frame_logits, onset_logits, thr_frame, thr_onset, lengths, B, P, T, counts, row_off, starts, ends,
                        capacity, stream, &cl);
+}
+
+extern "C" int mt_notes_batch_peak(const float* frame_logits, const float* onset_logits, float thr_frame, float thr_onset, const long long* lengths,
+                                   int B, int P, long long T, int* counts, long long* row_off, int* starts, int* ends, long long capacity,
+                                   int min_frames, int bridge_frames, int peak_reach, mt_stream_t stream) {
+    const NoteClean cl{min_frames, bridge_frames};
+    return notes_batch("mt_notes_batch_peak", frame_logits, onset_logits, thr_frame, thr_onset, lengths, B, P, T, counts, row_off, starts, ends,
+                       capacity, stream, &cl, true, peak_reach);
 }

@@ -134,7 +134,8 @@ def note_metrics_dataset(model, dataset, threshold: float = 0.5, onset_threshold
                          subset: Optional[int] = None, max_batch: int = 128, rank: int = 0, world: int = 1,
                          window_overlap: Optional[float] = None, note_reference: str = "roll",
                          offset_threshold: Optional[float] = None, min_note_frames: int = 1, bridge_frames: int = 0,
-                         smooth_on: float = 0.0, smooth_off: float = 0.0, refine_onsets: bool = False, refine_reach: int = 2) -> dict:
+                         smooth_on: float = 0.0, smooth_off: float = 0.0, refine_onsets: bool = False, refine_reach: int = 2,
+                         onset_detect: str = "edge", peak_reach: int = 1) -> dict:
     """Note-level metrics of every sample, identical on every rank: {"mean": {key: value}, "per_sample": {key: [values]}} over
     NOTE_METRIC_KEYS (onset / onset_offset x precision / recall / f1).  onset_threshold=None: notes are the runs of
     sigmoid(frame) > threshold (the frame decoder); otherwise the onset-gated decoder with the onset head at onset_threshold.
@@ -146,10 +147,14 @@ def note_metrics_dataset(model, dataset, threshold: float = 0.5, onset_threshold
     head is smoothed before the decoder (DESIGN.md 6c "Frame smoothing"); the result then names those two as well.
     refine_onsets (onset-gated or offset-gated decoder, note_reference="midi"): the notes are decoded as lists, their onsets refined to
     sub-frame ticks (mt_refine_onsets with reach refine_reach; DESIGN.md 6c "Sub-frame onsets"), copied to the host and scored there
-    with notes.note_match_ticks -- the device matcher takes estimates on the frame grid only; the result then names "refine_reach"."""
-    from .notes import check_cleanup, check_smoothing, note_match_counts, note_match_list, note_match_ticks, note_prf, notes_ticks_device
+    with notes.note_match_ticks -- the device matcher takes estimates on the frame grid only; the result then names "refine_reach".
+    onset_detect="peak" (onset-gated or offset-gated decoder): notes open at the peaks of the onset logits over peak_reach frames
+    (DESIGN.md 6c "Peak-picked onsets"), on either path; the result then names "onset_detect" and "peak_reach"."""
+    from .notes import (check_cleanup, check_onset_detect, check_smoothing, note_match_counts, note_match_list, note_match_ticks, note_prf,
+                        notes_ticks_device)
     clean = check_cleanup(min_note_frames, bridge_frames)
     smooth = check_smoothing(smooth_on, smooth_off)
+    peak = check_onset_detect(onset_detect, peak_reach, onset_threshold is not None)
     _check_note_reference(dataset, note_reference)
     onset, offset = onset_threshold is not None, offset_threshold is not None
     if offset and not onset:
@@ -166,12 +171,13 @@ def note_metrics_dataset(model, dataset, threshold: float = 0.5, onset_threshold
         if refine_onsets:
             est = notes_ticks_device(frame, on, threshold, onset_threshold, lengths, offset_logits=off,
                                      offset_threshold=offset_threshold if offset else 0.5, min_note_frames=clean[0], bridge_frames=clean[1],
-                                     smooth_on=smooth[0], smooth_off=smooth[1], refine_reach=refine_reach)
+                                     smooth_on=smooth[0], smooth_off=smooth[1], refine_reach=refine_reach, onset_detect=onset_detect,
+                                     peak_reach=peak_reach)
             counts = note_match_ticks(est, ref)
         else:
             counts = match(frame, ref, threshold, on, onset_threshold if onset else 0.5, lengths, offset_logits=off,
                            offset_threshold=offset_threshold if offset else 0.5, min_note_frames=clean[0], bridge_frames=clean[1],
-                           smooth_on=smooth[0], smooth_off=smooth[1])
+                           smooth_on=smooth[0], smooth_off=smooth[1], onset_detect=onset_detect, peak_reach=peak_reach)
         for m in note_prf(counts):
             for c in ("onset", "onset_offset"):
                 for k, v in zip(("precision", "recall", "f1"), m[c]):
@@ -184,6 +190,8 @@ def note_metrics_dataset(model, dataset, threshold: float = 0.5, onset_threshold
         out["smooth_on"], out["smooth_off"] = smooth
     if refine_onsets:
         out["refine_reach"] = int(refine_reach)
+    if peak:
+        out["onset_detect"], out["peak_reach"] = "peak", peak
     return out
 
 
@@ -193,6 +201,12 @@ def _refuse_smoothing(who: str, smooth_on, smooth_off) -> None:
     if check_smoothing(smooth_on, smooth_off) != (0.0, 0.0):
         raise ValueError(f"{who}: the tuners do not smooth the frame head (smooth_on / smooth_off): tune without smoothing, then evaluate "
                          "with it (note_metrics_dataset(..., smooth_on=, smooth_off=))")
+
+
+def _refuse_peak(who: str, onset_detect) -> None:
+    """The tuners run the sweep and grid kernels, which have no peak mode: onset_detect="peak" is refused, before any GPU work."""
+    from .notes import refuse_peak
+    refuse_peak(onset_detect, who)
 
 
 def _check_note_reference(dataset, note_reference: str) -> None:
@@ -220,11 +234,12 @@ def _note_groups(lr, dataset, onset: bool, note_reference: str, max_batch: int, 
 
 def tune_threshold(model, dataset, device="cuda", subset: Optional[int] = None, tune_range=(0.05, 0.95), tune_step=0.1,
                    tune_min_step=0.01, tune_rounds=6, rank: int = 0, world: int = 1, log=print, window_overlap: Optional[float] = None,
-                   smooth_on: float = 0.0, smooth_off: float = 0.0):
+                   smooth_on: float = 0.0, smooth_off: float = 0.0, onset_detect: str = "edge"):
     """Coarse-to-fine search of evaluate.py:556-618 (same candidate grids, same strict-improvement rule, same window
     and stopping rule); returns (best_threshold, best_mean_f1).  window_overlap: as evaluate_dataset.  Frame smoothing
-    (smooth_on, smooth_off) other than (0, 0) is refused."""
+    (smooth_on, smooth_off) other than (0, 0) is refused, and so is onset_detect="peak": the frame F1 decodes no notes."""
     _refuse_smoothing("tune_threshold", smooth_on, smooth_off)
+    _refuse_peak("tune_threshold", onset_detect)
     n = len(dataset) if subset is None else min(subset, len(dataset))
     mine = list(shard_range(n, rank, world))
     lr = _collect(model, dataset, mine, device, window_overlap)          # the only forward passes
@@ -288,15 +303,18 @@ def search_note_thresholds(mean_f1, two_axes: bool = True, tune_range=(0.05, 0.9
 def tune_note_thresholds(model, dataset, device="cuda", subset: Optional[int] = None, decoder: str = "onset", note_reference: str = "roll",
                          objective: str = "onset", tune_range=(0.05, 0.95), tune_step=0.1, tune_min_step=0.01, tune_rounds=6,
                          rank: int = 0, world: int = 1, log=print, window_overlap: Optional[float] = None, max_batch: int = 128,
-                         min_note_frames: int = 1, bridge_frames: int = 0, smooth_on: float = 0.0, smooth_off: float = 0.0):
+                         min_note_frames: int = 1, bridge_frames: int = 0, smooth_on: float = 0.0, smooth_off: float = 0.0,
+                         onset_detect: str = "edge"):
     """The thresholds of the note decoder that maximise the mean note F1 (`objective`: "onset" or "onset_offset"; unweighted mean
     over samples, as note_metrics_dataset) by search_note_thresholds: decoder="onset" searches (frame, onset) pairs, "frame" the
     frame threshold alone.  The model runs once; every round is one sweep pass over each group of note_metrics_dataset.
     -> (frame threshold, onset threshold or None, best mean F1), identical on every rank.  A candidate at or past 1 (the schedule's
     last grid point can be) decodes no note and scores 0, as it does for tune_threshold.  The sweep kernels do not clean notes:
-    anything but (min_note_frames, bridge_frames) = (1, 0) is refused, and so is frame smoothing (smooth_on, smooth_off) other than (0, 0)."""
+    anything but (min_note_frames, bridge_frames) = (1, 0) is refused, and so is frame smoothing (smooth_on, smooth_off) other than (0, 0).
+    Nor do they pick peaks: onset_detect="peak" is refused."""
     from .notes import check_cleanup, note_prf, note_sweep_counts
     _refuse_smoothing("tune_note_thresholds", smooth_on, smooth_off)
+    _refuse_peak("tune_note_thresholds", onset_detect)
     if check_cleanup(min_note_frames, bridge_frames) != (1, 0):
         raise ValueError("tune_note_thresholds: the threshold sweeps do not clean notes (min_note_frames / bridge_frames): tune "
                          "without cleanup, then evaluate with it (note_metrics_dataset(..., min_note_frames=, bridge_frames=))")
@@ -393,7 +411,7 @@ def fold_smoothings(f1: np.ndarray) -> np.ndarray:
 def tune_note_decoder(model, dataset, device="cuda", subset: Optional[int] = None, decoder: str = "onset", note_reference: str = "roll",
                       objective: str = "onset", cleanups=((1, 0),), tune_range=(0.05, 0.95), tune_step=0.1, tune_min_step=0.01,
                       tune_rounds=6, rank: int = 0, world: int = 1, log=print, window_overlap: Optional[float] = None, max_batch: int = 128,
-                      smooth_on: float = 0.0, smooth_off: float = 0.0, smoothings=None):
+                      smooth_on: float = 0.0, smooth_off: float = 0.0, smoothings=None, onset_detect: str = "edge"):
     """Every parameter of the note decoder at once, for the best mean note F1 (`objective`: "onset" or "onset_offset"; unweighted
     mean over samples, as note_metrics_dataset) by search_note_decoder: the thresholds of the heads that `decoder` reads ("frame":
     frame; "onset": frame, onset; "onset_offset": frame, onset, offset) times the candidates `cleanups`, a list of
@@ -405,8 +423,10 @@ def tune_note_decoder(model, dataset, device="cuda", subset: Optional[int] = Non
     part in every round as `cleanups` does: the search's discrete axis is cleanups x smoothings, cleanup-major, every round still one
     note_grid_counts call per group, and the result is (frame threshold, onset threshold or None, offset threshold or None,
     (min_note_frames, bridge_frames), (smooth_on, smooth_off), best mean F1).  A single smoothing (smooth_on, smooth_off) other than
-    (0, 0) is refused either way: the penalties are tuned through `smoothings`, not fixed beside the search."""
+    (0, 0) is refused either way: the penalties are tuned through `smoothings`, not fixed beside the search.  onset_detect="peak" is
+    refused: the grid kernels decode with the edge rule only."""
     from .notes import _smoothing_list, check_cleanup, check_smoothing, note_grid_counts, note_prf
+    _refuse_peak("tune_note_decoder", onset_detect)
     if smoothings is None:
         _refuse_smoothing("tune_note_decoder", smooth_on, smooth_off)
     else:

@@ -30,6 +30,10 @@
   * `refine_onsets_device` = sub-frame onsets in ticks of 100 us for the notes of any onset-gated decoder, from the three onset-head values
     around the peak near each note's start (mt_refine_onsets; DESIGN.md 6c "Sub-frame onsets"); `refine_onsets=` on the two note-list
     calls stamps the notes with them.  `note_match_ticks` scores such off-grid estimates against a note list on the host.
+  * `onset_detect="peak"`, `peak_reach=R` on the two matchers and the note-list calls = a note opens at every local maximum of the
+    onset logits over R frames that passes the onset threshold, not at the rising edges of the thresholded onset mask (DESIGN.md 6c
+    "Peak-picked onsets"; the mt_*_peak entry points): the detector for an onset head trained against triangular targets, on which
+    the edge rule merges re-struck keys.  "edge" calls exactly the entry points above.  The sweep and grid kernels have no peak mode.
 """
 from __future__ import annotations
 
@@ -122,6 +126,32 @@ def cleanup_frames(min_note_ms: float = 0.0, bridge_gap_ms: float = 0.0) -> Tupl
     return m, g
 
 
+MAX_PEAK_REACH = 8                                  # PEAK_MAX_REACH of csrc/note_decode.h
+ONSET_DETECTORS = ("edge", "peak")
+
+
+def check_onset_detect(onset_detect="edge", peak_reach=1, has_onset: bool = True) -> int:
+    """The checked onset detector of a decoder call -> 0 for "edge" (the rising edges of the onset mask), the reach R in [1, 8] for
+    "peak" (the local maxima of the onset logits over R frames; DESIGN.md 6c "Peak-picked onsets").  has_onset: the call has an onset
+    head; "peak" without one is refused.  Raises before any GPU work."""
+    if onset_detect not in ONSET_DETECTORS:
+        raise ValueError(f"onset_detect must be one of {ONSET_DETECTORS}, got {onset_detect!r}")
+    if isinstance(peak_reach, bool) or not isinstance(peak_reach, (int, np.integer)) or not 1 <= peak_reach <= MAX_PEAK_REACH:
+        raise ValueError(f"peak_reach must be an integer number of frames in [1, {MAX_PEAK_REACH}], got {peak_reach!r}")
+    if onset_detect == "edge":
+        return 0
+    if not has_onset:
+        raise ValueError("onset_detect='peak': peaks are picked on the onset head, and the frame decoder has none (pass onset_logits)")
+    return int(peak_reach)
+
+
+def refuse_peak(onset_detect, who: str) -> None:
+    """The calls that run the sweep and grid kernels take onset_detect only to refuse "peak": those kernels have no peak mode."""
+    if check_onset_detect(onset_detect):
+        raise ValueError(f"{who}: onset_detect='peak' is not supported here: peak detection inside the sweep and grid kernels is out of "
+                         "scope (they decode with the edge rule only); tune with 'edge' or score single configurations")
+
+
 MAX_SMOOTH_PENALTY = 64.0                           # logits; csrc/smooth.hip counts evidence in steps of 1/64 logit, capped at +-64 logits
 
 
@@ -136,13 +166,16 @@ def check_smoothing(smooth_on=0.0, smooth_off=0.0) -> Tuple[float, float]:
     return out[0], out[1]
 
 
-def _decode(family: str, clean: Tuple[int, int], x, on, off, thrs, rest, offset_head: bool = True) -> None:
+def _decode(family: str, clean: Tuple[int, int], x, on, off, thrs, rest, offset_head: bool = True, peak: int = 0) -> None:
     """Call the entry point of `family` (mt_note_match_counts, mt_note_match_list, mt_heads_to_notes, mt_notes_batch) that serves a
     decoder call: `family` itself or, with offset logits, `family`_off at no cleanup (1, 0), `family`_clean otherwise.  thrs = the
     (frame, onset, offset) thresholds, rest = the arguments after the heads and thresholds, the stream last (the cleanup goes before
-    it).  offset_head=False: a family without an offset head, whose _clean takes two heads as well."""
+    it).  offset_head=False: a family without an offset head, whose _clean takes two heads as well.  peak = check_onset_detect's
+    result: other than 0, `family`_peak at that reach, whatever the cleanup (its arguments are _clean's, the reach before the stream)."""
     two, three = (ptr(x), ptr(on), *thrs[:2]), (ptr(x), ptr(on), ptr(off), *thrs)
-    if clean != (1, 0):
+    if peak:
+        name, args = family + "_peak", (*(three if offset_head else two), *rest[:-1], *clean, peak, rest[-1])
+    elif clean != (1, 0):
         name, args = family + "_clean", (*(three if offset_head else two), *rest[:-1], *clean, rest[-1])
     elif off is None:
         name, args = family, (*two, *rest)
@@ -272,14 +305,17 @@ def _note_tables(ref_notes: Dict[str, torch.Tensor], B: int, P: int, dev):
 def note_match_counts(frame_logits: torch.Tensor, ref_roll: torch.Tensor, threshold: float = 0.5, onset_logits: Optional[torch.Tensor] = None,
                       onset_threshold: float = 0.5, lengths=None, offset_logits: Optional[torch.Tensor] = None,
                       offset_threshold: float = 0.5, min_note_frames: int = 1, bridge_frames: int = 0, smooth_on: float = 0.0,
-                      smooth_off: float = 0.0) -> torch.Tensor:
+                      smooth_off: float = 0.0, onset_detect: str = "edge", peak_reach: int = 1) -> torch.Tensor:
     """(B, P, T) frame logits (and onset logits for the onset-gated decoder) and (B, P, T) reference roll on the device -> (B, 4)
     int64 device tensor {n_ref, n_est, tp_onset, tp_onset_offset}.  lengths (B,) = valid frames per sample (None: all T).  With
     offset_logits (and onset_logits) the estimates come from the offset-gated decoder (mt_note_match_counts_off).  With
     (min_note_frames, bridge_frames) other than (1, 0) the estimates are cleaned in the decoder (mt_note_match_counts_clean).  With
-    (smooth_on, smooth_off) other than (0, 0) the frame head is smoothed first (smooth_frame_logits, over the same lengths)."""
+    (smooth_on, smooth_off) other than (0, 0) the frame head is smoothed first (smooth_frame_logits, over the same lengths).
+    onset_detect="peak" (needs onset_logits): notes open at the peaks of the onset logits over peak_reach frames
+    (mt_note_match_counts_peak; DESIGN.md 6c "Peak-picked onsets")."""
     clean = check_cleanup(min_note_frames, bridge_frames)
     smooth = check_smoothing(smooth_on, smooth_off)
+    peak = check_onset_detect(onset_detect, peak_reach, onset_logits is not None)
     x, on, off, thr, othr, kthr, ref = _heads(frame_logits, onset_logits, offset_logits, threshold, onset_threshold, offset_threshold,
                                               ref_roll=ref_roll, mismatch="shape mismatch: frame {frame}, ref {ref}, onset {onset}")
     B, P, T = x.shape
@@ -289,7 +325,8 @@ def note_match_counts(frame_logits: torch.Tensor, ref_roll: torch.Tensor, thresh
         x = _smoothed(x, thr, smooth, ln, False)
     counts = torch.empty(B, 4, dtype=torch.int64, device=dev)
     with torch.cuda.device(dev):
-        _decode("mt_note_match_counts", clean, x, on, off, (thr, othr, kthr), (ptr(ref), ptr(ln), ptr(counts), B, P, T, _lib.stream_ptr()))
+        _decode("mt_note_match_counts", clean, x, on, off, (thr, othr, kthr), (ptr(ref), ptr(ln), ptr(counts), B, P, T, _lib.stream_ptr()),
+                peak=peak)
     return counts
 
 
@@ -299,16 +336,20 @@ TICKS_PER_FRAME = 320              # one frame in ticks of 100 us
 def note_match_list(frame_logits: torch.Tensor, ref_notes: Dict[str, torch.Tensor], threshold: float = 0.5,
                     onset_logits: Optional[torch.Tensor] = None, onset_threshold: float = 0.5, lengths=None,
                     offset_logits: Optional[torch.Tensor] = None, offset_threshold: float = 0.5, min_note_frames: int = 1,
-                    bridge_frames: int = 0, smooth_on: float = 0.0, smooth_off: float = 0.0) -> torch.Tensor:
+                    bridge_frames: int = 0, smooth_on: float = 0.0, smooth_off: float = 0.0, onset_detect: str = "edge",
+                    peak_reach: int = 1) -> torch.Tensor:
     """note_match_counts against a note list: ref_notes = {"on", "off"} int32 ticks of 100 us and "ptr" int64 (B * P + 1,) on the
     device, row (b, p) owning on/off[ptr[b*P + p]:ptr[b*P + p + 1]] sorted by onset (MaestroDataset.ref_notes).  An estimated
     note [s, e) in frames has times 320 s, 320 e; onsets match within 500 ticks, offsets within max(500, 0.2 reference length).
     Notes that start at or past a sample's valid frames are not counted.  -> (B, 4) int64 {n_ref, n_est, tp_onset, tp_onset_offset}.
     With offset_logits (and onset_logits) the estimates come from the offset-gated decoder (mt_note_match_list_off); with
     (min_note_frames, bridge_frames) other than (1, 0) they are cleaned in the decoder (mt_note_match_list_clean); with
-    (smooth_on, smooth_off) other than (0, 0) the frame head is smoothed first (smooth_frame_logits, over the same lengths)."""
+    (smooth_on, smooth_off) other than (0, 0) the frame head is smoothed first (smooth_frame_logits, over the same lengths);
+    with onset_detect="peak" (needs onset_logits) notes open at the peaks of the onset logits over peak_reach frames
+    (mt_note_match_list_peak)."""
     clean = check_cleanup(min_note_frames, bridge_frames)
     smooth = check_smoothing(smooth_on, smooth_off)
+    peak = check_onset_detect(onset_detect, peak_reach, onset_logits is not None)
     x, on, off, thr, othr, kthr, _ = _heads(frame_logits, onset_logits, offset_logits, threshold, onset_threshold, offset_threshold)
     B, P, T = x.shape
     dev = x.device
@@ -319,7 +360,7 @@ def note_match_list(frame_logits: torch.Tensor, ref_notes: Dict[str, torch.Tenso
     counts = torch.empty(B, 4, dtype=torch.int64, device=dev)
     with torch.cuda.device(dev):
         _decode("mt_note_match_list", clean, x, on, off, (thr, othr, kthr),
-                (ptr(r_on), ptr(r_off), ptr(r_ptr), ptr(ln), ptr(counts), B, P, T, _lib.stream_ptr()))
+                (ptr(r_on), ptr(r_off), ptr(r_ptr), ptr(ln), ptr(counts), B, P, T, _lib.stream_ptr()), peak=peak)
     return counts
 
 
@@ -336,13 +377,15 @@ def _threshold_array(values, name: str) -> np.ndarray:
 
 
 def note_sweep_counts(frame_logits: torch.Tensor, ref, thresholds, onset_logits: Optional[torch.Tensor] = None, onset_thresholds=None,
-                      lengths=None) -> torch.Tensor:
+                      lengths=None, onset_detect: str = "edge") -> torch.Tensor:
     """note_match_counts (ref = a (B, P, T) roll) or note_match_list (ref = the {"on", "off", "ptr"} note list) at every pair of
     `thresholds` x `onset_thresholds` -> (B, Kf, Ko, 4) int64 device tensor; [b, i, j] is exactly what the single call returns at
     (thresholds[i], onset_thresholds[j]).  Without onset logits (the frame decoder) Ko = 1 and onset_thresholds is not read.  The
     logits are read, and their sigmoids evaluated, once per call of the kernel; a grid past its limits (16 per axis, 64 pairs) is
     cut into several calls here.  Nothing is allocated on the device but the result, and with a roll nothing synchronises (a note
-    list's ptr table is checked with one small read-back, as in note_match_list)."""
+    list's ptr table is checked with one small read-back, as in note_match_list).  onset_detect: "edge" only; the sweep kernel has no
+    peak mode and "peak" raises."""
+    refuse_peak(onset_detect, "note_sweep_counts")
     x = _rows(frame_logits, "frame_logits")
     on = None if onset_logits is None else _rows(onset_logits, "onset_logits")
     if on is not None and on.shape != x.shape:
@@ -391,7 +434,7 @@ GRID_MAX_K, GRID_MAX_CONFIGS = 16, 64              # mt_note_grid_*: values per 
 
 def note_grid_counts(frame_logits: torch.Tensor, ref, thresholds, onset_logits: Optional[torch.Tensor] = None, onset_thresholds=None,
                      offset_logits: Optional[torch.Tensor] = None, offset_thresholds=None, cleanups=None, lengths=None,
-                     smoothings=None) -> torch.Tensor:
+                     smoothings=None, onset_detect: str = "edge") -> torch.Tensor:
     """note_match_counts (ref = a (B, P, T) roll) or note_match_list (ref = the {"on", "off", "ptr"} note list) at every cell of
     `thresholds` x `onset_thresholds` x `offset_thresholds` x `cleanups` -> (B, Kf, Ko, Kk, Kc, 4) int64 device tensor; [b, i, j, k, c]
     is exactly what the single call returns at (thresholds[i], onset_thresholds[j], offset_thresholds[k]) with (min_note_frames,
@@ -405,7 +448,8 @@ def note_grid_counts(frame_logits: torch.Tensor, ref, thresholds, onset_logits: 
     well.  The Kf * Ks frame candidates are cut into tiles of at most 16; per tile one mt_frame_smooth_paths launch packs their Viterbi
     paths into bit masks (smooth_frame_paths), which mt_note_grid_counts_paths / mt_note_grid_list_paths read as their frame axis in
     place of thresholds (DESIGN.md 6c "Smoothing in the decoder grid").  (0, 0) goes the same way: its path is the threshold's
-    activity.  None: no such axis, and the calls above."""
+    activity.  None: no such axis, and the calls above.  onset_detect: "edge" only; the grid kernels have no peak mode and "peak" raises."""
+    refuse_peak(onset_detect, "note_grid_counts")
     if offset_logits is not None and onset_logits is None:
         raise ValueError("offset_logits: the offset-gated decoder needs onset_logits as well")
     x = _rows(frame_logits, "frame_logits")
@@ -501,7 +545,8 @@ def note_prf(counts) -> List[Dict[str, Tuple[float, float, float]]]:
 def heads_to_notes_device(frame_logits: torch.Tensor, onset_logits: Optional[torch.Tensor], threshold: float = 0.5,
                           onset_threshold: float = 0.5, fs: float = FS, min_midi: int = 21, offset_logits: Optional[torch.Tensor] = None,
                           offset_threshold: float = 0.5, min_note_frames: int = 1, bridge_frames: int = 0, smooth_on: float = 0.0,
-                          smooth_off: float = 0.0, refine_onsets: bool = False, refine_reach: int = 2) -> List[Tuple[int, float, float]]:
+                          smooth_off: float = 0.0, refine_onsets: bool = False, refine_reach: int = 2, onset_detect: str = "edge",
+                          peak_reach: int = 1) -> List[Tuple[int, float, float]]:
     """(n_chunks, 88, T) frame and onset logits ON THE DEVICE -> notes of the onset-gated decoder over the chunks concatenated in
     time, in the reference's note order (pitch-major, then time); only counts and two ints per note reach the host.  With
     offset_logits: the notes of the offset-gated decoder (mt_heads_to_notes_off), which end where the offset head fires.  With
@@ -509,24 +554,27 @@ def heads_to_notes_device(frame_logits: torch.Tensor, onset_logits: Optional[tor
     None: the frame decoder's notes, cleaned.  With (smooth_on, smooth_off) other than (0, 0) the frame head is smoothed first, over
     the chunks concatenated in time (smooth_frame_logits, chunks=True).  refine_onsets=True: one more launch (mt_refine_onsets, reach
     refine_reach) gives every note a sub-frame onset; its start is then on_tick / 1e4 seconds, its end unchanged (e / fs), and the
-    ticks ride in the note copy.  The frame decoder has no onset head to refine from: it raises."""
+    ticks ride in the note copy.  The frame decoder has no onset head to refine from: it raises.  onset_detect="peak" (needs
+    onset_logits): notes open at the peaks of the onset logits over peak_reach frames, neighbours across chunk boundaries
+    (mt_heads_to_notes_peak; DESIGN.md 6c "Peak-picked onsets"); the refined tick of a peak is the same at every refine_reach."""
     clean = check_cleanup(min_note_frames, bridge_frames)
     smooth = check_smoothing(smooth_on, smooth_off)
     reach = _check_refine(refine_onsets, refine_reach, onset_logits)
+    peak = check_onset_detect(onset_detect, peak_reach, onset_logits is not None)
     x, on, off, thr, othr, kthr, _ = _heads(frame_logits, onset_logits, offset_logits, threshold, onset_threshold, offset_threshold,
                                             onset_required=clean == (1, 0), mismatch="frame {frame} and onset {onset} logits differ in shape")
     if smooth != (0.0, 0.0):
         x = _smoothed(x, thr, smooth, None, True)
-    c, s, e, tick = _heads_to_notes_raw(x, on, off, (thr, othr, kthr), clean, reach)
+    c, s, e, tick = _heads_to_notes_raw(x, on, off, (thr, othr, kthr), clean, reach, peak)
     pitches = np.repeat(np.arange(x.shape[1]) + min_midi, c)
     if reach is not None:
         return [(int(pp), float(a) / TICKS_PER_SECOND, float(b) / fs) for pp, a, b in zip(pitches, tick, e)]
     return [(int(pp), float(a) / fs, float(b) / fs) for pp, a, b in zip(pitches, s, e)]
 
 
-def _heads_to_notes_raw(x, on, off, thrs, clean, reach: Optional[int]):
+def _heads_to_notes_raw(x, on, off, thrs, clean, reach: Optional[int], peak: int = 0):
     """The mt_heads_to_notes family on checked (NB, P, T) heads -> host arrays (counts (P,), starts, ends, ticks); ticks None without
-    `reach`, else mt_refine_onsets' onsets of the same notes, which ride in the note copy."""
+    `reach`, else mt_refine_onsets' onsets of the same notes, which ride in the note copy.  peak: check_onset_detect's result."""
     NB, P, T = x.shape
     dev = x.device
     counts = torch.empty(P, dtype=torch.int32, device=dev)
@@ -538,7 +586,8 @@ def _heads_to_notes_raw(x, on, off, thrs, clean, reach: Optional[int]):
             se = torch.empty(3, cap, dtype=torch.int32, device=dev)                            # starts | ends | ticks: one copy
             starts, ends = se[0], se[1]
         with torch.cuda.device(dev):
-            _decode("mt_heads_to_notes", clean, x, on, off, thrs, (NB, P, T, ptr(counts), ptr(starts), ptr(ends), cap, _lib.stream_ptr()))
+            _decode("mt_heads_to_notes", clean, x, on, off, thrs, (NB, P, T, ptr(counts), ptr(starts), ptr(ends), cap, _lib.stream_ptr()),
+                    peak=peak)
         c = counts.cpu().numpy()
         total = int(c.sum())
         if total <= cap:
@@ -556,24 +605,26 @@ def _heads_to_notes_raw(x, on, off, thrs, clean, reach: Optional[int]):
 def notes_batch_device(frame_logits: torch.Tensor, onset_logits: Optional[torch.Tensor] = None, threshold: float = 0.5,
                        onset_threshold: float = 0.5, lengths=None, fs: float = FS, min_midi: int = 21, min_note_frames: int = 1,
                        bridge_frames: int = 0, smooth_on: float = 0.0, smooth_off: float = 0.0, refine_onsets: bool = False,
-                       refine_reach: int = 2) -> List[List[Tuple[int, float, float]]]:
+                       refine_reach: int = 2, onset_detect: str = "edge", peak_reach: int = 1) -> List[List[Tuple[int, float, float]]]:
     """(B, P, T) frame logits of B whole recordings ON THE DEVICE, padded to T, with lengths (B,) valid frames each (None: all T) ->
     one note list per recording: what transcribe.notes_from_logits_device (onset_logits None) or heads_to_notes_device returns on
     that recording's rows trimmed to its length.  The padding is never read.  One launch of mt_notes_batch, one device-to-host copy
     of the counts and offsets and one of the notes; a second launch only when the first capacity guess was short.  With
     (min_note_frames, bridge_frames) other than (1, 0) the notes are cleaned in the decoder (mt_notes_batch_clean).  With
     (smooth_on, smooth_off) other than (0, 0) the frame head is smoothed first (smooth_frame_logits, over the same lengths).
-    refine_onsets=True (onset-gated decoder only): as in heads_to_notes_device, a note's start is its refined on_tick / 1e4 seconds."""
+    refine_onsets=True (onset-gated decoder only): as in heads_to_notes_device, a note's start is its refined on_tick / 1e4 seconds.
+    onset_detect="peak" (needs onset_logits): notes open at the peaks of the onset logits over peak_reach frames (mt_notes_batch_peak)."""
     clean = check_cleanup(min_note_frames, bridge_frames)
     smooth = check_smoothing(smooth_on, smooth_off)
     reach = _check_refine(refine_onsets, refine_reach, onset_logits)
+    peak = check_onset_detect(onset_detect, peak_reach, onset_logits is not None)
     x, on, _, thr, othr, _, _ = _heads(frame_logits, onset_logits, None, threshold, onset_threshold, 0.5,
                                        mismatch="frame {frame} and onset {onset} logits differ in shape")
     B, P, T = x.shape
     ln = _lengths(lengths, B, x.device)
     if smooth != (0.0, 0.0):
         x = _smoothed(x, thr, smooth, ln, False)
-    off, c, s, e, tick = _notes_batch_raw(x, on, ln, thr, othr, clean, reach)
+    off, c, s, e, tick = _notes_batch_raw(x, on, ln, thr, othr, clean, reach, peak)
     if reach is not None:
         s, fs_on = tick, float(TICKS_PER_SECOND)            # starts in ticks
     else:
@@ -587,9 +638,10 @@ def notes_batch_device(frame_logits: torch.Tensor, onset_logits: Optional[torch.
     return out
 
 
-def _notes_batch_raw(x, on, ln, thr, othr, clean, reach: Optional[int]):
+def _notes_batch_raw(x, on, ln, thr, othr, clean, reach: Optional[int], peak: int = 0):
     """mt_notes_batch / mt_notes_batch_clean on checked (B, P, T) heads -> host arrays (row_off (B * P + 1,), counts (B * P,), starts,
-    ends, ticks); ticks None without `reach`, else mt_refine_onsets' onsets of the same notes, which ride in the note copy."""
+    ends, ticks); ticks None without `reach`, else mt_refine_onsets' onsets of the same notes, which ride in the note copy.  peak:
+    check_onset_detect's result (mt_notes_batch_peak)."""
     B, P, T = x.shape
     dev = x.device
     rows = B * P
@@ -600,7 +652,7 @@ def _notes_batch_raw(x, on, ln, thr, othr, clean, reach: Optional[int]):
         se = torch.empty(2 if reach is None else 3, cap, dtype=torch.int32, device=dev)
         with torch.cuda.device(dev):
             _decode("mt_notes_batch", clean, x, on, None, (thr, othr, 0.5),
-                    (ptr(ln), B, P, T, ptr(counts), ptr(row_off), ptr(se[0]), ptr(se[1]), cap, _lib.stream_ptr()), offset_head=False)
+                    (ptr(ln), B, P, T, ptr(counts), ptr(row_off), ptr(se[0]), ptr(se[1]), cap, _lib.stream_ptr()), offset_head=False, peak=peak)
         host = meta.cpu().numpy()
         off, c = host[:rows + 1], host[rows + 1:].view(np.int32)[:rows]
         total = int(off[rows])
@@ -617,15 +669,17 @@ def _notes_batch_raw(x, on, ln, thr, othr, clean, reach: Optional[int]):
 
 def notes_ticks_device(frame_logits: torch.Tensor, onset_logits: torch.Tensor, threshold: float = 0.5, onset_threshold: float = 0.5,
                        lengths=None, offset_logits: Optional[torch.Tensor] = None, offset_threshold: float = 0.5, min_note_frames: int = 1,
-                       bridge_frames: int = 0, smooth_on: float = 0.0, smooth_off: float = 0.0, refine_reach: int = 2) -> Dict[str, np.ndarray]:
+                       bridge_frames: int = 0, smooth_on: float = 0.0, smooth_off: float = 0.0, refine_reach: int = 2,
+                       onset_detect: str = "edge", peak_reach: int = 1) -> Dict[str, np.ndarray]:
     """The notes of a padded batch (B, P, T) with refined onsets, as a note list on the host for note_match_ticks: {"on", "off"} int32
     ticks of 100 us (on = mt_refine_onsets' sub-frame onset, off = 320 e) and "ptr" int64 (B * P + 1,), in the layout of
     MaestroDataset.ref_notes.  The onset-gated decoder goes through mt_notes_batch* and one refinement launch for the whole batch; with
     offset_logits (the batched extractor reads two heads) every recording is decoded on its own valid frames with
-    mt_heads_to_notes_off / _clean and refined there."""
+    mt_heads_to_notes_off / _clean and refined there.  onset_detect="peak": the mt_*_peak entry points of either path, over peak_reach frames."""
     clean = check_cleanup(min_note_frames, bridge_frames)
     smooth = check_smoothing(smooth_on, smooth_off)
     reach = _check_refine(True, refine_reach, onset_logits)
+    peak = check_onset_detect(onset_detect, peak_reach, onset_logits is not None)
     x, on, off, thr, othr, kthr, _ = _heads(frame_logits, onset_logits, offset_logits, threshold, onset_threshold, offset_threshold,
                                             mismatch="frame {frame} and onset {onset} logits differ in shape")
     B, P, T = x.shape
@@ -633,7 +687,7 @@ def notes_ticks_device(frame_logits: torch.Tensor, onset_logits: torch.Tensor, t
     if smooth != (0.0, 0.0):
         x = _smoothed(x, thr, smooth, ln, False)
     if off is None:
-        ptrs, _, _, e, tick = _notes_batch_raw(x, on, ln, thr, othr, clean, reach)
+        ptrs, _, _, e, tick = _notes_batch_raw(x, on, ln, thr, othr, clean, reach, peak)
         return {"on": tick.astype(np.int32), "off": (e * TICKS_PER_FRAME).astype(np.int32), "ptr": ptrs.astype(np.int64)}
     lens = [T] * B if ln is None else [min(max(int(v), 0), T) for v in ln.cpu().numpy()]
     ons, offs, ptrs = [], [], [np.zeros(1, np.int64)]
@@ -642,7 +696,7 @@ def notes_ticks_device(frame_logits: torch.Tensor, onset_logits: torch.Tensor, t
             c, e, tick = np.zeros(P, np.int32), np.zeros(0, np.int32), np.zeros(0, np.int32)
         else:
             cut = lambda h: h[b:b + 1, :, :L].contiguous()
-            c, _, e, tick = _heads_to_notes_raw(cut(x), cut(on), cut(off), (thr, othr, kthr), clean, reach)
+            c, _, e, tick = _heads_to_notes_raw(cut(x), cut(on), cut(off), (thr, othr, kthr), clean, reach, peak)
         ons.append(tick)
         offs.append(e * TICKS_PER_FRAME)
         ptrs.append(ptrs[-1][-1] + np.cumsum(c, dtype=np.int64))

@@ -306,22 +306,35 @@ def check_refine_decoder(refine_onsets: bool, decoder: str, refine_reach: int = 
     _check_refine(True, refine_reach, True)
 
 
+def check_detect_decoder(onset_detect: str, decoder: str, peak_reach: int = 1) -> int:
+    """Peaks are picked on the onset head: refuse onset_detect="peak" with the frame decoder (and an unknown detector or a reach outside
+    1..8), before any GPU work -> notes.check_onset_detect's result."""
+    from .notes import check_onset_detect
+    peak = check_onset_detect(onset_detect, peak_reach)
+    if peak and decoder not in HEAD_DECODERS:
+        raise ValueError(f"onset_detect='peak' needs decoder 'onset' or 'onset_offset' (the frame decoder has no onset head to pick peaks "
+                         f"from), got {decoder!r}")
+    return peak
+
+
 @torch.no_grad()
 def transcribe_chunks_to_notes(model: "TranscriptionModel", chunks, threshold: float = THRESHOLD, batch: int = 128, n_mels: int = N_MELS,
                                device: str = "cuda", decoder: str = "frame", onset_threshold: float = THRESHOLD,
                                offset_threshold: float = THRESHOLD, min_note_frames: int = 1,
                                bridge_frames: int = 0, smooth_on: float = 0.0, smooth_off: float = 0.0, refine_onsets: bool = False,
-                               refine_reach: int = 2) -> List[Tuple[int, float, float]]:
+                               refine_reach: int = 2, onset_detect: str = "edge", peak_reach: int = 1) -> List[Tuple[int, float, float]]:
     """(n, 480000) waveform chunks -> notes; mel, forward, threshold, concatenation and run-length all on the GPU.  decoder="onset":
     notes start at rising edges of the onset head and last while frame or onset is active (notes.heads_to_notes_device);
     decoder="onset_offset": those notes, ended where the offset head fires.  min_note_frames / bridge_frames: note
     cleanup in the decoder, any of the three (DESIGN.md 6c "Note cleanup").  smooth_on / smooth_off: the frame head is smoothed before
     any of the three decodes it (DESIGN.md 6c "Frame smoothing").  refine_onsets (onset / onset_offset decoders): note starts are
     sub-frame onsets read off the onset head (DESIGN.md 6c "Sub-frame onsets"); on concatenated chunks the frame grid itself drifts
-    16 ms per chunk, so sub-frame times mean most with overlapping windows."""
+    16 ms per chunk, so sub-frame times mean most with overlapping windows.  onset_detect="peak" (onset / onset_offset decoders): notes
+    start at the peaks of the onset logits over peak_reach frames, not at the onset mask's edges (DESIGN.md 6c "Peak-picked onsets")."""
     from .notes import check_cleanup, check_smoothing
     check_decoder(decoder, model=model)
     check_refine_decoder(refine_onsets, decoder)
+    check_detect_decoder(onset_detect, decoder, peak_reach)
     clean = check_cleanup(min_note_frames, bridge_frames)
     smooth = check_smoothing(smooth_on, smooth_off)
     with_heads, with_offset = decoder in HEAD_DECODERS, decoder == "onset_offset"
@@ -346,7 +359,7 @@ def transcribe_chunks_to_notes(model: "TranscriptionModel", chunks, threshold: f
         notes = heads_to_notes_device(torch.cat(outs), torch.cat(onsets), threshold, onset_threshold, SR / HOP_LENGTH,
                                       offset_logits=torch.cat(offsets) if with_offset else None, offset_threshold=offset_threshold,
                                       min_note_frames=clean[0], bridge_frames=clean[1], smooth_on=smooth[0], smooth_off=smooth[1],
-                                      refine_onsets=refine_onsets, refine_reach=refine_reach)
+                                      refine_onsets=refine_onsets, refine_reach=refine_reach, onset_detect=onset_detect, peak_reach=peak_reach)
     else:
         notes = notes_from_logits_device(torch.cat(outs), threshold, SR / HOP_LENGTH, min_note_frames=clean[0], bridge_frames=clean[1],
                                          smooth_on=smooth[0], smooth_off=smooth[1])
@@ -421,16 +434,19 @@ def transcribe_windows_to_notes(model: "TranscriptionModel", y: torch.Tensor, ov
                                 n_mels: int = N_MELS, decoder: str = "frame", onset_threshold: float = THRESHOLD,
                                 offset_threshold: float = THRESHOLD, min_note_frames: int = 1,
                                 bridge_frames: int = 0, smooth_on: float = 0.0, smooth_off: float = 0.0, refine_onsets: bool = False,
-                                refine_reach: int = 2) -> List[Tuple[int, float, float]]:
+                                refine_reach: int = 2, onset_detect: str = "edge",
+                                peak_reach: int = 1) -> List[Tuple[int, float, float]]:
     """1-D device recording -> notes decoded from ONE (1, 88, 1 + n // 512) logit roll on the recording's frame grid, stitched from
     overlapping 30 s windows (windows.transcribe_windows): no per-chunk drift, no cold chunk edges inside the recording.
     min_note_frames / bridge_frames: note cleanup in the decoder (DESIGN.md 6c "Note cleanup"); smooth_on / smooth_off: the frame head
     is smoothed first (DESIGN.md 6c "Frame smoothing"); refine_onsets (onset / onset_offset decoders): note starts are sub-frame
-    onsets read off the onset head (DESIGN.md 6c "Sub-frame onsets")."""
+    onsets read off the onset head (DESIGN.md 6c "Sub-frame onsets"); onset_detect="peak" (the same decoders): note starts are the peaks
+    of the onset logits over peak_reach frames (DESIGN.md 6c "Peak-picked onsets")."""
     from .notes import check_cleanup, check_smoothing
     from .windows import transcribe_windows
     check_decoder(decoder, model=model)
     check_refine_decoder(refine_onsets, decoder)
+    check_detect_decoder(onset_detect, decoder, peak_reach)
     clean = check_cleanup(min_note_frames, bridge_frames)
     smooth = check_smoothing(smooth_on, smooth_off)
     with_offset = decoder == "onset_offset"
@@ -440,7 +456,7 @@ def transcribe_windows_to_notes(model: "TranscriptionModel", y: torch.Tensor, ov
         return heads_to_notes_device(heads[0][None], heads[1][None], threshold, onset_threshold, SR / HOP_LENGTH,
                                      offset_logits=heads[2][None] if with_offset else None, offset_threshold=offset_threshold,
                                      min_note_frames=clean[0], bridge_frames=clean[1], smooth_on=smooth[0], smooth_off=smooth[1],
-                                     refine_onsets=refine_onsets, refine_reach=refine_reach)
+                                     refine_onsets=refine_onsets, refine_reach=refine_reach, onset_detect=onset_detect, peak_reach=peak_reach)
     return notes_from_logits_device(heads[None], threshold, SR / HOP_LENGTH, min_note_frames=clean[0], bridge_frames=clean[1],
                                     smooth_on=smooth[0], smooth_off=smooth[1])
 
@@ -448,14 +464,16 @@ def transcribe_windows_to_notes(model: "TranscriptionModel", y: torch.Tensor, ov
 def transcribe_audio(audio_path: str, model_path: str, output_path=None, device=None, threshold: float = THRESHOLD, decoder: str = "frame",
                      onset_threshold: float = THRESHOLD, overlap: float = 0.0, offset_threshold: float = THRESHOLD, min_note_frames: int = 1,
                      bridge_frames: int = 0, smooth_on: float = 0.0, smooth_off: float = 0.0, refine_onsets: bool = False,
-                     refine_reach: int = 2, **model_kw):
+                     refine_reach: int = 2, onset_detect: str = "edge", peak_reach: int = 1, **model_kw):
     """overlap = 0: the reference's chunk concatenation (main.py:60-100, :164-186); overlap > 0 (seconds): overlapping windows
     stitched on the recording's own frame grid (transcribe_windows_to_notes).  smooth_on / smooth_off: frame smoothing before the
     decoder, in either mode (DESIGN.md 6c "Frame smoothing").  refine_onsets: sub-frame note starts from the onset head, in either
-    mode, with the onset and onset_offset decoders (DESIGN.md 6c "Sub-frame onsets")."""
+    mode, with the onset and onset_offset decoders (DESIGN.md 6c "Sub-frame onsets").  onset_detect="peak", peak_reach: peak-picked
+    note starts, in either mode, with the same two decoders (DESIGN.md 6c "Peak-picked onsets")."""
     from .notes import check_cleanup, check_smoothing
     check_decoder(decoder, model_type=model_kw.get("model_type", MODEL_TYPE))
     check_refine_decoder(refine_onsets, decoder, refine_reach)
+    check_detect_decoder(onset_detect, decoder, peak_reach)
     clean = check_cleanup(min_note_frames, bridge_frames)    # refused before any GPU work, like the decoder
     smooth = check_smoothing(smooth_on, smooth_off)
     if overlap:
@@ -474,14 +492,14 @@ def transcribe_audio(audio_path: str, model_path: str, output_path=None, device=
         notes = transcribe_windows_to_notes(model, y, overlap, threshold, n_mels=model_kw.get("n_mels", N_MELS), decoder=decoder,
                                             onset_threshold=onset_threshold, offset_threshold=offset_threshold, min_note_frames=clean[0],
                                             bridge_frames=clean[1], smooth_on=smooth[0], smooth_off=smooth[1], refine_onsets=refine_onsets,
-                                            refine_reach=refine_reach)
+                                            refine_reach=refine_reach, onset_detect=onset_detect, peak_reach=peak_reach)
     else:
         chunks, duration = split_into_chunks_device(y)
         print(f"Audio duration: {duration:.2f} seconds; {len(chunks)} chunks of {CHUNK_LENGTH}s")
         notes = transcribe_chunks_to_notes(model, chunks, threshold, n_mels=model_kw.get("n_mels", N_MELS), device=device, decoder=decoder,
                                            onset_threshold=onset_threshold, offset_threshold=offset_threshold, min_note_frames=clean[0],
                                            bridge_frames=clean[1], smooth_on=smooth[0], smooth_off=smooth[1], refine_onsets=refine_onsets,
-                                           refine_reach=refine_reach)
+                                           refine_reach=refine_reach, onset_detect=onset_detect, peak_reach=peak_reach)
     if output_path is None:
         p = Path(audio_path)
         output_path = p.parent / f"{p.stem}_transcription.mid"

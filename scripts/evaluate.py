@@ -27,6 +27,9 @@ decoder together, with any --decoder: its thresholds (frame; onset; offset) and 
 `--tune_note_decoder --tune_smooth_on 0 1 2 --tune_smooth_off 0 1 2` tunes the two penalties with everything else: every pair of the
 two lists is one more candidate of each round's grid (one packed-path launch per group and tile of 16 frame candidates), and the
 note metrics are reported at the chosen pair.
+`--note_metrics --decoder onset|onset_offset --onset_detect peak [--peak_reach N]` opens the notes at the local maxima of the onset
+logits, not at the rising edges of the thresholded onset head (DESIGN.md 6c "Peak-picked onsets"); with cleanup, smoothing,
+--window_overlap and --refine_onsets as before, not with the tuners.
 `--note_metrics --note_reference midi --decoder onset|onset_offset --refine_onsets [--refine_reach N]` gives every decoded note a
 sub-frame onset (notes.refine_onsets_device), copies the note lists to the host and scores them there in ticks of 100 us
 (notes.note_match_ticks); the same EVAL_NOTE_* lines.  Cleanup and smoothing flags stay allowed; the tuners are refused.
@@ -97,6 +100,15 @@ def main():
     ap.add_argument("--refine_reach", type=int, default=2,
                     help="--refine_onsets: frames the peak search may walk from a note's first frame (0..8; default 2 = the default "
                          "--onset_width of training)")
+    ap.add_argument("--onset_detect", choices=["edge", "peak"], default="edge",
+                    help="with --note_metrics --decoder onset / onset_offset: where a note opens.  edge (default): at every rising edge of "
+                         "the thresholded onset head; peak: at every local maximum of the onset logits within --peak_reach frames that "
+                         "passes the onset threshold (for a head trained with train_cnn.py --onset_target regress, whose triangles the "
+                         "edge rule merges when a key is re-struck within --onset_width frames).  Not with the three tuners: the sweep "
+                         "and grid kernels have no peak mode")
+    ap.add_argument("--peak_reach", type=int, default=1,
+                    help="--onset_detect peak: a peak must be the largest logit of this many frames on either side (1..8; default 1); "
+                         "peaks are then more than this many frames apart")
     ap.add_argument("--window_overlap", type=float, default=None,
                     help="full files only: run every recording in overlapping 30 s windows (this many seconds of overlap, 0.256 to 15) "
                          "stitched on its own frame grid, instead of one recurrence over the whole file; lifts the T * hidden_size < 2^24 "
@@ -191,6 +203,17 @@ def main():
                          "without it, then evaluate with it at the values reported")
         if not 0 <= args.refine_reach <= 8:
             ap.error("--refine_reach must lie in 0..8 frames")
+    if args.onset_detect != "edge" or args.peak_reach != 1:
+        if not args.note_metrics:
+            ap.error("--onset_detect / --peak_reach choose where the notes of --note_metrics open and need that flag")
+        if args.decoder not in ("onset", "onset_offset"):
+            ap.error("--onset_detect / --peak_reach read the onset head and need --decoder onset or onset_offset")
+        for flag in ("tune_threshold", "tune_note_thresholds", "tune_note_decoder"):
+            if getattr(args, flag):
+                ap.error(f"--onset_detect / --peak_reach cannot be combined with --{flag}: peak detection inside the sweep and grid "
+                         "kernels is out of scope; tune with the edge rule, then evaluate with peaks at the values reported")
+        if not 1 <= args.peak_reach <= 8:
+            ap.error("--peak_reach must lie in 1..8 frames (--onset_detect peak)")
     say = (lambda *a, **k: None) if args.headless else print
 
     if args.note_reference == "midi" and args.data_source != "full":
@@ -316,7 +339,8 @@ def main():
                                        note_reference=args.note_reference, offset_threshold=note_offset_threshold,
                                        min_note_frames=min_note_frames, bridge_frames=bridge_frames, smooth_on=smooth_on,
                                        smooth_off=smooth_off, **(dict(refine_onsets=True, refine_reach=args.refine_reach)
-                                                                 if args.refine_onsets else {}))
+                                                                 if args.refine_onsets else {}),
+                                       **(dict(onset_detect="peak", peak_reach=args.peak_reach) if args.onset_detect == "peak" else {}))
     if rank == 0:
         if args.headless:
             print(f"EVAL_MEAN_F1={mean_f1:.6f}")

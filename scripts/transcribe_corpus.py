@@ -54,6 +54,12 @@ def main():
                          "--smooth-off 0, the default = no smoothing); the penalties --tune_smooth_on / --tune_smooth_off of "
                          "scripts/evaluate.py chose apply here as they are")
     ap.add_argument("--smooth-off", type=float, default=0.0, help="frame smoothing: the same for switching a pitch off (0 to 64)")
+    ap.add_argument("--onset-detect", choices=["edge", "peak"], default="edge",
+                    help="--decoder onset: where a note opens.  edge (default): at every rising edge of the thresholded onset head; peak: "
+                         "at every local maximum of the onset logits within --peak-reach frames that passes --onset-threshold (a head "
+                         "trained with train_cnn.py --onset_target regress); --note-metrics scores the same notes")
+    ap.add_argument("--peak-reach", type=int, default=1,
+                    help="--onset-detect peak: a peak must be the largest logit of this many frames on either side (1..8; default 1)")
     ap.add_argument("--note-metrics", action="store_true",
                     help="also score notes against the runs of the reference roll (onset / onset+offset F1, mir_eval's criteria on the "
                          "32 ms grid): adds mean_note_onset_f1 / mean_note_onset_offset_f1 to the JSON line")
@@ -71,6 +77,10 @@ def main():
         from music_transcription_amd.notes import check_smoothing, cleanup_frames
         clean = dict(zip(("min_note_frames", "bridge_frames"), cleanup_frames(args.min_note_ms, args.bridge_gap_ms)))
         clean.update(zip(("smooth_on", "smooth_off"), check_smoothing(args.smooth_on, args.smooth_off)))
+        if args.onset_detect != "edge" or args.peak_reach != 1:
+            from music_transcription_amd.transcribe import check_detect_decoder
+            check_detect_decoder("peak", args.decoder, args.peak_reach)
+            clean.update(onset_detect=args.onset_detect, peak_reach=args.peak_reach)
     except ValueError as e:
         ap.error(str(e))
 

@@ -13,8 +13,11 @@ points) reads one array more, offset logits that mark the last active frame of e
 onset-gated entry point's in the same run (expected about 4/3 for the roll matcher, 3/2 for the list matcher and the note lists).
 The four cleaning kernels (mt_*_clean, DESIGN.md 6c "Note cleanup") run last, onset-gated at (min_note_frames, bridge_frames) = CLEAN: "*_clean" beside
 its counterpart of the same run, `over_plain` = its time over the counterpart's; they read the same bytes.
+`--onset-detect peak` adds the peak-picking kernels (mt_*_peak, DESIGN.md 6c "Peak-picked onsets") at reach 1 and 8, onset-gated without
+cleanup: "*_peak_r<R>" beside "*_clean_1_0", the _clean entry point at (1, 0) in the same process on the same logits, `peak_over_edge` =
+its time over that one's.  The same kernels but for where a note opens, the same bytes.
 
-    python tools/note_metrics_bench.py [--iters 50] [--out note_metrics.json]
+    python tools/note_metrics_bench.py [--iters 50] [--onset-detect peak] [--out note_metrics.json]
 """
 import argparse
 import json
@@ -180,6 +183,42 @@ def time_clean(out, frame, onset, ref, notes, lengths, iters):
         raise SystemExit(f"{out['case']} ({key}): another number of notes than the cleaning matcher: {out}")
 
 
+PEAK_REACHES = (1, 8)
+
+
+def time_peak(out, frame, onset, ref, notes, lengths, iters):
+    """The peak-picking entry points beside their _clean namesakes at (1, 0), called directly: the two matchers on both shapes,
+    mt_heads_to_notes_* on the chunks, mt_notes_batch_* on the recordings."""
+    import torch
+    from music_transcription_amd import _lib
+    B, P, T = frame.shape
+    dev = frame.device
+    lib, ptr, st = _lib.lib, _lib.ptr, _lib.stream_ptr()
+    ln = None if lengths is None else torch.tensor(lengths, dtype=torch.int64, device=dev)
+    c4 = torch.empty(B, 4, dtype=torch.int64, device=dev)
+    cap = B * P * T // 2 + 1
+    starts, ends = torch.empty(cap, dtype=torch.int32, device=dev), torch.empty(cap, dtype=torch.int32, device=dev)
+    heads = (ptr(frame), ptr(onset), None, 0.5, 0.5, 0.5)
+    families = [("note_match_counts", lambda f, tail: f(*heads, ptr(ref), ptr(ln), ptr(c4), B, P, T, 1, 0, *tail, st)),
+                ("note_match_list", lambda f, tail: f(*heads, ptr(notes["on"]), ptr(notes["off"]), ptr(notes["ptr"]), ptr(ln), ptr(c4), B, P, T, 1, 0,
+                                                      *tail, st))]
+    if lengths is None:
+        counts = torch.empty(P, dtype=torch.int32, device=dev)
+        families.append(("heads_to_notes", lambda f, tail: f(*heads, B, P, T, ptr(counts), ptr(starts), ptr(ends), cap, 1, 0, *tail, st)))
+    else:
+        counts, row_off = torch.empty(B * P, dtype=torch.int32, device=dev), torch.empty(B * P + 1, dtype=torch.int64, device=dev)
+        families.append(("notes_batch", lambda f, tail: f(ptr(frame), ptr(onset), 0.5, 0.5, ptr(ln), B, P, T, ptr(counts), ptr(row_off),
+                                                          ptr(starts), ptr(ends), cap, 1, 0, *tail, st)))
+    for family, call in families:
+        edge = getattr(lib, f"mt_{family}_clean")
+        base = device_ms(lambda: _lib.check(call(edge, ())), iters)
+        out[f"{family}_clean_1_0"] = {"ms": round(base, 4)}
+        for R in PEAK_REACHES:
+            peak = getattr(lib, f"mt_{family}_peak")
+            ms = device_ms(lambda: _lib.check(call(peak, (R,))), iters)
+            out[f"{family}_peak_r{R}"] = {"ms": round(ms, 4), "peak_over_edge": round(ms / base, 3)}
+
+
 def roll_notes(ref):
     """The runs of the (B, P, T) roll as a note list in ticks (320 per frame) on the device: {"on", "off", "ptr"}."""
     import torch
@@ -192,7 +231,7 @@ def roll_notes(ref):
     return {"on": (320 * s).int().contiguous(), "off": (320 * e).int().contiguous(), "ptr": ptr}
 
 
-def time_case(name, frame, onset, ref, lengths, iters):
+def time_case(name, frame, onset, ref, lengths, iters, peak=False):
     from music_transcription_amd.notes import note_match_counts, note_match_list
     B, P, T = frame.shape
     valid = B * T if lengths is None else int(sum(lengths))
@@ -222,12 +261,16 @@ def time_case(name, frame, onset, ref, lengths, iters):
     if lengths is not None:
         time_notes_batch(out, frame, onset, lengths, iters)
     time_clean(out, frame, onset, ref, notes, lengths, iters)
+    if peak:
+        time_peak(out, frame, onset, ref, notes, lengths, iters)
     return out
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--onset-detect", choices=["edge", "peak"], default="edge",
+                    help="peak: also time the mt_*_peak entry points beside their _clean namesakes at (1, 0)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
@@ -237,12 +280,12 @@ def main():
     dev = "cuda"
     res = []
     frame, onset, ref = make_case(128, 88, 938, None, 1, dev)
-    res.append(time_case("chunks 128 x 88 x 938", frame, onset, ref, None, args.iters))
+    res.append(time_case("chunks 128 x 88 x 938", frame, onset, ref, None, args.iters, args.onset_detect == "peak"))
     minutes = np.random.default_rng(2).uniform(10.0, 25.0, size=8)
     minutes[0] = 25.0
     lengths = [int(m * 60 * FS) for m in minutes]
     frame, onset, ref = make_case(8, 88, max(lengths), lengths, 3, dev)
-    res.append(time_case("recordings 8 x 10-25 min, padded", frame, onset, ref, lengths, args.iters))
+    res.append(time_case("recordings 8 x 10-25 min, padded", frame, onset, ref, lengths, args.iters, args.onset_detect == "peak"))
     res[-1]["lengths"] = lengths
     for r in res:
         print(json.dumps(r))
