@@ -683,6 +683,29 @@ int    mt_note_grid_list_paths(const unsigned long long* paths, int Kf, const fl
                                const float* thr_onset, int Ko, const float* thr_offset, int Kk, const int* clean, int Kc, const int* ref_on,
                                const int* ref_off, const long long* ref_ptr, const long long* lengths, unsigned long long* counts, int B,
                                int P, int T, mt_stream_t stream);
+/* Peak-picked onsets inside the decoder grid (DESIGN.md 6c "Peak picking in the decoder grid"): the four grid entry points with one
+ * more axis, Kr candidate reaches (peak_reach: a HOST array of Kr ints, taken by value at the call).  counts[b][i][j][k][c][r]
+ * (uint64 [B][Kf][Ko][Kk][Kc][Kr][4], zeroed on the stream) is bit for bit what mt_note_match_counts_peak / mt_note_match_list_peak
+ * returns at peak_reach[r] and the cell's other parameters (on paths: on the activity the paths stand for), and for peak_reach[r] == 0
+ * (the edge rule) what the namesake without _peak puts into the cell.  onset_logits is required; 1 <= Kr <= 16, every reach in 0..8,
+ * Kf * Ko * Kk * Kc * Kr <= 64; the other arguments, limits and refusals are the namesake's.  Any violation: MT_EINVAL before the
+ * first device call, nothing written. */
+int    mt_note_grid_counts_peak(const float* frame_logits, const float* onset_logits, const float* offset_logits, const float* thr_frame,
+                                int Kf, const float* thr_onset, int Ko, const float* thr_offset, int Kk, const int* clean, int Kc,
+                                const int* peak_reach, int Kr, const float* ref_roll, const long long* lengths, unsigned long long* counts,
+                                int B, int P, int T, mt_stream_t stream);
+int    mt_note_grid_list_peak(const float* frame_logits, const float* onset_logits, const float* offset_logits, const float* thr_frame,
+                              int Kf, const float* thr_onset, int Ko, const float* thr_offset, int Kk, const int* clean, int Kc,
+                              const int* peak_reach, int Kr, const int* ref_on, const int* ref_off, const long long* ref_ptr,
+                              const long long* lengths, unsigned long long* counts, int B, int P, int T, mt_stream_t stream);
+int    mt_note_grid_counts_paths_peak(const unsigned long long* paths, int Kf, const float* onset_logits, const float* offset_logits,
+                                      const float* thr_onset, int Ko, const float* thr_offset, int Kk, const int* clean, int Kc,
+                                      const int* peak_reach, int Kr, const float* ref_roll, const long long* lengths,
+                                      unsigned long long* counts, int B, int P, int T, mt_stream_t stream);
+int    mt_note_grid_list_paths_peak(const unsigned long long* paths, int Kf, const float* onset_logits, const float* offset_logits,
+                                    const float* thr_onset, int Ko, const float* thr_offset, int Kk, const int* clean, int Kc,
+                                    const int* peak_reach, int Kr, const int* ref_on, const int* ref_off, const long long* ref_ptr,
+                                    const long long* lengths, unsigned long long* counts, int B, int P, int T, mt_stream_t stream);
 
 /* ------------------------------------------------------------------ optimizer step (training)
  * clip_grad_norm_(max_norm) + torch.optim.Adam with coupled L2 weight decay over flat f32 buffers

@@ -181,6 +181,10 @@ _SIGS = {
     "mt_frame_smooth_paths": (i32, [vp, vp, vp, vp, i32, vp, i32, i32, ll, vp, vp, vp]),
     "mt_note_grid_counts_paths": (i32, [vp, i32, vp, vp, vp, i32, vp, i32, vp, i32, vp, vp, vp, i32, i32, i32, vp]),
     "mt_note_grid_list_paths": (i32, [vp, i32, vp, vp, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "mt_note_grid_counts_peak": (i32, [vp, vp, vp, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, vp, i32, i32, i32, vp]),
+    "mt_note_grid_list_peak": (i32, [vp, vp, vp, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "mt_note_grid_counts_paths_peak": (i32, [vp, i32, vp, vp, vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, vp, i32, i32, i32, vp]),
+    "mt_note_grid_list_paths_peak": (i32, [vp, i32, vp, vp, vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "mt_conv1_stats": (i32, [vp, vp, vp, vp, i32, i32, i32, vp]),
     "mt_bn_finalize": (i32, [vp, C.c_double, vp, vp, vp, vp, C.c_float, C.c_float, vp, vp, i32, vp, vp, vp, vp, i32, vp]),
     "mt_bn_stats_cl": (i32, [vp, ll, i32, vp, vp]),

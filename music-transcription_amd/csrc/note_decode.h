@@ -114,6 +114,12 @@ template <bool OFF>
 struct CarryPeak : CarryClean<OFF> {
     float xo = -__builtin_inff(), xp = -__builtin_inff();
 };
+// The decoder grid's peak instances (DESIGN.md 6c "Peak picking in the decoder grid"): the held window's start mask is built by the
+// caller when the window arrives and waits here for one call, in place of the logits.
+template <bool OFF>
+struct CarryStart : CarryClean<OFF> {
+    unsigned long long st = 0;
+};
 template <bool OFF, bool CLEAN = false, bool PEAK = false>
 using DecodeCarry =
     std::conditional_t<PEAK, CarryPeak<OFF>, std::conditional_t<CLEAN, CarryClean<OFF>, std::conditional_t<OFF, CarryOffset, CarryOnset>>>;
@@ -144,10 +150,15 @@ __device__ __forceinline__ unsigned long long peak_mask(unsigned long long om, f
 // PEAK: xo_n = this lane's onset logit of window w (-inf outside the row) arrives as well, and window w - 1 opens its notes at its
 // peaks (peak_mask over `reach` frames, its neighbours the windows w - 2 and w) instead of at the onset mask's rising edges.  A peak
 // is onset-active, peaks are >= 2 frames apart and bridging does not touch them, so the matchers' premises hold as before.
-template <bool OFF, bool PEAK = false>
+// GIVEN (with PEAK; the decoder grid's peak instances): st_n = the frames of window w where a note opens arrives instead of a logit,
+// a subset of om_n whose members are >= 2 frames apart (its peaks, or its rising edges), and window w - 1 opens its notes at the
+// mask that came with it; xo_n and reach are not read.
+template <bool OFF, bool PEAK = false, bool GIVEN = false>
 __device__ __forceinline__ WindowEvents clean_step(unsigned long long am_n, unsigned long long om_n, unsigned long long km_n, bool has_onset,
-                                                   const NoteClean& cl, int lane, DecodeCarry<OFF, true, PEAK>& c, float xo_n = 0.0f,
-                                                   int reach = 1) {
+                                                   const NoteClean& cl, int lane,
+                                                   std::conditional_t<GIVEN, CarryStart<OFF>, DecodeCarry<OFF, true, PEAK>>& c,
+                                                   float xo_n = 0.0f, int reach = 1, unsigned long long st_n = 0ull) {
+    static_assert(PEAK || !GIVEN, "a given start mask takes the place of the peaks");
     const unsigned long long below = (1ull << lane) - 1ull, above = ~((2ull << lane) - 1ull);      // bits under / over this lane
     // bridge: this lane's inactive run is next - prev - 1 frames long, prev / next = the active frames around it
     const unsigned long long am = c.am, ab = am & below, aa = am & above;
@@ -159,7 +170,10 @@ __device__ __forceinline__ WindowEvents clean_step(unsigned long long am_n, unsi
     const bool a = af >> lane & 1ull, o = has_onset ? (c.om >> lane & 1ull) : a;
     WindowEvents ev;
     unsigned long long pk = 0ull;
-    if constexpr (PEAK) {
+    if constexpr (GIVEN) {
+        pk = c.st;
+        c.st = st_n;
+    } else if constexpr (PEAK) {
         pk = peak_mask(c.om, c.xo, c.xp, xo_n, reach, lane);
         c.xp = c.xo;
         c.xo = xo_n;

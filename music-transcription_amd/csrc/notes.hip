@@ -666,33 +666,47 @@ struct GridArgs {
     int min_frames[SWEEP_MAX_K], bridge[SWEEP_MAX_K];
 };
 
-template <bool LIST, bool OFF>
+struct GridReach {
+    int r[SWEEP_MAX_K];                   // PEAK: the candidate reaches, 0 = the edge rule
+};
+
+template <bool LIST, bool OFF, bool PEAK = false>
 struct GridState {
     std::conditional_t<LIST, ListState, MatchState> s;
     int at;                               // RefCursor::at (LIST)
-    CarryClean<OFF> c;
+    std::conditional_t<PEAK, CarryStart<OFF>, CarryClean<OFF>> c;
 };
 
-template <bool LIST, bool OFF>
-__device__ __forceinline__ void grid_init(GridState<LIST, OFF>& st) {
+template <bool LIST, bool OFF, bool PEAK>
+__device__ __forceinline__ void grid_init(GridState<LIST, OFF, PEAK>& st) {
     if constexpr (LIST) list_init(st.s);
     else match_init(st.s);
     st.at = 0;
-    st.c = CarryClean<OFF>{};
+    st.c = {};
 }
 
 // counts[b][i][j][k][c] += the four counts of pitch row (b, p) = blockIdx.x; i < Kf, j < Ko, k < Kk, c < Kc, Kf Ko Kk Kc <= 64.
 // LIST: against ref_on / ref_off / ref_ptr as note_match_list_kernel, otherwise against the roll `ref` as note_match_kernel, CLEAN both.
-template <bool LIST, bool OFF, bool PATHS>
+// PEAK (the mt_note_grid_*_peak entry points, onset head required; DESIGN.md 6c "Peak picking in the decoder grid"): one more axis,
+// counts[b][i][j][k][c][r] with r < Kr, Kf Ko Kk Kc Kr <= 64: the cell opens its notes at the peaks of the onset logits over
+// reach.r[r] frames, as the PEAK instances of note_match_kernel do, or for a reach of 0 at the onset mask's rising edges, as every other
+// cell of the grid does.  The peaks at (thr_o[j], R) are omask[j] & ridge[R], ridge[R] = the frames whose logit is > every one up to R
+// frames before and >= every one up to R frames after it: no threshold in it, so the wave that stages a window builds ridge for every
+// candidate reach in one loop to the largest, next to the ballots, and a cell pays one AND.  The staging lanes 56..63 / 0..7 also load
+// their frame of the window before / after (-inf outside the row, never loaded), which is all of them a reach <= 8 can see.  Otherwise
+// reach is not read and Kr is 1.
+template <bool LIST, bool OFF, bool PATHS, bool PEAK = false>
 __device__ __forceinline__ void note_grid_rows(const float* __restrict__ frame, const unsigned long long* __restrict__ paths,
                                                const float* __restrict__ onset, const float* __restrict__ offset, const GridArgs& sh, int Kf,
                                                int Ko, int Kk, int Kc, const float* __restrict__ ref, const int* __restrict__ ref_on,
                                                const int* __restrict__ ref_off, const long long* __restrict__ ref_ptr,
-                                               const long long* __restrict__ lengths, unsigned long long* __restrict__ counts, int P, int T) {
-    using State = GridState<LIST, OFF>;
+                                               const long long* __restrict__ lengths, unsigned long long* __restrict__ counts, int P, int T,
+                                               const GridReach* reach = nullptr, int Kr = 1) {
+    using State = GridState<LIST, OFF, PEAK>;
     constexpr int PARK = sizeof(State) / 4;
     __shared__ unsigned long long fmask[NOTE_SLAB][SWEEP_MAX_K], omask[NOTE_SLAB][SWEEP_MAX_K];     // [window][threshold]: active lanes
     __shared__ unsigned long long kmask[OFF ? NOTE_SLAB : 1][SWEEP_MAX_K];
+    __shared__ unsigned long long ridge[PEAK ? NOTE_SLAB : 1][SWEEP_MAX_K];                         // [window][reach]: the ridge mask
     // roll: the windows' activity; their run starts / ends at [GRID_HOLD + window], before them those of the last slab's last windows
     __shared__ unsigned long long rmask[NOTE_SLAB], rstart[GRID_HOLD + NOTE_SLAB], rend[GRID_HOLD + NOTE_SLAB];
     __shared__ int parked[GRID_MAX_CONFIGS][PARK];
@@ -706,8 +720,9 @@ __device__ __forceinline__ void note_grid_rows(const float* __restrict__ frame, 
     if (L <= 0) return;                                        // no frame: no estimate, and no reference note starts below frame 0
     const int end_tick = TICKS_PER_FRAME * L;
     const size_t base = (size_t)row * T;
-    const int n_cfg = Kf * Ko * Kk * Kc;
+    const int n_cfg = Kf * Ko * Kk * Kc * (PEAK ? Kr : 1);
     float xf = 0.0f, xo, xk = 0.0f, xr = 0.0f, xb = 0.0f;      // this wave's window: frame, onset, offset, roll, roll one frame before it
+    float xo_b = 0.0f, xo_n = 0.0f;                            // PEAK: this lane's onset logit one window before / after (the reach's lanes)
     unsigned long long xp = 0;                                 // PATHS: lane i < Kf holds candidate i's word of this wave's window
     const size_t W = ((size_t)T + 63) >> 6;
     const auto load = [&](int s0) {
@@ -716,6 +731,11 @@ __device__ __forceinline__ void note_grid_rows(const float* __restrict__ frame, 
         if constexpr (PATHS) xp = (lane < Kf && g0 < L) ? paths[((size_t)lane * gridDim.x + (size_t)row) * W + (size_t)(g0 >> 6)] : 0ull;
         else xf = in ? frame[base + g] : 0.0f;
         xo = (in && onset) ? onset[base + g] : 0.0f;
+        if constexpr (PEAK) {                                  // a frame outside the row stands in as -inf and is not loaded
+            xo = in ? xo : -__builtin_inff();
+            xo_b = (lane >= 64 - PEAK_MAX_REACH && g >= 64 && g - 64 < L) ? onset[base + g - 64] : -__builtin_inff();
+            xo_n = (lane < PEAK_MAX_REACH && g + 64 < L) ? onset[base + g + 64] : -__builtin_inff();
+        }
         if constexpr (OFF) xk = in ? offset[base + g] : 0.0f;
         if (!LIST) {
             xr = in ? ref[base + g] : 0.0f;
@@ -724,6 +744,12 @@ __device__ __forceinline__ void note_grid_rows(const float* __restrict__ frame, 
     };
     load(0);
     __syncthreads();                                           // sh: the kernel's arguments, staged by its first lines
+    int max_reach = 0;
+    if constexpr (PEAK) {
+#pragma unroll
+        for (int r = 0; r < SWEEP_MAX_K; ++r)
+            if (r < Kr) max_reach = max(max_reach, __builtin_amdgcn_readfirstlane(reach->r[r]));
+    }
     for (int s0 = 0; s0 < L; s0 += 64 * NOTE_SLAB) {
         const bool last = s0 + 64 * NOTE_SLAB >= L;
         {                                                      // stage window `wave` of the slab
@@ -748,6 +774,18 @@ __device__ __forceinline__ void note_grid_rows(const float* __restrict__ frame, 
                         const unsigned long long m = __ballot(in && so > thr_o[j]);
                         if (lane == 0) omask[wave][j] = m;
                     }
+            }
+            if constexpr (PEAK) {                              // peak_mask's comparisons, the mask after every distance kept for its reaches
+                const int my_reach = lane < Kr ? reach->r[lane] : -1;
+                bool rg = true;
+#pragma unroll 1
+                for (int d = 1; d <= max_reach; ++d) {
+                    const float lo = __shfl(lane >= 64 - d ? xo_b : xo, (lane - d) & 63, 64);
+                    const float hi = __shfl(lane < d ? xo_n : xo, (lane + d) & 63, 64);
+                    rg = rg && xo > lo && xo >= hi;
+                    const unsigned long long m = __ballot(rg);
+                    if (my_reach == d) ridge[wave][lane] = m;
+                }
             }
             if constexpr (OFF) {
                 const float sk = logit_sigmoid(xk);
@@ -777,9 +815,11 @@ __device__ __forceinline__ void note_grid_rows(const float* __restrict__ frame, 
         const int n_win = min(NOTE_SLAB, (L - s0 + 63) >> 6);                  // windows of the slab that hold a frame below L
         const int n_pos = last ? n_win + GRID_FLUSH : NOTE_SLAB;               // the row ends with flush_clean's empty windows
         for (int cfg = wave; cfg < n_cfg; cfg += SWEEP_WAVES) {
-            const int ij = cfg / (Kk * Kc), kc = cfg - ij * (Kk * Kc);
+            const int cell = PEAK ? cfg / Kr : cfg, ri = PEAK ? cfg - cell * Kr : 0;
+            const int ij = cell / (Kk * Kc), kc = cell - ij * (Kk * Kc);
             const int i = ij / Ko, j = ij - i * Ko, k = kc / Kc, ci = kc - k * Kc;
             const NoteClean cl{__builtin_amdgcn_readfirstlane(cl_min[ci]), __builtin_amdgcn_readfirstlane(cl_bridge[ci])};
+            const int cell_reach = PEAK ? __builtin_amdgcn_readfirstlane(reach->r[ri]) : 0;
             State st;
             if (s0 == 0) grid_init(st);
             else unpark(st, parked[cfg]);
@@ -787,14 +827,18 @@ __device__ __forceinline__ void note_grid_rows(const float* __restrict__ frame, 
             if constexpr (LIST) cursor_open(r, ref_on, ref_off, ref_ptr, row, st.at, lane);
 #pragma unroll 1
             for (int pos = 0; pos < n_pos; ++pos) {
-                unsigned long long am = 0, om = 0, km = 0;
+                unsigned long long am = 0, om = 0, km = 0, sm = 0;
                 if (pos < n_win) {
                     const unsigned long long fm = uniform64(fmask[pos][i]);
                     om = onset ? uniform64(omask[pos][j]) : fm;
                     am = fm | om;
                     if constexpr (OFF) km = uniform64(kmask[pos][k]);
+                    // the window's starts: its peaks, or at reach 0 decode_window's rising edges (st.c.om = the window before it)
+                    if constexpr (PEAK) sm = cell_reach ? om & uniform64(ridge[pos][ri]) : om & ~((om << 1) | (st.c.om >> 63));
                 }
-                const WindowEvents est = clean_step<OFF>(am, om, km, onset != nullptr, cl, lane, st.c);
+                WindowEvents est;
+                if constexpr (PEAK) est = clean_step<OFF, true, true>(am, om, km, true, cl, lane, st.c, 0.0f, 0, sm);
+                else est = clean_step<OFF>(am, om, km, onset != nullptr, cl, lane, st.c);
                 const int g0 = s0 + 64 * pos - CLEAN_DELAY;
                 if constexpr (LIST) {
                     list_window(st.s, r, est, g0, lane, end_tick);
@@ -863,6 +907,26 @@ __global__ __launch_bounds__(64 * SWEEP_WAVES) void note_paths_grid_kernel(const
     __shared__ GridArgs sh;
     GRID_STAGE_ARGS(sh, args)
     note_grid_rows<LIST, OFF, true>(nullptr, paths, onset, offset, sh, Kf, Ko, Kk, Kc, ref, ref_on, ref_off, ref_ptr, lengths, counts, P, T);
+}
+
+// The peak instances: frame logits (PATHS false, paths == nullptr) or packed paths (frame == nullptr), the candidate reaches beside the
+// other axes.  The onset head is always there.
+template <bool LIST, bool OFF, bool PATHS>
+__global__ __launch_bounds__(64 * SWEEP_WAVES) void note_peak_grid_kernel(const float* __restrict__ frame, const unsigned long long* __restrict__ paths,
+                                                                          const float* __restrict__ onset, const float* __restrict__ offset,
+                                                                          GridArgs args, GridReach reach, int Kf, int Ko, int Kk, int Kc, int Kr,
+                                                                          const float* __restrict__ ref, const int* __restrict__ ref_on,
+                                                                          const int* __restrict__ ref_off, const long long* __restrict__ ref_ptr,
+                                                                          const long long* __restrict__ lengths,
+                                                                          unsigned long long* __restrict__ counts, int P, int T) {
+    __shared__ GridArgs sh;
+    __shared__ GridReach sh_reach;
+    GRID_STAGE_ARGS(sh, args)
+#pragma unroll
+    for (int n = 0; n < SWEEP_MAX_K; ++n)
+        if ((int)threadIdx.x == n) sh_reach.r[n] = reach.r[n];
+    note_grid_rows<LIST, OFF, PATHS, true>(frame, paths, onset, offset, sh, Kf, Ko, Kk, Kc, ref, ref_on, ref_off, ref_ptr, lengths, counts, P, T,
+                                           &sh_reach, Kr);
 }
 
 }  // namespace mt
@@ -1022,16 +1086,34 @@ extern "C" int mt_note_sweep_list(const float* frame_logits, const float* onset_
 
 // The checks the two grid entry points share; thresholds and cleanups end up in `a`, which the kernel takes by value.
 // paths: the frame axis is Kf candidates of packed paths (`frame` points at them) and has no thresholds.
+// peak (the _peak entry points): Kr candidate reaches as one more axis, 0 = the edge rule; they end up in `gr`.
+struct GridPeak {
+    const int* reach = nullptr;
+    int Kr = 1;
+    bool on = false;
+    GridReach gr = {};
+};
+
 static int grid_arguments(const char* who, const void* frame, const float* onset, const float* offset, const float* thr_frame, int Kf,
                           const float* thr_onset, int Ko, const float* thr_offset, int Kk, const int* clean, int Kc, GridArgs& a,
-                          bool paths = false) {
+                          bool paths, GridPeak& pk) {
     MT_REQUIRE(frame, MT_EINVAL, "%s: null pointer", who);
+    if (pk.on) {
+        MT_REQUIRE(onset, MT_EINVAL, "%s: needs onset_logits (the frame decoder has no onset head to pick peaks from)", who);
+        MT_REQUIRE(pk.reach && pk.Kr >= 1 && pk.Kr <= SWEEP_MAX_K, MT_EINVAL, "%s: needs 1 <= Kr <= %d candidate reaches, got %d", who,
+                   SWEEP_MAX_K, pk.Kr);
+        for (int n = 0; n < SWEEP_MAX_K; ++n) {
+            pk.gr.r[n] = n < pk.Kr ? pk.reach[n] : 0;
+            MT_REQUIRE(pk.gr.r[n] >= 0 && pk.gr.r[n] <= PEAK_MAX_REACH, MT_EINVAL, "%s: needs 0 <= peak_reach <= %d (0 = the edge rule), got %d",
+                       who, PEAK_MAX_REACH, pk.gr.r[n]);
+        }
+    }
     MT_REQUIRE(onset || !offset, MT_EINVAL, "%s: offset_logits without onset_logits (the offset-gated decoder opens its notes at onset edges)", who);
     MT_REQUIRE((thr_frame || paths) && (thr_onset || !onset) && (thr_offset || !offset), MT_EINVAL, "%s: null threshold array", who);
     const auto axis_ok = [](int K) { return K >= 1 && K <= SWEEP_MAX_K; };
-    MT_REQUIRE(axis_ok(Kf) && axis_ok(Ko) && axis_ok(Kk) && axis_ok(Kc) && Kf * Ko * Kk * Kc <= GRID_MAX_CONFIGS, MT_EINVAL,
-               "%s: needs 1 <= Kf, Ko, Kk, Kc <= %d and Kf * Ko * Kk * Kc <= %d, got %d, %d, %d, %d", who, SWEEP_MAX_K, GRID_MAX_CONFIGS, Kf, Ko,
-               Kk, Kc);
+    MT_REQUIRE(axis_ok(Kf) && axis_ok(Ko) && axis_ok(Kk) && axis_ok(Kc) && Kf * Ko * Kk * Kc * pk.Kr <= GRID_MAX_CONFIGS, MT_EINVAL,
+               "%s: needs 1 <= Kf, Ko, Kk, Kc <= %d and Kf * Ko * Kk * Kc%s <= %d, got %d, %d, %d, %d%s", who, SWEEP_MAX_K, pk.on ? " * Kr" : "",
+               GRID_MAX_CONFIGS, Kf, Ko, Kk, Kc, pk.on ? " (times Kr)" : "");
     MT_REQUIRE(onset || Ko == 1, MT_EINVAL, "%s: without onset logits (the frame decoder) Ko must be 1, got %d", who, Ko);
     MT_REQUIRE(offset || Kk == 1, MT_EINVAL, "%s: without offset logits Kk must be 1, got %d", who, Kk);
     MT_REQUIRE(clean || Kc == 1, MT_EINVAL, "%s: without a cleanup array (no cleanup: {1, 0}) Kc must be 1, got %d", who, Kc);
@@ -1052,11 +1134,17 @@ static int grid_arguments(const char* who, const void* frame, const float* onset
 template <bool LIST>
 static int note_grid(const char* who, const float* frame, const unsigned long long* paths, const float* onset, const float* offset,
                      const GridArgs& a, int Kf, int Ko, int Kk, int Kc, const float* ref, const int* ref_on, const int* ref_off,
-                     const long long* ref_ptr, const long long* lengths, unsigned long long* counts, int B, int P, int T, mt_stream_t stream) {
+                     const long long* ref_ptr, const long long* lengths, unsigned long long* counts, int B, int P, int T, mt_stream_t stream,
+                     const GridPeak& pk) {
     hipStream_t st = (hipStream_t)stream;
-    MT_CHECK_HIP(hipMemsetAsync(counts, 0, (size_t)B * Kf * Ko * Kk * Kc * 4 * sizeof(unsigned long long), st));
+    MT_CHECK_HIP(hipMemsetAsync(counts, 0, (size_t)B * Kf * Ko * Kk * Kc * pk.Kr * 4 * sizeof(unsigned long long), st));
     const dim3 grid(B * P), block(64 * SWEEP_WAVES);
-    if (paths) {
+    if (pk.on) {
+        const auto kernel = paths ? (offset ? note_peak_grid_kernel<LIST, true, true> : note_peak_grid_kernel<LIST, false, true>)
+                                  : (offset ? note_peak_grid_kernel<LIST, true, false> : note_peak_grid_kernel<LIST, false, false>);
+        hipLaunchKernelGGL(kernel, grid, block, 0, st, frame, paths, onset, offset, a, pk.gr, Kf, Ko, Kk, Kc, pk.Kr, ref, ref_on, ref_off, ref_ptr,
+                           lengths, counts, P, T);
+    } else if (paths) {
         const auto kernel = offset ? note_paths_grid_kernel<LIST, true> : note_paths_grid_kernel<LIST, false>;
         hipLaunchKernelGGL(kernel, grid, block, 0, st, paths, onset, offset, a, Kf, Ko, Kk, Kc, ref, ref_on, ref_off, ref_ptr, lengths, counts, P, T);
     } else {
@@ -1071,30 +1159,30 @@ static int note_grid(const char* who, const float* frame, const unsigned long lo
 static int note_grid_counts(const char* who, const float* frame_logits, const unsigned long long* paths, const float* onset_logits,
                             const float* offset_logits, const float* thr_frame, int Kf, const float* thr_onset, int Ko, const float* thr_offset,
                             int Kk, const int* clean, int Kc, const float* ref_roll, const long long* lengths, unsigned long long* counts, int B,
-                            int P, int T, mt_stream_t stream) {
+                            int P, int T, mt_stream_t stream, GridPeak pk = {}) {
     MT_REQUIRE(ref_roll && counts, MT_EINVAL, "%s: null pointer", who);
     MT_REQUIRE(B > 0 && P > 0 && T > 0 && (long long)B * P < 2147483647ll && T < (1 << 30), MT_EINVAL, "%s: bad dims", who);
     GridArgs a;
     if (const int rc = grid_arguments(who, paths ? (const void*)paths : (const void*)frame_logits, onset_logits, offset_logits, thr_frame, Kf,
-                                      thr_onset, Ko, thr_offset, Kk, clean, Kc, a, paths != nullptr))
+                                      thr_onset, Ko, thr_offset, Kk, clean, Kc, a, paths != nullptr, pk))
         return rc;
     return note_grid<false>(who, frame_logits, paths, onset_logits, offset_logits, a, Kf, Ko, Kk, Kc, ref_roll, nullptr, nullptr, nullptr, lengths,
-                            counts, B, P, T, stream);
+                            counts, B, P, T, stream, pk);
 }
 
 static int note_grid_list(const char* who, const float* frame_logits, const unsigned long long* paths, const float* onset_logits,
                           const float* offset_logits, const float* thr_frame, int Kf, const float* thr_onset, int Ko, const float* thr_offset,
                           int Kk, const int* clean, int Kc, const int* ref_on, const int* ref_off, const long long* ref_ptr,
-                          const long long* lengths, unsigned long long* counts, int B, int P, int T, mt_stream_t stream) {
+                          const long long* lengths, unsigned long long* counts, int B, int P, int T, mt_stream_t stream, GridPeak pk = {}) {
     MT_REQUIRE(ref_on && ref_off && ref_ptr && counts, MT_EINVAL, "%s: null pointer", who);
     MT_REQUIRE(B > 0 && P > 0 && T > 0 && (long long)B * P < 2147483647ll && (long long)T * TICKS_PER_FRAME < 2147483647ll - 64 * NOTE_SLAB,
                MT_EINVAL, "%s: bad dims (frame times must fit 31 bits of 100 us ticks)", who);
     GridArgs a;
     if (const int rc = grid_arguments(who, paths ? (const void*)paths : (const void*)frame_logits, onset_logits, offset_logits, thr_frame, Kf,
-                                      thr_onset, Ko, thr_offset, Kk, clean, Kc, a, paths != nullptr))
+                                      thr_onset, Ko, thr_offset, Kk, clean, Kc, a, paths != nullptr, pk))
         return rc;
     return note_grid<true>(who, frame_logits, paths, onset_logits, offset_logits, a, Kf, Ko, Kk, Kc, nullptr, ref_on, ref_off, ref_ptr, lengths,
-                           counts, B, P, T, stream);
+                           counts, B, P, T, stream, pk);
 }
 
 extern "C" int mt_note_grid_counts(const float* frame_logits, const float* onset_logits, const float* offset_logits, const float* thr_frame, int Kf,
@@ -1128,6 +1216,42 @@ extern "C" int mt_note_grid_list_paths(const unsigned long long* paths, int Kf, 
     MT_REQUIRE(paths, MT_EINVAL, "mt_note_grid_list_paths: null pointer");
     return note_grid_list("mt_note_grid_list_paths", nullptr, paths, onset_logits, offset_logits, nullptr, Kf, thr_onset, Ko, thr_offset, Kk, clean,
                           Kc, ref_on, ref_off, ref_ptr, lengths, counts, B, P, T, stream);
+}
+
+// The four with one more axis, the candidate reaches of peak-picked onsets, 0 = the edge rule (DESIGN.md 6c "Peak picking in the
+// decoder grid"): counts[b][i][j][k][c][r].  onset_logits is required.
+extern "C" int mt_note_grid_counts_peak(const float* frame_logits, const float* onset_logits, const float* offset_logits, const float* thr_frame,
+                                        int Kf, const float* thr_onset, int Ko, const float* thr_offset, int Kk, const int* clean, int Kc,
+                                        const int* peak_reach, int Kr, const float* ref_roll, const long long* lengths,
+                                        unsigned long long* counts, int B, int P, int T, mt_stream_t stream) {
+    return note_grid_counts("mt_note_grid_counts_peak", frame_logits, nullptr, onset_logits, offset_logits, thr_frame, Kf, thr_onset, Ko, thr_offset,
+                            Kk, clean, Kc, ref_roll, lengths, counts, B, P, T, stream, {peak_reach, Kr, true});
+}
+
+extern "C" int mt_note_grid_list_peak(const float* frame_logits, const float* onset_logits, const float* offset_logits, const float* thr_frame,
+                                      int Kf, const float* thr_onset, int Ko, const float* thr_offset, int Kk, const int* clean, int Kc,
+                                      const int* peak_reach, int Kr, const int* ref_on, const int* ref_off, const long long* ref_ptr,
+                                      const long long* lengths, unsigned long long* counts, int B, int P, int T, mt_stream_t stream) {
+    return note_grid_list("mt_note_grid_list_peak", frame_logits, nullptr, onset_logits, offset_logits, thr_frame, Kf, thr_onset, Ko, thr_offset, Kk,
+                          clean, Kc, ref_on, ref_off, ref_ptr, lengths, counts, B, P, T, stream, {peak_reach, Kr, true});
+}
+
+extern "C" int mt_note_grid_counts_paths_peak(const unsigned long long* paths, int Kf, const float* onset_logits, const float* offset_logits,
+                                              const float* thr_onset, int Ko, const float* thr_offset, int Kk, const int* clean, int Kc,
+                                              const int* peak_reach, int Kr, const float* ref_roll, const long long* lengths,
+                                              unsigned long long* counts, int B, int P, int T, mt_stream_t stream) {
+    MT_REQUIRE(paths, MT_EINVAL, "mt_note_grid_counts_paths_peak: null pointer");
+    return note_grid_counts("mt_note_grid_counts_paths_peak", nullptr, paths, onset_logits, offset_logits, nullptr, Kf, thr_onset, Ko, thr_offset,
+                            Kk, clean, Kc, ref_roll, lengths, counts, B, P, T, stream, {peak_reach, Kr, true});
+}
+
+extern "C" int mt_note_grid_list_paths_peak(const unsigned long long* paths, int Kf, const float* onset_logits, const float* offset_logits,
+                                            const float* thr_onset, int Ko, const float* thr_offset, int Kk, const int* clean, int Kc,
+                                            const int* peak_reach, int Kr, const int* ref_on, const int* ref_off, const long long* ref_ptr,
+                                            const long long* lengths, unsigned long long* counts, int B, int P, int T, mt_stream_t stream) {
+    MT_REQUIRE(paths, MT_EINVAL, "mt_note_grid_list_paths_peak: null pointer");
+    return note_grid_list("mt_note_grid_list_paths_peak", nullptr, paths, onset_logits, offset_logits, nullptr, Kf, thr_onset, Ko, thr_offset, Kk,
+                          clean, Kc, ref_on, ref_off, ref_ptr, lengths, counts, B, P, T, stream, {peak_reach, Kr, true});
 }
 
 extern "C" int mt_heads_to_notes(const float* frame_logits, const float* onset_logits, float thr_frame, float thr_onset, int NB, int P, int T,

@@ -16,7 +16,8 @@
   * `tune_note_decoder` = the same schedule over every parameter of the note decoder at once, whichever of the three decoders it
     is: up to three thresholds (frame, onset, offset) times a list of note-cleanup candidates, one grid pass per group and round
     (notes.note_grid_counts).  `search_note_decoder` is the search alone.  `smoothings=` adds a list of frame-smoothing penalty
-    pairs to the candidates of every round: the discrete axis of the search is then cleanups x smoothings.
+    pairs to the candidates of every round: the discrete axis of the search is then cleanups x smoothings.  `peak_reaches=` adds a
+    list of candidate reaches of the peak-picking onset detector, 0 = the edge rule, as its innermost factor.
   * `window_overlap` (seconds, whole-file datasets): every recording runs in overlapping 30 s windows stitched on its own
     frame grid (windows.collect_logits_windows) instead of one recurrence over the whole file;
   * recordings / chunks shard over ranks with no data-path collective (parallel.py); per-sample F1 values are
@@ -203,10 +204,11 @@ def _refuse_smoothing(who: str, smooth_on, smooth_off) -> None:
                          "with it (note_metrics_dataset(..., smooth_on=, smooth_off=))")
 
 
-def _refuse_peak(who: str, onset_detect) -> None:
-    """The tuners run the sweep and grid kernels, which have no peak mode: onset_detect="peak" is refused, before any GPU work."""
+def _refuse_peak(who: str, onset_detect, reaches: bool = False) -> None:
+    """The tuners run the sweep and grid kernels, which have no peak mode to fix: onset_detect="peak" is refused, before any GPU work
+    (reaches: the tuner has peak_reaches=, the grid's axis of candidate reaches, and the message says so)."""
     from .notes import refuse_peak
-    refuse_peak(onset_detect, who)
+    refuse_peak(onset_detect, who, reaches)
 
 
 def _check_note_reference(dataset, note_reference: str) -> None:
@@ -394,11 +396,15 @@ def search_note_decoder(mean_f1, n_axes: int = 3, n_clean: int = 1, tune_range=(
 NOTE_DECODER_AXES = {"frame": 1, "onset": 2, "onset_offset": 3}
 
 
-def decoder_candidate(index: int, cleanups: Sequence, smoothings: Sequence):
-    """Entry `index` of the tuner's discrete axis cleanups x smoothings, cleanup-major -> (cleanup, smoothing)."""
-    if not 0 <= index < len(cleanups) * len(smoothings):
-        raise ValueError(f"index {index} outside {len(cleanups)} x {len(smoothings)} candidates")
-    return cleanups[index // len(smoothings)], smoothings[index % len(smoothings)]
+def decoder_candidate(index: int, cleanups: Sequence, smoothings: Sequence, reaches: Optional[Sequence] = None):
+    """Entry `index` of the tuner's discrete axis cleanups x smoothings, cleanup-major -> (cleanup, smoothing); with reaches, of
+    cleanups x smoothings x reaches, reaches innermost -> (cleanup, smoothing, reach)."""
+    n_reach = 1 if reaches is None else len(reaches)
+    if not 0 <= index < len(cleanups) * len(smoothings) * n_reach:
+        raise ValueError(f"index {index} outside {len(cleanups)} x {len(smoothings)}" + (f" x {n_reach}" if reaches is not None else "")
+                         + " candidates")
+    pair = cleanups[index // n_reach // len(smoothings)], smoothings[index // n_reach % len(smoothings)]
+    return pair if reaches is None else (*pair, reaches[index % n_reach])
 
 
 def fold_smoothings(f1: np.ndarray) -> np.ndarray:
@@ -408,10 +414,19 @@ def fold_smoothings(f1: np.ndarray) -> np.ndarray:
     return np.ascontiguousarray(np.transpose(f1, (0, 1, 3, 4, 5, 2))).reshape(n, Kf, Ko, Kk, Kc * Ks)
 
 
+def fold_reaches(f1: np.ndarray) -> np.ndarray:
+    """(n, Kf, Ks, Ko, Kk, Kc, Kr) values as notes.note_grid_counts(smoothings=..., peak_reaches=...) orders them -> (n, Kf, Ko, Kk,
+    Kc * Ks * Kr), the last axis cleanup-major and reaches innermost: what search_note_decoder takes with n_clean = Kc * Ks * Kr and
+    decoder_candidate(..., reaches) reads back.  Without smoothings: the same on a Ks axis of length 1."""
+    n, Kf, Ks, Ko, Kk, Kc, Kr = f1.shape
+    return np.ascontiguousarray(np.transpose(f1, (0, 1, 3, 4, 5, 2, 6))).reshape(n, Kf, Ko, Kk, Kc * Ks * Kr)
+
+
 def tune_note_decoder(model, dataset, device="cuda", subset: Optional[int] = None, decoder: str = "onset", note_reference: str = "roll",
                       objective: str = "onset", cleanups=((1, 0),), tune_range=(0.05, 0.95), tune_step=0.1, tune_min_step=0.01,
                       tune_rounds=6, rank: int = 0, world: int = 1, log=print, window_overlap: Optional[float] = None, max_batch: int = 128,
-                      smooth_on: float = 0.0, smooth_off: float = 0.0, smoothings=None, onset_detect: str = "edge"):
+                      smooth_on: float = 0.0, smooth_off: float = 0.0, smoothings=None, onset_detect: str = "edge",
+                      peak_reaches=None):
     """Every parameter of the note decoder at once, for the best mean note F1 (`objective`: "onset" or "onset_offset"; unweighted
     mean over samples, as note_metrics_dataset) by search_note_decoder: the thresholds of the heads that `decoder` reads ("frame":
     frame; "onset": frame, onset; "onset_offset": frame, onset, offset) times the candidates `cleanups`, a list of
@@ -423,10 +438,19 @@ def tune_note_decoder(model, dataset, device="cuda", subset: Optional[int] = Non
     part in every round as `cleanups` does: the search's discrete axis is cleanups x smoothings, cleanup-major, every round still one
     note_grid_counts call per group, and the result is (frame threshold, onset threshold or None, offset threshold or None,
     (min_note_frames, bridge_frames), (smooth_on, smooth_off), best mean F1).  A single smoothing (smooth_on, smooth_off) other than
-    (0, 0) is refused either way: the penalties are tuned through `smoothings`, not fixed beside the search.  onset_detect="peak" is
-    refused: the grid kernels decode with the edge rule only."""
-    from .notes import _smoothing_list, check_cleanup, check_smoothing, note_grid_counts, note_prf
-    _refuse_peak("tune_note_decoder", onset_detect)
+    (0, 0) is refused either way: the penalties are tuned through `smoothings`, not fixed beside the search.
+    peak_reaches: a list of candidate reaches in [0, 8] of the peak-picking onset detector, 0 = the edge rule (decoder "onset" or
+    "onset_offset"; DESIGN.md 6c "Peak picking in the decoder grid"), the innermost factor of the discrete axis: cleanups x smoothings x
+    reaches, every round still one note_grid_counts call per group.  The result then names the detector before the best value:
+    (..., (min_note_frames, bridge_frames), [(smooth_on, smooth_off),] (onset_detect, peak_reach), best mean F1), ("edge", 0) or
+    ("peak", R); [R] fixes a reach while the rest is tuned.  A fixed onset_detect="peak" is refused, as a fixed smoothing is."""
+    from .notes import _smoothing_list, check_cleanup, check_peak_reaches, check_smoothing, note_grid_counts, note_prf
+    _refuse_peak("tune_note_decoder", onset_detect, reaches=True)
+    if peak_reaches is not None:
+        if decoder == "frame":
+            raise ValueError("tune_note_decoder: peak_reaches needs decoder 'onset' or 'onset_offset': peaks are picked on the onset head, "
+                             "and the frame decoder has none")
+        reaches = [int(r) for r in check_peak_reaches(peak_reaches)]
     if smoothings is None:
         _refuse_smoothing("tune_note_decoder", smooth_on, smooth_off)
     else:
@@ -452,7 +476,7 @@ def tune_note_decoder(model, dataset, device="cuda", subset: Optional[int] = Non
         if any((t <= 0.0).any() for t in axes):
             raise ValueError("tune_note_decoder: candidate thresholds must be positive (tune_range)")
         below = [np.flatnonzero(np.float32(t) < 1.0) for t in axes]
-        n_disc = len(cleanups) * (1 if smoothings is None else len(smoothings))
+        n_disc = len(cleanups) * (1 if smoothings is None else len(smoothings)) * (1 if peak_reaches is None else len(reaches))
         shape = tuple(len(t) for t in axes) + (n_disc,)
         K = int(np.prod(shape))
         local = np.zeros((len(lr),) + shape)                                               # thresholds >= 1: no notes, F1 0
@@ -461,9 +485,12 @@ def tune_note_decoder(model, dataset, device="cuda", subset: Optional[int] = Non
             fi, oj, kk = below
             for frame, on, ref, lengths, off in _note_groups(lr, dataset, onset, note_reference, max_batch, offset):
                 counts = note_grid_counts(frame, ref, axes[0][fi], on, axes[1][oj] if onset else None, off, axes[2][kk] if offset else None,
-                                          cleanups, lengths, smoothings=smoothings)
+                                          cleanups, lengths, smoothings=smoothings, peak_reaches=None if peak_reaches is None else reaches)
                 f1 = np.array([m[objective][2] for m in note_prf(counts)])
-                if smoothings is None:
+                if peak_reaches is not None:
+                    f1 = fold_reaches(f1.reshape(len(lengths), len(fi), 1 if smoothings is None else len(smoothings), len(oj), len(kk),
+                                                 len(cleanups), len(reaches)))
+                elif smoothings is None:
                     f1 = f1.reshape(len(lengths), len(fi), len(oj), len(kk), len(cleanups))
                 else:
                     f1 = fold_smoothings(f1.reshape(len(lengths), len(fi), len(smoothings), len(oj), len(kk), len(cleanups)))
@@ -473,6 +500,13 @@ def tune_note_decoder(model, dataset, device="cuda", subset: Optional[int] = Non
         allv = gather_values(flat_idx, local.reshape(-1).tolist(), n * K)
         return np.asarray(allv).reshape((n,) + shape).mean(axis=0) if n else np.zeros(shape)
 
+    if peak_reaches is not None:
+        smooths = [(0.0, 0.0)] if smoothings is None else smoothings
+        thr, othr, kthr, d, best = search_note_decoder(mean_f1, n_axes, len(cleanups) * len(smooths) * len(reaches), tune_range, tune_step,
+                                                       tune_min_step, tune_rounds, log)
+        clean, smooth, reach = decoder_candidate(d, cleanups, smooths, reaches)
+        detect = ("peak" if reach else "edge", reach)
+        return (thr, othr, kthr, clean, detect, best) if smoothings is None else (thr, othr, kthr, clean, smooth, detect, best)
     if smoothings is None:
         thr, othr, kthr, c, best = search_note_decoder(mean_f1, n_axes, len(cleanups), tune_range, tune_step, tune_min_step, tune_rounds, log)
         return thr, othr, kthr, cleanups[c], best

@@ -33,10 +33,13 @@
   * `onset_detect="peak"`, `peak_reach=R` on the two matchers and the note-list calls = a note opens at every local maximum of the
     onset logits over R frames that passes the onset threshold, not at the rising edges of the thresholded onset mask (DESIGN.md 6c
     "Peak-picked onsets"; the mt_*_peak entry points): the detector for an onset head trained against triangular targets, on which
-    the edge rule merges re-struck keys.  "edge" calls exactly the entry points above.  The sweep and grid kernels have no peak mode.
+    the edge rule merges re-struck keys.  "edge" calls exactly the entry points above.  The sweep kernel has no peak mode.
+  * `peak_reaches=` on `note_grid_counts` = a list of candidate reaches as the grid's last axis, 0 = the edge rule, so one pass scores
+    both detectors (the mt_note_grid_*_peak entry points; DESIGN.md 6c "Peak picking in the decoder grid").
 """
 from __future__ import annotations
 
+import itertools
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -145,11 +148,27 @@ def check_onset_detect(onset_detect="edge", peak_reach=1, has_onset: bool = True
     return int(peak_reach)
 
 
-def refuse_peak(onset_detect, who: str) -> None:
-    """The calls that run the sweep and grid kernels take onset_detect only to refuse "peak": those kernels have no peak mode."""
+def refuse_peak(onset_detect, who: str, reaches: bool = False) -> None:
+    """The calls that run the sweep and grid kernels take onset_detect only to refuse "peak": the sweep kernel has no peak mode, and the
+    grid's is an axis of candidate reaches (reaches=True: the call has a peak_reaches= argument, which the message names)."""
     if check_onset_detect(onset_detect):
         raise ValueError(f"{who}: onset_detect='peak' is not supported here: peak detection inside the sweep and grid kernels is out of "
-                         "scope (they decode with the edge rule only); tune with 'edge' or score single configurations")
+                         "scope (they decode with the edge rule only); tune with 'edge' or score single configurations"
+                         + ("; peak_reaches= is the way in: a list of candidate reaches as one more axis of the grid, 0 = the edge rule"
+                            if reaches else ""))
+
+
+def check_peak_reaches(peak_reaches, has_onset: bool = True) -> np.ndarray:
+    """The checked candidate reaches of a decoder grid -> int32 array: a non-empty list of integers in [0, 8], 0 = the edge rule, R >= 1 =
+    onset_detect="peak" at peak_reach=R (DESIGN.md 6c "Peak picking in the decoder grid").  Raises before any GPU work."""
+    if isinstance(peak_reaches, (str, bytes)) or not hasattr(peak_reaches, "__len__") or len(peak_reaches) == 0:
+        raise ValueError(f"peak_reaches: expected a non-empty list of reaches in [0, {MAX_PEAK_REACH}], got {peak_reaches!r}")
+    for r in peak_reaches:
+        if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or not 0 <= r <= MAX_PEAK_REACH:
+            raise ValueError(f"peak_reaches: a reach is an integer number of frames in [0, {MAX_PEAK_REACH}] (0 = the edge rule), got {r!r}")
+    if not has_onset:
+        raise ValueError("peak_reaches: peaks are picked on the onset head, and the frame decoder has none (pass onset_logits)")
+    return np.asarray([int(r) for r in peak_reaches], dtype=np.int32)
 
 
 MAX_SMOOTH_PENALTY = 64.0                           # logits; csrc/smooth.hip counts evidence in steps of 1/64 logit, capped at +-64 logits
@@ -434,7 +453,7 @@ GRID_MAX_K, GRID_MAX_CONFIGS = 16, 64              # mt_note_grid_*: values per 
 
 def note_grid_counts(frame_logits: torch.Tensor, ref, thresholds, onset_logits: Optional[torch.Tensor] = None, onset_thresholds=None,
                      offset_logits: Optional[torch.Tensor] = None, offset_thresholds=None, cleanups=None, lengths=None,
-                     smoothings=None, onset_detect: str = "edge") -> torch.Tensor:
+                     smoothings=None, onset_detect: str = "edge", peak_reaches=None) -> torch.Tensor:
     """note_match_counts (ref = a (B, P, T) roll) or note_match_list (ref = the {"on", "off", "ptr"} note list) at every cell of
     `thresholds` x `onset_thresholds` x `offset_thresholds` x `cleanups` -> (B, Kf, Ko, Kk, Kc, 4) int64 device tensor; [b, i, j, k, c]
     is exactly what the single call returns at (thresholds[i], onset_thresholds[j], offset_thresholds[k]) with (min_note_frames,
@@ -448,8 +467,14 @@ def note_grid_counts(frame_logits: torch.Tensor, ref, thresholds, onset_logits: 
     well.  The Kf * Ks frame candidates are cut into tiles of at most 16; per tile one mt_frame_smooth_paths launch packs their Viterbi
     paths into bit masks (smooth_frame_paths), which mt_note_grid_counts_paths / mt_note_grid_list_paths read as their frame axis in
     place of thresholds (DESIGN.md 6c "Smoothing in the decoder grid").  (0, 0) goes the same way: its path is the threshold's
-    activity.  None: no such axis, and the calls above.  onset_detect: "edge" only; the grid kernels have no peak mode and "peak" raises."""
-    refuse_peak(onset_detect, "note_grid_counts")
+    activity.  None: no such axis, and the calls above.
+    peak_reaches: a non-empty list of integers in [0, 8] (needs onset_logits) adds a last axis Kr before the 4 counts -> (B, Kf, Ko, Kk,
+    Kc, Kr, 4), with smoothings (B, Kf, Ks, Ko, Kk, Kc, Kr, 4); [..., r, :] is exactly what the single call returns at
+    onset_detect="peak", peak_reach=peak_reaches[r] and the cell's other parameters, and for a reach of 0 the edge call (the
+    mt_note_grid_*_peak entry points; DESIGN.md 6c "Peak picking in the decoder grid").  None: no such axis, and the calls above.
+    onset_detect: "edge" only; "peak" raises, the detector being an axis of the grid (peak_reaches) and not a mode of it."""
+    refuse_peak(onset_detect, "note_grid_counts", reaches=True)
+    reach = None if peak_reaches is None else check_peak_reaches(peak_reaches, onset_logits is not None)
     if offset_logits is not None and onset_logits is None:
         raise ValueError("offset_logits: the offset-gated decoder needs onset_logits as well")
     x = _rows(frame_logits, "frame_logits")
@@ -481,50 +506,54 @@ def note_grid_counts(frame_logits: torch.Tensor, ref, thresholds, onset_logits: 
         if roll.shape != x.shape:
             raise ValueError(f"shape mismatch: frame {tuple(x.shape)}, ref {tuple(roll.shape)}")
     ln = _lengths(lengths, B, dev)
-    Ko, Kk, Kc = len(to), len(tk), len(cl)
-    kc = min(Kc, GRID_MAX_K)                                 # tiles of kf x ko x kk x kc <= 64, the inner axes as wide as they go
-    kk = min(Kk, GRID_MAX_K, GRID_MAX_CONFIGS // kc)
-    ko = min(Ko, GRID_MAX_K, GRID_MAX_CONFIGS // (kc * kk))
+    Ko, Kk, Kc, Kr = len(to), len(tk), len(cl), 1 if reach is None else len(reach)
+    kr = min(Kr, GRID_MAX_K)                                 # tiles of kf x ko x kk x kc x kr <= 64, the inner axes as wide as they go
+    kc = min(Kc, GRID_MAX_K, GRID_MAX_CONFIGS // kr)
+    kk = min(Kk, GRID_MAX_K, GRID_MAX_CONFIGS // (kr * kc))
+    ko = min(Ko, GRID_MAX_K, GRID_MAX_CONFIGS // (kr * kc * kk))
+    tail = (4,) if reach is None else (Kr, 4)                # a result's last axes
 
     def tiles(out, head):
-        """Fill out (B, Kf, Ko, Kk, Kc, 4) tile by tile; head(i0, n) = the arguments of entries i0 .. i0 + n of the frame axis (those
+        """Fill out (B, Kf, Ko, Kk, Kc, *tail) tile by tile; head(i0, n) = the arguments of entries i0 .. i0 + n of the frame axis (those
         before thr_onset) and the suffix of the entry points that take them."""
         Kf = out.shape[1]
-        kf = min(Kf, GRID_MAX_K, GRID_MAX_CONFIGS // (kc * kk * ko))
-        for i0 in range(0, Kf, kf):
-            for j0 in range(0, Ko, ko):
-                for k0 in range(0, Kk, kk):
-                    for c0 in range(0, Kc, kc):
-                        n = min(kf, Kf - i0)
-                        b, k, c = (np.ascontiguousarray(v) for v in (to[j0:j0 + ko], tk[k0:k0 + kk], cl[c0:c0 + kc]))
-                        whole = (n, len(b), len(k), len(c)) == (Kf, Ko, Kk, Kc) and out.is_contiguous()
-                        t = out if whole else torch.empty(B, n, len(b), len(k), len(c), 4, dtype=torch.int64, device=dev)
-                        first, suffix = head(i0, n)
-                        axes = (*first, b.ctypes.data if on is not None else None, len(b), k.ctypes.data if off is not None else None, len(k),
-                                c.ctypes.data, len(c))
-                        if as_list:
-                            name = "mt_note_grid_list" + suffix
-                            check(getattr(lib, name)(*axes, ptr(r_on), ptr(r_off), ptr(r_ptr), ptr(ln), ptr(t), B, P, T, _lib.stream_ptr()), name)
-                        else:
-                            name = "mt_note_grid_counts" + suffix
-                            check(getattr(lib, name)(*axes, ptr(roll), ptr(ln), ptr(t), B, P, T, _lib.stream_ptr()), name)
-                        if not whole:
-                            out[:, i0:i0 + n, j0:j0 + len(b), k0:k0 + len(k), c0:c0 + len(c)] = t
+        kf = min(Kf, GRID_MAX_K, GRID_MAX_CONFIGS // (kr * kc * kk * ko))
+        for i0, j0, k0, c0, r0 in itertools.product(range(0, Kf, kf), range(0, Ko, ko), range(0, Kk, kk), range(0, Kc, kc), range(0, Kr, kr)):
+            n = min(kf, Kf - i0)
+            b, k, c = (np.ascontiguousarray(v) for v in (to[j0:j0 + ko], tk[k0:k0 + kk], cl[c0:c0 + kc]))
+            r = None if reach is None else np.ascontiguousarray(reach[r0:r0 + kr])
+            whole = (n, len(b), len(k), len(c)) == (Kf, Ko, Kk, Kc) and (r is None or len(r) == Kr) and out.is_contiguous()
+            t = out if whole else torch.empty(B, n, len(b), len(k), len(c), *(() if r is None else (len(r),)), 4, dtype=torch.int64,
+                                              device=dev)
+            first, suffix = head(i0, n)
+            axes = (*first, b.ctypes.data if on is not None else None, len(b), k.ctypes.data if off is not None else None, len(k),
+                    c.ctypes.data, len(c), *(() if r is None else (r.ctypes.data, len(r))))
+            if r is not None:
+                suffix += "_peak"
+            if as_list:
+                name = "mt_note_grid_list" + suffix
+                check(getattr(lib, name)(*axes, ptr(r_on), ptr(r_off), ptr(r_ptr), ptr(ln), ptr(t), B, P, T, _lib.stream_ptr()), name)
+            else:
+                name = "mt_note_grid_counts" + suffix
+                check(getattr(lib, name)(*axes, ptr(roll), ptr(ln), ptr(t), B, P, T, _lib.stream_ptr()), name)
+            if not whole:
+                at = (slice(None), slice(i0, i0 + n), slice(j0, j0 + len(b)), slice(k0, k0 + len(k)), slice(c0, c0 + len(c)))
+                out[at if r is None else (*at, slice(r0, r0 + len(r)))] = t
 
     with torch.cuda.device(dev):
         if smooth is None:
-            out = torch.empty(B, len(tf), Ko, Kk, Kc, 4, dtype=torch.int64, device=dev)
+            out = torch.empty(B, len(tf), Ko, Kk, Kc, *tail, dtype=torch.int64, device=dev)
 
             tiles(out, lambda i0, n: ((ptr(x), ptr(on), ptr(off), tf[i0:].ctypes.data, n), ""))         # (tf: contiguous float32)
             return out
         Ks = len(smooth)
         cand_thr = np.repeat(tf, Ks)                         # candidate i * Ks + s = (thresholds[i], smoothings[s]): frame-major
         cand = smooth * len(tf)
-        out = torch.empty(B, len(cand), Ko, Kk, Kc, 4, dtype=torch.int64, device=dev)
+        out = torch.empty(B, len(cand), Ko, Kk, Kc, *tail, dtype=torch.int64, device=dev)
         for q0 in range(0, len(cand), SMOOTH_MAX_K):
             paths = _paths(x, cand_thr[q0:q0 + SMOOTH_MAX_K], cand[q0:q0 + SMOOTH_MAX_K], ln)
             tiles(out[:, q0:q0 + len(paths)], lambda i0, n: ((ptr(paths[i0:i0 + n]), n, ptr(on), ptr(off)), "_paths"))
-    return out.reshape(B, len(tf), Ks, Ko, Kk, Kc, 4)
+    return out.reshape(B, len(tf), Ks, Ko, Kk, Kc, *tail)
 
 
 def _prf(tp: int, n_ref: int, n_est: int) -> Tuple[float, float, float]:

@@ -30,6 +30,9 @@ note metrics are reported at the chosen pair.
 `--note_metrics --decoder onset|onset_offset --onset_detect peak [--peak_reach N]` opens the notes at the local maxima of the onset
 logits, not at the rising edges of the thresholded onset head (DESIGN.md 6c "Peak-picked onsets"); with cleanup, smoothing,
 --window_overlap and --refine_onsets as before, not with the tuners.
+`--tune_note_decoder --decoder onset|onset_offset --tune_peak_reach 0 1 2` tunes that detector with everything else: every reach of the
+list, 0 = the edge rule, is one more candidate of each round's grid (DESIGN.md 6c "Peak picking in the decoder grid"), and the note
+metrics are reported at the chosen reach.
 `--note_metrics --note_reference midi --decoder onset|onset_offset --refine_onsets [--refine_reach N]` gives every decoded note a
 sub-frame onset (notes.refine_onsets_device), copies the note lists to the host and scores them there in ticks of 100 us
 (notes.note_match_ticks); the same EVAL_NOTE_* lines.  Cleanup and smoothing flags stay allowed; the tuners are refused.
@@ -105,7 +108,7 @@ def main():
                          "the thresholded onset head; peak: at every local maximum of the onset logits within --peak_reach frames that "
                          "passes the onset threshold (for a head trained with train_cnn.py --onset_target regress, whose triangles the "
                          "edge rule merges when a key is re-struck within --onset_width frames).  Not with the three tuners: the sweep "
-                         "and grid kernels have no peak mode")
+                         "kernels have no peak mode, and --tune_note_decoder tunes the detector through --tune_peak_reach")
     ap.add_argument("--peak_reach", type=int, default=1,
                     help="--onset_detect peak: a peak must be the largest logit of this many frames on either side (1..8; default 1); "
                          "peaks are then more than this many frames apart")
@@ -143,8 +146,20 @@ def main():
     ap.add_argument("--tune_smooth_off", type=float, nargs="+", default=[0.0],
                     help="--tune_note_decoder: the candidates for --smooth_off (default: 0); every pair of the two lists is tried, with "
                          "every cleanup pair, in every round")
+    ap.add_argument("--tune_peak_reach", type=int, nargs="+", default=None, metavar="R",
+                    help="--tune_note_decoder with --decoder onset or onset_offset: the candidate reaches of the peak-picking onset "
+                         "detector (--onset_detect peak --peak_reach R), integers in 0..8, 0 = the edge rule; every reach is tried with "
+                         "every cleanup and smoothing pair, in every round, and the note metrics are those at the chosen one; headless "
+                         "adds EVAL_NOTE_PEAK_REACH= (0: the edge rule won).  Default: absent, the edge rule alone")
     args = ap.parse_args()
     tune_cleanups = tune_smoothings = None
+    if args.tune_peak_reach is not None:
+        if not args.tune_note_decoder:
+            ap.error("--tune_peak_reach lists the candidate reaches of --tune_note_decoder and needs that flag")
+        if args.decoder not in ("onset", "onset_offset"):
+            ap.error("--tune_peak_reach picks peaks on the onset head and needs --decoder onset or onset_offset")
+        if not all(0 <= r <= 8 for r in args.tune_peak_reach):
+            ap.error("--tune_peak_reach: a reach must lie in 0..8 frames (0 = the edge rule)")
     if args.tune_note_decoder:
         if args.tune_note_thresholds:
             ap.error("--tune_note_decoder cannot be combined with --tune_note_thresholds: it tunes the thresholds itself")
@@ -211,7 +226,8 @@ def main():
         for flag in ("tune_threshold", "tune_note_thresholds", "tune_note_decoder"):
             if getattr(args, flag):
                 ap.error(f"--onset_detect / --peak_reach cannot be combined with --{flag}: peak detection inside the sweep and grid "
-                         "kernels is out of scope; tune with the edge rule, then evaluate with peaks at the values reported")
+                         "kernels is out of scope; tune with the edge rule, then evaluate with peaks at the values reported"
+                         + (" -- or let it tune the detector itself: --tune_peak_reach 0 1 2" if flag == "tune_note_decoder" else ""))
         if not 1 <= args.peak_reach <= 8:
             ap.error("--peak_reach must lie in 1..8 frames (--onset_detect peak)")
     say = (lambda *a, **k: None) if args.headless else print
@@ -315,12 +331,13 @@ def main():
         say(f"Best note thresholds: frame {note_threshold:.4f}" + ("" if note_onset_threshold is None else f", onset {note_onset_threshold:.4f}")
             + f" (mean {args.tune_note_objective} note F1 {tuned_note_f1:.6f})")
     note_min_ms = note_gap_ms = None
+    note_peak_reach = args.peak_reach if args.onset_detect == "peak" else 0
     if args.tune_note_decoder:
         tuned = E.tune_note_decoder(
             model, ds, dev, subset=args.subset, decoder=args.decoder, note_reference=args.note_reference, objective=args.tune_note_objective,
             cleanups=[c for _, _, c in tune_cleanups], tune_range=tuple(args.tune_range), tune_step=args.tune_step,
             tune_min_step=args.tune_min_step, tune_rounds=args.tune_rounds, rank=rank, world=world, log=say if rank == 0 else None,
-            window_overlap=args.window_overlap, smoothings=tune_smoothings)
+            window_overlap=args.window_overlap, smoothings=tune_smoothings, peak_reaches=args.tune_peak_reach)
         note_threshold, note_onset_threshold, note_offset_threshold, tuned_clean = tuned[:4]
         tuned_note_f1 = tuned[-1]
         if tune_smoothings is not None:                    # the note metrics below are those at the chosen penalties
@@ -328,10 +345,13 @@ def main():
         # (the first candidate with the chosen frames: different milliseconds can round to one pair, and the search keeps the first)
         note_min_ms, note_gap_ms = next((m, g) for m, g, c in tune_cleanups if c == tuned_clean)
         min_note_frames, bridge_frames = tuned_clean
+        if args.tune_peak_reach is not None:               # ... and at the chosen detector: ("edge", 0) or ("peak", R)
+            note_peak_reach = tuned[-2][1]
         say(f"Best note decoder: frame {note_threshold:.4f}" + ("" if note_onset_threshold is None else f", onset {note_onset_threshold:.4f}")
             + ("" if note_offset_threshold is None else f", offset {note_offset_threshold:.4f}")
             + f", min note {note_min_ms:g} ms, bridged gap {note_gap_ms:g} ms"
             + ("" if tune_smoothings is None else f", smoothing on {smooth_on:g} / off {smooth_off:g} logits")
+            + ("" if args.tune_peak_reach is None else f", onsets at peaks over {note_peak_reach} frames" if note_peak_reach else ", onsets at edges")
             + f" (mean {args.tune_note_objective} note F1 {tuned_note_f1:.6f})")
     if args.note_metrics:
         notes = E.note_metrics_dataset(model, ds, note_threshold, note_onset_threshold, dev,
@@ -340,7 +360,7 @@ def main():
                                        min_note_frames=min_note_frames, bridge_frames=bridge_frames, smooth_on=smooth_on,
                                        smooth_off=smooth_off, **(dict(refine_onsets=True, refine_reach=args.refine_reach)
                                                                  if args.refine_onsets else {}),
-                                       **(dict(onset_detect="peak", peak_reach=args.peak_reach) if args.onset_detect == "peak" else {}))
+                                       **(dict(onset_detect="peak", peak_reach=note_peak_reach) if note_peak_reach else {}))
     if rank == 0:
         if args.headless:
             print(f"EVAL_MEAN_F1={mean_f1:.6f}")
@@ -359,6 +379,8 @@ def main():
                     if tune_smoothings is not None:
                         print(f"EVAL_NOTE_SMOOTH_ON={smooth_on:g}")
                         print(f"EVAL_NOTE_SMOOTH_OFF={smooth_off:g}")
+                    if args.tune_peak_reach is not None:
+                        print(f"EVAL_NOTE_PEAK_REACH={note_peak_reach}")
         else:
             print(f"\nMean framewise F1 over {len(per_sample)} samples at threshold {threshold:.4f}: {mean_f1:.6f}")
             results = {"mean_f1": mean_f1, "threshold": threshold, "per_sample_f1": per_sample, "split": args.split,
@@ -377,6 +399,8 @@ def main():
                     results["note_metrics"].update(min_note_ms=note_min_ms, bridge_gap_ms=note_gap_ms)
                     if tune_smoothings is not None:
                         results["note_metrics"].update(smooth_on=smooth_on, smooth_off=smooth_off)
+                    if args.tune_peak_reach is not None:
+                        results["note_metrics"].update(tuned_peak_reach=note_peak_reach)
             os.makedirs(args.out_dir, exist_ok=True)
             with open(os.path.join(args.out_dir, "results.json"), "w") as f:
                 json.dump(results, f)

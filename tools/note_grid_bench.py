@@ -9,7 +9,11 @@ Each variant is warmed up, then timed with device events: --repeats windows of -
 the median window and the spread (min .. max) are reported, and `speedup` is the ratio of the medians (below 1: the grid is slower
 than the calls it replaces).  Before timing, the grid's counts are compared with the 64 calls' cell by cell; the tool stops if they differ.
 
-    python tools/note_grid_bench.py [--iters 3] [--repeats 7] [--out note_grid.json]
+--peak times the peak grid instead (DESIGN.md 6c "Peak picking in the decoder grid"): one 64-cell mt_note_grid_counts_peak /
+mt_note_grid_list_peak launch, 2 x 2 x 2 thresholds x 2 cleanups x reaches [0, 1, 2, 8], beside the 64 calls it replaces
+(mt_note_match_*_peak, at reach 0 mt_note_match_*_clean), compared first in the same way.
+
+    python tools/note_grid_bench.py [--peak] [--iters 3] [--repeats 7] [--out note_grid.json]
 """
 import argparse
 import json
@@ -27,9 +31,10 @@ from note_sweep_bench import spread_logits, timed  # noqa: E402
 
 GRID_F, GRID_O, GRID_K = [0.35, 0.5], [0.3, 0.5], [0.5, 0.65]
 CLEANUPS = [(1, 0), (2, 0), (3, 0), (1, 1), (2, 1), (3, 2), (4, 2), (6, 3)]        # (min_frames, bridge_frames): up to 192 ms / 96 ms
+PEAK_CLEANUPS, PEAK_REACHES = [(1, 0), (3, 2)], [0, 1, 2, 8]                        # --peak: 2 cleanups x 4 reaches in place of 8 cleanups
 
 
-def time_case(name, frame, onset, offset, ref, lengths, iters, repeats):
+def time_case(name, frame, onset, offset, ref, lengths, iters, repeats, peak=False):
     import torch
     from music_transcription_amd import _lib
     from music_transcription_amd._lib import check, lib, ptr
@@ -38,22 +43,33 @@ def time_case(name, frame, onset, offset, ref, lengths, iters, repeats):
     notes = roll_notes(ref)
     ln = None if lengths is None else torch.tensor(lengths, dtype=torch.int64, device=frame.device)
     gf, go, gk = (np.array(g, np.float32) for g in (GRID_F, GRID_O, GRID_K))
-    cl = np.array(CLEANUPS, np.int32)
-    c_grid = torch.empty(B, 2, 2, 2, 8, 4, dtype=torch.int64, device=frame.device)
+    cleanups = PEAK_CLEANUPS if peak else CLEANUPS
+    cl = np.array(cleanups, np.int32)
+    reaches = np.array(PEAK_REACHES if peak else [0], np.int32)
+    c_grid = torch.empty(B, 2, 2, 2, len(cl) * len(reaches), 4, dtype=torch.int64, device=frame.device)
     c_one = torch.empty(64, B, 4, dtype=torch.int64, device=frame.device)
     st = _lib.stream_ptr()
-    axes = (ptr(frame), ptr(onset), ptr(offset), gf.ctypes.data, 2, go.ctypes.data, 2, gk.ctypes.data, 2, cl.ctypes.data, 8)
+    axes = (ptr(frame), ptr(onset), ptr(offset), gf.ctypes.data, 2, go.ctypes.data, 2, gk.ctypes.data, 2, cl.ctypes.data, len(cl))
+    if peak:
+        axes += (reaches.ctypes.data, len(reaches))
+    grid_counts, grid_list = (lib.mt_note_grid_counts_peak, lib.mt_note_grid_list_peak) if peak else (lib.mt_note_grid_counts, lib.mt_note_grid_list)
+
+    def one_counts(n, a, b, k, m, g, r):                    # a reach of 0: the edge rule, the _clean entry point
+        head = (ptr(frame), ptr(onset), ptr(offset), a, b, k, ptr(ref), ptr(ln), ptr(c_one[n]), B, P, T, m, g)
+        check(lib.mt_note_match_counts_peak(*head, r, st) if r else lib.mt_note_match_counts_clean(*head, st))
+
+    def one_list(n, a, b, k, m, g, r):
+        head = (ptr(frame), ptr(onset), ptr(offset), a, b, k, ptr(notes["on"]), ptr(notes["off"]), ptr(notes["ptr"]), ptr(ln), ptr(c_one[n]),
+                B, P, T, m, g)
+        check(lib.mt_note_match_list_peak(*head, r, st) if r else lib.mt_note_match_list_clean(*head, st))
     calls = {
-        "roll": (lambda: check(lib.mt_note_grid_counts(*axes, ptr(ref), ptr(ln), ptr(c_grid), B, P, T, st)),
-                 lambda n, a, b, k, m, g: check(lib.mt_note_match_counts_clean(ptr(frame), ptr(onset), ptr(offset), a, b, k, ptr(ref), ptr(ln),
-                                                                               ptr(c_one[n]), B, P, T, m, g, st))),
-        "list": (lambda: check(lib.mt_note_grid_list(*axes, ptr(notes["on"]), ptr(notes["off"]), ptr(notes["ptr"]), ptr(ln), ptr(c_grid), B, P, T,
-                                                     st)),
-                 lambda n, a, b, k, m, g: check(lib.mt_note_match_list_clean(ptr(frame), ptr(onset), ptr(offset), a, b, k, ptr(notes["on"]),
-                                                                             ptr(notes["off"]), ptr(notes["ptr"]), ptr(ln), ptr(c_one[n]), B, P, T,
-                                                                             m, g, st))),
+        "roll": (lambda: check(grid_counts(*axes, ptr(ref), ptr(ln), ptr(c_grid), B, P, T, st)), one_counts),
+        "list": (lambda: check(grid_list(*axes, ptr(notes["on"]), ptr(notes["off"]), ptr(notes["ptr"]), ptr(ln), ptr(c_grid), B, P, T, st)),
+                 one_list),
     }
-    cells = [(float(a), float(b), float(k), int(m), int(g)) for a in gf for b in go for k in gk for m, g in CLEANUPS]
+    cells = [(float(a), float(b), float(k), int(m), int(g), int(r)) for a in gf for b in go for k in gk for m, g in cleanups for r in reaches]
+    if peak:
+        out["grid"] = "peak: 2 x 2 x 2 thresholds x 2 cleanups x reaches " + str(PEAK_REACHES)
     for kind, (grid_call, one_call) in calls.items():
         def grid():
             grid_call()
@@ -88,6 +104,7 @@ def main():
     ap.add_argument("--iters", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--peak", action="store_true", help="time the peak grid (mt_note_grid_*_peak) and the 64 _peak / _clean calls it replaces")
     args = ap.parse_args()
     import torch
     import music_transcription_amd  # noqa: F401  (loads libmt_hip.so)
@@ -99,7 +116,7 @@ def main():
     frame, onset, ref = make_case(128, 88, 938, None, 1, dev)
     _, offset, _ = make_case(128, 88, 938, None, 11, dev)
     res.append(time_case("chunks 128 x 88 x 938", spread_logits(frame, gen), spread_logits(onset, gen), spread_logits(offset, gen), ref, None,
-                         args.iters, args.repeats))
+                         args.iters, args.repeats, args.peak))
     print(json.dumps(res[-1]), flush=True)
     minutes = np.random.default_rng(2).uniform(10.0, 25.0, size=8)
     minutes[0] = 25.0
@@ -107,7 +124,7 @@ def main():
     frame, onset, ref = make_case(8, 88, max(lengths), lengths, 3, dev)
     _, offset, _ = make_case(8, 88, max(lengths), lengths, 13, dev)
     res.append(time_case("recordings 8 x 10-25 min, padded", spread_logits(frame, gen), spread_logits(onset, gen), spread_logits(offset, gen), ref,
-                         lengths, args.iters, args.repeats))
+                         lengths, args.iters, args.repeats, args.peak))
     print(json.dumps(res[-1]), flush=True)
     if args.out:
         with open(args.out, "w") as f:
