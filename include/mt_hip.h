@@ -617,6 +617,28 @@ int    mt_notes_batch_peak(const float* frame_logits, const float* onset_logits,
 int    mt_refine_onsets(const int* starts, const int* ends, const long long* row_off, long long rows, long long n,
                         const float* onset_logits, int NB, int P, long long T, const long long* lengths, int chunks, int reach,
                         int* on_tick, mt_stream_t stream);
+/* Note matching in ticks for estimates off the frame grid (csrc/note_ticks.hip, DESIGN.md 6c "Sub-frame onsets", Scoring): the counts of
+ * mt_note_match_list for an estimated note LIST, such as the notes of mt_notes_batch with the onsets of mt_refine_onsets (off = 320 e).
+ * Both sides are note lists in the layout of mt_note_match_list's reference: on / off int32 ticks of 100 us on the device, ptr int64
+ * with B*P + 1 entries rising from 0, row (b, p) owning [ptr[b*P + p], ptr[b*P + p + 1]); within a row on is non-decreasing (equal
+ * onsets are allowed) and 0 <= on < off.  counts[b] = {n_ref, n_est, tp_onset, tp_onset_offset} (uint64), zeroed on the stream and then
+ * fully written: nothing depends on what counts or workspace held.  A match needs |d on| <= 500 ticks, and for tp_onset_offset also
+ * 5 |d off| <= max(2500, ref_off - ref_on), in 64 bits; each tp is the size of a MAXIMUM matching of its row's graph, summed over the
+ * recording's P rows.  No row length, component size or search depth changes the result.  lengths (int64, device, B entries in frames,
+ * NULL = no clipping): with L = max(0, lengths[b]), reference notes with on >= 320 L are not counted and reference offsets are clipped
+ * to 320 L (mt_note_match_list's rule); estimates are taken as given.  An empty list is legal and its on / off may be NULL.
+ * workspace: mt_note_match_ticks_workspace(n_est, n_ref) bytes on the device for lists of n_est = est_ptr[B*P] and n_ref =
+ * ref_ptr[B*P] notes (at least 16; int32 words match[n_est] | stamp[n_est] | lo[n_ref] | hi[n_ref] | stack[2][n_ref], every word written
+ * before it is read).  A null ptr table, counts or workspace, on without off, B <= 0, P <= 0 or workspace_bytes below
+ * mt_note_match_ticks_workspace(0, 0): MT_EINVAL, nothing launched.  The two note totals are on the device, and the call neither copies
+ * nor synchronises, so the kernel itself compares workspace_bytes with what its tables need; a row whose tables need more, whose slices
+ * leave the tables or whose onsets are out of order reads no note and writes no workspace word, and bit 63 of the four counts[b] is set
+ * instead.  One memset and one launch on `stream`, one wave64 per pitch row: the reference notes' estimate slices by binary search, then
+ * one lane per connected component of the row (a greedy pass for tp_onset, whose graph is convex; augmenting paths for tp_onset_offset). */
+size_t mt_note_match_ticks_workspace(long long n_est, long long n_ref);
+int    mt_note_match_ticks(const int* est_on, const int* est_off, const long long* est_ptr, const int* ref_on, const int* ref_off,
+                           const long long* ref_ptr, const long long* lengths, unsigned long long* counts, int B, int P,
+                           void* workspace, size_t workspace_bytes, mt_stream_t stream);
 /* Frame smoothing (csrc/smooth.hip, DESIGN.md 6c "Frame smoothing"): per pitch row, the Viterbi path of a two-state (off / on) HMM over
  * the frame head, written as logits.  Evidence q_t = rint(clamp(x_t - logit(thr), -64, 64) * 64), forced to q_t >= 1 where the frame is
  * active as mt_predict_threshold has it and to q_t <= 0 where it is not; a = rint(64 * on_penalty), b = rint(64 * off_penalty); the

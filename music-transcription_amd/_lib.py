@@ -88,6 +88,8 @@ _SIGS = {
     "mt_augment_windows": (i32, [vp, vp, vp, vp, vp, vp, C.c_ulonglong, C.c_ulonglong, vp, C.c_uint, vp, i32, i32, vp, vp, sz, vp]),
     "mt_onset_regress_windows": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]),
     "mt_refine_onsets": (i32, [vp, vp, vp, ll, ll, vp, i32, i32, ll, vp, i32, i32, vp, vp]),
+    "mt_note_match_ticks_workspace": (sz, [ll, ll]),
+    "mt_note_match_ticks": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, sz, vp]),
     "mt_stitch_windows": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, ll, vp]),
     "mt_conv1_bn_relu_pool": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "mt_conv2_bn_relu_pool": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp]),

@@ -147,12 +147,13 @@ def note_metrics_dataset(model, dataset, threshold: float = 0.5, onset_threshold
     whichever of the three it is; the result then names the two ("min_note_frames", "bridge_frames").  smooth_on / smooth_off: the frame
     head is smoothed before the decoder (DESIGN.md 6c "Frame smoothing"); the result then names those two as well.
     refine_onsets (onset-gated or offset-gated decoder, note_reference="midi"): the notes are decoded as lists, their onsets refined to
-    sub-frame ticks (mt_refine_onsets with reach refine_reach; DESIGN.md 6c "Sub-frame onsets"), copied to the host and scored there
-    with notes.note_match_ticks -- the device matcher takes estimates on the frame grid only; the result then names "refine_reach".
+    sub-frame ticks (mt_refine_onsets with reach refine_reach; DESIGN.md 6c "Sub-frame onsets") and scored in ticks on the device
+    (notes.notes_ticks_tables_device, notes.note_match_ticks_device: a maximum matching per pitch row, the counts of the host matcher
+    notes.note_match_ticks) -- mt_note_match_list takes estimates on the frame grid only; the result then names "refine_reach".
     onset_detect="peak" (onset-gated or offset-gated decoder): notes open at the peaks of the onset logits over peak_reach frames
     (DESIGN.md 6c "Peak-picked onsets"), on either path; the result then names "onset_detect" and "peak_reach"."""
-    from .notes import (check_cleanup, check_onset_detect, check_smoothing, note_match_counts, note_match_list, note_match_ticks, note_prf,
-                        notes_ticks_device)
+    from .notes import (check_cleanup, check_onset_detect, check_smoothing, note_match_counts, note_match_list, note_match_ticks_device,
+                        note_prf, notes_ticks_tables_device)
     clean = check_cleanup(min_note_frames, bridge_frames)
     smooth = check_smoothing(smooth_on, smooth_off)
     peak = check_onset_detect(onset_detect, peak_reach, onset_threshold is not None)
@@ -170,11 +171,11 @@ def note_metrics_dataset(model, dataset, threshold: float = 0.5, onset_threshold
     match = note_match_list if note_reference == "midi" else note_match_counts
     for frame, on, ref, lengths, off in _note_groups(lr, dataset, onset, note_reference, max_batch, offset):
         if refine_onsets:
-            est = notes_ticks_device(frame, on, threshold, onset_threshold, lengths, offset_logits=off,
-                                     offset_threshold=offset_threshold if offset else 0.5, min_note_frames=clean[0], bridge_frames=clean[1],
-                                     smooth_on=smooth[0], smooth_off=smooth[1], refine_reach=refine_reach, onset_detect=onset_detect,
-                                     peak_reach=peak_reach)
-            counts = note_match_ticks(est, ref)
+            est = notes_ticks_tables_device(frame, on, threshold, onset_threshold, lengths, offset_logits=off,
+                                            offset_threshold=offset_threshold if offset else 0.5, min_note_frames=clean[0],
+                                            bridge_frames=clean[1], smooth_on=smooth[0], smooth_off=smooth[1], refine_reach=refine_reach,
+                                            onset_detect=onset_detect, peak_reach=peak_reach)
+            counts = note_match_ticks_device(est, ref, lengths=None)     # (the whole reference list, as the host matcher scores it)
         else:
             counts = match(frame, ref, threshold, on, onset_threshold if onset else 0.5, lengths, offset_logits=off,
                            offset_threshold=offset_threshold if offset else 0.5, min_note_frames=clean[0], bridge_frames=clean[1],

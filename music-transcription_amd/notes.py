@@ -29,7 +29,9 @@
     decoder grid").
   * `refine_onsets_device` = sub-frame onsets in ticks of 100 us for the notes of any onset-gated decoder, from the three onset-head values
     around the peak near each note's start (mt_refine_onsets; DESIGN.md 6c "Sub-frame onsets"); `refine_onsets=` on the two note-list
-    calls stamps the notes with them.  `note_match_ticks` scores such off-grid estimates against a note list on the host.
+    calls stamps the notes with them.  `note_match_ticks_device` scores such off-grid estimates against a note list on the device
+    (mt_note_match_ticks: a maximum matching per pitch row, one wave per row, one lane per connected component), from the device
+    tables of `notes_ticks_tables_device`; `note_match_ticks` is the same on the host, and the specification of the kernel.
   * `onset_detect="peak"`, `peak_reach=R` on the two matchers and the note-list calls = a note opens at every local maximum of the
     onset logits over R frames that passes the onset threshold, not at the rising edges of the thresholded onset mask (DESIGN.md 6c
     "Peak-picked onsets"; the mt_*_peak entry points): the detector for an onset head trained against triangular targets, on which
@@ -304,19 +306,28 @@ def smooth_frame_paths(frame_logits: torch.Tensor, thresholds, smoothings, lengt
     return tiles[0] if len(tiles) == 1 else torch.cat(tiles)
 
 
-def _note_tables(ref_notes: Dict[str, torch.Tensor], B: int, P: int, dev):
-    """The checked, contiguous (on, off, ptr) of a note list for B x P rows."""
+def _note_tables(ref_notes: Dict[str, torch.Tensor], B: int, P: int, dev, who: str = "ref_notes", sorted_rows: bool = False):
+    """The checked, contiguous (on, off, ptr) of a note list for B x P rows.  sorted_rows: `on` must also be non-decreasing inside
+    every row (checked on the device, in the same read-back as ptr)."""
     r_on, r_off, r_ptr = (ref_notes[k] for k in ("on", "off", "ptr"))
     for t, dt, name in ((r_on, torch.int32, "on"), (r_off, torch.int32, "off"), (r_ptr, torch.int64, "ptr")):
         if not torch.is_tensor(t) or t.device != dev or t.dtype != dt or t.dim() != 1:
-            raise ValueError(f"ref_notes[{name!r}]: expected a 1-d {dt} tensor on {dev}")
-    if r_ptr.numel() != B * P + 1 or r_on.numel() != r_off.numel():
-        raise ValueError(f"ref_notes: ptr has {r_ptr.numel()} entries for {B} x {P} rows, on / off have {r_on.numel()} / {r_off.numel()}")
+            raise ValueError(f"{who}[{name!r}]: expected a 1-d {dt} tensor on {dev}")
+    n = r_on.numel()
+    if r_ptr.numel() != B * P + 1 or n != r_off.numel():
+        raise ValueError(f"{who}: ptr has {r_ptr.numel()} entries for {B} x {P} rows, on / off have {n} / {r_off.numel()}")
     # the kernel indexes on / off through ptr: refuse a table that points outside them (one small read-back, evaluation only)
-    bad = (r_ptr[0] != 0) | (r_ptr[-1] != r_on.numel()) | (r_ptr[1:] < r_ptr[:-1]).any()
-    if bool(bad):
-        raise ValueError("ref_notes: ptr must rise from 0 to the number of notes")
-    if r_on.numel() == 0:                                   # no notes at all: the kernel still wants readable tables
+    bad = (r_ptr[0] != 0) | (r_ptr[-1] != n) | (r_ptr[1:] < r_ptr[:-1]).any()
+    if sorted_rows and n > 1:
+        first = torch.zeros(n + 1, dtype=torch.bool, device=dev)       # a row's first note may lie before its predecessor
+        first[r_ptr[:-1].clamp(0, n)] = True                           # (clamped: ptr is not known to be good yet; n = an empty last row)
+        bad = bad.to(torch.int32) + 2 * ((r_on[1:] < r_on[:-1]) & ~first[1:n]).any()
+    bad = int(bad)
+    if bad & 1:
+        raise ValueError(f"{who}: ptr must rise from 0 to the number of notes")
+    if bad:
+        raise ValueError(f"{who}: on must be non-decreasing inside every row")
+    if n == 0:                                              # no notes at all: the kernel still wants readable tables
         r_on = r_off = torch.zeros(1, dtype=torch.int32, device=dev)
     return r_on.contiguous(), r_off.contiguous(), r_ptr.contiguous()
 
@@ -601,9 +612,10 @@ def heads_to_notes_device(frame_logits: torch.Tensor, onset_logits: Optional[tor
     return [(int(pp), float(a) / fs, float(b) / fs) for pp, a, b in zip(pitches, s, e)]
 
 
-def _heads_to_notes_raw(x, on, off, thrs, clean, reach: Optional[int], peak: int = 0):
+def _heads_to_notes_raw(x, on, off, thrs, clean, reach: Optional[int], peak: int = 0, on_device: bool = False):
     """The mt_heads_to_notes family on checked (NB, P, T) heads -> host arrays (counts (P,), starts, ends, ticks); ticks None without
-    `reach`, else mt_refine_onsets' onsets of the same notes, which ride in the note copy.  peak: check_onset_detect's result."""
+    `reach`, else mt_refine_onsets' onsets of the same notes, which ride in the note copy.  peak: check_onset_detect's result.
+    on_device (needs `reach`): starts, ends and ticks stay int32 device tensors; only the counts (the capacity check) reach the host."""
     NB, P, T = x.shape
     dev = x.device
     counts = torch.empty(P, dtype=torch.int32, device=dev)
@@ -627,6 +639,8 @@ def _heads_to_notes_raw(x, on, off, thrs, clean, reach: Optional[int], peak: int
     row_off = torch.zeros(P + 1, dtype=torch.int64, device=dev)
     row_off[1:] = torch.cumsum(counts, 0)
     _refine(starts, ends, row_off, total, on, None, True, reach, se[2])
+    if on_device:
+        return c, se[0, :total], se[1, :total], se[2, :total]
     s, e, tick = se[:, :total].cpu().numpy()
     return c, s, e, tick
 
@@ -667,10 +681,11 @@ def notes_batch_device(frame_logits: torch.Tensor, onset_logits: Optional[torch.
     return out
 
 
-def _notes_batch_raw(x, on, ln, thr, othr, clean, reach: Optional[int], peak: int = 0):
+def _notes_batch_raw(x, on, ln, thr, othr, clean, reach: Optional[int], peak: int = 0, on_device: bool = False):
     """mt_notes_batch / mt_notes_batch_clean on checked (B, P, T) heads -> host arrays (row_off (B * P + 1,), counts (B * P,), starts,
     ends, ticks); ticks None without `reach`, else mt_refine_onsets' onsets of the same notes, which ride in the note copy.  peak:
-    check_onset_detect's result (mt_notes_batch_peak)."""
+    check_onset_detect's result (mt_notes_batch_peak).  on_device (needs `reach`): row_off, starts, ends and ticks stay device tensors
+    (int64, int32 x 3); the one read-back is the capacity check (row_off and counts, as before)."""
     B, P, T = x.shape
     dev = x.device
     rows = B * P
@@ -692,6 +707,8 @@ def _notes_batch_raw(x, on, ln, thr, othr, clean, reach: Optional[int], peak: in
         s, e = se[:, :total].cpu().numpy()
         return off, c, s, e, None
     _refine(se[0], se[1], row_off, total, on, ln, False, reach, se[2])
+    if on_device:
+        return row_off, c, se[0, :total], se[1, :total], se[2, :total]
     s, e, tick = se[:, :total].cpu().numpy()
     return off, c, s, e, tick
 
@@ -730,6 +747,73 @@ def notes_ticks_device(frame_logits: torch.Tensor, onset_logits: torch.Tensor, t
         offs.append(e * TICKS_PER_FRAME)
         ptrs.append(ptrs[-1][-1] + np.cumsum(c, dtype=np.int64))
     return {"on": np.concatenate(ons).astype(np.int32), "off": np.concatenate(offs).astype(np.int32), "ptr": np.concatenate(ptrs)}
+
+
+def notes_ticks_tables_device(frame_logits: torch.Tensor, onset_logits: torch.Tensor, threshold: float = 0.5, onset_threshold: float = 0.5,
+                              lengths=None, offset_logits: Optional[torch.Tensor] = None, offset_threshold: float = 0.5,
+                              min_note_frames: int = 1, bridge_frames: int = 0, smooth_on: float = 0.0, smooth_off: float = 0.0,
+                              refine_reach: int = 2, onset_detect: str = "edge", peak_reach: int = 1) -> Dict[str, torch.Tensor]:
+    """notes_ticks_device with the three tables left ON THE DEVICE, for note_match_ticks_device: the same arguments, the same notes,
+    {"on", "off"} int32 and "ptr" int64 device tensors.  Onset-gated decoder: mt_notes_batch*, mt_refine_onsets, off = 320 ends and
+    ptr = the extractor's row_off; the only read-back is the extractor's capacity check.  With offset_logits every recording is still
+    decoded on its own (the batched extractor reads two heads), its notes stay on the device, and the tables are put together there;
+    per recording the counts of its 88 rows reach the host (the capacity check of mt_heads_to_notes_*), and lengths once."""
+    clean = check_cleanup(min_note_frames, bridge_frames)
+    smooth = check_smoothing(smooth_on, smooth_off)
+    reach = _check_refine(True, refine_reach, onset_logits)
+    peak = check_onset_detect(onset_detect, peak_reach, onset_logits is not None)
+    x, on, off, thr, othr, kthr, _ = _heads(frame_logits, onset_logits, offset_logits, threshold, onset_threshold, offset_threshold,
+                                            mismatch="frame {frame} and onset {onset} logits differ in shape")
+    B, P, T = x.shape
+    dev = x.device
+    ln = _lengths(lengths, B, dev)
+    if smooth != (0.0, 0.0):
+        x = _smoothed(x, thr, smooth, ln, False)
+    if off is None:
+        row_off, _, _, e, tick = _notes_batch_raw(x, on, ln, thr, othr, clean, reach, peak, on_device=True)
+        return {"on": tick.contiguous(), "off": e * TICKS_PER_FRAME, "ptr": row_off.clone()}
+    lens = [T] * B if ln is None else [min(max(int(v), 0), T) for v in ln.cpu().numpy()]
+    ons, offs, ptrs = [], [], [np.zeros(1, np.int64)]
+    for b, L in enumerate(lens):
+        c = np.zeros(P, np.int32)
+        if L:
+            cut = lambda h: h[b:b + 1, :, :L].contiguous()
+            c, _, e, tick = _heads_to_notes_raw(cut(x), cut(on), cut(off), (thr, othr, kthr), clean, reach, peak, on_device=True)
+            ons.append(tick)
+            offs.append(e * TICKS_PER_FRAME)
+        ptrs.append(ptrs[-1][-1] + np.cumsum(c, dtype=np.int64))
+    none = torch.zeros(0, dtype=torch.int32, device=dev)
+    return {"on": torch.cat(ons + [none]), "off": torch.cat(offs + [none]), "ptr": torch.from_numpy(np.concatenate(ptrs)).to(dev)}
+
+
+def note_match_ticks_device(est_notes: Dict[str, torch.Tensor], ref_notes: Dict[str, torch.Tensor], lengths=None) -> torch.Tensor:
+    """note_match_ticks on the device (mt_note_match_ticks; DESIGN.md 6c "Sub-frame onsets", Scoring): both arguments {"on", "off"} int32
+    ticks of 100 us and "ptr" int64 DEVICE tensors in the layout of MaestroDataset.ref_notes, the same number of rows on both sides, a
+    multiple of 88 -> (B, 4) int64 device tensor {n_ref, n_est, tp_onset, tp_onset_offset}, equal to note_match_ticks on the same
+    lists.  lengths (B,) frames, None = no clipping: reference notes with on >= 320 lengths[b] are not counted and reference offsets
+    are clipped there, as in note_match_list; estimates are taken as given.  The tables are checked as note_match_list checks its
+    reference, and `on` must be non-decreasing inside every row on both sides (the kernel searches it); one small read-back per side
+    does both, and a bad table raises ValueError before any launch.  The kernel's workspace is allocated here."""
+    for d, who in ((est_notes, "est_notes"), (ref_notes, "ref_notes")):
+        for k in ("on", "off", "ptr"):
+            if not torch.is_tensor(d[k]) or not d[k].is_cuda:
+                raise ValueError(f"{who}[{k!r}]: expected a CUDA tensor")
+    dev = est_notes["ptr"].device
+    rows = est_notes["ptr"].numel() - 1
+    if rows <= 0 or rows % _lib.N_PITCH or ref_notes["ptr"].numel() - 1 != rows:
+        raise ValueError(f"note_match_ticks_device: {rows} estimated and {ref_notes['ptr'].numel() - 1} reference rows "
+                         f"(expected equal multiples of {_lib.N_PITCH})")
+    B, P = rows // _lib.N_PITCH, _lib.N_PITCH
+    n_est, n_ref = est_notes["on"].numel(), ref_notes["on"].numel()
+    e_on, e_off, e_ptr = _note_tables(est_notes, B, P, dev, "est_notes", sorted_rows=True)
+    r_on, r_off, r_ptr = _note_tables(ref_notes, B, P, dev, "ref_notes", sorted_rows=True)
+    ln = _lengths(lengths, B, dev)
+    counts = torch.empty(B, 4, dtype=torch.int64, device=dev)
+    ws = torch.empty(int(lib.mt_note_match_ticks_workspace(n_est, n_ref)), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.mt_note_match_ticks(ptr(e_on), ptr(e_off), ptr(e_ptr), ptr(r_on), ptr(r_off), ptr(r_ptr), ptr(ln), ptr(counts), B, P,
+                                      ptr(ws), ws.numel(), _lib.stream_ptr()), "mt_note_match_ticks")
+    return counts
 
 
 TICKS_PER_SECOND = 10000           # ticks of 100 us
@@ -825,7 +909,8 @@ def note_match_ticks(est_notes, ref_notes) -> np.ndarray:
     tp_onset_offset}, B = rows / 88.  mt_note_match_list's criteria: onsets match when |d on| <= 500 ticks, and for tp_onset_offset
     also 5 |d off| <= max(2500, reference length); each tp is a maximum matching, found per pitch row with augmenting paths.
     mt_note_match_list's streaming matcher relies on at most two frame-grid estimates inside a +-500 tick window, which refined
-    onsets do not guarantee; a device matcher for tick estimates does not exist."""
+    onsets do not guarantee.  This host matcher is the specification of the device one, note_match_ticks_device, which
+    evaluation uses; rows need not be sorted here."""
     def host(d, name):
         out = []
         for k in ("on", "off", "ptr"):

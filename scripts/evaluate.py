@@ -34,8 +34,9 @@ logits, not at the rising edges of the thresholded onset head (DESIGN.md 6c "Pea
 list, 0 = the edge rule, is one more candidate of each round's grid (DESIGN.md 6c "Peak picking in the decoder grid"), and the note
 metrics are reported at the chosen reach.
 `--note_metrics --note_reference midi --decoder onset|onset_offset --refine_onsets [--refine_reach N]` gives every decoded note a
-sub-frame onset (notes.refine_onsets_device), copies the note lists to the host and scores them there in ticks of 100 us
-(notes.note_match_ticks); the same EVAL_NOTE_* lines.  Cleanup and smoothing flags stay allowed; the tuners are refused.
+sub-frame onset (mt_refine_onsets) and scores the note lists on the device in ticks of 100 us (notes.notes_ticks_tables_device,
+notes.note_match_ticks_device: a maximum matching per pitch row; only the counts reach the host); the same EVAL_NOTE_* lines as the host
+matcher notes.note_match_ticks gives.  Cleanup and smoothing flags stay allowed; the tuners are refused.
 MIDI / plot outputs, background mode and the results browser are out of scope.
 """
 import argparse
@@ -99,7 +100,8 @@ def main():
     ap.add_argument("--refine_onsets", action="store_true",
                     help="with --note_metrics --note_reference midi --decoder onset / onset_offset: give every decoded note a sub-frame onset "
                          "from the onset head's values around its peak (a head trained with train_cnn.py --onset_target regress) and score "
-                         "the note lists on the host in 100 us ticks; prints the same EVAL_NOTE_* lines.  Not with the three tuners")
+                         "the note lists on the device in 100 us ticks (mt_note_match_ticks); prints the same EVAL_NOTE_* lines.  Not with the "
+                         "three tuners")
     ap.add_argument("--refine_reach", type=int, default=2,
                     help="--refine_onsets: frames the peak search may walk from a note's first frame (0..8; default 2 = the default "
                          "--onset_width of training)")
