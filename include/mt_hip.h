@@ -728,6 +728,31 @@ int    mt_note_grid_list_paths_peak(const unsigned long long* paths, int Kf, con
                                     const float* thr_onset, int Ko, const float* thr_offset, int Kk, const int* clean, int Kc,
                                     const int* peak_reach, int Kr, const int* ref_on, const int* ref_off, const long long* ref_ptr,
                                     const long long* lengths, unsigned long long* counts, int B, int P, int T, mt_stream_t stream);
+/* The decoder grid in ticks (csrc/notes_grid_ticks.hip, csrc/note_ticks.hip; DESIGN.md 6c "Decoder grid in ticks"): every cell of the
+ * grid of mt_note_grid_list_peak decoded into its own note list with refined onsets, and all of those lists scored in one launch.
+ * mt_notes_grid_ticks: frame / onset / offset logits [B][P][T] (offset_logits NULL: the onset-gated decoder, Kk = 1), lengths int64 [B]
+ * or NULL, and the axes of mt_note_grid_list_peak passed the same way (host arrays, taken by value; peak_reach is required, {0} = the
+ * edge rule alone), K = Kf * Ko * Kk * Kc * Kr <= 64 cells, cell index frame-major with the reach innermost; refine_reach in [0, 8].
+ * Out, cell-major: counts (int32, K*B*P) and row_off (int64, K*B*P + 1, the exclusive prefix of counts) at [(cell * B + b) * P + p], and for
+ * note n of that row on_tick[row_off[..] + n] = the onset mt_refine_onsets gives the note (to the bit), off_tick = 320 * its end frame.  The
+ * slice of a cell is, element for element, the table of mt_notes_batch_peak (reach R >= 1; mt_notes_batch_clean for R = 0) followed by
+ * mt_refine_onsets at the cell's parameters and, with offset_logits, that of mt_heads_to_notes_peak / _clean on each recording's valid
+ * frames.  capacity = the entries on_tick / off_tick can hold, in [0, 2^31): 0 counts only (the two may be NULL); when row_off[K*B*P]
+ * exceeds it nothing past it is written, no note is refined, and the caller comes back with larger buffers (the one read-back of the
+ * pair).  Every word of counts, row_off and the first row_off[K*B*P] entries of on_tick / off_tick is written.  64 * B * P and 320 * T
+ * must fit 31 bits.  Any violation: MT_EINVAL before the first device call.  Four launches on `stream` (count, prefix, fill, refine).
+ * mt_note_match_ticks_cells: mt_note_match_ticks for estimate tables of K * B * P rows against a reference of B * P rows; estimate row r
+ * is matched against reference row r mod (B * P), counts[cell][b] (uint64 [K][B][4]).  The workspace holds the reference-indexed arrays
+ * once per cell: mt_note_match_ticks_cells_workspace(n_est, n_ref, K) bytes, n_est = est_ptr[K*B*P].  The kernel's own checks, bit 63
+ * on a bad row included, are mt_note_match_ticks' and hold per (cell, recording); K = 1 is mt_note_match_ticks. */
+int    mt_notes_grid_ticks(const float* frame_logits, const float* onset_logits, const float* offset_logits, const float* thr_frame, int Kf,
+                           const float* thr_onset, int Ko, const float* thr_offset, int Kk, const int* clean, int Kc, const int* peak_reach,
+                           int Kr, int refine_reach, const long long* lengths, int B, int P, int T, int* counts, long long* row_off,
+                           int* on_tick, int* off_tick, long long capacity, mt_stream_t stream);
+size_t mt_note_match_ticks_cells_workspace(long long n_est, long long n_ref, int K);
+int    mt_note_match_ticks_cells(const int* est_on, const int* est_off, const long long* est_ptr, const int* ref_on, const int* ref_off,
+                                 const long long* ref_ptr, const long long* lengths, unsigned long long* counts, int K, int B, int P,
+                                 void* workspace, size_t workspace_bytes, mt_stream_t stream);
 
 /* ------------------------------------------------------------------ optimizer step (training)
  * clip_grad_norm_(max_norm) + torch.optim.Adam with coupled L2 weight decay over flat f32 buffers

@@ -39,8 +39,9 @@ from .ops import LossConfig, compute_loss, framewise_f1, heads_loss, mean_f1, pr
 from .optim import FusedAdamClip, LRSchedule, flatten_parameters, allreduce_mean_            # noqa: F401
 from .train import make_optimizer, train_one_epoch                                            # noqa: F401  (train.evaluate = validation loss)
 from .data import CachedMaestroDataset, collate_fn, write_cache_chunk, write_cache_metadata   # noqa: F401
-from .notes import (heads_to_notes_device, note_grid_counts, note_match_counts, note_match_list, note_match_ticks_device,        # noqa: F401
-                    note_prf, note_sweep_counts, notes_batch_device, notes_ticks_tables_device, smooth_frame_logits, smooth_frame_paths)
+from .notes import (heads_to_notes_device, note_grid_counts, note_grid_ticks_counts, note_match_counts, note_match_list,        # noqa: F401
+                    note_match_ticks_cells_device, note_match_ticks_device, note_prf, note_sweep_counts, notes_batch_device,
+                    notes_grid_ticks_tables_device, notes_ticks_tables_device, smooth_frame_logits, smooth_frame_paths)
 from .rawdata import Augment, DeviceBatchLoader, HybridMaestroDataset, MaestroDataset               # noqa: F401
 from .windows import WindowPlan, collect_logits_windows, plan_windows, transcribe_windows      # noqa: F401
 

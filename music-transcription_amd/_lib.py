@@ -187,6 +187,9 @@ _SIGS = {
     "mt_note_grid_list_peak": (i32, [vp, vp, vp, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "mt_note_grid_counts_paths_peak": (i32, [vp, i32, vp, vp, vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, vp, i32, i32, i32, vp]),
     "mt_note_grid_list_paths_peak": (i32, [vp, i32, vp, vp, vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "mt_notes_grid_ticks": (i32, [vp, vp, vp, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, ll, vp]),
+    "mt_note_match_ticks_cells_workspace": (sz, [ll, ll, i32]),
+    "mt_note_match_ticks_cells": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, sz, vp]),
     "mt_conv1_stats": (i32, [vp, vp, vp, vp, i32, i32, i32, vp]),
     "mt_bn_finalize": (i32, [vp, C.c_double, vp, vp, vp, vp, C.c_float, C.c_float, vp, vp, i32, vp, vp, vp, vp, i32, vp]),
     "mt_bn_stats_cl": (i32, [vp, ll, i32, vp, vp]),

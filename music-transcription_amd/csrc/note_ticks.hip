@@ -32,7 +32,8 @@ constexpr int TICKS_PER_FRAME = 320;
 constexpr long long TICK_NO_END = 1ll << 40;        // "no lengths": past every int32 tick
 constexpr unsigned long long TICK_BAD = 1ull << 63; // set in the four counts of a recording with a row that breaks the contract
 
-// workspace, in int32 words (NE / NR = all estimates / reference notes): match[NE] | stamp[NE] | lo[NR] | hi[NR] | stack_i[NR] | stack_j[NR]
+// workspace, in int32 words (NE / NR = all estimates / reference notes): match[NE] | stamp[NE] | lo[NR] | hi[NR] | stack_i[NR] | stack_j[NR];
+// over K cells (mt_note_match_ticks_cells) the four reference-indexed arrays come once per cell: match[NE] | stamp[NE] | K x (lo | hi | stack_i | stack_j)
 struct TickRow {
     const int* e_on;                                // the row's slices of the note tables
     const int* e_off;
@@ -145,20 +146,24 @@ __global__ __launch_bounds__(64 * TICK_WAVES) void note_match_ticks_kernel(const
                                                                            const int* __restrict__ ref_on, const int* __restrict__ ref_off,
                                                                            const long long* __restrict__ ref_ptr,
                                                                            const long long* __restrict__ lengths,
-                                                                           unsigned long long* __restrict__ counts, int rows, int P, int* ws,
-                                                                           unsigned long long ws_words) {
+                                                                           unsigned long long* __restrict__ counts, int rows, int rows_ref,
+                                                                           int P, int* ws, unsigned long long ws_words) {
     const int row = blockIdx.x * TICK_WAVES + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (row >= rows) return;
-    const int b = row / P;
-    unsigned long long* c = counts + 4 * (size_t)b;
-    const long long NE = est_ptr[rows], NR = ref_ptr[rows];
-    const long long e0 = est_ptr[row], e1 = est_ptr[row + 1], r0 = ref_ptr[row], r1 = ref_ptr[row + 1];
+    // mt_note_match_ticks_cells: estimate row `row` of cell row / rows_ref is matched against reference row row % rows_ref, with that
+    // cell's own copy of the reference-indexed workspace arrays; mt_note_match_ticks is the one-cell case, rows_ref == rows.
+    const int cell = row / rows_ref, rrow = row - cell * rows_ref, n_cells = rows / rows_ref;
+    const int b = rrow / P;
+    unsigned long long* c = counts + 4 * (size_t)(row / P);
+    const long long NE = est_ptr[rows], NR = ref_ptr[rows_ref];
+    const long long e0 = est_ptr[row], e1 = est_ptr[row + 1], r0 = ref_ptr[rrow], r1 = ref_ptr[rrow + 1];
     // The tables are on the device, so the host has not seen them: a row whose slices leave the tables, a workspace too small for the
     // tables, or onsets out of order inside the row touch nothing and mark the recording.
     bool ok = NE >= 0 && NR >= 0 && e0 >= 0 && e0 <= e1 && e1 <= NE && r0 >= 0 && r0 <= r1 && r1 <= NR && e1 - e0 < 0x7fffffffll &&
               r1 - r0 < 0x7fffffffll && (NE == 0 || (est_on && est_off)) && (NR == 0 || (ref_on && ref_off)) &&
-              NE < (1ll << 40) && NR < (1ll << 40) && 2 * (unsigned long long)NE + 4 * (unsigned long long)NR <= ws_words;
+              NE < (1ll << 40) && NR < (1ll << 40) &&
+              2 * (unsigned long long)NE + 4 * (unsigned long long)n_cells * (unsigned long long)NR <= ws_words;
     const int ne = ok ? (int)(e1 - e0) : 0, nr_all = ok ? (int)(r1 - r0) : 0;
     ok = ok && tick_sorted(est_on + e0, ne, lane) && tick_sorted(ref_on + r0, nr_all, lane);
     if (!ok) {
@@ -172,7 +177,7 @@ __global__ __launch_bounds__(64 * TICK_WAVES) void note_match_ticks_kernel(const
     w.r_off = ref_off + r0;
     w.match = ws + e0;
     w.stamp = ws + NE + e0;
-    w.lo = ws + 2 * NE + r0;
+    w.lo = ws + 2 * NE + 4 * (long long)cell * NR + r0;
     w.hi = w.lo + NR;
     w.stk_i = w.hi + NR;
     w.stk_j = w.stk_i + NR;
@@ -231,26 +236,46 @@ __global__ __launch_bounds__(64 * TICK_WAVES) void note_match_ticks_kernel(const
 
 using namespace mt;
 
-extern "C" size_t mt_note_match_ticks_workspace(long long n_est, long long n_ref) {
-    if (n_est < 0 || n_ref < 0 || n_est >= (1ll << 40) || n_ref >= (1ll << 40)) return 0;
-    const size_t bytes = sizeof(int) * (2 * (size_t)n_est + 4 * (size_t)n_ref);
+// K cells of estimates, B * P rows each, against one reference of B * P rows (K = 1: mt_note_match_ticks).
+static size_t match_ticks_workspace(long long n_est, long long n_ref, int K) {
+    if (K < 1 || n_est < 0 || n_ref < 0 || n_est >= (1ll << 40) || n_ref >= (1ll << 40)) return 0;
+    const size_t bytes = sizeof(int) * (2 * (size_t)n_est + 4 * (size_t)K * (size_t)n_ref);
     return bytes < 16 ? 16 : (bytes + 15) & ~(size_t)15;
 }
+
+static int match_ticks(const char* who, const int* est_on, const int* est_off, const long long* est_ptr, const int* ref_on, const int* ref_off,
+                       const long long* ref_ptr, const long long* lengths, unsigned long long* counts, int K, int B, int P, void* workspace,
+                       size_t workspace_bytes, mt_stream_t stream) {
+    MT_REQUIRE(est_ptr && ref_ptr && counts && workspace, MT_EINVAL, "%s: null pointer", who);
+    MT_REQUIRE((est_on == nullptr) == (est_off == nullptr) && (ref_on == nullptr) == (ref_off == nullptr), MT_EINVAL,
+               "%s: on and off of a note list are both null (an empty list) or neither", who);
+    MT_REQUIRE(K > 0 && B > 0 && P > 0 && (long long)K * B * P < 2147483647ll - TICK_WAVES, MT_EINVAL, "%s: bad dims", who);
+    MT_REQUIRE(workspace_bytes >= match_ticks_workspace(0, 0, 1) && ((size_t)workspace & 3) == 0, MT_EINVAL,
+               "%s: workspace of %zu bytes (%s_workspace gives the size; 4-byte aligned)", who, workspace_bytes, who);
+    hipStream_t st = (hipStream_t)stream;
+    MT_CHECK_HIP(hipMemsetAsync(counts, 0, (size_t)K * B * 4 * sizeof(unsigned long long), st));
+    const int rows_ref = B * P, rows = K * rows_ref;
+    hipLaunchKernelGGL(note_match_ticks_kernel, dim3((rows + TICK_WAVES - 1) / TICK_WAVES), dim3(64 * TICK_WAVES), 0, st, est_on, est_off, est_ptr,
+                       ref_on, ref_off, ref_ptr, lengths, counts, rows, rows_ref, P, (int*)workspace,
+                       (unsigned long long)(workspace_bytes / sizeof(int)));
+    MT_CHECK_LAUNCH();
+    return MT_OK;
+}
+
+extern "C" size_t mt_note_match_ticks_workspace(long long n_est, long long n_ref) { return match_ticks_workspace(n_est, n_ref, 1); }
 
 extern "C" int mt_note_match_ticks(const int* est_on, const int* est_off, const long long* est_ptr, const int* ref_on, const int* ref_off,
                                    const long long* ref_ptr, const long long* lengths, unsigned long long* counts, int B, int P,
                                    void* workspace, size_t workspace_bytes, mt_stream_t stream) {
-    MT_REQUIRE(est_ptr && ref_ptr && counts && workspace, MT_EINVAL, "mt_note_match_ticks: null pointer");
-    MT_REQUIRE((est_on == nullptr) == (est_off == nullptr) && (ref_on == nullptr) == (ref_off == nullptr), MT_EINVAL,
-               "mt_note_match_ticks: on and off of a note list are both null (an empty list) or neither");
-    MT_REQUIRE(B > 0 && P > 0 && (long long)B * P < 2147483647ll - TICK_WAVES, MT_EINVAL, "mt_note_match_ticks: bad dims");
-    MT_REQUIRE(workspace_bytes >= mt_note_match_ticks_workspace(0, 0) && ((size_t)workspace & 3) == 0, MT_EINVAL,
-               "mt_note_match_ticks: workspace of %zu bytes (mt_note_match_ticks_workspace gives the size; 4-byte aligned)", workspace_bytes);
-    hipStream_t st = (hipStream_t)stream;
-    MT_CHECK_HIP(hipMemsetAsync(counts, 0, (size_t)B * 4 * sizeof(unsigned long long), st));
-    const int rows = B * P;
-    hipLaunchKernelGGL(note_match_ticks_kernel, dim3((rows + TICK_WAVES - 1) / TICK_WAVES), dim3(64 * TICK_WAVES), 0, st, est_on, est_off, est_ptr,
-                       ref_on, ref_off, ref_ptr, lengths, counts, rows, P, (int*)workspace, (unsigned long long)(workspace_bytes / sizeof(int)));
-    MT_CHECK_LAUNCH();
-    return MT_OK;
+    return match_ticks("mt_note_match_ticks", est_on, est_off, est_ptr, ref_on, ref_off, ref_ptr, lengths, counts, 1, B, P, workspace,
+                       workspace_bytes, stream);
+}
+
+extern "C" size_t mt_note_match_ticks_cells_workspace(long long n_est, long long n_ref, int K) { return match_ticks_workspace(n_est, n_ref, K); }
+
+extern "C" int mt_note_match_ticks_cells(const int* est_on, const int* est_off, const long long* est_ptr, const int* ref_on, const int* ref_off,
+                                         const long long* ref_ptr, const long long* lengths, unsigned long long* counts, int K, int B, int P,
+                                         void* workspace, size_t workspace_bytes, mt_stream_t stream) {
+    return match_ticks("mt_note_match_ticks_cells", est_on, est_off, est_ptr, ref_on, ref_off, ref_ptr, lengths, counts, K, B, P, workspace,
+                       workspace_bytes, stream);
 }

@@ -7,6 +7,7 @@
 //   mt_refine_onsets: the inverse at decode time -- per decoded note the peak of sigmoid(onset) near the note's first frame and the
 //     analytic vertex of the triangle through the peak and its two neighbours, as an onset in ticks.
 #include "mt_common.h"
+#include "onset_refine.h"
 
 namespace mt {
 
@@ -78,34 +79,7 @@ __global__ void refine_onsets_kernel(const int* __restrict__ starts, const int* 
         base = lo * T;
         pstride = 0;
     }
-    auto prob = [&](long long g) -> float {
-        if (g < 0 || g >= L) return 0.0f;
-        const float v = CHUNKS ? x[base + (g / T) * pstride + g % T] : x[base + g];
-        return 1.0f / (1.0f + expf(-v));
-    };
-    long long top = s + reach;
-    top = e - 1 < top ? e - 1 : top;
-    top = L - 1 < top ? L - 1 : top;
-    long long k = s;
-    float B = prob(k);
-    while (k + 1 <= top) {
-        const float nx = prob(k + 1);
-        if (!(nx > B)) break;
-        B = nx;
-        ++k;
-    }
-    const float A = prob(k - 1), Cq = prob(k + 1);
-    const float m = fminf(A, Cq);
-    float shift = 0.0f;
-    if (B - m >= 0x1p-10f) {
-        shift = Cq > A ? (Cq - A) / (2.0f * (B - A)) : (Cq - A) / (2.0f * (B - Cq));
-        shift = fminf(fmaxf(shift, -0.5f), 0.5f);
-    }
-    long long tick = k * TICKS_PER_FRAME + (long long)rintf((float)TICKS_PER_FRAME * shift);
-    const long long cap = e * TICKS_PER_FRAME - 1;
-    tick = tick > cap ? cap : tick;
-    tick = tick < 0 ? 0 : tick;
-    out[i] = (int)(tick > 0x7fffffffll ? 0x7fffffffll : tick);
+    out[i] = refine_tick<CHUNKS>(s, e, x, base, pstride, T, L, reach);
 }
 
 }  // namespace mt

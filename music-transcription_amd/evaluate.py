@@ -427,7 +427,7 @@ def tune_note_decoder(model, dataset, device="cuda", subset: Optional[int] = Non
                       objective: str = "onset", cleanups=((1, 0),), tune_range=(0.05, 0.95), tune_step=0.1, tune_min_step=0.01,
                       tune_rounds=6, rank: int = 0, world: int = 1, log=print, window_overlap: Optional[float] = None, max_batch: int = 128,
                       smooth_on: float = 0.0, smooth_off: float = 0.0, smoothings=None, onset_detect: str = "edge",
-                      peak_reaches=None):
+                      peak_reaches=None, refine_onsets: bool = False, refine_reach: int = 2):
     """Every parameter of the note decoder at once, for the best mean note F1 (`objective`: "onset" or "onset_offset"; unweighted
     mean over samples, as note_metrics_dataset) by search_note_decoder: the thresholds of the heads that `decoder` reads ("frame":
     frame; "onset": frame, onset; "onset_offset": frame, onset, offset) times the candidates `cleanups`, a list of
@@ -444,9 +444,22 @@ def tune_note_decoder(model, dataset, device="cuda", subset: Optional[int] = Non
     "onset_offset"; DESIGN.md 6c "Peak picking in the decoder grid"), the innermost factor of the discrete axis: cleanups x smoothings x
     reaches, every round still one note_grid_counts call per group.  The result then names the detector before the best value:
     (..., (min_note_frames, bridge_frames), [(smooth_on, smooth_off),] (onset_detect, peak_reach), best mean F1), ("edge", 0) or
-    ("peak", R); [R] fixes a reach while the rest is tuned.  A fixed onset_detect="peak" is refused, as a fixed smoothing is."""
-    from .notes import _smoothing_list, check_cleanup, check_peak_reaches, check_smoothing, note_grid_counts, note_prf
+    ("peak", R); [R] fixes a reach while the rest is tuned.  A fixed onset_detect="peak" is refused, as a fixed smoothing is.
+    refine_onsets (decoder "onset" or "onset_offset", note_reference="midi"; DESIGN.md 6c "Decoder grid in ticks"): the objective is the
+    figure note_metrics_dataset(refine_onsets=True, refine_reach=...) reports -- every cell's notes with sub-frame onsets, scored in
+    ticks -- and every round is one notes.note_grid_ticks_counts call per group in place of note_grid_counts; the search and the result
+    are the same.  The tick grid has no smoothing axis: with `smoothings` it raises.  Without refine_onsets nothing changes."""
+    from .notes import (_check_refine, _smoothing_list, check_cleanup, check_peak_reaches, check_smoothing, note_grid_counts,
+                        note_grid_ticks_counts, note_prf)
     _refuse_peak("tune_note_decoder", onset_detect, reaches=True)
+    if refine_onsets:
+        if decoder not in ("onset", "onset_offset") or note_reference != "midi":
+            raise ValueError("tune_note_decoder: refine_onsets: sub-frame onsets are read off the onset head and scored against the MIDI note "
+                             "list in ticks: it needs decoder 'onset' or 'onset_offset' and note_reference='midi'")
+        if smoothings is not None:
+            raise ValueError("tune_note_decoder: refine_onsets cannot be combined with smoothings: the tick grid (note_grid_ticks_counts) "
+                             "reads frame logits, and the packed-paths frame axis that carries the smoothing candidates is not part of it")
+        _check_refine(True, refine_reach, True)
     if peak_reaches is not None:
         if decoder == "frame":
             raise ValueError("tune_note_decoder: peak_reaches needs decoder 'onset' or 'onset_offset': peaks are picked on the onset head, "
@@ -485,8 +498,13 @@ def tune_note_decoder(model, dataset, device="cuda", subset: Optional[int] = Non
         if all(len(v) for v in below):
             fi, oj, kk = below
             for frame, on, ref, lengths, off in _note_groups(lr, dataset, onset, note_reference, max_batch, offset):
-                counts = note_grid_counts(frame, ref, axes[0][fi], on, axes[1][oj] if onset else None, off, axes[2][kk] if offset else None,
-                                          cleanups, lengths, smoothings=smoothings, peak_reaches=None if peak_reaches is None else reaches)
+                if refine_onsets:
+                    counts = note_grid_ticks_counts(frame, on, ref, axes[0][fi], axes[1][oj], off, axes[2][kk] if offset else None, cleanups,
+                                                    None if peak_reaches is None else reaches, lengths, refine_reach)
+                else:
+                    counts = note_grid_counts(frame, ref, axes[0][fi], on, axes[1][oj] if onset else None, off,
+                                              axes[2][kk] if offset else None, cleanups, lengths, smoothings=smoothings,
+                                              peak_reaches=None if peak_reaches is None else reaches)
                 f1 = np.array([m[objective][2] for m in note_prf(counts)])
                 if peak_reaches is not None:
                     f1 = fold_reaches(f1.reshape(len(lengths), len(fi), 1 if smoothings is None else len(smoothings), len(oj), len(kk),

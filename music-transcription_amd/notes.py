@@ -38,6 +38,10 @@
     the edge rule merges re-struck keys.  "edge" calls exactly the entry points above.  The sweep kernel has no peak mode.
   * `peak_reaches=` on `note_grid_counts` = a list of candidate reaches as the grid's last axis, 0 = the edge rule, so one pass scores
     both detectors (the mt_note_grid_*_peak entry points; DESIGN.md 6c "Peak picking in the decoder grid").
+  * `note_grid_ticks_counts` = the counts of `notes_ticks_tables_device` + `note_match_ticks_device` -- refined onsets, scored in ticks --
+    at every cell of such a grid: one launch pair decodes every cell into its refined note list (`notes_grid_ticks_tables_device`,
+    mt_notes_grid_ticks) and one launch scores all of them (`note_match_ticks_cells_device`, mt_note_match_ticks_cells); DESIGN.md 6c
+    "Decoder grid in ticks".
 """
 from __future__ import annotations
 
@@ -814,6 +818,167 @@ def note_match_ticks_device(est_notes: Dict[str, torch.Tensor], ref_notes: Dict[
         check(lib.mt_note_match_ticks(ptr(e_on), ptr(e_off), ptr(e_ptr), ptr(r_on), ptr(r_off), ptr(r_ptr), ptr(ln), ptr(counts), B, P,
                                       ptr(ws), ws.numel(), _lib.stream_ptr()), "mt_note_match_ticks")
     return counts
+
+
+def _grid_ticks_tables(x, on, off, ln, axes, refine_reach: int):
+    """mt_notes_grid_ticks on checked heads and one tile of axes (tf, to, tk, cl, reach: contiguous arrays, at most 64 cells) -> device
+    tensors (row_off int64 (K * B * P + 1,), on_tick, off_tick int32 (total,)).  One read-back per launch pair: the total of the count
+    pass, which is also the capacity check; a second pair only when the first guess was short."""
+    tf, to, tk, cl, reach = axes
+    B, P, T = x.shape
+    dev = x.device
+    K = len(tf) * len(to) * len(tk) * len(cl) * len(reach)
+    rows = K * B * P
+    row_off = torch.empty(rows + 1, dtype=torch.int64, device=dev)
+    counts = torch.empty(rows, dtype=torch.int32, device=dev)
+    cap = K * max(1024, (B * T) // 16)
+    while True:
+        if cap >= 2 ** 31:
+            raise ValueError(f"note_grid_ticks_counts: {cap} notes in one tile of the grid do not fit 31 bits; score fewer cells per call")
+        tab = torch.empty(2, cap, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            check(lib.mt_notes_grid_ticks(ptr(x), ptr(on), ptr(off), tf.ctypes.data, len(tf), to.ctypes.data, len(to),
+                                          tk.ctypes.data if off is not None else None, len(tk), cl.ctypes.data, len(cl), reach.ctypes.data,
+                                          len(reach), refine_reach, ptr(ln), B, P, T, ptr(counts), ptr(row_off), ptr(tab[0]), ptr(tab[1]), cap,
+                                          _lib.stream_ptr()), "mt_notes_grid_ticks")
+        total = int(row_off[rows])
+        if total <= cap:
+            return row_off, tab[0, :total], tab[1, :total]
+        cap = total
+
+
+def _grid_ticks_axes(frame_logits, onset_logits, offset_logits, thresholds, onset_thresholds, offset_thresholds, cleanups, peak_reaches,
+                     lengths, refine_reach):
+    """The checked arguments the two tick-grid calls share -> (x, on, off, ln, (tf, to, tk, cl, reach), refine_reach)."""
+    if onset_logits is None:
+        raise ValueError("onset_logits: refined onsets are read off the onset head; the tick grid needs the onset or the offset-gated decoder")
+    rr = _check_refine(True, refine_reach, onset_logits)
+    reach = np.zeros(1, np.int32) if peak_reaches is None else check_peak_reaches(peak_reaches, True)
+    x = _rows(frame_logits, "frame_logits")
+    heads = []
+    for name, lg, ths in (("onset", onset_logits, onset_thresholds), ("offset", offset_logits, offset_thresholds)):
+        if lg is None:
+            heads.append((None, np.full(1, 0.5, np.float32)))
+            continue
+        h = _rows(lg, f"{name}_logits")
+        if h.shape != x.shape:
+            raise ValueError(f"shape mismatch: frame {tuple(x.shape)}, {name} {tuple(h.shape)}")
+        if ths is None:
+            raise ValueError(f"{name}_thresholds: needed with {name}_logits")
+        heads.append((h, _threshold_array(ths, f"{name}_thresholds")))
+    (on, to), (off, tk) = heads
+    tf = _threshold_array(thresholds, "thresholds")
+    pairs = [(1, 0)] if cleanups is None else [check_cleanup(*c) for c in cleanups]
+    if not pairs:
+        raise ValueError("cleanups: expected a non-empty list of (min_note_frames, bridge_frames) pairs")
+    cl = np.asarray(pairs, dtype=np.int32).reshape(-1, 2)
+    if x.shape[1] != _lib.N_PITCH:
+        raise ValueError(f"frame_logits: the tick grid scores against a note list of {_lib.N_PITCH} pitch rows, got {x.shape[1]}")
+    return x, on, off, _lengths(lengths, x.shape[0], x.device), (tf, to, tk, cl, reach), rr
+
+
+def notes_grid_ticks_tables_device(frame_logits: torch.Tensor, onset_logits: torch.Tensor, thresholds, onset_thresholds,
+                                   offset_logits: Optional[torch.Tensor] = None, offset_thresholds=None, cleanups=None, peak_reaches=None,
+                                   lengths=None, refine_reach: int = 2) -> Dict[str, torch.Tensor]:
+    """The refined note lists of every cell of a decoder grid in one launch pair (mt_notes_grid_ticks; DESIGN.md 6c "Decoder grid in
+    ticks"), for at most 64 cells with at most 16 values per axis: {"on", "off"} int32 and "ptr" int64 (K * B * 88 + 1,) DEVICE tensors,
+    cell-major -- rows [cell * B * 88, (cell + 1) * B * 88) are, element for element, notes_ticks_tables_device's tables at the cell's
+    parameters (onset_detect="peak", peak_reach=R for a reach R >= 1, "edge" for 0; no smoothing), ptr counted from the stacked table's
+    start.  The cell index runs frame-major over thresholds x onset_thresholds x offset_thresholds x cleanups x peak_reaches (None =
+    [0], the edge rule).  With offset_logits: the offset-gated decoder on each recording's valid frames, without the loop over
+    recordings.  "cells" = K."""
+    x, on, off, ln, axes, rr = _grid_ticks_axes(frame_logits, onset_logits, offset_logits, thresholds, onset_thresholds, offset_thresholds,
+                                                cleanups, peak_reaches, lengths, refine_reach)
+    K = int(np.prod([len(a) for a in axes]))
+    if K > GRID_MAX_CONFIGS or max(len(a) for a in axes) > GRID_MAX_K:
+        raise ValueError(f"notes_grid_ticks_tables_device: at most {GRID_MAX_K} values per axis and {GRID_MAX_CONFIGS} cells per call, got "
+                         f"{[len(a) for a in axes]}; note_grid_ticks_counts tiles larger grids")
+    row_off, t_on, t_off = _grid_ticks_tables(x, on, off, ln, [np.ascontiguousarray(a) for a in axes], rr)
+    return {"on": t_on, "off": t_off, "ptr": row_off, "cells": K}
+
+
+def note_match_ticks_cells_device(est_notes: Dict[str, torch.Tensor], ref_notes: Dict[str, torch.Tensor], cells: int,
+                                  lengths=None, checked: bool = True) -> torch.Tensor:
+    """note_match_ticks_device for K = `cells` estimate tables stacked cell-major (K * B * 88 rows, as notes_grid_ticks_tables_device
+    leaves them) against one reference of B * 88 rows -> (K, B, 4) int64 device tensor; [k] is what note_match_ticks_device returns on
+    cell k's slice (mt_note_match_ticks_cells).  ref_notes is checked as note_match_ticks_device checks it, and so are the estimates
+    (one small read-back per side); checked=False leaves the estimates to the kernel's own checks, which touch nothing on a bad row and
+    set bit 63 of the four counts of its (cell, recording)."""
+    for d, who in ((est_notes, "est_notes"), (ref_notes, "ref_notes")):
+        for k in ("on", "off", "ptr"):
+            if not torch.is_tensor(d[k]) or not d[k].is_cuda:
+                raise ValueError(f"{who}[{k!r}]: expected a CUDA tensor")
+    K = int(cells)
+    dev = ref_notes["ptr"].device
+    rows = ref_notes["ptr"].numel() - 1
+    if K < 1 or rows <= 0 or rows % _lib.N_PITCH or est_notes["ptr"].numel() - 1 != K * rows:
+        raise ValueError(f"note_match_ticks_cells_device: {est_notes['ptr'].numel() - 1} estimated rows for {K} cells of {rows} reference "
+                         f"rows (expected cells * rows, rows a multiple of {_lib.N_PITCH})")
+    B, P = rows // _lib.N_PITCH, _lib.N_PITCH
+    n_est, n_ref = est_notes["on"].numel(), ref_notes["on"].numel()
+    r_on, r_off, r_ptr = _note_tables(ref_notes, B, P, dev, "ref_notes", sorted_rows=True)
+    if checked:
+        e_on, e_off, e_ptr = _note_tables(est_notes, K * B, P, dev, "est_notes", sorted_rows=True)
+    else:
+        e_on, e_off, e_ptr = (est_notes[k].contiguous() for k in ("on", "off", "ptr"))
+        if n_est == 0:
+            e_on = e_off = torch.zeros(1, dtype=torch.int32, device=dev)
+    return _match_cells(e_on, e_off, e_ptr, n_est, r_on, r_off, r_ptr, n_ref, _lengths(lengths, B, dev), K, B, P)
+
+
+def _match_cells(e_on, e_off, e_ptr, n_est: int, r_on, r_off, r_ptr, n_ref: int, ln, K: int, B: int, P: int) -> torch.Tensor:
+    """mt_note_match_ticks_cells on checked, contiguous tables -> (K, B, 4) int64 device tensor.  The workspace is allocated here."""
+    dev = e_ptr.device
+    counts = torch.empty(K, B, 4, dtype=torch.int64, device=dev)
+    ws = torch.empty(int(lib.mt_note_match_ticks_cells_workspace(n_est, n_ref, K)), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.mt_note_match_ticks_cells(ptr(e_on), ptr(e_off), ptr(e_ptr), ptr(r_on), ptr(r_off), ptr(r_ptr), ptr(ln), ptr(counts), K, B, P,
+                                            ptr(ws), ws.numel(), _lib.stream_ptr()), "mt_note_match_ticks_cells")
+    return counts
+
+
+def note_grid_ticks_counts(frame_logits: torch.Tensor, onset_logits: torch.Tensor, ref_notes: Dict[str, torch.Tensor], thresholds,
+                           onset_thresholds, offset_logits: Optional[torch.Tensor] = None, offset_thresholds=None, cleanups=None,
+                           peak_reaches=None, lengths=None, refine_reach: int = 2) -> torch.Tensor:
+    """note_match_ticks_device(notes_ticks_tables_device(cell, lengths), ref_notes) at every cell of `thresholds` x `onset_thresholds` x
+    `offset_thresholds` x `cleanups` [x `peak_reaches`] -> (B, Kf, Ko, Kk, Kc[, Kr], 4) int64 device tensor, the axes, their conventions
+    and the tiling rule those of note_grid_counts (16 values per axis and 64 cells per kernel call, the inner axes as wide as they go):
+    the note-level counts of the path evaluation reports with refine_onsets -- refined onsets, scored in ticks by a maximum matching --
+    for a whole decoder grid (DESIGN.md 6c "Decoder grid in ticks").  Per tile one mt_notes_grid_ticks launch pair decodes every cell
+    into its refined note list (the logits read and their sigmoids evaluated once per window, not once per cell; one read-back, the
+    total of the count pass) and one mt_note_match_ticks_cells launch scores all of them.  (B, 88, T) logits of the onset-gated or,
+    with offset_logits, the offset-gated decoder; ref_notes: {"on", "off", "ptr"} device tables, checked as note_match_ticks_device
+    checks them (one small read-back per call).  lengths bound the decoding only: the whole reference list is scored, as
+    evaluate.note_metrics_dataset(refine_onsets=True) scores it.  peak_reaches: as in note_grid_counts, None = the edge rule and no such axis.  Frame
+    smoothing is not an axis here (the packed-paths frame axis is out of scope)."""
+    x, on, off, ln, (tf, to, tk, cl, reach), rr = _grid_ticks_axes(frame_logits, onset_logits, offset_logits, thresholds, onset_thresholds,
+                                                                   offset_thresholds, cleanups, peak_reaches, lengths, refine_reach)
+    B, P, T = x.shape
+    dev = x.device
+    for k in ("on", "off", "ptr"):
+        if not torch.is_tensor(ref_notes[k]) or not ref_notes[k].is_cuda:
+            raise ValueError(f"ref_notes[{k!r}]: expected a CUDA tensor")
+    n_ref = ref_notes["on"].numel()
+    r_on, r_off, r_ptr = _note_tables(ref_notes, B, P, dev, "ref_notes", sorted_rows=True)
+    Kf, Ko, Kk, Kc, Kr = len(tf), len(to), len(tk), len(cl), len(reach)
+    kr = min(Kr, GRID_MAX_K)                                 # tiles of kf x ko x kk x kc x kr <= 64, the inner axes as wide as they go
+    kc = min(Kc, GRID_MAX_K, GRID_MAX_CONFIGS // kr)
+    kk = min(Kk, GRID_MAX_K, GRID_MAX_CONFIGS // (kr * kc))
+    ko = min(Ko, GRID_MAX_K, GRID_MAX_CONFIGS // (kr * kc * kk))
+    kf = min(Kf, GRID_MAX_K, GRID_MAX_CONFIGS // (kr * kc * kk * ko))
+    out = torch.empty(B, Kf, Ko, Kk, Kc, Kr, 4, dtype=torch.int64, device=dev)
+    for i0, j0, k0, c0, r0 in itertools.product(range(0, Kf, kf), range(0, Ko, ko), range(0, Kk, kk), range(0, Kc, kc), range(0, Kr, kr)):
+        axes = [np.ascontiguousarray(v) for v in (tf[i0:i0 + kf], to[j0:j0 + ko], tk[k0:k0 + kk], cl[c0:c0 + kc], reach[r0:r0 + kr])]
+        shape = [len(a) for a in axes]
+        K = int(np.prod(shape))
+        row_off, e_on, e_off = _grid_ticks_tables(x, on, off, ln, axes, rr)
+        n_est = e_on.numel()
+        if n_est == 0:                                       # no notes at all: the kernel still wants readable tables
+            e_on = e_off = torch.zeros(1, dtype=torch.int32, device=dev)
+        c = _match_cells(e_on, e_off, row_off, n_est, r_on, r_off, r_ptr, n_ref, None, K, B, P)    # (the whole reference list)
+        out[:, i0:i0 + shape[0], j0:j0 + shape[1], k0:k0 + shape[2], c0:c0 + shape[3], r0:r0 + shape[4]] = \
+            c.reshape(*shape, B, 4).permute(5, 0, 1, 2, 3, 4, 6)
+    return out if peak_reaches is not None else out[:, :, :, :, :, 0]
 
 
 TICKS_PER_SECOND = 10000           # ticks of 100 us

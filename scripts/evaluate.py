@@ -36,7 +36,8 @@ metrics are reported at the chosen reach.
 `--note_metrics --note_reference midi --decoder onset|onset_offset --refine_onsets [--refine_reach N]` gives every decoded note a
 sub-frame onset (mt_refine_onsets) and scores the note lists on the device in ticks of 100 us (notes.notes_ticks_tables_device,
 notes.note_match_ticks_device: a maximum matching per pitch row; only the counts reach the host); the same EVAL_NOTE_* lines as the host
-matcher notes.note_match_ticks gives.  Cleanup and smoothing flags stay allowed; the tuners are refused.
+matcher notes.note_match_ticks gives.  Cleanup and smoothing flags stay allowed; the tuners are refused here (from Python,
+evaluate.tune_note_decoder(refine_onsets=True) tunes the decoder on that figure; DESIGN.md 6c "Decoder grid in ticks").
 MIDI / plot outputs, background mode and the results browser are out of scope.
 """
 import argparse
@@ -216,8 +217,10 @@ def main():
             ap.error("--refine_onsets reads the onset head and needs --decoder onset or onset_offset")
         for flag in ("tune_threshold", "tune_note_thresholds", "tune_note_decoder"):
             if getattr(args, flag):
-                ap.error(f"--refine_onsets cannot be combined with --{flag}: the tuners count on the device, on the frame grid; tune "
-                         "without it, then evaluate with it at the values reported")
+                ap.error(f"--refine_onsets cannot be combined with --{flag}: this script's tuners count on the frame grid; tune "
+                         "without it, then evaluate with it at the values reported"
+                         + (" (from Python, evaluate.tune_note_decoder(refine_onsets=True) tunes on refined onsets, scored in ticks)"
+                            if flag == "tune_note_decoder" else ""))
         if not 0 <= args.refine_reach <= 8:
             ap.error("--refine_reach must lie in 0..8 frames")
     if args.onset_detect != "edge" or args.peak_reach != 1:
